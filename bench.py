@@ -174,6 +174,8 @@ def latency_main(args):
             r = pl.plan_cycle(p, q, sp, max_pts=M, **inputs)
             pl.synchronize()
         out[name] = (time.perf_counter() - t0) / steps * 1e3
+        if name == "device_resident_inputs":      # the line's value: its last timed call is what --dump-outputs writes
+            dumped = dump_outputs(args.dump_outputs, r) if args.dump_outputs else None
     pl.set_timing(True)
     for _ in range(5):
         r = pl.plan_cycle(p, q, sp, max_pts=M, **dev)
@@ -189,7 +191,7 @@ def latency_main(args):
                                    "resident in HBM", "scenes_per_gpu": 1, "lattice": f"col={cfg.col} x row={cfg.row}",
                        "obstacles": cfg.n_obs, "scene_dist": args.scene_dist},
             "roofline": None, "latency_ms": {k: round(v, 4) for k, v in out.items()}, "kernels_ms": kernels,
-            "scene_status": st,
+            "scene_status": st, "dumped_outputs": dumped,
             "note": "a single scene occupies one wavefront per kernel: the cycle is launch and dependent-instruction latency, "
                     "no roofline applies"}
     if not args.no_cpu_baseline:
@@ -197,6 +199,45 @@ def latency_main(args):
         line["cpu_baseline"] = {**cb, "value": round(1e3 / cb["value"], 2), "unit": "ms per planning cycle"}
     print(json.dumps(line), flush=True)
     pl.close()
+
+
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_PADDED = {"dp_s": "dp_len", "dp_l": "dp_len", "path_s": "path_len", "path_l": "path_len", "traj": "traj_len"}
+
+
+def dump_outputs(path, res, speed=None, seed=0):
+    """Write the arrays of one step's results (CycleResult, and SpeedDpResult as speed_<name>) as path/<name>.npy in float64,
+    every array batch-major.  The padding beyond a scene's length (its content is unspecified) is written
+    as 0, so that two runs compare element for element.  When the batch does not fit in DUMP_MAX_BYTES, the same fixed, seeded
+    sample of scenes is taken from every array; scene_index.npy holds the batch index of every row written.  Returns a summary
+    for the JSON line."""
+    import dataclasses
+    host = {}
+    for prefix, r in (("", res), ("speed_", speed)):
+        if r is None:
+            continue
+        for f in dataclasses.fields(r):
+            v = getattr(r, f.name)
+            if v is not None:
+                host[prefix + f.name] = v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+    B = len(next(iter(host.values())))
+    assert all(len(a) == B for a in host.values()), {k: a.shape for k, a in host.items()}
+    per_scene = 8 + sum(8 * (a.size // max(B, 1)) for a in host.values())      # float64, scene_index included
+    n = min(B, max(1, DUMP_MAX_BYTES // per_scene))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(seed).choice(B, n, replace=False))
+    for k, ln in DUMP_PADDED.items():
+        if k in host:
+            a = host[k].astype(np.float64)
+            a[np.arange(a.shape[1])[None, :] >= host[ln][:, None]] = 0.0
+            host[k] = a
+    host["scene_index"] = np.arange(B)
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for k, a in host.items():
+        a = np.ascontiguousarray(a[idx], dtype=np.float64)
+        np.save(os.path.join(path, k + ".npy"), a)
+        total += a.nbytes
+    return {"dir": path, "scenes": int(n), "of": int(B), "dtype": "float64", "bytes": int(total), "arrays": sorted(host)}
 
 
 def scene_kwargs(args):
@@ -303,9 +344,14 @@ def main():
                          "dram_leg (32768 scenes: the edge tensor streams from HBM), cfg5_leg (BASELINE configs[4], 4096 scenes), "
                          "latency_leg (configs[1], one scene per call), survey_leg / tight_corridor_leg (SURVEY 8(d)'s arc radii), "
                          "host_io_leg (NumPy in and out, PCIe included), gather_path_leg (the N > 1 per-step code on one GPU)")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0,
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
                     help="repeat the timed block of --steps steps until this much time is covered (at most 64 blocks) and report the "
-                         "median block (ms_per_step), the fastest and the slowest (ms_per_step_min_max, timed_blocks); 0 = one block")
+                         "median block (ms_per_step), the fastest and the slowest (ms_per_step_min_max, timed_blocks); default 0: "
+                         "one block, exactly --steps timed steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the arrays plan_cycle - and with --config "
+                         "cfg5 speed_dp - returned) as DIR/<name>.npy in float64, at most 64 MB (a fixed, seeded sample of the scenes "
+                         "when the batch is larger); rank 0 only")
     ap.add_argument("--cpu-sample", type=int, default=48)
     ap.add_argument("--cpu-pool", type=int, default=-1, help="processes of the multi-core CPU baseline (0 = skip, "
                     "-1 = the cores this process may use - affinity and cgroup quota - up to 64)")
@@ -317,12 +363,8 @@ def main():
         return self_launch(args, sys.argv[1:])
 
     from emplanner_carla_amd import _lib as L
-    # lane mode: a hardware queue per stream; must precede HIP's initialisation (_lib.py).  Twelve since round 5: three lanes, the
-    # main stream, the gather stream and torch's fit into eight - until RCCL brings its own streams (N > 1): a one-rank
-    # ProcessGroupNCCL with an all_gather per step beside three lanes measured 0.243 ms per step on 8 queues, 0.211 on 12 or 16 or
-    # 24 (staged: 0.227 either way; without the collective 0.197 whatever the count) - tools/rccl_lanes_probe.py.  Not more than
-    # needed: the queues are the GPU's, and two processes of 16 on ONE GPU (the two-rank test) ran four times slower than of 12
-    L.configure_hw_queues(12)
+    # The hardware queue count is the environment's (HIP's default of four when nothing says otherwise): bench.py leaves it as it
+    # finds it - the queues are shared by every process on the GPU - and --pipeline auto lets the library pick the form that fits
     import torch
     import torch.distributed as dist
     from emplanner_carla_amd import dist as emp_dist
@@ -410,6 +452,7 @@ def main():
             dyn = S.make_dynamic_batch(range(lo, lo + count), 16)
             st_ring.append(([t(a) for a in dyn[:4]], t(dyn[4])))
     step_no = [0]
+    speed_res = [None]              # the S-T half's result of the latest step (configs[4])
     torch.cuda.synchronize()
 
     pl = Planner(dev_index)
@@ -432,7 +475,7 @@ def main():
     auto_choice = None
     if args.pipeline == "auto" and not args.no_pipeline:
         # emp_set_pipeline(EMP_PIPELINE_AUTO): three lanes if every stream of this process gets a hardware queue of its own - the
-        # queues configure_hw_queues(12) asked for above, unless the environment already said otherwise - else the staged form.
+        # queues the process was started with - else the staged form.
         # Beside the lanes and the planner's own streams the process runs torch's stream and, with the exchange, the gather
         # stream and RCCL's.
         will_gather = (world > 1 or args.force_gather_path) and args.gather != "none"
@@ -468,7 +511,7 @@ def main():
             if wide:      # the S-T half reads nothing of the cycle: it need not wait for the cycles in flight
                 pl.set_fence(False)
                 sets = pl.st_graph(*st_ring[ib][0])
-                pl.speed_dp(sdp, *sets, st_ring[ib][1], tables=False)
+                speed_res[0] = pl.speed_dp(sdp, *sets, st_ring[ib][1], tables=False)
                 pl.set_fence(True)
         return sg.submit(res) if with_gather[0] else res, res
 
@@ -516,6 +559,12 @@ def main():
             break
     elapsed = float(np.median(block_s))                  # seconds per block of args.steps steps
     local_elapsed = float(np.median(local_block_s))
+    # what the last timed step computed (complete at the closing fence), before anything after the timed region plans again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, res, speed_res[0] if wide else None)
+        lo = (step_no[0] - 1) % n_in * total + start
+        dumped["scene_seeds"] = [lo, lo + count]          # the input batch the last step planned: scenes.make_batch(range(*...))
 
     sweep_ms, sweep_launches = pl.kernel_ms("dp_sweep"), pl.kernel_launches("dp_sweep")
     sweep_samples = pl.kernel_samples("dp_sweep") * 1e3 if sweep_launches > 0 else None
@@ -791,9 +840,12 @@ def main():
             # the clock probe's - then the diagnostic pass (2 + min(steps, 5) steps) and one pass per input batch)
             "untimed_steps_between_the_timed_region_and_the_diagnostic_pass": probe_steps,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "ms_per_step_is": f"the median of timed_blocks blocks of {args.steps} steps each (every block between two fences, max over ranks)",
+            "ms_per_step_is": (f"the median of timed_blocks blocks of {args.steps} steps each (every block between two fences, max over ranks)"
+                               if len(block_s) > 1 else f"one block of {args.steps} steps between two fences (max over ranks) / {args.steps}"),
             "ms_per_step_min_max": [round(min(block_s) / args.steps * 1e3, 4), round(max(block_s) / args.steps * 1e3, 4)],
             "timed_blocks": len(block_s), "timed_ms_total": round(sum(block_s) * 1e3, 2),
+            "timed_steps": len(block_s) * args.steps,
+            "dumped_outputs": dumped,
             "higher_is_better": True, "scaling": scaling,
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": ("BASELINE configs[2]/[3]" if not wide else "BASELINE configs[4]")

@@ -110,6 +110,14 @@ def _run_ranks(ctx, target, args_of_rank, world=2):
     return got
 
 
+def _cpu_barrier(dist):
+    """The ranks' last rendezvous before destroy_process_group, on the CPU: dist.barrier() asks torch for the machine's
+    accelerator to place its tensor and so opens the GPU in every rank of these CPU-only tests - on a GPU box eight ranks
+    would hold it open at once."""
+    import torch
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, world, port, total, width, q):
     import torch
     import torch.distributed as dist
@@ -122,7 +130,7 @@ def _worker(rank, world, port, total, width, q):
              * torch.ones(1, width, dtype=torch.float64) + torch.arange(width, dtype=torch.float64) * 1e-3)
     out = gather_records(local, total)
     q.put((rank, out.numpy()))
-    dist.barrier()
+    _cpu_barrier(dist)
     dist.destroy_process_group()
 
 
@@ -150,7 +158,7 @@ def _worker_dst(rank, world, port, total, width, q):
     local = local + torch.arange(width, dtype=torch.float64) * 1e-3
     out = gather_records(local, total, dst=0)
     q.put((rank, None if out is None else out.numpy()))
-    dist.barrier()
+    _cpu_barrier(dist)
     dist.destroy_process_group()
 
 
@@ -204,7 +212,7 @@ def _worker_steps(rank, world, port, total, fields, dst, q):
     else:
         u = sg.unpack(last)
         q.put((rank, {k: v.numpy() for k, v in u.items()}))
-    dist.barrier()
+    _cpu_barrier(dist)
     dist.destroy_process_group()
 
 
@@ -252,7 +260,7 @@ def _worker_steps_big(rank, world, port, total, q):
         last = sg.submit(stub.plan_cycle(list(range(start, start + count)), step))
     sg.drain()
     q.put((rank, None if last is None else last.numpy()))
-    dist.barrier()
+    _cpu_barrier(dist)
     dist.destroy_process_group()
 
 
