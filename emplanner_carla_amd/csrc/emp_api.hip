@@ -22,6 +22,45 @@ namespace emp {
 thread_local std::string g_create_error;
 constexpr int kMaxTiledRow = 32;       // the tiled kernels (scenes packed into wavefronts, pair table in LDS) up to here
 
+// Asked by every launch of this file before it is issued: none while the call's Stage still takes inputs (packed inputs may not
+// have been sent yet - emp_context.h Stage::ready()).
+static int launch_gate(emp_ctx* ctx) {
+    if (ctx->stage_open) return fail(ctx, EMP_ERR_INVALID, "internal: kernel launch before Stage::ready() (packed inputs may be unsent)");
+    return EMP_OK;
+}
+
+// A plain launch on the context's stream: nothing for an empty grid; timed under `name` unless that is null.
+template <typename K, typename... A>
+static int launch(emp_ctx* ctx, const char* name, K kern, dim3 grid, dim3 block, size_t lds, A... args) {
+    if ((size_t)grid.x * grid.y * grid.z == 0) return EMP_OK;
+    if (const int rc = launch_gate(ctx)) return rc;
+    KernelTimer t(ctx, name);
+    hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, args...);
+    EMP_LAUNCH_CHECK(ctx);
+    return EMP_OK;
+}
+
+// The scheduling of one emp_plan_cycle call between its launchers (stand-alone entry points pass nullptr: none of it).
+struct CycleSched {
+    // STAGED: the event the front stage's LAST kernel (the sweep) is asked to signal when it completes (hipExtLaunchKernelGGL's
+    // stop event: no marker packet behind the kernel); the sweep's launcher reports the event it did attach - its own timing
+    // event when the kernel is being timed, else front_stop
+    hipEvent_t front_stop = nullptr, front_attached = nullptr;
+    // what the next sweep (EMP_OPT_SWEEP_EXCLUSIVE: the previous call's back stage) and the next edge-cost launch
+    // (EMP_OPT_EDGE_AFTER_ENRICH) wait for on their stream; each is consumed by the launch that waits
+    hipEvent_t sweep_wait = nullptr, edge_wait = nullptr;
+    // The planning cycle leaves the DP backtrack to the densification kernel (dp_sweep_kernel, BT == false): the caller offers
+    // the two buffers, the sweep's launcher sets bt_deferred when it used them (compiled row counts only).
+    unsigned char* bt_pre = nullptr;
+    int* bt_term = nullptr;
+    bool bt_deferred = false;
+    // STAGED: an event the next densification / path-QP launch is asked to signal from its own dispatch (hipExtLaunchKernelGGL's
+    // stop event) instead of a marker packet behind it - a marker idles the back queue ~6 us, twice per step; `stop_attached`
+    // says whether the launcher did (it does not while the kernel carries timing events)
+    hipEvent_t attach_stop = nullptr;
+    bool stop_attached = false;
+};
+
 static int make_dp_dev(emp_ctx* ctx, const emp_dp_params* p, int B, int max_obs, DpDev* d) {
     EMP_REQUIRE(ctx, p != nullptr, "dp params are NULL");
     EMP_REQUIRE(ctx, p->row >= 1 && p->row <= kMaxWideRow, "row must be in [1, 1024]");
@@ -67,8 +106,7 @@ static int dp_pair_table(emp_ctx* ctx, const DpDev& d, const double** out) {
         pt.valid = false;
     }
     if (!pt.valid || memcmp(key, pt.key, sizeof(key)) != 0) {
-        hipLaunchKernelGGL(dp_pair_table_kernel, dim3(1), dim3(256), 0, ctx->stream, d, (double*)tb.p);
-        EMP_LAUNCH_CHECK(ctx);
+        if (const int rc = launch(ctx, nullptr, dp_pair_table_kernel, dim3(1), dim3(256), 0, d, (double*)tb.p)) return rc;
         ++ctx->alloc_gen;                 // (a captured cycle graph does not carry this launch: EMP_OPT_CYCLE_GRAPH)
         memcpy(pt.key, key, sizeof(key));
         pt.valid = true;
@@ -78,17 +116,14 @@ static int dp_pair_table(emp_ctx* ctx, const DpDev& d, const double** out) {
 }
 
 static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const double* obs_l, const int* n_obs,
-                       const double* start, double* start_cost, double* edge, bool tiled) {
+                       const double* start, double* start_cost, double* edge, bool tiled, CycleSched* cs) {
     if (d.B == 0) return EMP_OK;
     if (wide(d)) {          // more than 32 rows: generic kernel, canonical tensor whatever `tiled` says (emp_dp_kernels.h)
         const double* pair_tab = nullptr;
         { const int prc = dp_pair_table(ctx, d, &pair_tab); if (prc) return prc; }
         EMP_REQUIRE(ctx, d.B <= 0x7fffffff && d.col - 1 <= 65535, "batch or lattice too large for the wide-row edge kernel's grid");
-        KernelTimer t(ctx, "dp_edge");
-        hipLaunchKernelGGL(dp_edge_wide_kernel, dim3(d.B, d.col > 1 ? d.col - 1 : 1), dim3(std::min(((d.row + 63) / 64) * 64, 256)), 0, ctx->stream,
-                           d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge);
-        EMP_LAUNCH_CHECK(ctx);
-        return EMP_OK;
+        return launch(ctx, "dp_edge", dp_edge_wide_kernel, dim3(d.B, d.col > 1 ? d.col - 1 : 1), dim3(std::min(((d.row + 63) / 64) * 64, 256)), 0,
+                      d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge);
     }
     // per block: pair table, the tile's obstacles, sample offsets; per wavefront: the longitudinal box terms of its column
     // ([S][mask width] doubles, emp_dp_kernels.h: box_dx2)
@@ -191,9 +226,9 @@ static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
     // EMP_OPT_EDGE_AFTER_ENRICH (staged pipeline): the edge kernel starts behind the previous call's densification kernel,
     // so that the path QP that follows it on the back queue is dispatched BEFORE this kernel's sixteen-wavefront blocks
     // take the compute units (emp_plan_cycle)
-    if (ctx->edge_wait) {
-        EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->edge_wait, 0));
-        ctx->edge_wait = nullptr;
+    if (cs && cs->edge_wait) {
+        EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, cs->edge_wait, 0));
+        cs->edge_wait = nullptr;
     }
     if (ring && ctx->opt[EMP_OPT_EDGE_CLOCK_PROBE]) {          // measurement: two reference ticks per wavefront of this launch
         const size_t waves_total = (size_t)grid.x * grid.y * wpb;
@@ -201,12 +236,9 @@ static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
         if (grc) return grc;
         if (!ctx->edge_probe_done) EMP_HIP(ctx, hipEventCreateWithFlags(&ctx->edge_probe_done, hipEventDisableTiming));
         ctx->edge_probe_waves = (long)waves_total;
-        {
-            KernelTimer t(ctx, "dp_edge");
-            hipLaunchKernelGGL(kern_ring, grid, block, lds, ctx->stream, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
-                               cols_per_chunk, (unsigned long long*)ctx->edge_probe.p);
-        }
-        EMP_LAUNCH_CHECK(ctx);
+        if (const int rc = launch(ctx, "dp_edge", kern_ring, grid, block, lds, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
+                                  cols_per_chunk, (unsigned long long*)ctx->edge_probe.p))
+            return rc;
         EMP_HIP(ctx, hipEventRecord(ctx->edge_probe_done, ctx->stream));
         return EMP_OK;
     }
@@ -216,7 +248,8 @@ static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
     const int leo = ctx->opt[EMP_OPT_LANE_EDGE_ORDER];
     const bool ordered = ctx->pipe_mode >= 2 && ctx->active_lane >= 0 && (leo == 1 || (leo == 2 && d.B >= 8192));
     if (ordered && ctx->lane_edge_done) EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->lane_edge_done, 0));
-    KernelTimer t(ctx, "dp_edge");
+    if (const int rc = launch_gate(ctx)) return rc;
+    KernelTimer t(ctx, "dp_edge");       // (open until the event below is recorded)
     if (ring) {
         hipLaunchKernelGGL(kern_ring, grid, block, lds, ctx->stream, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
                            cols_per_chunk, (unsigned long long*)nullptr);
@@ -235,22 +268,19 @@ static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
 }
 
 static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, const double* edge,
-                        const int* n_obs, double* rows, double* min_cost, int* status) {
+                        const int* n_obs, double* rows, double* min_cost, int* status, CycleSched* cs) {
     if (d.B == 0) return EMP_OK;
     if (wide(d)) {          // more than 32 rows: one block per scene, predecessors in device memory
         emp_ctx::Buf& pre = ctx->named["dp_wide_pre_" + std::to_string(ctx->active_lane)];
         const int grc = grow_buffer(ctx, pre, (size_t)d.B * d.col * d.row * sizeof(unsigned short));
         if (grc) return grc;
-        KernelTimer t(ctx, "dp_sweep");
-        hipLaunchKernelGGL(dp_sweep_wide_kernel, dim3(d.B), dim3(std::min(((d.row + 63) / 64) * 64, 256)), 2 * (size_t)d.row * sizeof(double),
-                           ctx->stream, d, start_cost, edge, n_obs, (unsigned short*)pre.p, rows, min_cost, status);
-        EMP_LAUNCH_CHECK(ctx);
-        return EMP_OK;
+        return launch(ctx, "dp_sweep", dp_sweep_wide_kernel, dim3(d.B), dim3(std::min(((d.row + 63) / 64) * 64, 256)),
+                      2 * (size_t)d.row * sizeof(double), d, start_cost, edge, n_obs, (unsigned short*)pre.p, rows, min_cost, status);
     }
     // EMP_OPT_SWEEP_EXCLUSIVE (staged pipeline): the sweep starts once the previous call's back stage is done
-    if (ctx->sweep_wait) {
-        EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->sweep_wait, 0));
-        ctx->sweep_wait = nullptr;
+    if (cs && cs->sweep_wait) {
+        EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, cs->sweep_wait, 0));
+        cs->sweep_wait = nullptr;
     }
     // EMP_OPT_SWEEP_CLOCK_PROBE: four ticks per wavefront (emp_dp_kernels.h), read by emp_sweep_clock_mhz
     unsigned long long* probe = nullptr;
@@ -263,21 +293,25 @@ static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, 
         ctx->probe_launches++;
     }
     KernelTimer t(ctx, "dp_sweep", true);   // the roofline kernel: events stamped by the dispatch itself
+    unsigned char* const bt_pre = cs ? cs->bt_pre : nullptr;
+    int* const bt_term = cs ? cs->bt_term : nullptr;
+    bool deferred = false;
+    hipEvent_t stop_ev = t.stop ? t.stop : cs ? cs->front_stop : nullptr;
 #define EMP_SWEEP(R, PD, WPB) EMP_SWEEP_NT(R, PD, WPB, false)
 #define EMP_SWEEP_NT(R, PD, WPB, NT)                                                                        \
     do {                                                                                                    \
         const size_t lds = (size_t)(WPB) * (d.col * 64 + 64 * sizeof(double));                              \
         EMP_REQUIRE(ctx, lds <= 160 * 1024, "too many columns for the predecessor table in LDS");           \
-        const bool defer = (R) > 0 && ctx->bt_pre && ctx->bt_term;                                          \
+        const bool defer = (R) > 0 && bt_pre && bt_term;                                                    \
         if (lds > 48 * 1024)                                                                                \
             EMP_HIP(ctx, hipFuncSetAttribute(defer ? (const void*)dp_sweep_kernel<R, PD, WPB, NT, false>    \
                                                    : (const void*)dp_sweep_kernel<R, PD, WPB, NT, true>,    \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
-        hipEvent_t stop_ev = t.stop ? t.stop : ctx->front_stop;                                             \
+        if (const int rc = launch_gate(ctx)) return rc;                                                     \
         if (ctx->capturing && defer) {      /* a stream capture records plain launches only */              \
             hipLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT, false>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
-                               ctx->stream, d, start_cost, edge, n_obs, rows, min_cost, status, ctx->bt_pre, ctx->bt_term, probe); \
-            ctx->bt_deferred = true;                                                                        \
+                               ctx->stream, d, start_cost, edge, n_obs, rows, min_cost, status, bt_pre, bt_term, probe); \
+            deferred = true;                                                                                \
         } else if (ctx->capturing) {                                                                        \
             hipLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
                                ctx->stream, d, start_cost, edge, n_obs, rows, min_cost, status,             \
@@ -285,14 +319,13 @@ static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, 
         } else if (defer) {                                                                                 \
             hipExtLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT, false>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
                                   ctx->stream, t.start, stop_ev, 0, d, start_cost, edge, n_obs, rows, min_cost, status, \
-                                  ctx->bt_pre, ctx->bt_term, probe);                                        \
-            ctx->bt_deferred = true;                                                                        \
+                                  bt_pre, bt_term, probe);                                                  \
+            deferred = true;                                                                                \
         } else {                                                                                            \
             hipExtLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
                                   ctx->stream, t.start, stop_ev, 0, d, start_cost, edge, n_obs, rows, min_cost, status, \
                                   (unsigned char*)nullptr, (int*)nullptr, probe);                           \
         }                                                                                                   \
-        ctx->front_attached = stop_ev;                                                                      \
     } while (0)
     // Ring depth PD (columns in flight per wavefront), measured at 4096 scenes: 2 is best for rows 5..12 (row 9:
     // 20.4 us against 23.2 at PD = 8, 21.4 at PD = 1), 3 for the 21-row lattice; nontemporal loads change nothing.
@@ -324,6 +357,10 @@ static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, 
 #undef EMP_SWEEP_AUTO
 #undef EMP_SWEEP
 #undef EMP_SWEEP_NT
+    if (cs) {
+        cs->front_attached = stop_ev;
+        cs->bt_deferred = deferred;
+    }
     EMP_LAUNCH_CHECK(ctx);
     if (probe) {
         if (!ctx->clock_probe_done) EMP_HIP(ctx, hipEventCreateWithFlags(&ctx->clock_probe_done, hipEventDisableTiming));
@@ -332,20 +369,23 @@ static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, 
     return EMP_OK;
 }
 
-// A launch that signals ctx->attach_stop from its own dispatch when the caller offered one and the kernel carries no timing
-// events (emp_context.h); else a plain launch.
+// A launch that signals cs->attach_stop from its own dispatch when the caller offered one and the kernel carries no timing
+// events (CycleSched); else a plain launch.
 template <typename K, typename... A>
-static void launch_attaching(emp_ctx* ctx, bool timed, K kern, dim3 grid, dim3 block, size_t lds, A... args) {
-    if (ctx->attach_stop && !timed) {
-        hipExtLaunchKernelGGL(kern, grid, block, lds, ctx->stream, nullptr, ctx->attach_stop, 0, args...);
-        ctx->stop_attached = true;
+static int launch_attaching(emp_ctx* ctx, CycleSched* cs, bool timed, K kern, dim3 grid, dim3 block, size_t lds, A... args) {
+    if (const int rc = launch_gate(ctx)) return rc;
+    if (cs && cs->attach_stop && !timed) {
+        hipExtLaunchKernelGGL(kern, grid, block, lds, ctx->stream, nullptr, cs->attach_stop, 0, args...);
+        cs->stop_attached = true;
     } else {
         hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, args...);
     }
+    EMP_LAUNCH_CHECK(ctx);
+    return EMP_OK;
 }
 
 static int dev_dp_enrich(emp_ctx* ctx, const DpDev& d, const double* rows, const double* start, int max_pts,
-                         double* path_s, double* path_l, int* path_len, int* status, int or_status,
+                         double* path_s, double* path_l, int* path_len, int* status, int or_status, CycleSched* cs,
                          const unsigned char* pre = nullptr, const int* term = nullptr, const int* n_obs = nullptr,
                          double* rows_out = nullptr) {
     if (d.B == 0) return EMP_OK;
@@ -354,10 +394,8 @@ static int dev_dp_enrich(emp_ctx* ctx, const DpDev& d, const double* rows, const
     if (lds > 48 * 1024)
         EMP_HIP(ctx, hipFuncSetAttribute((const void*)dp_enrich_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     KernelTimer t(ctx, "dp_enrich");
-    launch_attaching(ctx, t.stop != nullptr, dp_enrich_wave_kernel, dim3(d.B), dim3(64), lds, d, rows, start, max_pts, path_s, path_l,
-                     path_len, status, or_status, pre, term, n_obs, rows_out);
-    EMP_LAUNCH_CHECK(ctx);
-    return EMP_OK;
+    return launch_attaching(ctx, cs, t.stop != nullptr, dp_enrich_wave_kernel, dim3(d.B), dim3(64), lds, d, rows, start, max_pts, path_s,
+                            path_l, path_len, status, or_status, pre, term, n_obs, rows_out);
 }
 
 // DP_algorithm up to the backtrack.  `edge_scratch` may be NULL: taken from the named scratch.
@@ -393,6 +431,7 @@ static int dev_dp_fused(emp_ctx* ctx, const DpDev& d, const double* obs_s, const
         if (lds > 48 * 1024)                                                                                          \
             EMP_HIP(ctx, hipFuncSetAttribute((const void*)dp_fused_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
                                              (int)lds));                                                              \
+        if (const int rc_ = launch_gate(ctx)) return rc_;                                                             \
         hipLaunchKernelGGL(dp_fused_kernel<R>, dim3(d.tiles), dim3(256), lds, ctx->stream, d, pair_tab, obs_s, obs_l,   \
                            n_obs, start, rows, min_cost, status, nc);                                                 \
     } while (0)
@@ -410,20 +449,36 @@ static int dev_dp_fused(emp_ctx* ctx, const DpDev& d, const double* obs_s, const
 
 // DP_algorithm up to the backtrack, in either form.
 static int dev_dp_plan(emp_ctx* ctx, const DpDev& d, const double* obs_s, const double* obs_l, const int* n_obs,
-                       const double* start, emp_dp_mode mode, double* rows, double* min_cost, int* status) {
+                       const double* start, emp_dp_mode mode, double* rows, double* min_cost, int* status, CycleSched* cs) {
     if (d.B == 0) return EMP_OK;
     // the single-kernel form lives on the tiled layout: lattices wider than 32 rows take the two-kernel form either way
     if (mode == EMP_DP_FUSED && !wide(d)) return dev_dp_fused(ctx, d, obs_s, obs_l, n_obs, start, rows, min_cost, status);
     double *edge, *start_cost;
     int rc = dp_edge_tensor(ctx, d, &edge, &start_cost);
     if (rc) return rc;
-    if ((rc = dev_dp_edge(ctx, d, obs_s, obs_l, n_obs, start, start_cost, edge, true))) return rc;
-    return dev_dp_sweep(ctx, d, start_cost, edge, n_obs, rows, min_cost, status);
+    if ((rc = dev_dp_edge(ctx, d, obs_s, obs_l, n_obs, start, start_cost, edge, true, cs))) return rc;
+    return dev_dp_sweep(ctx, d, start_cost, edge, n_obs, rows, min_cost, status, cs);
 }
 
 }  // namespace emp
 
 using namespace emp;
+
+// The preamble of a staged entry point, behind its argument checks: the context's device, then the call's Stage.
+#define EMP_STAGE(st, ...)                       \
+    EMP_HIP(ctx, hipSetDevice(ctx->device));    \
+    Stage st(ctx, __VA_ARGS__)
+
+// A launch on the stream that carries a record-packing call (the main stream, or the result stream of the pipelined cycle),
+// with its timing events there.
+template <typename K, typename... A>
+static int launch_on(emp_ctx* ctx, hipStream_t stream, const char* name, K kern, dim3 grid, dim3 block, A... args) {
+    const hipStream_t saved = ctx->stream;
+    ctx->stream = stream;
+    const int rc = launch(ctx, name, kern, grid, block, 0, args...);
+    ctx->stream = saved;
+    return rc;
+}
 
 extern "C" {
 
@@ -595,36 +650,25 @@ int emp_pack_records(emp_ctx* ctx, int32_t B, int32_t col, int32_t max_pts, int3
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && col >= 1 && max_pts >= 1 && path_cap >= 1 && path_cap <= max_pts, "bad sizes");
     EMP_REQUIRE(ctx, status && traj_len && path_len && dp_rows && path_s && path_l && traj && rec, "NULL array");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
     const bool on_rs = on_result_stream && ctx->pipelined() && where == EMP_DEVICE;
-    Stage st(ctx, where, on_rs);             // on the result stream the launch is ordered behind the cycle by the stream itself
-    int rc;
-    const int *d_st, *d_tl, *d_pl;
-    const double *d_rows, *d_ps, *d_pll, *d_traj;
-    double* d_rec;
+    EMP_STAGE(st, where, on_rs);             // on the result stream the launch is ordered behind the cycle by the stream itself
     const size_t width = 3 + (size_t)col + 2 * (size_t)path_cap + 4 * ((size_t)path_cap + 1);
-    if ((rc = st.in(status, (size_t)B, &d_st))) return rc;
-    if ((rc = st.in(traj_len, (size_t)B, &d_tl))) return rc;
-    if ((rc = st.in(path_len, (size_t)B, &d_pl))) return rc;
-    if ((rc = st.in(dp_rows, (size_t)B * col, &d_rows))) return rc;
-    if ((rc = st.in(path_s, (size_t)B * max_pts, &d_ps))) return rc;
-    if ((rc = st.in(path_l, (size_t)B * max_pts, &d_pll))) return rc;
-    if ((rc = st.in(traj, (size_t)B * (max_pts + 1) * 4, &d_traj))) return rc;
+    const int* d_st = st.in(status, (size_t)B);
+    const int* d_tl = st.in(traj_len, (size_t)B);
+    const int* d_pl = st.in(path_len, (size_t)B);
+    const double* d_rows = st.in(dp_rows, (size_t)B * col);
+    const double* d_ps = st.in(path_s, (size_t)B * max_pts);
+    const double* d_pll = st.in(path_l, (size_t)B * max_pts);
+    const double* d_traj = st.in(traj, (size_t)B * (max_pts + 1) * 4);
     // the kernel writes every slot of rec: no zero fill (it would be queued on ctx->stream, unordered with a launch on
     // the result stream)
-    if ((rc = st.out(rec, (size_t)B * width, &d_rec, false))) return rc;
-    if (B) {
-        const size_t total = (size_t)B * width;
-        hipStream_t target = on_rs ? ctx->result_stream() : ctx->stream, saved = ctx->stream;
-        ctx->stream = target;                                  // (the timer's events belong on the stream that carries the launch)
-        {
-            KernelTimer t(ctx, "pack_records");
-            hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, target, B, col, max_pts,
-                               path_cap, d_st, d_tl, d_pl, d_rows, d_ps, d_pll, d_traj, d_rec);
-        }
-        ctx->stream = saved;
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    double* d_rec = st.out(rec, (size_t)B * width, false);
+    if (const int rc = st.ready()) return rc;
+    const size_t total = (size_t)B * width;
+    if (const int rc = launch_on(ctx, on_rs ? ctx->result_stream() : ctx->stream, "pack_records", pack_records_kernel,
+                                 dim3((unsigned)((total + 255) / 256)), dim3(256), B, col, max_pts, path_cap, d_st, d_tl, d_pl, d_rows,
+                                 d_ps, d_pll, d_traj, d_rec))
+        return rc;
     return st.finish();
 }
 
@@ -647,30 +691,18 @@ int emp_pack_trajectory_records(emp_ctx* ctx, int32_t B, int32_t max_pts, int32_
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_pts >= 1 && path_cap >= 1 && path_cap <= max_pts, "bad sizes");
     EMP_REQUIRE(ctx, status && traj_len && traj && rec, "NULL array");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
     const bool on_rs = on_result_stream && ctx->pipelined() && where == EMP_DEVICE;
-    Stage st(ctx, where, on_rs);
-    int rc;
-    const int *d_st, *d_tl;
-    const double* d_traj;
-    double* d_rec;
+    EMP_STAGE(st, where, on_rs);
     const size_t width = 2 + 4 * ((size_t)path_cap + 1);
-    if ((rc = st.in(status, (size_t)B, &d_st))) return rc;
-    if ((rc = st.in(traj_len, (size_t)B, &d_tl))) return rc;
-    if ((rc = st.in(traj, (size_t)B * (max_pts + 1) * 4, &d_traj))) return rc;
-    if ((rc = st.out(rec, (size_t)B * width, &d_rec, false))) return rc;      // every slot is written by the kernel
-    if (B) {
-        const size_t total = (size_t)B * width;
-        hipStream_t target = on_rs ? ctx->result_stream() : ctx->stream, saved = ctx->stream;
-        ctx->stream = target;
-        {
-            KernelTimer t(ctx, "pack_records");
-            hipLaunchKernelGGL(pack_trajectory_records_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, target, B, max_pts,
-                               path_cap, d_st, d_tl, d_traj, d_rec);
-        }
-        ctx->stream = saved;
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    const int* d_st = st.in(status, (size_t)B);
+    const int* d_tl = st.in(traj_len, (size_t)B);
+    const double* d_traj = st.in(traj, (size_t)B * (max_pts + 1) * 4);
+    double* d_rec = st.out(rec, (size_t)B * width, false);      // every slot is written by the kernel
+    if (const int rc = st.ready()) return rc;
+    const size_t total = (size_t)B * width;
+    if (const int rc = launch_on(ctx, on_rs ? ctx->result_stream() : ctx->stream, "pack_records", pack_trajectory_records_kernel,
+                                 dim3((unsigned)((total + 255) / 256)), dim3(256), B, max_pts, path_cap, d_st, d_tl, d_traj, d_rec))
+        return rc;
     return st.finish();
 }
 
@@ -950,27 +982,19 @@ int emp_dp_edge_costs(emp_ctx* ctx, const emp_dp_params* p, int32_t B, int32_t m
                       double* edge, emp_edge_layout layout, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     DpDev d;
-    int rc = make_dp_dev(ctx, p, B, max_obs, &d);
-    if (rc) return rc;
+    if (const int rc = make_dp_dev(ctx, p, B, max_obs, &d)) return rc;
     EMP_REQUIRE(ctx, n_obs && start && edge, "n_obs, start and edge are required");
     EMP_REQUIRE(ctx, max_obs == 0 || (obs_s && obs_l), "obs_s / obs_l are required when max_obs > 0");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    const double *d_os, *d_ol, *d_start;
-    const int* d_n;
-    double *d_c0, *d_e;
-    if ((rc = st.in(obs_s, (size_t)B * max_obs, &d_os))) return rc;
-    if ((rc = st.in(obs_l, (size_t)B * max_obs, &d_ol))) return rc;
-    if ((rc = st.in(n_obs, (size_t)B, &d_n))) return rc;
-    if ((rc = st.in(start, (size_t)B * 4, &d_start))) return rc;
-    if ((rc = st.out(start_cost, (size_t)B * d.row, &d_c0))) return rc;
-    if ((rc = st.out(edge, (size_t)emp_edge_tensor_elems(p, B, layout), &d_e, layout == EMP_EDGE_TILED))) return rc;  // canonical: fully written
-    if (max_obs == 0) {  // kernels index [b * max_obs + m] only for m < n_obs == 0
-        double* dummy;
-        if ((rc = st.tmp(1, &dummy))) return rc;
-        d_os = d_ol = dummy;
-    }
-    if ((rc = dev_dp_edge(ctx, d, d_os, d_ol, d_n, d_start, d_c0, d_e, layout == EMP_EDGE_TILED))) return rc;
+    EMP_STAGE(st, where);
+    const double* d_os = st.in(obs_s, (size_t)B * max_obs);
+    const double* d_ol = st.in(obs_l, (size_t)B * max_obs);
+    const int* d_n = st.in(n_obs, (size_t)B);
+    const double* d_start = st.in(start, (size_t)B * 4);
+    double* d_c0 = st.out(start_cost, (size_t)B * d.row);
+    double* d_e = st.out(edge, (size_t)emp_edge_tensor_elems(p, B, layout), layout == EMP_EDGE_TILED);  // canonical: fully written
+    if (max_obs == 0) d_os = d_ol = st.tmp<double>(1);   // kernels index [b * max_obs + m] only for m < n_obs == 0
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = dev_dp_edge(ctx, d, d_os, d_ol, d_n, d_start, d_c0, d_e, layout == EMP_EDGE_TILED, nullptr)) return rc;
     return st.finish();
 }
 
@@ -978,20 +1002,16 @@ int emp_dp_sweep(emp_ctx* ctx, const emp_dp_params* p, int32_t B, const double* 
                  double* rows, double* min_cost, int32_t* status, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     DpDev d;
-    int rc = make_dp_dev(ctx, p, B, 0, &d);
-    if (rc) return rc;
+    if (const int rc = make_dp_dev(ctx, p, B, 0, &d)) return rc;
     EMP_REQUIRE(ctx, start_cost && edge && rows && status, "start_cost, edge, rows and status are required");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    const double *d_c0, *d_e;
-    double *d_rows, *d_min;
-    int* d_st;
-    if ((rc = st.in(start_cost, (size_t)B * d.row, &d_c0))) return rc;
-    if ((rc = st.in(edge, tiled_elems(d), &d_e))) return rc;
-    if ((rc = st.out(rows, (size_t)B * d.col, &d_rows))) return rc;
-    if ((rc = st.out(min_cost, (size_t)B, &d_min))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
-    if ((rc = dev_dp_sweep(ctx, d, d_c0, d_e, nullptr, d_rows, d_min, d_st))) return rc;
+    EMP_STAGE(st, where);
+    const double* d_c0 = st.in(start_cost, (size_t)B * d.row);
+    const double* d_e = st.in(edge, tiled_elems(d));
+    double* d_rows = st.out(rows, (size_t)B * d.col);
+    double* d_min = st.out(min_cost, (size_t)B);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = dev_dp_sweep(ctx, d, d_c0, d_e, nullptr, d_rows, d_min, d_st, nullptr)) return rc;
     return st.finish();
 }
 
@@ -1000,29 +1020,20 @@ int emp_dp_plan(emp_ctx* ctx, const emp_dp_params* p, int32_t B, int32_t max_obs
                 double* min_cost, int32_t* status, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     DpDev d;
-    int rc = make_dp_dev(ctx, p, B, max_obs, &d);
-    if (rc) return rc;
+    if (const int rc = make_dp_dev(ctx, p, B, max_obs, &d)) return rc;
     EMP_REQUIRE(ctx, n_obs && start && rows && status, "n_obs, start, rows and status are required");
     EMP_REQUIRE(ctx, max_obs == 0 || (obs_s && obs_l), "obs_s / obs_l are required when max_obs > 0");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    const double *d_os, *d_ol, *d_start;
-    const int* d_n;
-    double *d_rows, *d_min;
-    int* d_st;
-    if ((rc = st.in(obs_s, (size_t)B * max_obs, &d_os))) return rc;
-    if ((rc = st.in(obs_l, (size_t)B * max_obs, &d_ol))) return rc;
-    if ((rc = st.in(n_obs, (size_t)B, &d_n))) return rc;
-    if ((rc = st.in(start, (size_t)B * 4, &d_start))) return rc;
-    if ((rc = st.out(rows, (size_t)B * d.col, &d_rows))) return rc;
-    if ((rc = st.out(min_cost, (size_t)B, &d_min))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
-    if (max_obs == 0) {
-        double* dummy;
-        if ((rc = st.tmp(1, &dummy))) return rc;
-        d_os = d_ol = dummy;
-    }
-    if ((rc = dev_dp_plan(ctx, d, d_os, d_ol, d_n, d_start, mode, d_rows, d_min, d_st))) return rc;
+    EMP_STAGE(st, where);
+    const double* d_os = st.in(obs_s, (size_t)B * max_obs);
+    const double* d_ol = st.in(obs_l, (size_t)B * max_obs);
+    const int* d_n = st.in(n_obs, (size_t)B);
+    const double* d_start = st.in(start, (size_t)B * 4);
+    double* d_rows = st.out(rows, (size_t)B * d.col);
+    double* d_min = st.out(min_cost, (size_t)B);
+    int* d_st = st.out(status, (size_t)B);
+    if (max_obs == 0) d_os = d_ol = st.tmp<double>(1);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = dev_dp_plan(ctx, d, d_os, d_ol, d_n, d_start, mode, d_rows, d_min, d_st, nullptr)) return rc;
     return st.finish();
 }
 
@@ -1031,22 +1042,18 @@ int emp_dp_enrich(emp_ctx* ctx, const emp_dp_params* p, int32_t B, const double*
                   emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     DpDev d;
-    int rc = make_dp_dev(ctx, p, B, 0, &d);
-    if (rc) return rc;
+    if (const int rc = make_dp_dev(ctx, p, B, 0, &d)) return rc;
     EMP_REQUIRE(ctx, rows && start && path_s && path_l && path_len && status, "NULL argument");
     EMP_REQUIRE(ctx, max_pts >= 1, "max_pts must be >= 1");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    const double *d_rows, *d_start;
-    double *d_ps, *d_pl;
-    int *d_len, *d_st;
-    if ((rc = st.in(rows, (size_t)B * d.col, &d_rows))) return rc;
-    if ((rc = st.in(start, (size_t)B * 4, &d_start))) return rc;
-    if ((rc = st.out(path_s, (size_t)B * max_pts, &d_ps))) return rc;
-    if ((rc = st.out(path_l, (size_t)B * max_pts, &d_pl))) return rc;
-    if ((rc = st.out(path_len, (size_t)B, &d_len))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
-    if ((rc = dev_dp_enrich(ctx, d, d_rows, d_start, max_pts, d_ps, d_pl, d_len, d_st, 0))) return rc;
+    EMP_STAGE(st, where);
+    const double* d_rows = st.in(rows, (size_t)B * d.col);
+    const double* d_start = st.in(start, (size_t)B * 4);
+    double* d_ps = st.out(path_s, (size_t)B * max_pts);
+    double* d_pl = st.out(path_l, (size_t)B * max_pts);
+    int* d_len = st.out(path_len, (size_t)B);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = dev_dp_enrich(ctx, d, d_rows, d_start, max_pts, d_ps, d_pl, d_len, d_st, 0, nullptr)) return rc;
     return st.finish();
 }
 
@@ -1088,12 +1095,9 @@ static int dev_project(emp_ctx* ctx, int B, int max_ref, int max_obs, const doub
     if (lds > 48 * 1024)
         EMP_HIP(ctx, hipFuncSetAttribute((const void*)frenet_project_wave_kernel,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    KernelTimer t(ctx, "project");
-    hipLaunchKernelGGL(frenet_project_wave_kernel, dim3(B), dim3(64), lds, ctx->stream, B, max_ref, max_obs, ref_line,
-                       n_ref, origin_xy, start_xy, start_v, start_a, obs_xy, n_obs, s_map, obs_s, obs_l, begin_sl, start,
-                       obs_cap < 0 ? max_obs : obs_cap, dyn, n_obs_out);
-    EMP_LAUNCH_CHECK(ctx);
-    return EMP_OK;
+    return launch(ctx, "project", frenet_project_wave_kernel, dim3(B), dim3(64), lds, B, max_ref, max_obs, ref_line, n_ref, origin_xy,
+                  start_xy, start_v, start_a, obs_xy, n_obs, s_map, obs_s, obs_l, begin_sl, start, obs_cap < 0 ? max_obs : obs_cap, dyn,
+                  n_obs_out);
 }
 
 template <typename K>
@@ -1104,10 +1108,22 @@ static int set_lds(emp_ctx* ctx, K kernel, size_t bytes) {
     return EMP_OK;
 }
 
+// smooth_reference_line, one wavefront per scene (emp_reference_line, and the front end of emp_plan_cycle)
+template <typename... A>
+static int dev_reference_line(emp_ctx* ctx, const emp_smooth_params* sp, int B, int max_global, A... args) {
+    if (B == 0) return EMP_OK;
+    const SmoothQpParams sx{sp->w_smooth, sp->w_length, sp->w_ref, sp->x_thre};
+    const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
+    const size_t lds = (2 * (size_t)kRefLinePoints + 2 * (size_t)BoxRangeQp::words(kRefLinePoints, kRefLinePoints) +
+                        (size_t)kRefLinePoints) * sizeof(double);
+    if (const int rc = set_lds(ctx, reference_line_wave_kernel, lds)) return rc;
+    return launch(ctx, "reference_line", reference_line_wave_kernel, dim3(B), dim3(64), lds, B, max_global, sx, sy, args...);
+}
+
 static int dev_cycle_qp(emp_ctx* ctx, int B, int max_pts, int max_obs, const QpDev& Q, const double* dp_s,
                         const double* dp_l, const int* dp_len, const double* obs_s, const double* obs_l,
                         const int* n_obs, const double* start, double* path_s, double* path_l, int* path_len,
-                        int* status) {
+                        int* status, CycleSched* cs) {
     if (B == 0) return EMP_OK;
     const int cap = (max_pts + Q.decimate - 1) / Q.decimate;          // most stations a scene can have
     const size_t per_group = ((size_t)5 * cap + 4 * (size_t)max_obs + path_qp_words(cap)) * sizeof(double);
@@ -1128,21 +1144,18 @@ static int dev_cycle_qp(emp_ctx* ctx, int B, int max_pts, int max_obs, const QpD
         auto kern = cap <= 26 ? cycle_qp_rows_kernel<8, 3> : cap <= 34 ? cycle_qp_rows_kernel<8, 4> : cycle_qp_rows_kernel<16, 4>;
         if ((rc = set_lds(ctx, kern, per_wave))) return rc;
         const int spw = 64 / gp;
-        launch_attaching(ctx, t.stop != nullptr, kern, dim3((B + spw - 1) / spw), dim3(64), per_wave, B, max_pts,
-                         max_obs, cap, Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
+        return launch_attaching(ctx, cs, t.stop != nullptr, kern, dim3((B + spw - 1) / spw), dim3(64), per_wave, B, max_pts,
+                                max_obs, cap, Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
     } else if (cap <= 34) {                                           // N, ns <= 32: two scenes per wavefront
         const size_t per_pair = 2 * ((size_t)5 * cap + 4 * (size_t)max_obs + path_qp_words_pair()) * sizeof(double);
         auto kern = cycle_qp_wave_kernel<32>;
         if ((rc = set_lds(ctx, kern, per_pair))) return rc;
-        launch_attaching(ctx, t.stop != nullptr, kern, dim3((B + 1) / 2), dim3(64), per_pair, B, max_pts,
-                         max_obs, cap, Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
-    } else {
-        if ((rc = set_lds(ctx, cycle_qp_wave_kernel<64>, per_group))) return rc;
-        launch_attaching(ctx, t.stop != nullptr, cycle_qp_wave_kernel<64>, dim3(B), dim3(64), per_group, B, max_pts, max_obs, cap, Q,
-                         dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
+        return launch_attaching(ctx, cs, t.stop != nullptr, kern, dim3((B + 1) / 2), dim3(64), per_pair, B, max_pts,
+                                max_obs, cap, Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
     }
-    EMP_LAUNCH_CHECK(ctx);
-    return EMP_OK;
+    if ((rc = set_lds(ctx, cycle_qp_wave_kernel<64>, per_group))) return rc;
+    return launch_attaching(ctx, cs, t.stop != nullptr, cycle_qp_wave_kernel<64>, dim3(B), dim3(64), per_group, B, max_pts, max_obs, cap,
+                            Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
 }
 
 static int dev_cycle_cartesian(emp_ctx* ctx, int B, int max_ref, int max_pts, int path_cap, const emp_smooth_params* sp,
@@ -1161,23 +1174,15 @@ static int dev_cycle_cartesian(emp_ctx* ctx, int B, int max_ref, int max_pts, in
         const int spw = cap <= 32 ? 4 : 2;
         const size_t lds4 = ((size_t)spw * ((size_t)max_ref + 5 * (size_t)cap) + 2 * (size_t)BoxRangeQp::words(cap, cap)) * sizeof(double);
         auto k4 = cap <= 24 ? cycle_cartesian_rows_kernel<8, 3> : cap <= 32 ? cycle_cartesian_rows_kernel<8, 4> : cycle_cartesian_rows_kernel<16, 4>;
-        int rc4 = set_lds(ctx, k4, lds4);
-        if (rc4) return rc4;
-        KernelTimer t4(ctx, "to_cartesian");
+        if (const int rc = set_lds(ctx, k4, lds4)) return rc;
         const int force_fb = ctx->opt[EMP_OPT_SMOOTH_FORCE_FALLBACK] ? 1 : 0;                        // test hook
-        hipLaunchKernelGGL(k4, dim3((B + spw - 1) / spw), dim3(64), lds4, ctx->stream, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map,
-                           n_ref, begin_sl, path_s, path_l, path_len, traj, traj_len, status, force_fb);
-        EMP_LAUNCH_CHECK(ctx);
-        return EMP_OK;
+        return launch(ctx, "to_cartesian", k4, dim3((B + spw - 1) / spw), dim3(64), lds4, B, max_ref, max_pts, cap, sx, sy, ref_line,
+                      s_map, n_ref, begin_sl, path_s, path_l, path_len, traj, traj_len, status, force_fb);
     }
     auto kern = cap > 32 ? cycle_cartesian_wave_kernel_wide : cycle_cartesian_wave_kernel_narrow;
-    int rc = set_lds(ctx, kern, lds);
-    if (rc) return rc;
-    KernelTimer t(ctx, "to_cartesian");
-    hipLaunchKernelGGL(kern, dim3(B), dim3(64), lds, ctx->stream, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref,
-                       begin_sl, path_s, path_l, path_len, traj, traj_len, status);
-    EMP_LAUNCH_CHECK(ctx);
-    return EMP_OK;
+    if (const int rc = set_lds(ctx, kern, lds)) return rc;
+    return launch(ctx, "to_cartesian", kern, dim3(B), dim3(64), lds, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref,
+                  begin_sl, path_s, path_l, path_len, traj, traj_len, status);
 }
 
 }  // namespace emp
@@ -1192,27 +1197,23 @@ int emp_frenet_project(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_obs
     EMP_REQUIRE(ctx, B >= 0 && max_ref >= 2 && max_obs >= 0, "bad sizes");
     EMP_REQUIRE(ctx, ref_line && n_ref && origin_xy && start_xy && start_v && start_a && s_map && start, "NULL argument");
     EMP_REQUIRE(ctx, max_obs == 0 || (obs_xy && n_obs && obs_s && obs_l), "obstacle arrays required when max_obs > 0");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ref, *d_o, *d_sxy, *d_v, *d_a, *d_oxy;
-    const int *d_nr, *d_no;
-    double *d_sm, *d_os, *d_ol, *d_bsl, *d_start;
-    if ((rc = st.in(ref_line, (size_t)B * max_ref * 4, &d_ref))) return rc;
-    if ((rc = st.in(n_ref, (size_t)B, &d_nr))) return rc;
-    if ((rc = st.in(origin_xy, (size_t)B * 2, &d_o))) return rc;
-    if ((rc = st.in(start_xy, (size_t)B * 2, &d_sxy))) return rc;
-    if ((rc = st.in(start_v, (size_t)B * 2, &d_v))) return rc;
-    if ((rc = st.in(start_a, (size_t)B * 2, &d_a))) return rc;
-    if ((rc = st.in(obs_xy, (size_t)B * max_obs * 2, &d_oxy))) return rc;
-    if ((rc = st.in(max_obs ? n_obs : nullptr, (size_t)B, &d_no))) return rc;
-    if ((rc = st.out(s_map, (size_t)B * max_ref, &d_sm))) return rc;
-    if ((rc = st.out(obs_s, (size_t)B * max_obs, &d_os))) return rc;
-    if ((rc = st.out(obs_l, (size_t)B * max_obs, &d_ol))) return rc;
-    if ((rc = st.out(begin_sl, (size_t)B * 2, &d_bsl))) return rc;
-    if ((rc = st.out(start, (size_t)B * 4, &d_start))) return rc;
-    if ((rc = dev_project(ctx, B, max_ref, max_obs, d_ref, d_nr, d_o, d_sxy, d_v, d_a, d_oxy, d_no, d_sm, d_os, d_ol,
-                          d_bsl, d_start)))
+    EMP_STAGE(st, where);
+    const double* d_ref = st.in(ref_line, (size_t)B * max_ref * 4);
+    const int* d_nr = st.in(n_ref, (size_t)B);
+    const double* d_o = st.in(origin_xy, (size_t)B * 2);
+    const double* d_sxy = st.in(start_xy, (size_t)B * 2);
+    const double* d_v = st.in(start_v, (size_t)B * 2);
+    const double* d_a = st.in(start_a, (size_t)B * 2);
+    const double* d_oxy = st.in(obs_xy, (size_t)B * max_obs * 2);
+    const int* d_no = st.in(max_obs ? n_obs : nullptr, (size_t)B);
+    double* d_sm = st.out(s_map, (size_t)B * max_ref);
+    double* d_os = st.out(obs_s, (size_t)B * max_obs);
+    double* d_ol = st.out(obs_l, (size_t)B * max_obs);
+    double* d_bsl = st.out(begin_sl, (size_t)B * 2);
+    double* d_start = st.out(start, (size_t)B * 4);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = dev_project(ctx, B, max_ref, max_obs, d_ref, d_nr, d_o, d_sxy, d_v, d_a, d_oxy, d_no, d_sm, d_os, d_ol, d_bsl,
+                                   d_start))
         return rc;
     return st.finish();
 }
@@ -1224,27 +1225,19 @@ static int match_common(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_pt
     EMP_REQUIRE(ctx, B >= 0 && max_ref >= 1 && max_pts >= 1, "bad sizes");
     EMP_REQUIRE(ctx, ref_line && n_ref && xy && n_pts && match_index && proj, "NULL argument");
     EMP_REQUIRE(ctx, !windowed || (is_first_run && pre_match_index), "is_first_run / pre_match_index required");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ref, *d_xy;
-    const int *d_nr, *d_np, *d_first, *d_pre;
-    int* d_mi;
-    double* d_pr;
-    if ((rc = st.in(ref_line, (size_t)B * max_ref * 4, &d_ref))) return rc;
-    if ((rc = st.in(n_ref, (size_t)B, &d_nr))) return rc;
-    if ((rc = st.in(xy, (size_t)B * max_pts * 2, &d_xy))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.in(is_first_run, (size_t)B, &d_first))) return rc;
-    if ((rc = st.in(pre_match_index, (size_t)B, &d_pre))) return rc;
-    if ((rc = st.out(match_index, (size_t)B * max_pts, &d_mi))) return rc;
-    if ((rc = st.out(proj, (size_t)B * max_pts * 4, &d_pr))) return rc;
-    if (B) {
-        KernelTimer t(ctx, "match");
-        hipLaunchKernelGGL(match_points_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_ref, max_pts, d_ref, d_nr,
-                           d_xy, d_np, d_first, d_pre, d_mi, d_pr, windowed);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_ref = st.in(ref_line, (size_t)B * max_ref * 4);
+    const int* d_nr = st.in(n_ref, (size_t)B);
+    const double* d_xy = st.in(xy, (size_t)B * max_pts * 2);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    const int* d_first = st.in(is_first_run, (size_t)B);
+    const int* d_pre = st.in(pre_match_index, (size_t)B);
+    int* d_mi = st.out(match_index, (size_t)B * max_pts);
+    double* d_pr = st.out(proj, (size_t)B * max_pts * 4);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "match", match_points_kernel, grid1(B, 64), dim3(64), 0, B, max_ref, max_pts, d_ref, d_nr, d_xy,
+                              d_np, d_first, d_pre, d_mi, d_pr, windowed))
+        return rc;
     return st.finish();
 }
 
@@ -1265,21 +1258,14 @@ int emp_heading_kappa(emp_ctx* ctx, int32_t B, int32_t max_pts, const double* xy
                       double* kappa, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_pts >= 2 && xy && n_pts && theta && kappa, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double* d_xy;
-    const int* d_np;
-    double *d_t, *d_k;
-    if ((rc = st.in(xy, (size_t)B * max_pts * 2, &d_xy))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.out(theta, (size_t)B * max_pts, &d_t))) return rc;
-    if ((rc = st.out(kappa, (size_t)B * max_pts, &d_k))) return rc;
-    if (B) {
-        KernelTimer t(ctx, "heading");
-        hipLaunchKernelGGL(heading_kappa_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_pts, d_xy, d_np, d_t, d_k);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_xy = st.in(xy, (size_t)B * max_pts * 2);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    double* d_t = st.out(theta, (size_t)B * max_pts);
+    double* d_k = st.out(kappa, (size_t)B * max_pts);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "heading", heading_kappa_kernel, grid1(B, 64), dim3(64), 0, B, max_pts, d_xy, d_np, d_t, d_k))
+        return rc;
     return st.finish();
 }
 
@@ -1289,28 +1275,20 @@ int emp_lmin_lmax(emp_ctx* ctx, int32_t B, int32_t max_pts, int32_t max_obs, con
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_pts >= 1 && max_obs >= 0, "bad sizes");
     EMP_REQUIRE(ctx, dp_s && dp_l && n_pts && n_obs && l_min && l_max && status, "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_s, *d_l, *d_os, *d_ol;
-    const int *d_np, *d_no;
-    double *d_lo, *d_hi;
-    int* d_st;
-    if ((rc = st.in(dp_s, (size_t)B * max_pts, &d_s))) return rc;
-    if ((rc = st.in(dp_l, (size_t)B * max_pts, &d_l))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.in(obs_s, (size_t)B * max_obs, &d_os))) return rc;
-    if ((rc = st.in(obs_l, (size_t)B * max_obs, &d_ol))) return rc;
-    if ((rc = st.in(n_obs, (size_t)B, &d_no))) return rc;
-    if ((rc = st.out(l_min, (size_t)B * max_pts, &d_lo))) return rc;
-    if ((rc = st.out(l_max, (size_t)B * max_pts, &d_hi))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
-    if (B) {
-        KernelTimer t(ctx, "lmin_lmax");
-        hipLaunchKernelGGL(lmin_lmax_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_pts, max_obs, d_s, d_l, d_np,
-                           d_os, d_ol, d_no, obs_length, obs_width, d_lo, d_hi, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_s = st.in(dp_s, (size_t)B * max_pts);
+    const double* d_l = st.in(dp_l, (size_t)B * max_pts);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    const double* d_os = st.in(obs_s, (size_t)B * max_obs);
+    const double* d_ol = st.in(obs_l, (size_t)B * max_obs);
+    const int* d_no = st.in(n_obs, (size_t)B);
+    double* d_lo = st.out(l_min, (size_t)B * max_pts);
+    double* d_hi = st.out(l_max, (size_t)B * max_pts);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "lmin_lmax", lmin_lmax_kernel, grid1(B, 64), dim3(64), 0, B, max_pts, max_obs, d_s, d_l, d_np,
+                              d_os, d_ol, d_no, obs_length, obs_width, d_lo, d_hi, d_st))
+        return rc;
     return st.finish();
 }
 
@@ -1322,30 +1300,23 @@ int emp_path_qp(emp_ctx* ctx, const emp_qp_params* q, int32_t B, int32_t max_pts
     EMP_REQUIRE(ctx, qp_reserved_ok(q), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
     EMP_REQUIRE(ctx, l_min && l_max && n_pts && start_l3 && qp_l && qp_dl && qp_ddl && status, "NULL argument");
     EMP_REQUIRE(ctx, q->ds > 0, "ds must be > 0");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_lo, *d_hi, *d_s3;
-    const int* d_np;
-    double *d_l, *d_dl, *d_ddl;
-    int *d_it, *d_st;
-    if ((rc = st.in(l_min, (size_t)B * max_pts, &d_lo))) return rc;
-    if ((rc = st.in(l_max, (size_t)B * max_pts, &d_hi))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.in(start_l3, (size_t)B * 3, &d_s3))) return rc;
-    if ((rc = st.out(qp_l, (size_t)B * max_pts, &d_l))) return rc;
-    if ((rc = st.out(qp_dl, (size_t)B * max_pts, &d_dl))) return rc;
-    if ((rc = st.out(qp_ddl, (size_t)B * max_pts, &d_ddl))) return rc;
-    if ((rc = st.out(iters, (size_t)B, &d_it))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
+    EMP_STAGE(st, where);
+    const double* d_lo = st.in(l_min, (size_t)B * max_pts);
+    const double* d_hi = st.in(l_max, (size_t)B * max_pts);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    const double* d_s3 = st.in(start_l3, (size_t)B * 3);
+    double* d_l = st.out(qp_l, (size_t)B * max_pts);
+    double* d_dl = st.out(qp_dl, (size_t)B * max_pts);
+    double* d_ddl = st.out(qp_ddl, (size_t)B * max_pts);
+    int* d_it = st.out(iters, (size_t)B);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
     if (B) {
-        const QpDev Q = make_qp_dev(q);
         const size_t lds = (size_t)path_qp_words(max_pts) * sizeof(double);
-        if ((rc = set_lds(ctx, path_qp_wave_kernel, lds))) return rc;
-        KernelTimer t(ctx, "path_qp");
-        hipLaunchKernelGGL(path_qp_wave_kernel, dim3(B), dim3(64), lds, ctx->stream, B, max_pts, max_pts, Q, d_lo, d_hi,
-                           d_np, d_s3, d_l, d_dl, d_ddl, d_it, d_st);
-        EMP_LAUNCH_CHECK(ctx);
+        if (const int rc = set_lds(ctx, path_qp_wave_kernel, lds)) return rc;
+        if (const int rc = launch(ctx, "path_qp", path_qp_wave_kernel, dim3(B), dim3(64), lds, B, max_pts, max_pts, make_qp_dev(q),
+                                  d_lo, d_hi, d_np, d_s3, d_l, d_dl, d_ddl, d_it, d_st))
+            return rc;
     }
     return st.finish();
 }
@@ -1355,28 +1326,21 @@ int emp_smooth_line(emp_ctx* ctx, const emp_smooth_params* sp, int32_t B, int32_
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, sp && B >= 0 && max_pts >= 2 && max_pts <= 256, "bad sizes (max_pts must be in [2, 256])");
     EMP_REQUIRE(ctx, xy && n_pts && out && status, "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double* d_xy;
-    const int* d_np;
-    double* d_out;
-    int *d_it, *d_st;
-    if ((rc = st.in(xy, (size_t)B * max_pts * 2, &d_xy))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.out(out, (size_t)B * max_pts * 4, &d_out))) return rc;
-    if ((rc = st.out(iters, (size_t)B, &d_it))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
+    EMP_STAGE(st, where);
+    const double* d_xy = st.in(xy, (size_t)B * max_pts * 2);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    double* d_out = st.out(out, (size_t)B * max_pts * 4);
+    int* d_it = st.out(iters, (size_t)B);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
     if (B) {
         const SmoothQpParams sx{sp->w_smooth, sp->w_length, sp->w_ref, sp->x_thre};
         const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
         const size_t lds = (2 * (size_t)BoxRangeQp::words(max_pts, max_pts) + (size_t)max_pts) * sizeof(double);
         auto kern = max_pts > 32 ? smooth_wave_kernel<true> : smooth_wave_kernel<false>;
-        if ((rc = set_lds(ctx, kern, lds))) return rc;
-        KernelTimer t(ctx, "smooth");
-        hipLaunchKernelGGL(kern, dim3(B), dim3(64), lds, ctx->stream, B, max_pts, max_pts, sx, sy, d_xy, d_np,
-                           d_out, d_it, d_st);
-        EMP_LAUNCH_CHECK(ctx);
+        if (const int rc = set_lds(ctx, kern, lds)) return rc;
+        if (const int rc = launch(ctx, "smooth", kern, dim3(B), dim3(64), lds, B, max_pts, max_pts, sx, sy, d_xy, d_np, d_out, d_it, d_st))
+            return rc;
     }
     return st.finish();
 }
@@ -1389,34 +1353,20 @@ int emp_reference_line(emp_ctx* ctx, const emp_smooth_params* sp, int32_t B, int
     EMP_REQUIRE(ctx, sp && B >= 0 && max_global >= 1, "bad sizes");
     EMP_REQUIRE(ctx, global_path && n_global && pred_xy && pre_match_index && ref_line && n_ref && match_index && status,
                 "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_g, *d_xy;
-    const int *d_ng, *d_first = nullptr, *d_pre;
-    double* d_ref;
-    int *d_nr, *d_m, *d_it = nullptr, *d_st;
-    if ((rc = st.in(global_path, (size_t)B * max_global * 4, &d_g))) return rc;
-    if ((rc = st.in(n_global, (size_t)B, &d_ng))) return rc;
-    if ((rc = st.in(pred_xy, (size_t)B * 2, &d_xy))) return rc;
-    if (is_first_run && (rc = st.in(is_first_run, (size_t)B, &d_first))) return rc;
-    if ((rc = st.in(pre_match_index, (size_t)B, &d_pre))) return rc;
-    if ((rc = st.out(ref_line, (size_t)B * kRefLinePoints * 4, &d_ref, false))) return rc;
-    if ((rc = st.out(n_ref, (size_t)B, &d_nr, false))) return rc;
-    if ((rc = st.out(match_index, (size_t)B, &d_m, false))) return rc;
-    if (iters && (rc = st.out(iters, (size_t)B, &d_it, false))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st, false))) return rc;
-    if (B) {
-        const SmoothQpParams sx{sp->w_smooth, sp->w_length, sp->w_ref, sp->x_thre};
-        const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
-        const size_t lds = (2 * (size_t)kRefLinePoints + 2 * (size_t)BoxRangeQp::words(kRefLinePoints, kRefLinePoints) +
-                            (size_t)kRefLinePoints) * sizeof(double);
-        if ((rc = set_lds(ctx, reference_line_wave_kernel, lds))) return rc;
-        KernelTimer t(ctx, "reference_line");
-        hipLaunchKernelGGL(reference_line_wave_kernel, dim3(B), dim3(64), lds, ctx->stream, B, max_global, sx, sy, d_g, d_ng,
-                           d_xy, d_first, d_pre, d_ref, d_nr, d_m, d_it, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_g = st.in(global_path, (size_t)B * max_global * 4);
+    const int* d_ng = st.in(n_global, (size_t)B);
+    const double* d_xy = st.in(pred_xy, (size_t)B * 2);
+    const int* d_first = st.in(is_first_run, (size_t)B);
+    const int* d_pre = st.in(pre_match_index, (size_t)B);
+    double* d_ref = st.out(ref_line, (size_t)B * kRefLinePoints * 4, false);
+    int* d_nr = st.out(n_ref, (size_t)B, false);
+    int* d_m = st.out(match_index, (size_t)B, false);
+    int* d_it = st.out(iters, (size_t)B, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = dev_reference_line(ctx, sp, B, max_global, d_g, d_ng, d_xy, d_first, d_pre, d_ref, d_nr, d_m, d_it, d_st, 0))
+        return rc;
     return st.finish();
 }
 
@@ -1428,29 +1378,21 @@ int emp_frenet_path_to_xy(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_
     EMP_REQUIRE(ctx, B >= 0 && max_ref >= 2 && max_pts >= 1, "bad sizes");
     EMP_REQUIRE(ctx, ref_line && s_map && n_ref && begin_sl && path_s && path_l && n_pts && target_xy && n_out && status,
                 "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ref, *d_sm, *d_b, *d_ps, *d_pl;
-    const int *d_nr, *d_np;
-    double* d_t;
-    int *d_no, *d_st;
-    if ((rc = st.in(ref_line, (size_t)B * max_ref * 4, &d_ref))) return rc;
-    if ((rc = st.in(s_map, (size_t)B * max_ref, &d_sm))) return rc;
-    if ((rc = st.in(n_ref, (size_t)B, &d_nr))) return rc;
-    if ((rc = st.in(begin_sl, (size_t)B * 2, &d_b))) return rc;
-    if ((rc = st.in(path_s, (size_t)B * max_pts, &d_ps))) return rc;
-    if ((rc = st.in(path_l, (size_t)B * max_pts, &d_pl))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.out(target_xy, (size_t)B * (max_pts + 1) * 2, &d_t))) return rc;
-    if ((rc = st.out(n_out, (size_t)B, &d_no))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
-    if (B) {
-        KernelTimer t(ctx, "path_to_xy");
-        hipLaunchKernelGGL(path_to_xy_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_ref, max_pts, d_ref, d_sm,
-                           d_nr, d_b, d_ps, d_pl, d_np, d_t, d_no, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_ref = st.in(ref_line, (size_t)B * max_ref * 4);
+    const double* d_sm = st.in(s_map, (size_t)B * max_ref);
+    const int* d_nr = st.in(n_ref, (size_t)B);
+    const double* d_b = st.in(begin_sl, (size_t)B * 2);
+    const double* d_ps = st.in(path_s, (size_t)B * max_pts);
+    const double* d_pl = st.in(path_l, (size_t)B * max_pts);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    double* d_t = st.out(target_xy, (size_t)B * (max_pts + 1) * 2);
+    int* d_no = st.out(n_out, (size_t)B);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "path_to_xy", path_to_xy_kernel, grid1(B, 64), dim3(64), 0, B, max_ref, max_pts, d_ref, d_sm,
+                              d_nr, d_b, d_ps, d_pl, d_np, d_t, d_no, d_st))
+        return rc;
     return st.finish();
 }
 
@@ -1597,85 +1539,69 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
         ctx->cycle_graph = nullptr;
         ctx->cycle_seen = 0;
     }
+    // (the slot form of in() / out(): with EMP_HOST_PINNED the device pointers are known only at inputs_ready() / outputs_ready())
     Stage st(ctx, where, piped, pinned);
-    const double *d_ref = nullptr, *d_o, *d_sxy, *d_v, *d_a, *d_oxy, *d_glob = nullptr;
+    const double *d_ref = nullptr, *d_o, *d_sxy, *d_v, *d_a, *d_oxy, *d_dyn, *d_glob = nullptr;
     const int *d_nr = nullptr, *d_no, *d_nglob = nullptr, *d_prem = nullptr;
     if (front) {
-        if ((rc = st.in(io->global_path, (size_t)B * io->max_global * 4, &d_glob))) return rc;
-        if ((rc = st.in(io->n_global, (size_t)B, &d_nglob))) return rc;
-        if ((rc = st.in(io->pre_match_index, (size_t)B, &d_prem))) return rc;
+        st.in(io->global_path, (size_t)B * io->max_global * 4, &d_glob);
+        st.in(io->n_global, (size_t)B, &d_nglob);
+        st.in(io->pre_match_index, (size_t)B, &d_prem);
     } else {
-        if ((rc = st.in(io->ref_line, (size_t)B * max_ref * 4, &d_ref))) return rc;
-        if ((rc = st.in(io->n_ref, (size_t)B, &d_nr))) return rc;
+        st.in(io->ref_line, (size_t)B * max_ref * 4, &d_ref);
+        st.in(io->n_ref, (size_t)B, &d_nr);
     }
-    if ((rc = st.in(io->origin_xy, (size_t)B * 2, &d_o))) return rc;
-    if ((rc = st.in(io->start_xy, (size_t)B * 2, &d_sxy))) return rc;
-    if ((rc = st.in(io->start_v, (size_t)B * 2, &d_v))) return rc;
-    if ((rc = st.in(io->start_a, (size_t)B * 2, &d_a))) return rc;
-    if ((rc = st.in(io->obs_xy, (size_t)B * max_obs * 2, &d_oxy))) return rc;
-    if ((rc = st.in(io->n_obs, (size_t)B, &d_no))) return rc;
-    const double* d_dyn = nullptr;
-    if (has_dyn && (rc = st.in(io->dyn_dis_speed, (size_t)B * 2, &d_dyn))) return rc;
-    if ((rc = st.inputs_ready())) return rc;
+    st.in(io->origin_xy, (size_t)B * 2, &d_o);
+    st.in(io->start_xy, (size_t)B * 2, &d_sxy);
+    st.in(io->start_v, (size_t)B * 2, &d_v);
+    st.in(io->start_a, (size_t)B * 2, &d_a);
+    st.in(io->obs_xy, (size_t)B * max_obs * 2, &d_oxy);
+    st.in(io->n_obs, (size_t)B, &d_no);
+    st.in(io->dyn_dis_speed, (size_t)B * 2, &d_dyn);
+    st.inputs_ready();
     // outputs (optional ones fall back to device temporaries); no memsets: every kernel of the cycle writes its
     // rows completely, padding included
     double *d_rows, *d_dps, *d_dpl, *d_ps, *d_pl, *d_traj;
-    int *d_dplen, *d_plen, *d_tlen, *d_st;
-    if ((rc = st.out(io->dp_rows, (size_t)B * d.col, &d_rows, false))) return rc;
-    if (!d_rows && (rc = st.tmp((size_t)B * d.col, &d_rows, false))) return rc;
-    if ((rc = st.out(io->dp_s, (size_t)B * max_pts, &d_dps, false))) return rc;
-    if (!d_dps && (rc = st.tmp((size_t)B * max_pts, &d_dps, false))) return rc;
-    if ((rc = st.out(io->dp_l, (size_t)B * max_pts, &d_dpl, false))) return rc;
-    if (!d_dpl && (rc = st.tmp((size_t)B * max_pts, &d_dpl, false))) return rc;
-    if ((rc = st.out(io->dp_len, (size_t)B, &d_dplen, false))) return rc;
-    if (!d_dplen && (rc = st.tmp((size_t)B, &d_dplen, false))) return rc;
-    if ((rc = st.out(io->path_s, (size_t)B * max_pts, &d_ps, false))) return rc;
-    if (!d_ps && (rc = st.tmp((size_t)B * max_pts, &d_ps, false))) return rc;
-    if ((rc = st.out(io->path_l, (size_t)B * max_pts, &d_pl, false))) return rc;
-    if (!d_pl && (rc = st.tmp((size_t)B * max_pts, &d_pl, false))) return rc;
-    if ((rc = st.out(io->path_len, (size_t)B, &d_plen, false))) return rc;
-    if (!d_plen && (rc = st.tmp((size_t)B, &d_plen, false))) return rc;
-    if ((rc = st.out(io->traj, (size_t)B * (max_pts + 1) * 4, &d_traj, false))) return rc;
-    if ((rc = st.out(io->traj_len, (size_t)B, &d_tlen, false))) return rc;
-    if ((rc = st.out(io->status, (size_t)B, &d_st, false))) return rc;
-    int *d_match = nullptr, *d_rst = nullptr;
+    int *d_dplen, *d_plen, *d_tlen, *d_st, *d_match = nullptr, *d_rst = nullptr;
+    st.out(io->dp_rows, (size_t)B * d.col, &d_rows, false);
+    if (!d_rows) d_rows = st.tmp<double>((size_t)B * d.col);
+    st.out(io->dp_s, (size_t)B * max_pts, &d_dps, false);
+    if (!d_dps) d_dps = st.tmp<double>((size_t)B * max_pts);
+    st.out(io->dp_l, (size_t)B * max_pts, &d_dpl, false);
+    if (!d_dpl) d_dpl = st.tmp<double>((size_t)B * max_pts);
+    st.out(io->dp_len, (size_t)B, &d_dplen, false);
+    if (!d_dplen) d_dplen = st.tmp<int>((size_t)B);
+    st.out(io->path_s, (size_t)B * max_pts, &d_ps, false);
+    if (!d_ps) d_ps = st.tmp<double>((size_t)B * max_pts);
+    st.out(io->path_l, (size_t)B * max_pts, &d_pl, false);
+    if (!d_pl) d_pl = st.tmp<double>((size_t)B * max_pts);
+    st.out(io->path_len, (size_t)B, &d_plen, false);
+    if (!d_plen) d_plen = st.tmp<int>((size_t)B);
+    st.out(io->traj, (size_t)B * (max_pts + 1) * 4, &d_traj, false);
+    st.out(io->traj_len, (size_t)B, &d_tlen, false);
+    st.out(io->status, (size_t)B, &d_st, false);
     if (front) {
-        if ((rc = st.out(io->match_index, (size_t)B, &d_match, false))) return rc;
-        if ((rc = st.out(io->ref_status, (size_t)B, &d_rst, false))) return rc;
+        st.out(io->match_index, (size_t)B, &d_match, false);
+        st.out(io->ref_status, (size_t)B, &d_rst, false);
     }
-    if ((rc = st.outputs_ready())) return rc;
+    st.outputs_ready();
     // intermediates
-    double *d_sm, *d_os, *d_ol, *d_bsl, *d_start;
     const int mo = obs_cap > 0 ? obs_cap : 1;
-    if ((rc = st.tmp((size_t)B * max_ref, &d_sm))) return rc;
-    if ((rc = st.tmp((size_t)B * mo, &d_os))) return rc;
-    if ((rc = st.tmp((size_t)B * mo, &d_ol))) return rc;
-    if ((rc = st.tmp((size_t)B * 2, &d_bsl))) return rc;
-    if ((rc = st.tmp((size_t)B * 4, &d_start))) return rc;
-    int* d_zero_nobs = nullptr;
-    if (max_obs == 0) {
-        if ((rc = st.tmp((size_t)B, &d_zero_nobs, true))) return rc;
-        d_no = d_zero_nobs;
-    }
-    int* d_ntot = nullptr;
-    if (has_dyn && (rc = st.tmp((size_t)B, &d_ntot, false))) return rc;
-    double* d_ref_w = nullptr;
-    int* d_nr_w = nullptr;
-    if (front) {
-        if ((rc = st.tmp((size_t)B * kRefLinePoints * 4, &d_ref_w))) return rc;
-        if ((rc = st.tmp((size_t)B, &d_nr_w))) return rc;
-    }
+    double* d_sm = st.tmp<double>((size_t)B * max_ref);
+    double* d_os = st.tmp<double>((size_t)B * mo);
+    double* d_ol = st.tmp<double>((size_t)B * mo);
+    double* d_bsl = st.tmp<double>((size_t)B * 2);
+    double* d_start = st.tmp<double>((size_t)B * 4);
+    if (max_obs == 0) d_no = st.tmp<int>((size_t)B, true);
+    int* d_ntot = has_dyn ? st.tmp<int>((size_t)B) : nullptr;
+    double* d_ref_w = front ? st.tmp<double>((size_t)B * kRefLinePoints * 4) : nullptr;
+    int* d_nr_w = front ? st.tmp<int>((size_t)B) : nullptr;
+    if ((rc = st.ready())) return rc;
     if (B == 0) return st.finish();
     if (front) {          // ref test_9.py:99-110, one wavefront per scene; the predicted location is the planning start
-        const SmoothQpParams sx{sp->w_smooth, sp->w_length, sp->w_ref, sp->x_thre};
-        const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
-        const size_t lds = (2 * (size_t)kRefLinePoints + 2 * (size_t)BoxRangeQp::words(kRefLinePoints, kRefLinePoints) +
-                            (size_t)kRefLinePoints) * sizeof(double);
-        if ((rc = set_lds(ctx, reference_line_wave_kernel, lds))) return rc;
-        KernelTimer t(ctx, "reference_line");
-        hipLaunchKernelGGL(reference_line_wave_kernel, dim3(B), dim3(64), lds, ctx->stream, B, (int)io->max_global, sx, sy, d_glob,
-                           d_nglob, d_sxy, (const int*)nullptr, d_prem, d_ref_w, d_nr_w, d_match, (int*)nullptr, d_rst, 2);
-        EMP_LAUNCH_CHECK(ctx);
+        if ((rc = dev_reference_line(ctx, sp, B, (int)io->max_global, d_glob, d_nglob, d_sxy, (const int*)nullptr, d_prem, d_ref_w,
+                                     d_nr_w, d_match, (int*)nullptr, d_rst, 2)))
+            return rc;
         d_ref = d_ref_w;
         d_nr = d_nr_w;
     }
@@ -1683,41 +1609,27 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
                           d_bsl, d_start, mo, d_dyn, d_ntot)))
         return rc;
     if (has_dyn) d_no = d_ntot;                            // downstream stages see the projected + virtual obstacles
+    CycleSched cs;
     // the sweep may leave the backtrack to the densification kernel (emp_dp_kernels.h, BT == false): two temporaries for it
-    unsigned char* d_pre = nullptr;
-    int* d_term = nullptr;
     if (mode == EMP_DP_TWO_KERNEL && !wide(d)) {
-        if ((rc = st.tmp((size_t)d.tiles * d.col * 64, &d_pre, false))) return rc;
-        if ((rc = st.tmp((size_t)B, &d_term, false))) return rc;
+        cs.bt_pre = st.tmp<unsigned char>((size_t)d.tiles * d.col * 64);
+        cs.bt_term = st.tmp<int>((size_t)B);
+        if ((rc = st.ready())) return rc;        // (staged behind the projection launch: checked here)
     }
-    ctx->front_stop = staged ? lane.ln->ev_front : nullptr;
-    ctx->front_attached = nullptr;
-    ctx->sweep_wait = nullptr;
+    if (staged) cs.front_stop = lane.ln->ev_front;
     if (staged && ctx->opt[EMP_OPT_SWEEP_EXCLUSIVE]) {       // the previous call's back stage: its lane is the one before ours
         emp_ctx::Lane& prev = ctx->lanes[(ctx->lane + ctx->lanes_in_use() - 1) % ctx->lanes_in_use()];
         if (ctx->opt[EMP_OPT_SWEEP_EXCLUSIVE] == 2) {        // ... only its densification and path QP: the sweep runs beside the Cartesian tail
-            if (prev.qp_valid) ctx->sweep_wait = prev.ev_qp;
+            if (prev.qp_valid) cs.sweep_wait = prev.ev_qp;
         } else if (prev.done_valid) {
-            ctx->sweep_wait = prev.ev_done;
+            cs.sweep_wait = prev.ev_done;
         }
     }
-    ctx->edge_wait = nullptr;
     if (staged && ctx->opt[EMP_OPT_EDGE_AFTER_ENRICH] && mode == EMP_DP_TWO_KERNEL && !wide(d)) {
         emp_ctx::Lane& prev = ctx->lanes[(ctx->lane + ctx->lanes_in_use() - 1) % ctx->lanes_in_use()];
-        if (prev.enrich_valid) ctx->edge_wait = prev.ev_enrich;
+        if (prev.enrich_valid) cs.edge_wait = prev.ev_enrich;
     }
-    ctx->bt_pre = d_pre;
-    ctx->bt_term = d_term;
-    ctx->bt_deferred = false;
-    rc = dev_dp_plan(ctx, d, d_os, d_ol, d_no, d_start, mode, d_rows, nullptr, d_st);
-    ctx->front_stop = nullptr;
-    ctx->sweep_wait = nullptr;
-    ctx->edge_wait = nullptr;
-    ctx->bt_pre = nullptr;
-    ctx->bt_term = nullptr;
-    const bool deferred = ctx->bt_deferred;
-    ctx->bt_deferred = false;
-    if (rc) return rc;
+    if ((rc = dev_dp_plan(ctx, d, d_os, d_ol, d_no, d_start, mode, d_rows, nullptr, d_st, &cs))) return rc;
     const QpDev Q = make_qp_dev(q);
     // EMP_OPT_SWEEP_EXCLUSIVE: a marker behind the sweep on the front stream.  Measured, not understood: which of two
     // regimes the two queues settle in depends on it.  With it the kernels keep the durations of the overlapped step (edge
@@ -1731,7 +1643,7 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
     if (staged) {      // the back stage (short kernels that last as long as their slowest scene) goes to the back stream
         // behind the sweep's own completion event where the launch attached one (a marker packet behind the sweep costs the
         // front queue ~5 us per step), else behind an event recorded here
-        hipEvent_t front_done = ctx->front_attached;
+        hipEvent_t front_done = cs.front_attached;
         if (!front_done) {
             EMP_HIP(ctx, hipEventRecord(lane.ln->ev_front, ctx->stream));
             front_done = lane.ln->ev_front;
@@ -1743,27 +1655,22 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
     // themselves where possible: a marker packet behind each idled the back queue ~6 us, and with the edge kernel's round-4 diet
     // the back queue is what bounds the step.
     const bool want_enrich_ev = staged && ctx->opt[EMP_OPT_EDGE_AFTER_ENRICH] != 0;
-    ctx->attach_stop = want_enrich_ev ? lane.ln->ev_enrich : nullptr;
-    ctx->stop_attached = false;
-    if ((rc = dev_dp_enrich(ctx, d, d_rows, d_start, max_pts, d_dps, d_dpl, d_dplen, d_st, 1, deferred ? d_pre : nullptr,
-                            deferred ? d_term : nullptr, d_no, d_rows))) {
-        ctx->attach_stop = nullptr;
+    cs.attach_stop = want_enrich_ev ? lane.ln->ev_enrich : nullptr;
+    if ((rc = dev_dp_enrich(ctx, d, d_rows, d_start, max_pts, d_dps, d_dpl, d_dplen, d_st, 1, &cs, cs.bt_deferred ? cs.bt_pre : nullptr,
+                            cs.bt_deferred ? cs.bt_term : nullptr, d_no, d_rows)))
         return rc;
-    }
-    ctx->attach_stop = nullptr;
     if (want_enrich_ev) {
-        if (!ctx->stop_attached) EMP_HIP(ctx, hipEventRecord(lane.ln->ev_enrich, ctx->stream));
+        if (!cs.stop_attached) EMP_HIP(ctx, hipEventRecord(lane.ln->ev_enrich, ctx->stream));
         lane.ln->enrich_valid = true;
     } else if (staged) {
         lane.ln->enrich_valid = false;
     }
-    ctx->attach_stop = staged ? lane.ln->ev_qp : nullptr;
-    ctx->stop_attached = false;
-    rc = dev_cycle_qp(ctx, B, max_pts, mo, Q, d_dps, d_dpl, d_dplen, d_os, d_ol, d_no, d_start, d_ps, d_pl, d_plen, d_st);
-    ctx->attach_stop = nullptr;
-    if (rc) return rc;
+    cs.attach_stop = staged ? lane.ln->ev_qp : nullptr;
+    cs.stop_attached = false;
+    if ((rc = dev_cycle_qp(ctx, B, max_pts, mo, Q, d_dps, d_dpl, d_dplen, d_os, d_ol, d_no, d_start, d_ps, d_pl, d_plen, d_st, &cs)))
+        return rc;
     if (staged) {
-        if (!ctx->stop_attached) EMP_HIP(ctx, hipEventRecord(lane.ln->ev_qp, ctx->stream));
+        if (!cs.stop_attached) EMP_HIP(ctx, hipEventRecord(lane.ln->ev_qp, ctx->stream));
         lane.ln->qp_valid = true;
     }
     const int path_cap = (max_pts + Q.decimate - 1) / Q.decimate + (Q.midpoint ? 1 : 0);
@@ -1860,17 +1767,11 @@ int emp_host_free(emp_ctx* ctx, void* ptr) {
 int emp_quintic_coefficients(emp_ctx* ctx, int32_t n, const double* bc, double* coeff, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, n >= 0 && bc && coeff, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double* d_bc;
-    double* d_c;
-    if ((rc = st.in(bc, (size_t)n * 8, &d_bc))) return rc;
-    if ((rc = st.out(coeff, (size_t)n * 6, &d_c))) return rc;
-    if (n) {
-        hipLaunchKernelGGL(quintic_kernel, grid1(n, 64), dim3(64), 0, ctx->stream, n, d_bc, d_c);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_bc = st.in(bc, (size_t)n * 8);
+    double* d_c = st.out(coeff, (size_t)n * 6);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, quintic_kernel, grid1(n, 64), dim3(64), 0, n, d_bc, d_c)) return rc;
     return st.finish();
 }
 
@@ -1878,18 +1779,13 @@ int emp_obs_cost_n(emp_ctx* ctx, int32_t n, int32_t samples, double w_collision,
                    const double* square_d, double* cost, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, n >= 0 && samples >= 0 && cost && (square_d || (size_t)n * samples == 0), "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double* d_sq;
-    double* d_c;
-    if ((rc = st.in(square_d, (size_t)n * samples, &d_sq))) return rc;
-    if ((rc = st.out(cost, (size_t)n, &d_c))) return rc;
-    if (n) {
-        hipLaunchKernelGGL(obs_cost_kernel, grid1(n, 64), dim3(64), 0, ctx->stream, n, samples, w_collision, danger_dis, safe_dis,
-                           d_sq, d_c);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_sq = st.in(square_d, (size_t)n * samples);
+    double* d_c = st.out(cost, (size_t)n);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, obs_cost_kernel, grid1(n, 64), dim3(64), 0, n, samples, w_collision, danger_dis,
+                              safe_dis, d_sq, d_c))
+        return rc;
     return st.finish();
 }
 
@@ -1903,23 +1799,17 @@ int emp_free_edge_costs(emp_ctx* ctx, int32_t n, int32_t max_obs, const double* 
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, n >= 0 && max_obs >= 0 && edges && w_smooth3 && cost, "bad argument");
     EMP_REQUIRE(ctx, max_obs == 0 || (obs_s && obs_l && n_obs), "obs_s / obs_l / n_obs are required when max_obs > 0");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
     const double w0 = w_smooth3[0], w1 = w_smooth3[1], w2 = w_smooth3[2];      // host memory, like the parameter structs
-    Stage st(ctx, where);
-    int rc;
-    const double *d_e, *d_os, *d_ol;
-    const int* d_n;
-    double* d_c;
-    if ((rc = st.in(edges, (size_t)n * 8, &d_e))) return rc;
-    if ((rc = st.in(obs_s, (size_t)n * max_obs, &d_os))) return rc;
-    if ((rc = st.in(obs_l, (size_t)n * max_obs, &d_ol))) return rc;
-    if ((rc = st.in(n_obs, (size_t)n, &d_n))) return rc;
-    if ((rc = st.out(cost, (size_t)n, &d_c))) return rc;
-    if (n) {
-        hipLaunchKernelGGL(free_edge_cost_kernel, grid1(n, 64), dim3(64), 0, ctx->stream, n, max_obs, d_e, d_os, d_ol, d_n, w_collision,
-                           w0, w1, w2, w_ref, d_c);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_e = st.in(edges, (size_t)n * 8);
+    const double* d_os = st.in(obs_s, (size_t)n * max_obs);
+    const double* d_ol = st.in(obs_l, (size_t)n * max_obs);
+    const int* d_n = st.in(n_obs, (size_t)n);
+    double* d_c = st.out(cost, (size_t)n);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, free_edge_cost_kernel, grid1(n, 64), dim3(64), 0, n, max_obs, d_e, d_os, d_ol, d_n,
+                              w_collision, w0, w1, w2, w_ref, d_c))
+        return rc;
     return st.finish();
 }
 
@@ -1932,20 +1822,13 @@ int emp_s_map(emp_ctx* ctx, int32_t B, int32_t max_ref, const double* ref_line, 
               const double* origin_xy, double* s_map, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_ref >= 1 && ref_line && n_ref && origin_xy && s_map, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ref, *d_o;
-    const int* d_nr;
-    double* d_sm;
-    if ((rc = st.in(ref_line, (size_t)B * max_ref * 4, &d_ref))) return rc;
-    if ((rc = st.in(n_ref, (size_t)B, &d_nr))) return rc;
-    if ((rc = st.in(origin_xy, (size_t)B * 2, &d_o))) return rc;
-    if ((rc = st.out(s_map, (size_t)B * max_ref, &d_sm))) return rc;
-    if (B) {
-        hipLaunchKernelGGL(s_map_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_ref, d_ref, d_nr, d_o, d_sm);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_ref = st.in(ref_line, (size_t)B * max_ref * 4);
+    const int* d_nr = st.in(n_ref, (size_t)B);
+    const double* d_o = st.in(origin_xy, (size_t)B * 2);
+    double* d_sm = st.out(s_map, (size_t)B * max_ref);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, s_map_kernel, grid1(B, 64), dim3(64), 0, B, max_ref, d_ref, d_nr, d_o, d_sm)) return rc;
     return st.finish();
 }
 
@@ -1955,25 +1838,19 @@ int emp_s_l(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_pts, const dou
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_ref >= 1 && max_pts >= 1 && ref_line && s_map && n_ref && xy && n_pts && s,
                 "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ref, *d_sm, *d_xy;
-    const int *d_nr, *d_np, *d_mi;
-    double *d_s, *d_l;
-    if ((rc = st.in(ref_line, (size_t)B * max_ref * 4, &d_ref))) return rc;
-    if ((rc = st.in(s_map, (size_t)B * max_ref, &d_sm))) return rc;
-    if ((rc = st.in(n_ref, (size_t)B, &d_nr))) return rc;
-    if ((rc = st.in(xy, (size_t)B * max_pts * 2, &d_xy))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.in(match_index, (size_t)B * max_pts, &d_mi))) return rc;
-    if ((rc = st.out(s, (size_t)B * max_pts, &d_s))) return rc;
-    if ((rc = st.out(l, (size_t)B * max_pts, &d_l))) return rc;
-    if (B) {
-        hipLaunchKernelGGL(s_l_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_ref, max_pts, d_ref, d_sm, d_nr,
-                           d_xy, d_np, d_mi, d_s, d_l);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_ref = st.in(ref_line, (size_t)B * max_ref * 4);
+    const double* d_sm = st.in(s_map, (size_t)B * max_ref);
+    const int* d_nr = st.in(n_ref, (size_t)B);
+    const double* d_xy = st.in(xy, (size_t)B * max_pts * 2);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    const int* d_mi = st.in(match_index, (size_t)B * max_pts);
+    double* d_s = st.out(s, (size_t)B * max_pts);
+    double* d_l = st.out(l, (size_t)B * max_pts);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, s_l_kernel, grid1(B, 64), dim3(64), 0, B, max_ref, max_pts, d_ref, d_sm, d_nr, d_xy,
+                              d_np, d_mi, d_s, d_l))
+        return rc;
     return st.finish();
 }
 
@@ -1983,25 +1860,19 @@ int emp_s_l_deri(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_pts, cons
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_ref >= 1 && max_pts >= 1 && ref_line && n_ref && xy && v_xy && a_xy && n_pts &&
                          origin_xy && out, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ref, *d_xy, *d_v, *d_a, *d_o;
-    const int *d_nr, *d_np;
-    double* d_out;
-    if ((rc = st.in(ref_line, (size_t)B * max_ref * 4, &d_ref))) return rc;
-    if ((rc = st.in(n_ref, (size_t)B, &d_nr))) return rc;
-    if ((rc = st.in(xy, (size_t)B * max_pts * 2, &d_xy))) return rc;
-    if ((rc = st.in(v_xy, (size_t)B * max_pts * 2, &d_v))) return rc;
-    if ((rc = st.in(a_xy, (size_t)B * max_pts * 2, &d_a))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.in(origin_xy, (size_t)B * 2, &d_o))) return rc;
-    if ((rc = st.out(out, (size_t)B * max_pts * 7, &d_out))) return rc;
-    if (B) {
-        hipLaunchKernelGGL(s_l_deri_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_ref, max_pts, d_ref, d_nr,
-                           d_xy, d_v, d_a, d_np, d_o, d_out);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_ref = st.in(ref_line, (size_t)B * max_ref * 4);
+    const int* d_nr = st.in(n_ref, (size_t)B);
+    const double* d_xy = st.in(xy, (size_t)B * max_pts * 2);
+    const double* d_v = st.in(v_xy, (size_t)B * max_pts * 2);
+    const double* d_a = st.in(a_xy, (size_t)B * max_pts * 2);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    const double* d_o = st.in(origin_xy, (size_t)B * 2);
+    double* d_out = st.out(out, (size_t)B * max_pts * 7);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, s_l_deri_kernel, grid1(B, 64), dim3(64), 0, B, max_ref, max_pts, d_ref, d_nr, d_xy, d_v,
+                              d_a, d_np, d_o, d_out))
+        return rc;
     return st.finish();
 }
 
@@ -2011,26 +1882,19 @@ int emp_proj_point(emp_ctx* ctx, int32_t n, int32_t max_ref, const double* ref_l
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, n >= 0 && max_ref >= 1 && ref_line && s_map && n_ref && s && pre_match_index && out && index &&
                          status, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ref, *d_sm, *d_s;
-    const int *d_nr, *d_pre;
-    double* d_out;
-    int *d_idx, *d_st;
-    if ((rc = st.in(ref_line, (size_t)n * max_ref * 4, &d_ref))) return rc;
-    if ((rc = st.in(s_map, (size_t)n * max_ref, &d_sm))) return rc;
-    if ((rc = st.in(n_ref, (size_t)n, &d_nr))) return rc;
-    if ((rc = st.in(s, (size_t)n, &d_s))) return rc;
-    if ((rc = st.in(pre_match_index, (size_t)n, &d_pre))) return rc;
-    if ((rc = st.out(out, (size_t)n * 4, &d_out))) return rc;
-    if ((rc = st.out(index, (size_t)n, &d_idx))) return rc;
-    if ((rc = st.out(status, (size_t)n, &d_st))) return rc;
-    if (n) {
-        hipLaunchKernelGGL(proj_point_kernel, grid1(n, 64), dim3(64), 0, ctx->stream, n, max_ref, d_ref, d_sm, d_nr, d_s,
-                           d_pre, d_out, d_idx, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_ref = st.in(ref_line, (size_t)n * max_ref * 4);
+    const double* d_sm = st.in(s_map, (size_t)n * max_ref);
+    const int* d_nr = st.in(n_ref, (size_t)n);
+    const double* d_s = st.in(s, (size_t)n);
+    const int* d_pre = st.in(pre_match_index, (size_t)n);
+    double* d_out = st.out(out, (size_t)n * 4);
+    int* d_idx = st.out(index, (size_t)n);
+    int* d_st = st.out(status, (size_t)n);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, proj_point_kernel, grid1(n, 64), dim3(64), 0, n, max_ref, d_ref, d_sm, d_nr, d_s, d_pre,
+                              d_out, d_idx, d_st))
+        return rc;
     return st.finish();
 }
 
@@ -2038,20 +1902,13 @@ int emp_trajectory_index2s(emp_ctx* ctx, int32_t B, int32_t max_pts, const doubl
                            const int32_t* n_pts, double* index2s, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_pts >= 1 && x && y && n_pts && index2s, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_x, *d_y;
-    const int* d_np;
-    double* d_o;
-    if ((rc = st.in(x, (size_t)B * max_pts, &d_x))) return rc;
-    if ((rc = st.in(y, (size_t)B * max_pts, &d_y))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.out(index2s, (size_t)B * max_pts, &d_o))) return rc;
-    if (B) {
-        hipLaunchKernelGGL(index2s_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_pts, d_x, d_y, d_np, d_o);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_x = st.in(x, (size_t)B * max_pts);
+    const double* d_y = st.in(y, (size_t)B * max_pts);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    double* d_o = st.out(index2s, (size_t)B * max_pts);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, index2s_kernel, grid1(B, 64), dim3(64), 0, B, max_pts, d_x, d_y, d_np, d_o)) return rc;
     return st.finish();
 }
 
@@ -2061,42 +1918,29 @@ int emp_frenet2cartesian(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_p
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_ref >= 2 && max_pts >= 1 && ref_line && index2s && n_ref && sl && n_pts && out &&
                          status, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ref, *d_i2s, *d_sl;
-    const int *d_nr, *d_np;
-    double* d_out;
-    int* d_st;
-    if ((rc = st.in(ref_line, (size_t)B * max_ref * 4, &d_ref))) return rc;
-    if ((rc = st.in(index2s, (size_t)B * max_ref, &d_i2s))) return rc;
-    if ((rc = st.in(n_ref, (size_t)B, &d_nr))) return rc;
-    if ((rc = st.in(sl, (size_t)B * max_pts * 4, &d_sl))) return rc;
-    if ((rc = st.in(n_pts, (size_t)B, &d_np))) return rc;
-    if ((rc = st.out(out, (size_t)B * max_pts * 4, &d_out))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
-    if (B) {
-        hipLaunchKernelGGL(frenet2cartesian_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_ref, max_pts, d_ref,
-                           d_i2s, d_nr, d_sl, d_np, d_out, d_st, proj_only);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_ref = st.in(ref_line, (size_t)B * max_ref * 4);
+    const double* d_i2s = st.in(index2s, (size_t)B * max_ref);
+    const int* d_nr = st.in(n_ref, (size_t)B);
+    const double* d_sl = st.in(sl, (size_t)B * max_pts * 4);
+    const int* d_np = st.in(n_pts, (size_t)B);
+    double* d_out = st.out(out, (size_t)B * max_pts * 4);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, frenet2cartesian_kernel, grid1(B, 64), dim3(64), 0, B, max_ref, max_pts, d_ref, d_i2s,
+                              d_nr, d_sl, d_np, d_out, d_st, proj_only))
+        return rc;
     return st.finish();
 }
 
 int emp_dy_obs_deri(emp_ctx* ctx, int32_t n, const double* in, double* out, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, n >= 0 && in && out, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double* d_in;
-    double* d_out;
-    if ((rc = st.in(in, (size_t)n * 5, &d_in))) return rc;
-    if ((rc = st.out(out, (size_t)n * 3, &d_out))) return rc;
-    if (n) {
-        hipLaunchKernelGGL(dy_obs_deri_kernel, grid1(n, 64), dim3(64), 0, ctx->stream, n, d_in, d_out);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_in = st.in(in, (size_t)n * 5);
+    double* d_out = st.out(out, (size_t)n * 3);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, dy_obs_deri_kernel, grid1(n, 64), dim3(64), 0, n, d_in, d_out)) return rc;
     return st.finish();
 }
 
@@ -2108,26 +1952,19 @@ extern "C" int emp_enrich_nodes(emp_ctx* ctx, int32_t B, int32_t max_nodes, doub
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_nodes >= 1 && max_pts >= 1 && resolution > 0, "bad sizes");
     EMP_REQUIRE(ctx, node_s && node_l && n_nodes && start && path_s && path_l && path_len && status, "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_ns, *d_nl, *d_start;
-    const int* d_nn;
-    double *d_ps, *d_pl;
-    int *d_len, *d_st;
-    if ((rc = st.in(node_s, (size_t)B * max_nodes, &d_ns))) return rc;
-    if ((rc = st.in(node_l, (size_t)B * max_nodes, &d_nl))) return rc;
-    if ((rc = st.in(n_nodes, (size_t)B, &d_nn))) return rc;
-    if ((rc = st.in(start, (size_t)B * 4, &d_start))) return rc;
-    if ((rc = st.out(path_s, (size_t)B * max_pts, &d_ps))) return rc;
-    if ((rc = st.out(path_l, (size_t)B * max_pts, &d_pl))) return rc;
-    if ((rc = st.out(path_len, (size_t)B, &d_len))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st))) return rc;
-    if (B) {
-        hipLaunchKernelGGL(enrich_nodes_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_nodes, resolution, d_ns,
-                           d_nl, d_nn, d_start, max_pts, d_ps, d_pl, d_len, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_ns = st.in(node_s, (size_t)B * max_nodes);
+    const double* d_nl = st.in(node_l, (size_t)B * max_nodes);
+    const int* d_nn = st.in(n_nodes, (size_t)B);
+    const double* d_start = st.in(start, (size_t)B * 4);
+    double* d_ps = st.out(path_s, (size_t)B * max_pts);
+    double* d_pl = st.out(path_l, (size_t)B * max_pts);
+    int* d_len = st.out(path_len, (size_t)B);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, enrich_nodes_kernel, grid1(B, 64), dim3(64), 0, B, max_nodes, resolution, d_ns, d_nl,
+                              d_nn, d_start, max_pts, d_ps, d_pl, d_len, d_st))
+        return rc;
     return st.finish();
 }
 
@@ -2156,30 +1993,23 @@ static emp::StDev make_st_dev(const emp_speed_dp_params* p, int B, int max_obs) 
 int emp_st_graph(emp_ctx* ctx, int32_t B, int32_t max_obs, const double* obs_s, const double* obs_l,
                  const double* obs_s_dot, const double* obs_l_dot, double* s_in, double* s_out, double* t_in,
                  double* t_out, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_obs >= 1, "bad sizes");
     EMP_REQUIRE(ctx, obs_s && obs_l && obs_s_dot && obs_l_dot && s_in && s_out && t_in && t_out, "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
+    EMP_STAGE(st, where);
     const size_t n = (size_t)B * max_obs;
-    const double *d_s, *d_l, *d_sd, *d_ld;
-    double *d_si, *d_so, *d_ti, *d_to;
-    if ((rc = st.in(obs_s, n, &d_s))) return rc;
-    if ((rc = st.in(obs_l, n, &d_l))) return rc;
-    if ((rc = st.in(obs_s_dot, n, &d_sd))) return rc;
-    if ((rc = st.in(obs_l_dot, n, &d_ld))) return rc;
-    if ((rc = st.out(s_in, n, &d_si, false))) return rc;
-    if ((rc = st.out(s_out, n, &d_so, false))) return rc;
-    if ((rc = st.out(t_in, n, &d_ti, false))) return rc;
-    if ((rc = st.out(t_out, n, &d_to, false))) return rc;
-    if (B) {
-        KernelTimer t(ctx, "st_graph");
-        hipLaunchKernelGGL(st_graph_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_obs, d_s, d_l, d_sd, d_ld, d_si,
-                           d_so, d_ti, d_to);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    const double* d_s = st.in(obs_s, n);
+    const double* d_l = st.in(obs_l, n);
+    const double* d_sd = st.in(obs_s_dot, n);
+    const double* d_ld = st.in(obs_l_dot, n);
+    double* d_si = st.out(s_in, n, false);
+    double* d_so = st.out(s_out, n, false);
+    double* d_ti = st.out(t_in, n, false);
+    double* d_to = st.out(t_out, n, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "st_graph", st_graph_kernel, grid1(B, 64), dim3(64), 0, B, max_obs, d_s, d_l, d_sd, d_ld, d_si,
+                              d_so, d_ti, d_to))
+        return rc;
     return st.finish();
 }
 
@@ -2187,130 +2017,99 @@ int emp_speed_dp(emp_ctx* ctx, const emp_speed_dp_params* p, int32_t B, int32_t 
                  const double* s_out, const double* t_in, const double* t_out, const double* plan_start_s_dot,
                  double* cost, double* s_dot, int32_t* node, int32_t* end_node, double* speed_s, double* speed_t,
                  emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p != nullptr, "speed dp params are NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_obs >= 1 && max_obs <= st::kMaxObs, "bad sizes (max_obs must be in [1, 64])");
     EMP_REQUIRE(ctx, s_in && s_out && t_in && t_out && plan_start_s_dot && end_node && speed_s && speed_t, "NULL argument");
     // ref :281 w_cost_obs ** (1.5 - d): complex for a negative base, and the reference fails on its next comparison
     EMP_REQUIRE(ctx, !(p->w_cost_obs < 0.0), "w_cost_obs must not be negative");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage stg(ctx, where);
-    int rc;
-    const size_t n = (size_t)B * max_obs, nt = (size_t)B * st::kRows * st::kCols;
-    const double *d_si, *d_so, *d_ti, *d_to, *d_v;
-    double *d_c = nullptr, *d_sd = nullptr, *d_ss, *d_tt;
-    int *d_n = nullptr, *d_e;
-    if ((rc = stg.in(s_in, n, &d_si))) return rc;
-    if ((rc = stg.in(s_out, n, &d_so))) return rc;
-    if ((rc = stg.in(t_in, n, &d_ti))) return rc;
-    if ((rc = stg.in(t_out, n, &d_to))) return rc;
-    if ((rc = stg.in(plan_start_s_dot, (size_t)B, &d_v))) return rc;
-    if (cost && (rc = stg.out(cost, nt, &d_c, false))) return rc;
-    if (s_dot && (rc = stg.out(s_dot, nt, &d_sd, false))) return rc;
-    if (node && (rc = stg.out(node, nt, &d_n, false))) return rc;
-    if ((rc = stg.out(end_node, (size_t)B * 2, &d_e, false))) return rc;
-    if ((rc = stg.out(speed_s, (size_t)B * st::kCols, &d_ss, false))) return rc;
-    if ((rc = stg.out(speed_t, (size_t)B * st::kCols, &d_tt, false))) return rc;
+    EMP_STAGE(st, where);
+    const size_t n = (size_t)B * max_obs, nt = (size_t)B * emp::st::kRows * emp::st::kCols;
+    const double* d_si = st.in(s_in, n);
+    const double* d_so = st.in(s_out, n);
+    const double* d_ti = st.in(t_in, n);
+    const double* d_to = st.in(t_out, n);
+    const double* d_v = st.in(plan_start_s_dot, (size_t)B);
+    double* d_c = st.out(cost, nt, false);
+    double* d_sd = st.out(s_dot, nt, false);
+    int* d_n = st.out(node, nt, false);
+    int* d_e = st.out(end_node, (size_t)B * 2, false);
+    double* d_ss = st.out(speed_s, (size_t)B * emp::st::kCols, false);
+    double* d_tt = st.out(speed_t, (size_t)B * emp::st::kCols, false);
     // heaviest scenes first (emp_st_kernels.h: st_count_kernel); pointless when every block is resident at once
-    int* d_order = nullptr;
-    if (B > 512) {
-        unsigned char* d_key;
-        int* d_hist;
-        if ((rc = stg.tmp<int>((size_t)B, &d_order))) return rc;
-        if ((rc = stg.tmp<unsigned char>((size_t)B, &d_key))) return rc;
-        if ((rc = stg.tmp<int>(2 * (size_t)kStKeys, &d_hist, true))) return rc;
+    const bool order = B > 512;
+    int* d_order = order ? st.tmp<int>((size_t)B) : nullptr;
+    unsigned char* d_key = order ? st.tmp<unsigned char>((size_t)B) : nullptr;
+    int* d_hist = order ? st.tmp<int>(2 * (size_t)kStKeys, true) : nullptr;
+    if (const int rc = st.ready()) return rc;
+    if (order) {           // two launches, one timing interval
+        if (const int rc = launch_gate(ctx)) return rc;
         KernelTimer t(ctx, "speed_dp_order");
         hipLaunchKernelGGL(st_count_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, max_obs, d_si, d_key, d_hist);
         hipLaunchKernelGGL(st_scatter_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, d_key, d_hist, d_hist + kStKeys, d_order);
         EMP_LAUNCH_CHECK(ctx);
     }
-    if (B) {
-        const StDev d = make_st_dev(p, B, max_obs);
-        KernelTimer t(ctx, "speed_dp");
-        if (max_obs <= 32)
-            hipLaunchKernelGGL(speed_dp_kernel<uint32_t>, dim3(B), dim3(kStBlock), speed_dp_lds_bytes(max_obs), ctx->stream, d,
-                               d_si, d_so, d_ti, d_to, d_v, d_c, d_sd, d_n, d_e, d_ss, d_tt, d_order);
-        else
-            hipLaunchKernelGGL(speed_dp_kernel<uint64_t>, dim3(B), dim3(kStBlock), speed_dp_lds_bytes(max_obs), ctx->stream, d,
-                               d_si, d_so, d_ti, d_to, d_v, d_c, d_sd, d_n, d_e, d_ss, d_tt, d_order);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    return stg.finish();
+    if (const int rc = launch(ctx, "speed_dp", max_obs <= 32 ? speed_dp_kernel<uint32_t> : speed_dp_kernel<uint64_t>, dim3(B),
+                              dim3(kStBlock), speed_dp_lds_bytes(max_obs), make_st_dev(p, B, max_obs), d_si, d_so, d_ti, d_to, d_v,
+                              d_c, d_sd, d_n, d_e, d_ss, d_tt, d_order))
+        return rc;
+    return st.finish();
 }
 
 int emp_st_edge_costs(emp_ctx* ctx, const emp_speed_dp_params* p, int32_t B, int32_t n_edges, int32_t max_obs,
                       const double* edges, const double* s_in, const double* s_out, const double* t_in,
                       const double* t_out, double* total, double* obs, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p != nullptr, "speed dp params are NULL");
     EMP_REQUIRE(ctx, B >= 0 && B <= 65535 && n_edges >= 0 && max_obs >= 1 && max_obs <= st::kMaxObs,
                 "bad sizes (B <= 65535, max_obs in [1, 64])");
     EMP_REQUIRE(ctx, edges && s_in && s_out && t_in && t_out && total, "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage stg(ctx, where);
-    int rc;
+    EMP_STAGE(st, where);
     const size_t n = (size_t)B * max_obs, ne = (size_t)B * n_edges;
-    const double *d_e, *d_si, *d_so, *d_ti, *d_to;
-    double *d_t, *d_o = nullptr;
-    if ((rc = stg.in(edges, ne * 5, &d_e))) return rc;
-    if ((rc = stg.in(s_in, n, &d_si))) return rc;
-    if ((rc = stg.in(s_out, n, &d_so))) return rc;
-    if ((rc = stg.in(t_in, n, &d_ti))) return rc;
-    if ((rc = stg.in(t_out, n, &d_to))) return rc;
-    if ((rc = stg.out(total, ne, &d_t, false))) return rc;
-    if (obs && (rc = stg.out(obs, ne, &d_o, false))) return rc;
-    if (ne) {
-        const StDev d = make_st_dev(p, B, max_obs);
-        dim3 grid((n_edges + 63) / 64, B);
-        hipLaunchKernelGGL(st_edge_cost_kernel, grid, dim3(64), 7 * (size_t)max_obs * sizeof(double), ctx->stream, d, n_edges, d_e, d_si, d_so, d_ti, d_to, d_t,
-                           d_o);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    return stg.finish();
+    const double* d_e = st.in(edges, ne * 5);
+    const double* d_si = st.in(s_in, n);
+    const double* d_so = st.in(s_out, n);
+    const double* d_ti = st.in(t_in, n);
+    const double* d_to = st.in(t_out, n);
+    double* d_t = st.out(total, ne, false);
+    double* d_o = st.out(obs, ne, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, st_edge_cost_kernel, dim3((n_edges + 63) / 64, B), dim3(64), 7 * (size_t)max_obs * sizeof(double),
+                              make_st_dev(p, B, max_obs), n_edges, d_e, d_si, d_so, d_ti, d_to, d_t, d_o))
+        return rc;
+    return st.finish();
 }
 
 int emp_st_collision_cost(emp_ctx* ctx, int32_t n, double w_cost_obs, const double* min_dis, double* cost, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, n >= 0 && min_dis && cost, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage stg(ctx, where);
-    int rc;
-    const double* d_d;
-    double* d_c;
-    if ((rc = stg.in(min_dis, (size_t)n, &d_d))) return rc;
-    if ((rc = stg.out(cost, (size_t)n, &d_c, false))) return rc;
-    if (n) {
-        hipLaunchKernelGGL(st_collision_cost_kernel, grid1(n, 64), dim3(64), 0, ctx->stream, n, st::make_pow_base(w_cost_obs), d_d, d_c);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    return stg.finish();
+    EMP_STAGE(st, where);
+    const double* d_d = st.in(min_dis, (size_t)n);
+    double* d_c = st.out(cost, (size_t)n, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, st_collision_cost_kernel, grid1(n, 64), dim3(64), 0, n, emp::st::make_pow_base(w_cost_obs),
+                              d_d, d_c))
+        return rc;
+    return st.finish();
 }
 
 int emp_speed_start_condition(emp_ctx* ctx, int32_t n, const double* vx, const double* vy, const double* ax, const double* ay,
                               const double* heading, double* s_dot, double* s_dot2, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, n >= 0 && vx && vy && ax && ay && heading && s_dot && s_dot2, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage stg(ctx, where);
-    int rc;
-    const double *d_vx, *d_vy, *d_ax, *d_ay, *d_h;
-    double *d_s1, *d_s2;
-    if ((rc = stg.in(vx, (size_t)n, &d_vx))) return rc;
-    if ((rc = stg.in(vy, (size_t)n, &d_vy))) return rc;
-    if ((rc = stg.in(ax, (size_t)n, &d_ax))) return rc;
-    if ((rc = stg.in(ay, (size_t)n, &d_ay))) return rc;
-    if ((rc = stg.in(heading, (size_t)n, &d_h))) return rc;
-    if ((rc = stg.out(s_dot, (size_t)n, &d_s1, false))) return rc;
-    if ((rc = stg.out(s_dot2, (size_t)n, &d_s2, false))) return rc;
-    if (n) {
-        hipLaunchKernelGGL(st_start_condition_kernel, grid1(n, 64), dim3(64), 0, ctx->stream, n, d_vx, d_vy, d_ax, d_ay, d_h, d_s1, d_s2);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    return stg.finish();
+    EMP_STAGE(st, where);
+    const double* d_vx = st.in(vx, (size_t)n);
+    const double* d_vy = st.in(vy, (size_t)n);
+    const double* d_ax = st.in(ax, (size_t)n);
+    const double* d_ay = st.in(ay, (size_t)n);
+    const double* d_h = st.in(heading, (size_t)n);
+    double* d_s1 = st.out(s_dot, (size_t)n, false);
+    double* d_s2 = st.out(s_dot2, (size_t)n, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, nullptr, st_start_condition_kernel, grid1(n, 64), dim3(64), 0, n, d_vx, d_vy, d_ax, d_ay, d_h,
+                              d_s1, d_s2))
+        return rc;
+    return st.finish();
 }
 
 // ---- S-T speed planning back end (reference speed_planning_test.py:308-620) ---------------------
@@ -2328,112 +2127,87 @@ int emp_speed_convex_space(emp_ctx* ctx, int32_t B, int32_t n_slots, int32_t max
                            const double* path_kappa, const int32_t* path_len, const double* s_in, const double* s_out,
                            const double* t_in, const double* t_out, double* s_lb, double* s_ub, double* s_dot_lb,
                            double* s_dot_ub, int32_t* status, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && n_slots >= 1 && max_path >= 1, "bad sizes");
     EMP_REQUIRE(ctx, dp_speed_s && dp_speed_t && path_index2s && path_kappa && path_len && s_in && s_out && t_in && t_out &&
                          s_lb && s_ub && s_dot_lb && s_dot_ub && status, "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage stg(ctx, where);
-    int rc;
-    const double *d_ds, *d_dt, *d_i2s, *d_k, *d_si, *d_so, *d_ti, *d_to;
-    const int* d_pl;
-    double *d_lb, *d_ub, *d_vlb, *d_vub;
-    int* d_st;
-    if ((rc = stg.in(dp_speed_s, (size_t)B * stb::kDp, &d_ds))) return rc;
-    if ((rc = stg.in(dp_speed_t, (size_t)B * stb::kDp, &d_dt))) return rc;
-    if ((rc = stg.in(path_index2s, (size_t)B * max_path, &d_i2s))) return rc;
-    if ((rc = stg.in(path_kappa, (size_t)B * max_path, &d_k))) return rc;
-    if ((rc = stg.in(path_len, (size_t)B, &d_pl))) return rc;
-    if ((rc = stg.in(s_in, (size_t)B * n_slots, &d_si))) return rc;
-    if ((rc = stg.in(s_out, (size_t)B * n_slots, &d_so))) return rc;
-    if ((rc = stg.in(t_in, (size_t)B * n_slots, &d_ti))) return rc;
-    if ((rc = stg.in(t_out, (size_t)B * n_slots, &d_to))) return rc;
-    if ((rc = stg.out(s_lb, (size_t)B * stb::kDp, &d_lb, false))) return rc;
-    if ((rc = stg.out(s_ub, (size_t)B * stb::kDp, &d_ub, false))) return rc;
-    if ((rc = stg.out(s_dot_lb, (size_t)B * stb::kDp, &d_vlb, false))) return rc;
-    if ((rc = stg.out(s_dot_ub, (size_t)B * stb::kDp, &d_vub, false))) return rc;
-    if ((rc = stg.out(status, (size_t)B, &d_st, false))) return rc;
-    if (B) {
-        KernelTimer t(ctx, "speed_convex_space");
-        hipLaunchKernelGGL(stb::convex_space_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, n_slots, max_path,
-                           max_lateral_accel, d_ds, d_dt, d_i2s, d_k, d_pl, d_si, d_so, d_ti, d_to, d_lb, d_ub, d_vlb, d_vub,
-                           d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    return stg.finish();
+    EMP_STAGE(st, where);
+    const double* d_ds = st.in(dp_speed_s, (size_t)B * stb::kDp);
+    const double* d_dt = st.in(dp_speed_t, (size_t)B * stb::kDp);
+    const double* d_i2s = st.in(path_index2s, (size_t)B * max_path);
+    const double* d_k = st.in(path_kappa, (size_t)B * max_path);
+    const int* d_pl = st.in(path_len, (size_t)B);
+    const double* d_si = st.in(s_in, (size_t)B * n_slots);
+    const double* d_so = st.in(s_out, (size_t)B * n_slots);
+    const double* d_ti = st.in(t_in, (size_t)B * n_slots);
+    const double* d_to = st.in(t_out, (size_t)B * n_slots);
+    double* d_lb = st.out(s_lb, (size_t)B * stb::kDp, false);
+    double* d_ub = st.out(s_ub, (size_t)B * stb::kDp, false);
+    double* d_vlb = st.out(s_dot_lb, (size_t)B * stb::kDp, false);
+    double* d_vub = st.out(s_dot_ub, (size_t)B * stb::kDp, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "speed_convex_space", stb::convex_space_kernel, grid1(B, 64), dim3(64), 0, B, n_slots, max_path,
+                              max_lateral_accel, d_ds, d_dt, d_i2s, d_k, d_pl, d_si, d_so, d_ti, d_to, d_lb, d_ub, d_vlb, d_vub,
+                              d_st))
+        return rc;
+    return st.finish();
 }
 
 int emp_speed_qp(emp_ctx* ctx, const emp_speed_qp_params* p, int32_t B, const double* plan_start_s_dot,
                  const double* plan_start_s_dot2, const double* dp_speed_s, const double* dp_speed_t, const double* s_lb,
                  const double* s_ub, const double* s_dot_lb, const double* s_dot_ub, double* qp_s, double* qp_s_dot,
                  double* qp_s_dot2, double* relative_time, int32_t* iters, int32_t* status, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p != nullptr && B >= 0, "bad argument");
     EMP_REQUIRE(ctx, plan_start_s_dot && plan_start_s_dot2 && dp_speed_s && dp_speed_t && s_lb && s_ub && s_dot_lb && s_dot_ub &&
                          qp_s && qp_s_dot && qp_s_dot2 && relative_time && status, "NULL argument");
     EMP_REQUIRE(ctx, p->w_cost_s_dot2 > 0 && p->w_cost_v_ref > 0 && p->w_cost_jerk >= 0, "weights must be positive");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage stg(ctx, where);
-    int rc;
-    const double *d_v0, *d_a0, *d_ds, *d_dt, *d_lb, *d_ub, *d_vlb, *d_vub;
-    double *d_qs, *d_qv, *d_qa, *d_qt;
-    int *d_it, *d_st;
-    if ((rc = stg.in(plan_start_s_dot, (size_t)B, &d_v0))) return rc;
-    if ((rc = stg.in(plan_start_s_dot2, (size_t)B, &d_a0))) return rc;
-    if ((rc = stg.in(dp_speed_s, (size_t)B * stb::kDp, &d_ds))) return rc;
-    if ((rc = stg.in(dp_speed_t, (size_t)B * stb::kDp, &d_dt))) return rc;
-    if ((rc = stg.in(s_lb, (size_t)B * stb::kDp, &d_lb))) return rc;
-    if ((rc = stg.in(s_ub, (size_t)B * stb::kDp, &d_ub))) return rc;
-    if ((rc = stg.in(s_dot_lb, (size_t)B * stb::kDp, &d_vlb))) return rc;
-    if ((rc = stg.in(s_dot_ub, (size_t)B * stb::kDp, &d_vub))) return rc;
-    if ((rc = stg.out(qp_s, (size_t)B * stb::kQp, &d_qs, false))) return rc;
-    if ((rc = stg.out(qp_s_dot, (size_t)B * stb::kQp, &d_qv, false))) return rc;
-    if ((rc = stg.out(qp_s_dot2, (size_t)B * stb::kQp, &d_qa, false))) return rc;
-    if ((rc = stg.out(relative_time, (size_t)B * stb::kQp, &d_qt, false))) return rc;
-    if ((rc = stg.out(iters, (size_t)B, &d_it, false))) return rc;
-    if ((rc = stg.out(status, (size_t)B, &d_st, false))) return rc;
-    if (B) {
-        const stb::SpeedQpParams prm{p->w_cost_s_dot2, p->w_cost_v_ref, p->w_cost_jerk, p->reference_speed};
-        const size_t lds = 2 * (size_t)(stb::speed_qp_words(stb::kQp) + 1) * sizeof(double);
-        KernelTimer t(ctx, "speed_qp");
-        hipLaunchKernelGGL(stb::speed_qp_kernel<32>, dim3((B + 1) / 2), dim3(64), lds, ctx->stream, B, prm, d_v0, d_a0, d_ds,
-                           d_dt, d_lb, d_ub, d_vlb, d_vub, d_qs, d_qv, d_qa, d_qt, d_it, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    return stg.finish();
+    EMP_STAGE(st, where);
+    const double* d_v0 = st.in(plan_start_s_dot, (size_t)B);
+    const double* d_a0 = st.in(plan_start_s_dot2, (size_t)B);
+    const double* d_ds = st.in(dp_speed_s, (size_t)B * stb::kDp);
+    const double* d_dt = st.in(dp_speed_t, (size_t)B * stb::kDp);
+    const double* d_lb = st.in(s_lb, (size_t)B * stb::kDp);
+    const double* d_ub = st.in(s_ub, (size_t)B * stb::kDp);
+    const double* d_vlb = st.in(s_dot_lb, (size_t)B * stb::kDp);
+    const double* d_vub = st.in(s_dot_ub, (size_t)B * stb::kDp);
+    double* d_qs = st.out(qp_s, (size_t)B * stb::kQp, false);
+    double* d_qv = st.out(qp_s_dot, (size_t)B * stb::kQp, false);
+    double* d_qa = st.out(qp_s_dot2, (size_t)B * stb::kQp, false);
+    double* d_qt = st.out(relative_time, (size_t)B * stb::kQp, false);
+    int* d_it = st.out(iters, (size_t)B, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    const stb::SpeedQpParams prm{p->w_cost_s_dot2, p->w_cost_v_ref, p->w_cost_jerk, p->reference_speed};
+    const size_t lds = 2 * (size_t)(stb::speed_qp_words(stb::kQp) + 1) * sizeof(double);
+    if (const int rc = launch(ctx, "speed_qp", stb::speed_qp_kernel<32>, dim3((B + 1) / 2), dim3(64), lds, B, prm, d_v0, d_a0, d_ds,
+                              d_dt, d_lb, d_ub, d_vlb, d_vub, d_qs, d_qv, d_qa, d_qt, d_it, d_st))
+        return rc;
+    return st.finish();
 }
 
 int emp_speed_increase_points(emp_ctx* ctx, int32_t B, const double* s_init, const double* s_dot_init,
                               const double* s_dot2_init, const double* relative_time_init, double* s, double* s_dot,
                               double* s_dot2, double* relative_time, int32_t* status, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && s_init && s_dot_init && s_dot2_init && relative_time_init && s && s_dot && s_dot2 &&
                          relative_time && status, "bad argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage stg(ctx, where);
-    int rc;
-    const double *d_qs, *d_qv, *d_qa, *d_qt;
-    double *d_s, *d_v, *d_a, *d_t;
-    int* d_st;
-    if ((rc = stg.in(s_init, (size_t)B * stb::kQp, &d_qs))) return rc;
-    if ((rc = stg.in(s_dot_init, (size_t)B * stb::kQp, &d_qv))) return rc;
-    if ((rc = stg.in(s_dot2_init, (size_t)B * stb::kQp, &d_qa))) return rc;
-    if ((rc = stg.in(relative_time_init, (size_t)B * stb::kQp, &d_qt))) return rc;
-    if ((rc = stg.out(s, (size_t)B * stb::kDense, &d_s, false))) return rc;
-    if ((rc = stg.out(s_dot, (size_t)B * stb::kDense, &d_v, false))) return rc;
-    if ((rc = stg.out(s_dot2, (size_t)B * stb::kDense, &d_a, false))) return rc;
-    if ((rc = stg.out(relative_time, (size_t)B * stb::kDense, &d_t, false))) return rc;
-    if ((rc = stg.out(status, (size_t)B, &d_st, false))) return rc;
-    if (B) {
-        KernelTimer t(ctx, "speed_increase_points");
-        hipLaunchKernelGGL(stb::densify_kernel, dim3(B), dim3(64), 0, ctx->stream, B, d_qs, d_qv, d_qa, d_qt, d_s, d_v, d_a, d_t,
-                           d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    return stg.finish();
+    EMP_STAGE(st, where);
+    const double* d_qs = st.in(s_init, (size_t)B * stb::kQp);
+    const double* d_qv = st.in(s_dot_init, (size_t)B * stb::kQp);
+    const double* d_qa = st.in(s_dot2_init, (size_t)B * stb::kQp);
+    const double* d_qt = st.in(relative_time_init, (size_t)B * stb::kQp);
+    double* d_s = st.out(s, (size_t)B * stb::kDense, false);
+    double* d_v = st.out(s_dot, (size_t)B * stb::kDense, false);
+    double* d_a = st.out(s_dot2, (size_t)B * stb::kDense, false);
+    double* d_t = st.out(relative_time, (size_t)B * stb::kDense, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "speed_increase_points", stb::densify_kernel, dim3(B), dim3(64), 0, B, d_qs, d_qv, d_qa, d_qt,
+                              d_s, d_v, d_a, d_t, d_st))
+        return rc;
+    return st.finish();
 }
 
 int emp_path_speed_merge(emp_ctx* ctx, int32_t B, int32_t max_path, const double* s, const double* s_dot,
@@ -2441,42 +2215,33 @@ int emp_path_speed_merge(emp_ctx* ctx, int32_t B, int32_t max_path, const double
                          const double* path_s, const double* x_init, const double* y_init, const double* heading_init,
                          const double* kappa_init, const int32_t* n_init, double* trajectory, int32_t* status,
                          emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, B >= 0 && max_path >= 1, "bad sizes");
     EMP_REQUIRE(ctx, s && s_dot && s_dot2 && relative_time && current_time && path_s && x_init && y_init && heading_init &&
                          kappa_init && n_init && trajectory && status, "NULL argument");
     const size_t lds = (size_t)5 * max_path * sizeof(double);
     EMP_REQUIRE(ctx, lds <= 64 * 1024, "path too long for the LDS-resident merge kernel");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage stg(ctx, where);
-    int rc;
-    const double *d_s, *d_v, *d_a, *d_t, *d_now, *d_ps, *d_x, *d_y, *d_h, *d_k;
-    const int* d_n;
-    double* d_out;
-    int* d_st;
-    if ((rc = stg.in(s, (size_t)B * stb::kDense, &d_s))) return rc;
-    if ((rc = stg.in(s_dot, (size_t)B * stb::kDense, &d_v))) return rc;
-    if ((rc = stg.in(s_dot2, (size_t)B * stb::kDense, &d_a))) return rc;
-    if ((rc = stg.in(relative_time, (size_t)B * stb::kDense, &d_t))) return rc;
-    if ((rc = stg.in(current_time, (size_t)B, &d_now))) return rc;
-    if ((rc = stg.in(path_s, (size_t)B * max_path, &d_ps))) return rc;
-    if ((rc = stg.in(x_init, (size_t)B * max_path, &d_x))) return rc;
-    if ((rc = stg.in(y_init, (size_t)B * max_path, &d_y))) return rc;
-    if ((rc = stg.in(heading_init, (size_t)B * max_path, &d_h))) return rc;
-    if ((rc = stg.in(kappa_init, (size_t)B * max_path, &d_k))) return rc;
-    if ((rc = stg.in(n_init, (size_t)B, &d_n))) return rc;
-    if ((rc = stg.out(trajectory, (size_t)B * 7 * stb::kDense, &d_out, false))) return rc;
-    if ((rc = stg.out(status, (size_t)B, &d_st, false))) return rc;
-    if (B) {
-        if (lds > 48 * 1024)
-            EMP_HIP(ctx, hipFuncSetAttribute((const void*)stb::merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        KernelTimer t(ctx, "path_speed_merge");
-        hipLaunchKernelGGL(stb::merge_kernel, dim3(B), dim3(64), lds, ctx->stream, B, max_path, d_s, d_v, d_a, d_t, d_now, d_ps,
-                           d_x, d_y, d_h, d_k, d_n, d_out, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    return stg.finish();
+    EMP_STAGE(st, where);
+    const double* d_s = st.in(s, (size_t)B * stb::kDense);
+    const double* d_v = st.in(s_dot, (size_t)B * stb::kDense);
+    const double* d_a = st.in(s_dot2, (size_t)B * stb::kDense);
+    const double* d_t = st.in(relative_time, (size_t)B * stb::kDense);
+    const double* d_now = st.in(current_time, (size_t)B);
+    const double* d_ps = st.in(path_s, (size_t)B * max_path);
+    const double* d_x = st.in(x_init, (size_t)B * max_path);
+    const double* d_y = st.in(y_init, (size_t)B * max_path);
+    const double* d_h = st.in(heading_init, (size_t)B * max_path);
+    const double* d_k = st.in(kappa_init, (size_t)B * max_path);
+    const int* d_n = st.in(n_init, (size_t)B);
+    double* d_out = st.out(trajectory, (size_t)B * 7 * stb::kDense, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (B && lds > 48 * 1024)
+        EMP_HIP(ctx, hipFuncSetAttribute((const void*)stb::merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (const int rc = launch(ctx, "path_speed_merge", stb::merge_kernel, dim3(B), dim3(64), lds, B, max_path, d_s, d_v, d_a, d_t,
+                              d_now, d_ps, d_x, d_y, d_h, d_k, d_n, d_out, d_st))
+        return rc;
+    return st.finish();
 }
 
 }  // extern "C"
@@ -2502,50 +2267,45 @@ void emp_mpc_params_default(emp_mpc_params* p) {
     p->r = 1.0;
 }
 
+static mpc::Params mpc_params(const emp_mpc_params* p) {
+    mpc::Params prm;
+    prm.a = p->a; prm.b = p->b; prm.Cf = p->Cf; prm.Cr = p->Cr; prm.m = p->m; prm.Iz = p->Iz;
+    for (int i = 0; i < 4; ++i) {
+        prm.q[i] = p->q_diag[i];
+        prm.f[i] = p->f_diag[i];
+    }
+    prm.r = p->r;
+    return prm;
+}
+
 int emp_mpc_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t max_path, const double* target_path,
                     const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
                     double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
                     double* H, double* f, int32_t* iters, int32_t* status, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
     EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_path, *d_state, *d_vx;
-    const int *d_np, *d_mi;
-    double *d_steer, *d_u = nullptr, *d_e = nullptr, *d_k = nullptr, *d_pp = nullptr, *d_H = nullptr, *d_f = nullptr;
-    int *d_mo, *d_it = nullptr, *d_st;
-    if ((rc = st.in(target_path, (size_t)B * max_path * 4, &d_path))) return rc;
-    if ((rc = st.in(n_path, (size_t)B, &d_np))) return rc;
-    if ((rc = st.in(state, (size_t)B * 5, &d_state))) return rc;
-    if ((rc = st.in(vx, (size_t)B, &d_vx))) return rc;
-    if ((rc = st.in(min_index, (size_t)B, &d_mi))) return rc;
-    if ((rc = st.out(steer, (size_t)B, &d_steer, false))) return rc;
-    if (u && (rc = st.out(u, (size_t)B * mpc::kNu, &d_u, false))) return rc;
-    if (e_rr && (rc = st.out(e_rr, (size_t)B * 4, &d_e, false))) return rc;
-    if (k_r && (rc = st.out(k_r, (size_t)B, &d_k, false))) return rc;
-    if ((rc = st.out(min_index_out, (size_t)B, &d_mo, false))) return rc;
-    if (pre_pro && (rc = st.out(pre_pro, (size_t)B * 4, &d_pp, false))) return rc;
-    if (H && (rc = st.out(H, (size_t)B * mpc::kNu * mpc::kNu, &d_H, false))) return rc;
-    if (f && (rc = st.out(f, (size_t)B * mpc::kNu, &d_f, false))) return rc;
-    if (iters && (rc = st.out(iters, (size_t)B, &d_it, false))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st, false))) return rc;
-    if (B) {
-        mpc::Params prm;
-        prm.a = p->a; prm.b = p->b; prm.Cf = p->Cf; prm.Cr = p->Cr; prm.m = p->m; prm.Iz = p->Iz;
-        for (int i = 0; i < 4; ++i) {
-            prm.q[i] = p->q_diag[i];
-            prm.f[i] = p->f_diag[i];
-        }
-        prm.r = p->r;
-        KernelTimer t(ctx, "mpc_lateral");
-        hipLaunchKernelGGL(mpc::mpc_lateral_kernel, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave), dim3(64), 0,
-                           ctx->stream, B, max_path, prm, d_path, d_np, d_state, d_vx, d_mi, d_steer, d_u, d_e, d_k, d_mo, d_pp,
-                           d_H, d_f, d_it, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
+    const int* d_np = st.in(n_path, (size_t)B);
+    const double* d_state = st.in(state, (size_t)B * 5);
+    const double* d_vx = st.in(vx, (size_t)B);
+    const int* d_mi = st.in(min_index, (size_t)B);
+    double* d_steer = st.out(steer, (size_t)B, false);
+    double* d_u = st.out(u, (size_t)B * mpc::kNu, false);
+    double* d_e = st.out(e_rr, (size_t)B * 4, false);
+    double* d_k = st.out(k_r, (size_t)B, false);
+    int* d_mo = st.out(min_index_out, (size_t)B, false);
+    double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
+    double* d_H = st.out(H, (size_t)B * mpc::kNu * mpc::kNu, false);
+    double* d_f = st.out(f, (size_t)B * mpc::kNu, false);
+    int* d_it = st.out(iters, (size_t)B, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "mpc_lateral", mpc::mpc_lateral_kernel, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave),
+                              dim3(64), 0, B, max_path, mpc_params(p), d_path, d_np, d_state, d_vx, d_mi, d_steer, d_u, d_e, d_k, d_mo,
+                              d_pp, d_H, d_f, d_it, d_st))
+        return rc;
     return st.finish();
 }
 
@@ -2559,43 +2319,27 @@ int emp_lqr_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
                     const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
                     double* steer, double* K, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
                     int32_t* sweeps, int32_t* status, emp_mem where) {
-    using namespace emp;
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
     EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
-    EMP_HIP(ctx, hipSetDevice(ctx->device));
-    Stage st(ctx, where);
-    int rc;
-    const double *d_path, *d_state, *d_vx;
-    const int *d_np, *d_mi;
-    double *d_steer, *d_K = nullptr, *d_e = nullptr, *d_k = nullptr, *d_pp = nullptr;
-    int *d_mo, *d_sw = nullptr, *d_st;
-    if ((rc = st.in(target_path, (size_t)B * max_path * 4, &d_path))) return rc;
-    if ((rc = st.in(n_path, (size_t)B, &d_np))) return rc;
-    if ((rc = st.in(state, (size_t)B * 5, &d_state))) return rc;
-    if ((rc = st.in(vx, (size_t)B, &d_vx))) return rc;
-    if ((rc = st.in(min_index, (size_t)B, &d_mi))) return rc;
-    if ((rc = st.out(steer, (size_t)B, &d_steer, false))) return rc;
-    if (K && (rc = st.out(K, (size_t)B * 4, &d_K, false))) return rc;
-    if (e_rr && (rc = st.out(e_rr, (size_t)B * 4, &d_e, false))) return rc;
-    if (k_r && (rc = st.out(k_r, (size_t)B, &d_k, false))) return rc;
-    if ((rc = st.out(min_index_out, (size_t)B, &d_mo, false))) return rc;
-    if (pre_pro && (rc = st.out(pre_pro, (size_t)B * 4, &d_pp, false))) return rc;
-    if (sweeps && (rc = st.out(sweeps, (size_t)B, &d_sw, false))) return rc;
-    if ((rc = st.out(status, (size_t)B, &d_st, false))) return rc;
-    if (B) {
-        mpc::Params prm;
-        prm.a = p->a; prm.b = p->b; prm.Cf = p->Cf; prm.Cr = p->Cr; prm.m = p->m; prm.Iz = p->Iz;
-        for (int i = 0; i < 4; ++i) {
-            prm.q[i] = p->q_diag[i];
-            prm.f[i] = p->f_diag[i];
-        }
-        prm.r = p->r;
-        KernelTimer t(ctx, "lqr_lateral");
-        hipLaunchKernelGGL(lqr::lqr_lateral_kernel, grid1(B, 64), dim3(64), 0, ctx->stream, B, max_path, prm, d_path, d_np,
-                           d_state, d_vx, d_mi, d_steer, d_K, d_e, d_k, d_mo, d_pp, d_sw, d_st);
-        EMP_LAUNCH_CHECK(ctx);
-    }
+    EMP_STAGE(st, where);
+    const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
+    const int* d_np = st.in(n_path, (size_t)B);
+    const double* d_state = st.in(state, (size_t)B * 5);
+    const double* d_vx = st.in(vx, (size_t)B);
+    const int* d_mi = st.in(min_index, (size_t)B);
+    double* d_steer = st.out(steer, (size_t)B, false);
+    double* d_K = st.out(K, (size_t)B * 4, false);
+    double* d_e = st.out(e_rr, (size_t)B * 4, false);
+    double* d_k = st.out(k_r, (size_t)B, false);
+    int* d_mo = st.out(min_index_out, (size_t)B, false);
+    double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
+    int* d_sw = st.out(sweeps, (size_t)B, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "lqr_lateral", lqr::lqr_lateral_kernel, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(p), d_path,
+                              d_np, d_state, d_vx, d_mi, d_steer, d_K, d_e, d_k, d_mo, d_pp, d_sw, d_st))
+        return rc;
     return st.finish();
 }
 

@@ -109,15 +109,7 @@ struct emp_ctx {
     char* arena_d_in = nullptr;         // device, kArena bytes each
     char* arena_d_out = nullptr;
     bool arena_failed = false;          // an allocation failed once: the per-array path from then on
-    // STAGED: the event the front stage's LAST kernel (the sweep) is asked to signal when it completes (hipExtLaunchKernelGGL's
-    // stop event: no marker packet behind the kernel), and the event that launch did attach - its own timing event when the
-    // kernel is being timed, else front_stop, else nullptr (launchers that attach nothing: the caller records an event).
-    hipEvent_t front_stop = nullptr, front_attached = nullptr;
-    // The planning cycle leaves the DP backtrack to the densification kernel (dp_sweep_kernel, BT == false): the caller offers
-    // the two buffers, the sweep's launcher sets bt_deferred when it used them (compiled row counts only).
-    unsigned char* bt_pre = nullptr;
-    int* bt_term = nullptr;
-    bool bt_deferred = false;
+    bool stage_open = false;            // a Stage is in its input phase: kernel launches are refused until its ready()
     int pipe_mode = 0;                  // 0 off, 1 STAGED, n >= 2 LANES with n lanes
     int lane = 0;                       // lane of the latest pipelined cycle call
     uint64_t cycle_calls = 0;           // pipelined emp_plan_cycle calls issued so far (emp_cycle_ticket)
@@ -134,16 +126,8 @@ struct emp_ctx {
     long long cycle_graph_replays = 0;
     unsigned long long alloc_gen = 0, cycle_graph_gen = 0;
     bool capturing = false;             // launchers avoid what a stream capture cannot record (hipExtLaunchKernelGGL)
-    hipEvent_t edge_wait = nullptr;     // EMP_OPT_EDGE_AFTER_ENRICH: what the next edge-cost launch waits for on its stream
     hipEvent_t lane_edge_done = nullptr; // EMP_OPT_LANE_EDGE_ORDER: recorded behind the latest edge-cost launch of a lane-mode call (a lane's ev_edge)
-    // STAGED: an event the next densification / path-QP launch is asked to signal from its own dispatch (hipExtLaunchKernelGGL's
-    // stop event) instead of a marker packet behind it - a marker idles the back queue ~6 us, twice per step; `stop_attached`
-    // says whether the launcher did (it does not while the kernel carries timing events)
-    hipEvent_t attach_stop = nullptr;
-    bool stop_attached = false;
     hipEvent_t sweep_marker = nullptr;  // EMP_OPT_SWEEP_EXCLUSIVE: recorded on the front stream behind the sweep (emp_api.hip)
-    // EMP_OPT_SWEEP_EXCLUSIVE: the event the next sweep launch waits for on its own stream (the previous call's back stage)
-    hipEvent_t sweep_wait = nullptr;
     // EMP_OPT_SWEEP_CLOCK_PROBE: a ring of kProbeSlots launches x [tiles][4] ticks (shader-clock begin / end, reference
     // begin / end); probe_launches counts the launches recorded since the option was last switched on
     static constexpr int kProbeSlots = 32;
@@ -176,15 +160,17 @@ inline int fail(emp_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
+// the error of a failed HIP call (`what`: the call's text), or EMP_OK
+inline int hip_error(emp_ctx* ctx, hipError_t e, const char* what) {
+    if (e == hipSuccess) return EMP_OK;
+    (void)hipGetLastError();    // the runtime keeps the error for the next hipGetLastError(): without this, the launch check
+                                // of the NEXT call would report this call's failure
+    return fail(ctx, e == hipErrorOutOfMemory ? EMP_ERR_NOMEM : EMP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
 #define EMP_HIP(ctx, call)                                                                         \
     do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (void)hipGetLastError(); /* the runtime keeps the error for the next hipGetLastError(): without this, \
-                                        the launch check of the NEXT call would report this call's failure */ \
-            return emp::fail((ctx), e_ == hipErrorOutOfMemory ? EMP_ERR_NOMEM : EMP_ERR_HIP,       \
-                             std::string(#call) + ": " + hipGetErrorString(e_));                   \
-        }                                                                                          \
+        if (const int rc_ = emp::hip_error((ctx), (call), #call)) return rc_;                      \
     } while (0)
 
 #define EMP_REQUIRE(ctx, cond, msg)                                                               \
@@ -235,8 +221,14 @@ inline int pool_get(emp_ctx* ctx, size_t bytes, void** out) {
     return EMP_OK;
 }
 
-// Staging of one call's arguments.  For EMP_DEVICE pointers pass through; for EMP_HOST inputs are copied
-// to pool buffers and outputs are copied back in finish().
+// (inside Stage: keeps the first failure of a HIP call, true when it succeeded)
+#define EMP_KEEP(call) keep(emp::hip_error(ctx_, (call), #call))
+
+// Staging of one call's arguments.  For EMP_DEVICE pointers pass through; for EMP_HOST inputs are copied to the device and
+// outputs are copied back in finish().  A call stages its inputs, then its outputs and temporaries, then calls ready(): the one
+// check in front of its first launch.  Every staging call does nothing once one has failed; ready() returns that first failure,
+// sends the packed inputs still on the host and ends the input phase.  Until then the context refuses kernel launches
+// (emp_api.hip: launch_gate), and after it in() is refused.
 class Stage {
   public:
     // in_cycle: the pipelined emp_plan_cycle (and a launch placed on its lane) orders itself; every OTHER call in
@@ -248,61 +240,54 @@ class Stage {
     Stage(emp_ctx* c, emp_mem where, bool in_cycle = false, bool async_host = false)
         : ctx_(c), dev_(where == EMP_DEVICE), async_(async_host && where != EMP_DEVICE) {
         c->cursor = 0;
+        c->stage_open = true;
         arena_ = !dev_ && !async_ && where == EMP_HOST && !c->capturing;
         if (!in_cycle && c->pipelined() && c->fence)
             for (auto& ln : c->lanes)
                 if (ln.done_valid) (void)hipStreamWaitEvent(c->stream, ln.ev_done, 0);
     }
+    ~Stage() { ctx_->stage_open = false; }
+    Stage(const Stage&) = delete;
+    Stage& operator=(const Stage&) = delete;
 
+    // The device copy of an input (null for a null host pointer).  async_host: the device pointers are known only once every
+    // input is (inputs_ready() fills *slot then) - emp_plan_cycle's form with a slot.
     template <typename T>
-    int in(const T* host, size_t n, const T** out) {
-        if (host == nullptr) { *out = nullptr; return EMP_OK; }
-        if (dev_) { *out = host; return EMP_OK; }
-        if (async_) {            // deferred: inputs_ready() places all inputs of the call at once and fills *out then
-            ins_.push_back({(void*)host, nullptr, n * sizeof(T), (void**)out});
-            *out = reinterpret_cast<const T*>(kPending);
-            return EMP_OK;
-        }
-        if (arena_ && arena_take(n * sizeof(T), &in_used_)) {      // packed: one copy for all small inputs (flush_inputs)
-            const size_t off = in_used_ - arena_round(n * sizeof(T));
-            if (n) memcpy(ctx_->arena_h_in + off, host, n * sizeof(T));
-            *out = (const T*)(ctx_->arena_d_in + off);
-            return EMP_OK;
-        }
-        void* d = nullptr;
-        int rc = pool_get(ctx_, n * sizeof(T), &d);
-        if (rc) return rc;
-        if (n) EMP_HIP(ctx_, hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, ctx_->stream));
-        *out = (const T*)d;
-        return EMP_OK;
-    }
-    // The packed inputs gathered so far go to the device: ONE copy on the context's stream.  Called by every out() and tmp() -
-    // each entry point declares its outputs and temporaries behind its inputs and in front of its first launch - and by finish(),
-    // which refuses a call that launched with inputs still pending (a new entry point that breaks the order fails loudly).
-    int flush_inputs() {
-        if (in_used_ > in_sent_) {
-            EMP_HIP(ctx_, hipMemcpyAsync(ctx_->arena_d_in + in_sent_, ctx_->arena_h_in + in_sent_, in_used_ - in_sent_,
-                                         hipMemcpyHostToDevice, ctx_->stream));
-            in_sent_ = in_used_;
-        }
-        return EMP_OK;
+    const T* in(const T* host, size_t n) { return (const T*)stage_in(host, n * sizeof(T), nullptr); }
+    template <typename T>
+    void in(const T* host, size_t n, const T** slot) { *slot = (const T*)stage_in(host, n * sizeof(T), (void**)slot); }
+    // Outputs are zero-filled on the context's stream before the kernels run, so padding beyond a scene's length reads as 0 in
+    // both memory spaces (pass zero=false for arrays the kernels fully overwrite).  async_host: outputs_ready() fills *slot.
+    template <typename T>
+    T* out(T* host, size_t n, bool zero = true) { return (T*)stage_out(host, n * sizeof(T), zero, nullptr); }
+    template <typename T>
+    void out(T* host, size_t n, T** slot, bool zero) { *slot = (T*)stage_out(host, n * sizeof(T), zero, (void**)slot); }
+    // device-only temporary
+    template <typename T>
+    T* tmp(size_t n, bool zero = false) {
+        if (!flush_inputs()) return nullptr;
+        void* v = get(n * sizeof(T));
+        if (v && zero && n) EMP_KEEP(hipMemsetAsync(v, 0, n * sizeof(T), ctx_->stream));
+        return rc_ ? nullptr : (T*)v;
     }
     // async_host: every input of the call is known.  Arrays that lie side by side in host memory (a HostRing slot is ONE
     // page-locked block: api.py) get one device block at the same offsets and cross PCIe as ONE copy - a copy command costs
     // 10-20 us of host and engine time whatever its size, and a call has nine inputs; others are copied one by one.  Then the
     // compute stream waits for the copy stream.
-    int inputs_ready() {
-        if (!async_) return EMP_OK;
-        int rc = place(ins_, true);
-        if (rc) return rc;
-        EMP_HIP(ctx_, hipEventRecord(ctx_->ev_h2d, ctx_->copy_stream));
-        EMP_HIP(ctx_, hipStreamWaitEvent(ctx_->stream, ctx_->ev_h2d, 0));
-        return EMP_OK;
+    void inputs_ready() {
+        if (!async_ || rc_ || !place(ins_, true)) return;
+        if (EMP_KEEP(hipEventRecord(ctx_->ev_h2d, ctx_->copy_stream))) EMP_KEEP(hipStreamWaitEvent(ctx_->stream, ctx_->ev_h2d, 0));
     }
     // async_host: every output of the call is known - device buffers for them, one block where the host arrays are one block
-    int outputs_ready() {
-        if (!async_) return EMP_OK;
-        return place(backs_, false);
+    void outputs_ready() {
+        if (async_ && !rc_) place(backs_, false);
+    }
+    // The check in front of the call's first launch (see above).  A temporary staged after it (emp_plan_cycle) is checked by
+    // calling it again.
+    int ready() {
+        flush_inputs();
+        open_ = ctx_->stage_open = false;
+        return rc_;
     }
     // async_host: copy the outputs back on the d2h stream once `after` (the cycle's completion event) has fired, then signal `done`
     int finish_async(hipEvent_t after, hipEvent_t done) {
@@ -317,58 +302,8 @@ class Stage {
         return EMP_OK;
     }
     bool async_host() const { return async_; }
-    // Outputs are zero-filled on the context's stream before the kernels run, so padding beyond a scene's
-    // length reads as 0 in both memory spaces (pass zero=false for arrays the kernels fully overwrite).
-    template <typename T>
-    int out(T* host, size_t n, T** outp, bool zero = true) {
-        if (host == nullptr) { *outp = nullptr; return EMP_OK; }
-        T* d = host;
-        if (async_) {            // deferred: outputs_ready()
-            backs_.push_back({host, nullptr, n * sizeof(T), (void**)outp});
-            *outp = reinterpret_cast<T*>(kPending);
-            return EMP_OK;
-        }
-        if (!dev_) {
-            int rcf = flush_inputs();
-            if (rcf) return rcf;
-            if (arena_ && arena_take(n * sizeof(T), &out_used_)) {       // packed: one zero fill, one copy back (finish)
-                const size_t off = out_used_ - arena_round(n * sizeof(T));
-                if (!out_zeroed_) {      // the whole output arena once per call instead of a memset per array
-                    EMP_HIP(ctx_, hipMemsetAsync(ctx_->arena_d_out, 0, emp_ctx::kArena, ctx_->stream));
-                    out_zeroed_ = true;
-                }
-                arena_backs_.push_back({host, nullptr, n * sizeof(T), nullptr});
-                arena_offs_.push_back(off);
-                *outp = (T*)(ctx_->arena_d_out + off);
-                return EMP_OK;
-            }
-            void* v = nullptr;
-            int rc = pool_get(ctx_, n * sizeof(T), &v);
-            if (rc) return rc;
-            d = (T*)v;
-            backs_.push_back({host, d, n * sizeof(T), nullptr});
-        }
-        if (zero && n) EMP_HIP(ctx_, hipMemsetAsync(d, 0, n * sizeof(T), ctx_->stream));
-        *outp = d;
-        return EMP_OK;
-    }
-    // device-only temporary
-    template <typename T>
-    int tmp(size_t n, T** outp, bool zero = false) {
-        if (!dev_ && !async_) {
-            int rcf = flush_inputs();
-            if (rcf) return rcf;
-        }
-        void* v = nullptr;
-        int rc = pool_get(ctx_, n * sizeof(T), &v);
-        if (rc) return rc;
-        if (zero && n) EMP_HIP(ctx_, hipMemsetAsync(v, 0, n * sizeof(T), ctx_->stream));
-        *outp = (T*)v;
-        return EMP_OK;
-    }
     int finish() {
-        if (in_used_ > in_sent_)      // (cannot happen with the entry points as they are: see flush_inputs)
-            return emp::fail(ctx_, EMP_ERR_INVALID, "internal: packed inputs were never sent (an entry point launched before declaring its outputs)");
+        if (rc_) return rc_;
         for (auto& b : backs_)
             if (b.bytes) EMP_HIP(ctx_, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, ctx_->stream));
         if (out_used_) EMP_HIP(ctx_, hipMemcpyAsync(ctx_->arena_h_out, ctx_->arena_d_out, out_used_, hipMemcpyDeviceToHost, ctx_->stream));
@@ -377,7 +312,6 @@ class Stage {
             if (arena_backs_[i].bytes) memcpy(arena_backs_[i].host, ctx_->arena_h_out + arena_offs_[i], arena_backs_[i].bytes);
         return EMP_OK;
     }
-    bool on_device() const { return dev_; }
 
   private:
     struct Back {
@@ -387,6 +321,74 @@ class Stage {
         void** slot;       // async_host: where the device pointer goes once it is known
     };
     static constexpr uintptr_t kPending = 8;     // non-null placeholder of a deferred pointer (never dereferenced)
+    // keeps the first failure of the call; true when `rc` is none
+    bool keep(int rc) {
+        if (rc) rc_ = rc;
+        return rc == EMP_OK;
+    }
+    bool refuse(const char* msg) { return keep(emp::fail(ctx_, EMP_ERR_INVALID, msg)); }
+    void* get(size_t bytes) {
+        void* d = nullptr;
+        return keep(pool_get(ctx_, bytes, &d)) ? d : nullptr;
+    }
+    // deferred (async_host): the device pointer is written to *slot by place()
+    void* defer(std::vector<Back>& v, void* host, size_t bytes, void** slot) {
+        if (!slot) {
+            refuse("internal: an EMP_HOST_PINNED array was staged without a slot");
+            return nullptr;
+        }
+        v.push_back({host, nullptr, bytes, slot});
+        return (void*)kPending;
+    }
+    const void* stage_in(const void* host, size_t bytes, void** slot) {
+        if (rc_ || !host) return nullptr;
+        if (!open_) {
+            refuse("internal: Stage::in() after ready()");
+            return nullptr;
+        }
+        if (dev_) return host;
+        if (async_) return defer(ins_, (void*)host, bytes, slot);
+        if (arena_ && arena_take(bytes, &in_used_)) {      // packed: one copy for all small inputs (flush_inputs)
+            const size_t off = in_used_ - arena_round(bytes);
+            if (bytes) memcpy(ctx_->arena_h_in + off, host, bytes);
+            return ctx_->arena_d_in + off;
+        }
+        void* d = get(bytes);
+        if (d && bytes) EMP_KEEP(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, ctx_->stream));
+        return rc_ ? nullptr : d;
+    }
+    void* stage_out(void* host, size_t bytes, bool zero, void** slot) {
+        if (!flush_inputs() || !host) return nullptr;
+        if (async_) return defer(backs_, host, bytes, slot);
+        void* d = host;
+        if (!dev_) {
+            if (arena_ && arena_take(bytes, &out_used_)) {       // packed: one zero fill, one copy back (finish)
+                const size_t off = out_used_ - arena_round(bytes);
+                if (!out_zeroed_) {      // the whole output arena once per call instead of a memset per array
+                    if (!EMP_KEEP(hipMemsetAsync(ctx_->arena_d_out, 0, emp_ctx::kArena, ctx_->stream))) return nullptr;
+                    out_zeroed_ = true;
+                }
+                arena_backs_.push_back({host, nullptr, bytes, nullptr});
+                arena_offs_.push_back(off);
+                return ctx_->arena_d_out + off;
+            }
+            if (!(d = get(bytes))) return nullptr;
+            backs_.push_back({host, d, bytes, nullptr});
+        }
+        if (zero && bytes && !EMP_KEEP(hipMemsetAsync(d, 0, bytes, ctx_->stream))) return nullptr;
+        return d;
+    }
+    // The packed inputs gathered so far go to the device: ONE copy on the context's stream, issued by the first out() or tmp()
+    // and by ready().  False once the call has failed.
+    bool flush_inputs() {
+        if (!rc_ && in_used_ > in_sent_) {
+            if (!EMP_KEEP(hipMemcpyAsync(ctx_->arena_d_in + in_sent_, ctx_->arena_h_in + in_sent_, in_used_ - in_sent_,
+                                         hipMemcpyHostToDevice, ctx_->stream)))
+                return false;
+            in_sent_ = in_used_;
+        }
+        return rc_ == EMP_OK;
+    }
     // device memory for a call's arrays (async_host).  ONE device block with the host offsets - and one PCIe copy per direction -
     // only where that provably touches nothing but the call's own arrays: all of them inside ONE emp_host_alloc allocation of
     // this context, with at most kBlockGap bytes (alignment padding) between neighbours.  Outputs moved as a block overwrite
@@ -414,34 +416,30 @@ class Stage {
             }
         return false;
     }
-    int place(std::vector<Back>& v, bool inputs) {
-        if (v.empty()) return EMP_OK;
+    bool place(std::vector<Back>& v, bool inputs) {
+        if (v.empty()) return true;
         uintptr_t lo = 0;
         size_t span = 0;
         if (one_block(v, &lo, &span)) {
-            void* d = nullptr;
-            int rc = pool_get(ctx_, span, &d);
-            if (rc) return rc;
+            void* d = get(span);
+            if (!d) return false;
             for (auto& b : v) {
                 b.dev = b.bytes ? (char*)d + ((uintptr_t)b.host - lo) : d;
                 *b.slot = b.dev;
             }
-            if (inputs) {
-                EMP_HIP(ctx_, hipMemcpyAsync(d, (void*)lo, span, hipMemcpyHostToDevice, ctx_->copy_stream));
-            } else {
-                block_out_ = {(void*)lo, d, span, nullptr};
-            }
-            return EMP_OK;
+            if (inputs) return EMP_KEEP(hipMemcpyAsync(d, (void*)lo, span, hipMemcpyHostToDevice, ctx_->copy_stream));
+            block_out_ = {(void*)lo, d, span, nullptr};
+            return true;
         }
         for (auto& b : v) {
-            void* d = nullptr;
-            int rc = pool_get(ctx_, b.bytes, &d);
-            if (rc) return rc;
+            void* d = get(b.bytes);
+            if (!d) return false;
             b.dev = d;
             *b.slot = d;
-            if (inputs && b.bytes) EMP_HIP(ctx_, hipMemcpyAsync(d, b.host, b.bytes, hipMemcpyHostToDevice, ctx_->copy_stream));
+            if (inputs && b.bytes && !EMP_KEEP(hipMemcpyAsync(d, b.host, b.bytes, hipMemcpyHostToDevice, ctx_->copy_stream)))
+                return false;
         }
-        return EMP_OK;
+        return true;
     }
     static size_t arena_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     // room for `bytes` in an arena whose fill mark is *used?  Creates the four arenas on first use; false = take the per-array path
@@ -470,16 +468,19 @@ class Stage {
         return true;
     }
     emp_ctx* ctx_;
-    bool dev_, async_, arena_ = false, out_zeroed_ = false;
+    int rc_ = EMP_OK;                            // the call's first failure
+    bool dev_, async_, arena_ = false, out_zeroed_ = false, open_ = true;
     size_t in_used_ = 0, in_sent_ = 0, out_used_ = 0;
     std::vector<Back> arena_backs_;
     std::vector<size_t> arena_offs_;
     std::vector<Back> backs_, ins_;
     Back block_out_ = {nullptr, nullptr, 0, nullptr};
 };
+#undef EMP_KEEP
 
 // RAII kernel timer: when ctx->timing is on, brackets a launch with a fresh HIP event pair on the context's
-// stream.  emp_kernel_ms() later averages all pairs recorded since timing was (re-)enabled.
+// stream (none for a null name: a kernel that is never timed).  emp_kernel_ms() later averages all pairs recorded since
+// timing was (re-)enabled.
 struct KernelTimer {
     emp_ctx* ctx;
     hipEvent_t start = nullptr, stop = nullptr;
@@ -488,7 +489,7 @@ struct KernelTimer {
     // hipExtLaunchKernelGGL, which stamps the kernel's own begin and end (no extra stream packets, and the
     // interval excludes the wait between the record and the kernel's start)
     KernelTimer(emp_ctx* c, const char* name, bool attach = false) : ctx(c), attached(attach) {
-        if (!c->timing) return;
+        if (!c->timing || !name) return;
         if (!c->timing_filter.empty() && c->timing_filter != name) return;
         emp_ctx::Ev& e = c->events[name];
         if (e.used == e.pairs.size()) {
