@@ -83,6 +83,17 @@ class MpcParams(C.Structure):
                 ("Iz", C.c_double), ("q_diag", C.c_double * 4), ("f_diag", C.c_double * 4), ("r", C.c_double)]
 
 
+class PidParams(C.Structure):
+    """emp_pid_params: the gains of Longitudinal_PID_controller (controller.py:622-638)."""
+    _fields_ = [("K_P", C.c_double), ("K_I", C.c_double), ("K_D", C.c_double), ("dt", C.c_double),
+                ("error_threshold", C.c_double)]
+
+
+PID_BUFFER = 60                    # EMP_PID_BUFFER: the error deque's maxlen (controller.py:637)
+MPC_FF_CONTROLS = 8                # EMP_MPC_FF_CONTROLS
+EMP_LAT_MPC, EMP_LAT_LQR = 0, 1
+
+
 class SpeedQpParams(C.Structure):
     """emp_speed_qp_params: keyword arguments of the reference's speed_QP (speed_planning_test.py:410-411)."""
     _fields_ = [("w_cost_s_dot2", C.c_double), ("w_cost_v_ref", C.c_double), ("w_cost_jerk", C.c_double),
@@ -179,6 +190,12 @@ PROTOTYPES = {
     "emp_mpc_lateral": (C.c_int, [_vp, C.POINTER(MpcParams), _i32, _i32] + [_vp] * 15 + [C.c_int]),
     "emp_lqr_params_default": (None, [C.POINTER(MpcParams)]),
     "emp_lqr_lateral": (C.c_int, [_vp, C.POINTER(MpcParams), _i32, _i32] + [_vp] * 13 + [C.c_int]),
+    "emp_pid_params_default": (None, [C.POINTER(PidParams)]),
+    "emp_pid_longitudinal": (C.c_int, [_vp, C.POINTER(PidParams), _i32] + [_vp] * 7 + [C.c_int]),
+    "emp_mpc_ff_params_default": (None, [C.POINTER(MpcParams)]),
+    "emp_mpc_ff_lateral": (C.c_int, [_vp, C.POINTER(MpcParams), _i32, _i32] + [_vp] * 15 + [C.c_int]),
+    "emp_vehicle_control": (C.c_int, [_vp, _i32, C.POINTER(MpcParams), C.POINTER(PidParams), _i32, _i32] + [_vp] * 19
+                            + [C.c_int]),
     "emp_speed_dp_params_default": (None, [C.POINTER(SpeedDpParams)]),
     "emp_st_graph": (C.c_int, [_vp, _i32, _i32] + [_vp] * 8 + [C.c_int]),
     "emp_speed_dp": (C.c_int, [_vp, C.POINTER(SpeedDpParams), _i32, _i32] + [_vp] * 11 + [C.c_int]),
@@ -217,7 +234,7 @@ def load():
         fn = getattr(lib, name)   # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args
-    if lib.emp_abi_version() != 11:
+    if lib.emp_abi_version() != 12:
         raise RuntimeError("libemplanner.so ABI version mismatch")
     _lib = lib
     return lib

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from ._lib import DpParams, QpParams, SmoothParams, SpeedDpParams, SpeedQpParams, MpcParams, EmpError
+from ._lib import DpParams, QpParams, SmoothParams, SpeedDpParams, SpeedQpParams, MpcParams, PidParams, EmpError
 
 
 def dp_params(row=12, col=6, sample_s=15, sample_l=1.5, sampling_res=2, w_collision_cost=1e12,
@@ -70,6 +70,39 @@ def lqr_params(vehicle_para=(1.015, 2.910 - 1.015, 1412, -148970, -82204, 1537),
                r=1.0) -> MpcParams:
     """Parameters of Lateral_LQR_controller._control (controller.py:592-598); vehicle_para unpacked as in mpc_params."""
     return mpc_params(vehicle_para=vehicle_para, q_diag=q_diag, r=r)
+
+
+def mpc_ff_params(vehicle_para=(1.015, 2.910 - 1.015, 1412, -148970, -82204, 1537), q_diag=(200.0, 1.0, 1.0, 1.0),
+                  f_diag=(10.0, 10.0, 10.0, 10.0), r=1.0) -> MpcParams:
+    """Parameters of Lateral_MPC__with_feedforward_controller.MPC_control (controller.py:974-979); vehicle_para unpacked as
+    in mpc_params."""
+    return mpc_params(vehicle_para=vehicle_para, q_diag=q_diag, f_diag=f_diag, r=r)
+
+
+def pid_params(K_P=1.15, K_I=0.0, K_D=0.0, dt=0.01, error_threshold=1.0) -> PidParams:
+    """Gains of Longitudinal_PID_controller (controller.py:622-638; its defaults)."""
+    return PidParams(float(K_P), float(K_I), float(K_D), float(dt), float(error_threshold))
+
+
+@dataclass
+class PidResult:
+    command: object      # (B,) K_P e + K_I integral + K_D derivative
+    err: object          # (B, 60) the error buffer after the call, oldest first; entries past n_err are 0
+    n_err: object        # (B,) int32 entries in the buffer
+
+
+@dataclass
+class VehicleControlResult:
+    control: object      # (B, 3) throttle, steer, brake (carla.VehicleControl's three fields)
+    lat_command: object  # (B,) raw lateral command (what mpc_lateral / lqr_lateral return as steer)
+    lon_command: object  # (B,) PID command
+    min_index: object    # (B,) int32
+    e_rr: object         # (B, 4)
+    k_r: object          # (B,)
+    pre_pro: object      # (B, 4)
+    err: object          # (B, 60) PID error buffer after the step (unchanged where status != 0)
+    n_err: object        # (B,) int32
+    status: object       # (B,) int32 status of the lateral law
 
 
 @dataclass
@@ -135,6 +168,18 @@ class SpeedDpResult:
 
 def _is_torch(x):
     return hasattr(x, "data_ptr") and hasattr(x, "device")
+
+
+def _same_array(x, dtype):
+    """``x`` itself as an output of a call that updates it in place: it must already have the call's dtype and layout (a
+    converted copy would leave the caller's array untouched)."""
+    if _is_torch(x):
+        ok = x.is_contiguous() and str(x.dtype) == {np.float64: "torch.float64", np.int32: "torch.int32"}[dtype]
+    else:
+        ok = isinstance(x, np.ndarray) and x.dtype == dtype and x.flags.c_contiguous and x.flags.writeable
+    if not ok:
+        raise ValueError(f"in_place needs a contiguous, writable {np.dtype(dtype).name} array")
+    return x
 
 
 class _Args:
@@ -783,6 +828,81 @@ class Planner:
             a.inp(state, np.float64, (B, 5)), a.inp(vx, np.float64, (B,)), a.inp(min_index, np.int32, (B,)), sp_, Kp, ep, kp,
             mip, ppp, swp, stp, a.where))
         return LqrResult(steer, K, e, k, mi, pp, sw, st)
+
+    def mpc_ff_lateral(self, p: MpcParams, target_path, n_path, state, vx, min_index, qp_matrices=False) -> MpcResult:
+        """ref Lateral_MPC__with_feedforward_controller.MPC_control for B vehicles (inputs as mpc_lateral; vx unclamped,
+        min_index only the fallback of a whole-path search).  u is (B, 8); H (B, 8, 8) and f (B, 8) with qp_matrices."""
+        a = self._args(target_path, state)
+        B, M = int(target_path.shape[0]), int(target_path.shape[1])
+        nu = L.MPC_FF_CONTROLS
+        steer, sp_ = a.out((B,), np.float64)
+        u, up = a.out((B, nu), np.float64)
+        e, ep = a.out((B, 4), np.float64)
+        k, kp = a.out((B,), np.float64)
+        mi, mip = a.out((B,), np.int32)
+        pp, ppp = a.out((B, 4), np.float64)
+        H, Hp = a.out((B, nu, nu), np.float64) if qp_matrices else (None, None)
+        f, fp = a.out((B, nu), np.float64) if qp_matrices else (None, None)
+        it, itp = a.out((B,), np.int32)
+        st, stp = a.out((B,), np.int32)
+        self._check(self._lib.emp_mpc_ff_lateral(
+            self._h, C.byref(p), B, M, a.inp(target_path, np.float64, (B, M, 4)), a.inp(n_path, np.int32, (B,)),
+            a.inp(state, np.float64, (B, 5)), a.inp(vx, np.float64, (B,)), a.inp(min_index, np.int32, (B,)), sp_, up, ep, kp,
+            mip, ppp, Hp, fp, itp, stp, a.where))
+        return MpcResult(steer, u, e, k, mi, pp, H, f, it, st)
+
+    # ---- longitudinal PID and the fused vehicle-control step (reference controller/controller.py:614-724) -------
+    def pid_longitudinal(self, p: PidParams, speed_kmh, target_speed, err, n_err, in_place=False) -> PidResult:
+        """ref Longitudinal_PID_controller.PID_control for B vehicles: speed_kmh (B,) = 3.6 |velocity|, target_speed (B,),
+        err (B, 60) the error deque oldest first with n_err (B,) entries.  in_place=True writes the new buffer back into
+        ``err`` / ``n_err`` (they must then be float64 / int32 and contiguous): a fleet keeps its PID state where it lives."""
+        a = self._args(speed_kmh, err)
+        B = len(speed_kmh)
+        nb = L.PID_BUFFER
+        cmd, cp = a.out((B,), np.float64)
+        ein, niin = a.inp(err, np.float64, (B, nb)), a.inp(n_err, np.int32, (B,))
+        if in_place:
+            eo, eop = a.out((B, nb), np.float64, into=_same_array(err, np.float64))
+            no, nop = a.out((B,), np.int32, into=_same_array(n_err, np.int32))
+        else:
+            eo, eop = a.out((B, nb), np.float64)
+            no, nop = a.out((B,), np.int32)
+        self._check(self._lib.emp_pid_longitudinal(
+            self._h, C.byref(p), B, a.inp(speed_kmh, np.float64, (B,)), a.inp(target_speed, np.float64, (B,)), ein, niin, cp,
+            eop, nop, a.where))
+        return PidResult(cmd, eo, no)
+
+    def vehicle_control(self, lat: MpcParams, pid: PidParams, target_path, n_path, state, vx, min_index, speed_kmh,
+                        target_speed, err, n_err, lateral="mpc", in_place=False) -> VehicleControlResult:
+        """ref Vehicle_control.run_step for B vehicles in one kernel launch: the lateral law (``lateral`` = "mpc": as
+        mpc_lateral, "lqr": as lqr_lateral, with ``lat`` as their params and the same inputs), the PID step (as
+        pid_longitudinal) and the actuation.  in_place=True updates ``err`` / ``n_err`` as pid_longitudinal does."""
+        law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
+        if law is None:
+            raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+        a = self._args(target_path, state, err)
+        B, M = int(target_path.shape[0]), int(target_path.shape[1])
+        nb = L.PID_BUFFER
+        ins = [a.inp(target_path, np.float64, (B, M, 4)), a.inp(n_path, np.int32, (B,)), a.inp(state, np.float64, (B, 5)),
+               a.inp(vx, np.float64, (B,)), a.inp(min_index, np.int32, (B,)), a.inp(speed_kmh, np.float64, (B,)),
+               a.inp(target_speed, np.float64, (B,)), a.inp(err, np.float64, (B, nb)), a.inp(n_err, np.int32, (B,))]
+        ctl, ctp = a.out((B, 3), np.float64)
+        lc, lcp = a.out((B,), np.float64)
+        oc, ocp = a.out((B,), np.float64)
+        mi, mip = a.out((B,), np.int32)
+        e, ep = a.out((B, 4), np.float64)
+        k, kp = a.out((B,), np.float64)
+        pp, ppp = a.out((B, 4), np.float64)
+        if in_place:
+            eo, eop = a.out((B, nb), np.float64, into=_same_array(err, np.float64))
+            no, nop = a.out((B,), np.int32, into=_same_array(n_err, np.int32))
+        else:
+            eo, eop = a.out((B, nb), np.float64)
+            no, nop = a.out((B,), np.int32)
+        st, stp = a.out((B,), np.int32)
+        self._check(self._lib.emp_vehicle_control(
+            self._h, law, C.byref(lat), C.byref(pid), B, M, *ins, ctp, lcp, ocp, mip, ep, kp, ppp, eop, nop, stp, a.where))
+        return VehicleControlResult(ctl, lc, oc, mi, e, k, pp, eo, no, st)
 
     # ---- S-T speed DP (reference planner/speed_planning_test.py) ------------------------------
     def st_graph(self, obs_s, obs_l, obs_s_dot, obs_l_dot):

@@ -2302,9 +2302,9 @@ int emp_mpc_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
     int* d_it = st.out(iters, (size_t)B, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, "mpc_lateral", mpc::mpc_lateral_kernel, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave),
+    if (const int rc = launch(ctx, "mpc_lateral", mpc::mpc_lateral_kernel<false>, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave),
                               dim3(64), 0, B, max_path, mpc_params(p), d_path, d_np, d_state, d_vx, d_mi, d_steer, d_u, d_e, d_k, d_mo,
-                              d_pp, d_H, d_f, d_it, d_st))
+                              d_pp, d_H, d_f, d_it, d_st, mpc::CtlIO{}))
         return rc;
     return st.finish();
 }
@@ -2337,9 +2337,154 @@ int emp_lqr_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
     int* d_sw = st.out(sweeps, (size_t)B, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, "lqr_lateral", lqr::lqr_lateral_kernel, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(p), d_path,
-                              d_np, d_state, d_vx, d_mi, d_steer, d_K, d_e, d_k, d_mo, d_pp, d_sw, d_st))
+    if (const int rc = launch(ctx, "lqr_lateral", lqr::lqr_lateral_kernel<false>, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(p),
+                              d_path, d_np, d_state, d_vx, d_mi, d_steer, d_K, d_e, d_k, d_mo, d_pp, d_sw, d_st, mpc::CtlIO{}))
         return rc;
+    return st.finish();
+}
+
+}  // extern "C"
+
+// ---- longitudinal PID, feed-forward MPC, fused vehicle control (reference controller/controller.py:614-990) ----------
+namespace {
+
+// ref: Longitudinal_PID_controller.PID_control for B vehicles, one per lane
+__global__ __launch_bounds__(256) void pid_longitudinal_kernel(int B, ctl::PidParams p, const double* __restrict__ speed_kmh,
+                                                               const double* __restrict__ target_speed, const double* err_in,
+                                                               const int* n_err_in, double* __restrict__ command, double* err_out,
+                                                               int* n_err_out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int n = 0;
+    command[b] = ctl::pid_step(p, speed_kmh[b], target_speed[b], err_in + (size_t)b * ctl::kPidBuffer, n_err_in[b],
+                               err_out + (size_t)b * ctl::kPidBuffer, &n);
+    n_err_out[b] = n;
+}
+
+ctl::PidParams pid_params(const emp_pid_params* p) { return ctl::PidParams{p->K_P, p->K_I, p->K_D, p->dt, p->error_threshold}; }
+
+}  // namespace
+
+extern "C" {
+
+void emp_pid_params_default(emp_pid_params* p) {
+    if (!p) return;
+    p->K_P = 1.15;                                          // ref controller.py:622
+    p->K_I = 0.0;
+    p->K_D = 0.0;
+    p->dt = 0.01;
+    p->error_threshold = 1.0;                               // ref :638
+}
+
+int emp_pid_longitudinal(emp_ctx* ctx, const emp_pid_params* p, int32_t B, const double* speed_kmh, const double* target_speed,
+                         const double* err_in, const int32_t* n_err_in, double* command, double* err_out, int32_t* n_err_out,
+                         emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, p && B >= 0, "bad sizes");
+    EMP_REQUIRE(ctx, speed_kmh && target_speed && err_in && n_err_in && command && err_out && n_err_out, "NULL argument");
+    EMP_STAGE(st, where);
+    const double* d_v = st.in(speed_kmh, (size_t)B);
+    const double* d_t = st.in(target_speed, (size_t)B);
+    const double* d_ei = st.in(err_in, (size_t)B * ctl::kPidBuffer);
+    const int* d_ni = st.in(n_err_in, (size_t)B);
+    double* d_c = st.out(command, (size_t)B, false);
+    double* d_eo = st.out(err_out, (size_t)B * ctl::kPidBuffer, false);
+    int* d_no = st.out(n_err_out, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "pid_longitudinal", pid_longitudinal_kernel, grid1(B, 256), dim3(256), 0, B, pid_params(p), d_v, d_t,
+                              d_ei, d_ni, d_c, d_eo, d_no))
+        return rc;
+    return st.finish();
+}
+
+void emp_mpc_ff_params_default(emp_mpc_params* p) {
+    if (!p) return;
+    emp_mpc_params_default(p);                              // vehicle_para as there
+    const double q[4] = {200.0, 1.0, 1.0, 1.0};             // ref controller.py:974-979
+    for (int i = 0; i < 4; ++i) {
+        p->q_diag[i] = q[i];
+        p->f_diag[i] = 10.0;
+    }
+    p->r = 1.0;
+}
+
+int emp_mpc_ff_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t max_path, const double* target_path,
+                       const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
+                       double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
+                       double* H, double* f, int32_t* iters, int32_t* status, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
+    EMP_STAGE(st, where);
+    const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
+    const int* d_np = st.in(n_path, (size_t)B);
+    const double* d_state = st.in(state, (size_t)B * 5);
+    const double* d_vx = st.in(vx, (size_t)B);
+    const int* d_mi = st.in(min_index, (size_t)B);
+    double* d_steer = st.out(steer, (size_t)B, false);
+    double* d_u = st.out(u, (size_t)B * mpcff::kNu, false);
+    double* d_e = st.out(e_rr, (size_t)B * 4, false);
+    double* d_k = st.out(k_r, (size_t)B, false);
+    int* d_mo = st.out(min_index_out, (size_t)B, false);
+    double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
+    double* d_H = st.out(H, (size_t)B * mpcff::kNu * mpcff::kNu, false);
+    double* d_f = st.out(f, (size_t)B * mpcff::kNu, false);
+    int* d_it = st.out(iters, (size_t)B, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "mpc_ff_lateral", mpcff::mpc_ff_lateral_kernel,
+                              dim3((B + mpcff::kGroupsPerWave - 1) / mpcff::kGroupsPerWave), dim3(64), 0, B, max_path, mpc_params(p),
+                              d_path, d_np, d_state, d_vx, d_mi, d_steer, d_u, d_e, d_k, d_mo, d_pp, d_H, d_f, d_it, d_st))
+        return rc;
+    return st.finish();
+}
+
+int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, int32_t B,
+                        int32_t max_path, const double* target_path, const int32_t* n_path, const double* state,
+                        const double* vx, const int32_t* min_index, const double* speed_kmh, const double* target_speed,
+                        const double* err_in, const int32_t* n_err_in, double* control, double* lat_command,
+                        double* lon_command, int32_t* min_index_out, double* e_rr, double* k_r, double* pre_pro,
+                        double* err_out, int32_t* n_err_out, int32_t* status, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, lateral == EMP_LAT_MPC || lateral == EMP_LAT_LQR, "lateral must be EMP_LAT_MPC or EMP_LAT_LQR");
+    EMP_REQUIRE(ctx, lat && pid && B >= 0 && max_path >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && speed_kmh && target_speed && err_in && n_err_in &&
+                         control && min_index_out && err_out && n_err_out && status,
+                "NULL argument");
+    EMP_STAGE(st, where);
+    const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
+    const int* d_np = st.in(n_path, (size_t)B);
+    const double* d_state = st.in(state, (size_t)B * 5);
+    const double* d_vx = st.in(vx, (size_t)B);
+    const int* d_mi = st.in(min_index, (size_t)B);
+    mpc::CtlIO io{pid_params(pid), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    io.speed_kmh = st.in(speed_kmh, (size_t)B);
+    io.target_speed = st.in(target_speed, (size_t)B);
+    io.err_in = st.in(err_in, (size_t)B * ctl::kPidBuffer);
+    io.n_err_in = st.in(n_err_in, (size_t)B);
+    io.control = st.out(control, (size_t)B * 3, false);
+    io.lon_command = st.out(lon_command, (size_t)B, false);
+    io.err_out = st.out(err_out, (size_t)B * ctl::kPidBuffer, false);
+    io.n_err_out = st.out(n_err_out, (size_t)B, false);
+    double* d_lat = lat_command ? st.out(lat_command, (size_t)B, false) : st.tmp<double>((size_t)B);
+    double* d_e = st.out(e_rr, (size_t)B * 4, false);
+    double* d_k = st.out(k_r, (size_t)B, false);
+    int* d_mo = st.out(min_index_out, (size_t)B, false);
+    double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
+    int* d_st = st.out(status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (lateral == EMP_LAT_MPC) {
+        if (const int rc = launch(ctx, "vehicle_control", mpc::mpc_lateral_kernel<true>,
+                                  dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave), dim3(64), 0, B, max_path, mpc_params(lat),
+                                  d_path, d_np, d_state, d_vx, d_mi, d_lat, (double*)nullptr, d_e, d_k, d_mo, d_pp, (double*)nullptr,
+                                  (double*)nullptr, (int*)nullptr, d_st, io))
+            return rc;
+    } else {
+        if (const int rc = launch(ctx, "vehicle_control", lqr::lqr_lateral_kernel<true>, grid1(B, 64), dim3(64), 0, B, max_path,
+                                  mpc_params(lat), d_path, d_np, d_state, d_vx, d_mi, d_lat, (double*)nullptr, d_e, d_k, d_mo, d_pp,
+                                  (int*)nullptr, d_st, io))
+            return rc;
+    }
     return st.finish();
 }
 

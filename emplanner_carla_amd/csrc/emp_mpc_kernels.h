@@ -12,8 +12,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "emp_qp_wave.h"
+#include "emp_qp_wave.h"          // closes its `fp contract(fast)` region at its end
 #include "emp_tail_kernels.h"   // status bits
+#include "emp_control_core.h"   // PID step and actuation of the fused vehicle-control kernels
 
 namespace emp {
 namespace mpc {
@@ -212,7 +213,45 @@ __device__ inline int box_qp_full12(const double (&h)[kNu], double f_r, int r, i
     return state;
 }
 
-// ref: Lateral_MPC_controller._control (:313-337) for B vehicles; grid = ceil(B / 5), block = 64.
+// The longitudinal half of Vehicle_control.run_step (ref :680-724) that the fused vehicle-control kernels append to a lateral
+// law (emp_vehicle_control): the PID step and the actuation, for vehicle b whose lateral law gave `lat` with status `lat_status`.
+// A vehicle the lateral law failed on gets zero controls and its PID state back unchanged (the reference raises in _control()
+// before PID_control runs, :700-702).  err_out / n_err_out may be the memory of err_in / n_err_in.
+struct CtlIO {
+    ctl::PidParams pid;
+    const double* speed_kmh;       // [B]
+    const double* target_speed;    // [B]
+    const double* err_in;          // [B][60]
+    const int* n_err_in;           // [B]
+    double* control;               // [B][3] throttle, steer, brake
+    double* lon_command;           // [B] or null
+    double* err_out;               // [B][60]
+    int* n_err_out;                // [B]
+};
+
+__device__ inline void control_epilogue(const CtlIO& io, int b, int lat_status, double lat) {
+    const double* ein = io.err_in + (size_t)b * ctl::kPidBuffer;
+    double* eout = io.err_out + (size_t)b * ctl::kPidBuffer;
+    double* c3 = io.control + 3 * (size_t)b;
+    if (lat_status == 0) {
+        int n = 0;
+        const double acc = ctl::pid_step(io.pid, io.speed_kmh[b], io.target_speed[b], ein, io.n_err_in[b], eout, &n);
+        io.n_err_out[b] = n;
+        if (io.lon_command) io.lon_command[b] = acc;
+        ctl::actuate(lat, acc, &c3[0], &c3[1], &c3[2]);
+    } else {
+        const int n = io.n_err_in[b];
+        for (int i = 0; i < ctl::kPidBuffer; ++i) eout[i] = ein[i];
+        io.n_err_out[b] = n;
+        if (io.lon_command) io.lon_command[b] = 0.0;
+        c3[0] = c3[1] = c3[2] = 0.0;
+    }
+}
+
+// ref: Lateral_MPC_controller._control (:313-337) for B vehicles; grid = ceil(B / 5), block = 64.  kFused: then the longitudinal
+// half of Vehicle_control.run_step (control_epilogue) on the lane that holds u[0] - emp_vehicle_control in one launch; the
+// lateral arithmetic is the same in both instantiations.
+template <bool kFused>
 __global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Params prm, const double* __restrict__ target_path,
                                                          const int* __restrict__ n_path, const double* __restrict__ state,
                                                          const double* __restrict__ vx, const int* __restrict__ min_index_in,
@@ -220,7 +259,7 @@ __global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Pa
                                                          double* __restrict__ e_rr_out, double* __restrict__ k_r_out,
                                                          int* __restrict__ min_index_out, double* __restrict__ pre_pro,
                                                          double* __restrict__ H_out, double* __restrict__ f_out,
-                                                         int* __restrict__ iters_out, int* __restrict__ status) {
+                                                         int* __restrict__ iters_out, int* __restrict__ status, CtlIO io) {
     const int lane = threadIdx.x & 63;
     const int grp = lane / kNu, r = lane - grp * kNu;
     const int gb = grp * kNu;
@@ -381,7 +420,9 @@ __global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Pa
                 pre_pro[4 * b + 3] = py + e_s * st;
             }
             if (iters_out) iters_out[b] = it;
-            status[b] = bad_index ? kStSOutOfRange : ((!inv_ok || rc != 0) ? kStQpFailed : 0);
+            const int stat = bad_index ? kStSOutOfRange : ((!inv_ok || rc != 0) ? kStQpFailed : 0);
+            status[b] = stat;
+            if constexpr (kFused) control_epilogue(io, b, stat, steer[b]);
         }
     }
 }
@@ -410,12 +451,15 @@ __device__ __forceinline__ M4 matmul(const M4& A, const M4& B) {
     return C;
 }
 
+// kFused: as mpc_lateral_kernel<true> - one vehicle per lane, so every lane runs its own epilogue.
+template <bool kFused>
 __global__ void lqr_lateral_kernel(int B, int max_path, mpc::Params prm, const double* __restrict__ target_path,
                                    const int* __restrict__ n_path, const double* __restrict__ state,
                                    const double* __restrict__ vx, const int* __restrict__ min_index_in,
                                    double* __restrict__ steer, double* __restrict__ K_out, double* __restrict__ e_rr_out,
                                    double* __restrict__ k_r_out, int* __restrict__ min_index_out,
-                                   double* __restrict__ pre_pro, int* __restrict__ sweeps_out, int* __restrict__ status) {
+                                   double* __restrict__ pre_pro, int* __restrict__ sweeps_out, int* __restrict__ status,
+                                   mpc::CtlIO io) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double x = state[5 * b], y = state[5 * b + 1], fi = state[5 * b + 2];
@@ -561,8 +605,340 @@ __global__ void lqr_lateral_kernel(int B, int max_path, mpc::Params prm, const d
         pre_pro[4 * b + 3] = py + e_s * st;
     }
     if (sweeps_out) sweeps_out[b] = sweeps;
-    status[b] = bad_index ? kStSOutOfRange : (inv_ok ? 0 : kStQpFailed);
+    const int stat = bad_index ? kStSOutOfRange : (inv_ok ? 0 : kStQpFailed);
+    status[b] = stat;
+    if constexpr (kFused) mpc::control_epilogue(io, b, stat, steer[b]);
 }
 
 }  // namespace lqr
+
+// ---------------------------------------------------------------------------------------------
+// Lateral MPC with feed-forward, ref controller/controller.py class Lateral_MPC__with_feedforward_controller (:727-990):
+// MPC_control from explicit inputs.  Differences from Lateral_MPC_controller: N = 4 steps x P = 2 controls (:737-739); no
+// clamp on Vx (:758-776) but Vx + 0.0001 in the model, its C terms included (:789-809); C_bar with k_r x the RAW Vx (:821);
+// e_fi = fi - theta_r, not its sine (:889); the match search covers the whole path (:850-866, min_index is only the fallback);
+// Q_bar's first block is Q as well (:934-936, multiplied by C's zero block row); and R_bar regularises only the first P steps'
+// controls (`for i in range(P)`, :939-940).  With two controls per step sharing one column of C, H then has a 2-D null space
+// along u4 - u5 and u6 - u7: the box barrier still gives the interior point a unique iterate, and u0..u3 and the pair sums
+// u4 + u5, u6 + u7 are what the problem determines.
+//
+// Mapping: one vehicle per GROUP of 8 lanes (lane r owns control r), eight vehicles per wavefront - no idle lane.  The
+// nearest-point search is spread over the group's lanes (lane r scans points r, r + 8, ...) and reduced to the smallest
+// distance, lowest index on ties (the reference's strict < keeps the first minimum).
+// ---------------------------------------------------------------------------------------------
+namespace mpcff {
+
+using mpc::M4;
+using mpc::V4;
+using mpc::grp_bcast;
+
+constexpr int kN = 4, kP = 2, kNu = kN * kP;     // ref :737-739
+constexpr int kGroupsPerWave = 64 / kNu;
+constexpr int kRegularised = kP * kP;            // R_bar's blocks i < P (ref :939-940): controls 0..3
+
+__device__ __forceinline__ int grp_bcast_int(int v, int group_base, int k) {
+    return __builtin_amdgcn_ds_bpermute((group_base + k) << 2, v);
+}
+template <class Op>
+__device__ __forceinline__ double grp_reduce8(double v, int group_base, Op op) {
+    double acc = grp_bcast(v, group_base, 0);
+#pragma unroll
+    for (int k = 1; k < kNu; ++k) acc = op(acc, grp_bcast(v, group_base, k));
+    return acc;
+}
+
+// box_qp_full12 (the same Mehrotra interior point, G = I) on an 8-lane group.  H may be singular (see above): M = H +
+// diag(wu + wl) stays positive definite because the barrier weights are.  Returns 0 ok / 2 failed (group-uniform).
+__device__ inline int box_qp_full8(const double (&h)[kNu], double f_r, int r, int gb, bool live, double* u_out, int* iters_out) {
+    const double eps_p = 1e-10, eps_mu = 1e-13, eps_d_rel = 1e-10;
+    const double lo = -1.0, hi = 1.0;
+    double u = 0.0, su = 1.0, sl = 1.0, zu = 1.0, zl = 1.0;
+    const double qscale = fmax(1.0, grp_reduce8(fabs(f_r), gb, [](double a, double b) { return fmax(a, b); }));
+    int state = live ? 1 : 0, iters = 0;
+    bool acceptable = false;
+    const int rows = 2 * kNu;
+    while (__any(state == 1)) {
+        const bool run = state == 1;
+        const double rpu = u - hi + su, rpl = lo - u + sl;
+        const double isu = fast_rcp(su), isl = fast_rcp(sl), izu = fast_rcp(zu), izl = fast_rcp(zl);
+        const double wu = zu * isu, wl = zl * isl;
+        double hu = 0.0;
+#pragma unroll
+        for (int c = 0; c < kNu; ++c) hu = __builtin_fma(h[c], grp_bcast(u, gb, c), hu);
+        const double rd = (hu + f_r) + (zu - zl);
+        const double rd_max = grp_reduce8(fabs(rd), gb, [](double a, double b) { return fmax(a, b); });
+        const double rp_max = grp_reduce8(fmax(fabs(rpu), fabs(rpl)), gb, [](double a, double b) { return fmax(a, b); });
+        const double zmax = grp_reduce8(fmax(zu, zl), gb, [](double a, double b) { return fmax(a, b); });
+        const double mu = grp_reduce8(su * zu + sl * zl, gb, [](double a, double b) { return a + b; }) / (double)rows;
+        if (run) {
+            const double dscale = fmax(qscale, zmax);
+            if (rd_max <= eps_d_rel * dscale && rp_max <= eps_p && mu <= eps_mu) state = 0;
+            else if (!(mu == mu) || mu > 1e30 || (iters >= kQpStallIter && rp_max > kQpStallResidual)) state = 2;
+            else if (iters >= kQpMaxIter) state = acceptable ? 0 : 2;
+            if (rd_max <= 100.0 * eps_d_rel * dscale && rp_max <= 10.0 * eps_p && mu <= 1000.0 * eps_mu) acceptable = true;
+        }
+        const bool go = state == 1;
+        // dense Cholesky of M = H + diag(wu + wl), row r on lane r (box_qp_full12)
+        double a[kNu], rinv = 1.0;
+#pragma unroll
+        for (int c = 0; c < kNu; ++c) a[c] = go ? h[c] : ((c == r) ? 1.0 : 0.0);
+#pragma unroll
+        for (int c = 0; c < kNu; ++c)
+            if (c == r && go) a[c] += wu + wl;
+        bool bad = false;
+#pragma unroll
+        for (int k = 0; k < kNu; ++k) {
+            double rowk[kNu];
+#pragma unroll
+            for (int j = k; j < kNu; ++j) rowk[j] = grp_bcast(a[j], gb, k);
+            const double piv = rowk[k];
+            if (!(piv > 0.0)) bad = true;
+            const double rs = fast_rsqrt(piv > 0.0 ? piv : 1.0);
+            const double lik = a[k] * rs;
+#pragma unroll
+            for (int j = k + 1; j < kNu; ++j) {
+                const double ukj = rowk[j] * rs;
+                if (r > k) a[j] = __builtin_fma(-lik, ukj, a[j]);
+                else if (r == k) a[j] = ukj;
+            }
+            if (r >= k) a[k] = (r == k) ? piv * rs : lik;
+            if (r == k) rinv = rs;
+        }
+        if (go && bad) state = acceptable ? 0 : 2;
+        const bool go2 = state == 1;
+        auto solve = [&](double b) {
+#pragma unroll
+            for (int k = 0; k < kNu; ++k) {                     // L y = b
+                const double yk = grp_bcast(b * rinv, gb, k);
+                if (r == k) b = yk;
+                else if (r > k) b = __builtin_fma(-a[k], yk, b);
+            }
+#pragma unroll
+            for (int k = kNu - 1; k >= 0; --k) {                // L' x = y
+                const double xk = grp_bcast(b * rinv, gb, k);
+                if (r == k) b = xk;
+                else if (r < k) b = __builtin_fma(-a[k], xk, b);
+            }
+            return b;
+        };
+        const double dua = solve(go2 ? -rd - ((wu * rpu - zu) - (wl * rpl - zl)) : 0.0);
+        const double dsua = -rpu - dua, dsla = -rpl + dua;
+        const double dzua = -zu - wu * dsua, dzla = -zl - wl * dsla;
+        double ratio = go2 ? fmax(fmax(-dsua * isu, -dsla * isl), fmax(-dzua * izu, -dzla * izl)) : 0.0;
+        ratio = grp_reduce8(ratio, gb, [](double x, double y) { return fmax(x, y); });
+        const double a_aff = (ratio > 1.0) ? fast_rcp(ratio) : 1.0;
+        double mu_aff = go2 ? (su + a_aff * dsua) * (zu + a_aff * dzua) + (sl + a_aff * dsla) * (zl + a_aff * dzla) : 0.0;
+        mu_aff = grp_reduce8(mu_aff, gb, [](double x, double y) { return x + y; }) / (double)rows;
+        double sigma = (mu > 0.0) ? mu_aff * fast_rcp(mu) : 0.0;
+        sigma = sigma * sigma * sigma;
+        const double rcu = su * zu + dsua * dzua - sigma * mu, rcl = sl * zl + dsla * dzla - sigma * mu;
+        const double du = solve(go2 ? -rd - ((zu * rpu - rcu) * isu - (zl * rpl - rcl) * isl) : 0.0);
+        const double dsu = -rpu - du, dsl = -rpl + du;
+        const double dzu = -(rcu + zu * dsu) * isu, dzl = -(rcl + zl * dsl) * isl;
+        ratio = go2 ? fmax(fmax(-dsu * isu, -dsl * isl), fmax(-dzu * izu, -dzl * izl)) : 0.0;
+        ratio = grp_reduce8(ratio, gb, [](double x, double y) { return fmax(x, y); });
+        const double tau = qp_step_fraction(mu);
+        const double alpha = (ratio > tau) ? tau * fast_rcp(ratio) : 1.0;
+        if (go2) {
+            su += alpha * dsu;
+            sl += alpha * dsl;
+            zu += alpha * dzu;
+            zl += alpha * dzl;
+            u += alpha * du;
+            ++iters;
+        }
+    }
+    *u_out = u;
+    *iters_out = iters;
+    return state;
+}
+
+// ref: Lateral_MPC__with_feedforward_controller.MPC_control (:972-990) for B vehicles; grid = ceil(B / 8), block = 64.
+__global__ __launch_bounds__(64) void mpc_ff_lateral_kernel(int B, int max_path, mpc::Params prm, const double* __restrict__ target_path,
+                                                            const int* __restrict__ n_path, const double* __restrict__ state,
+                                                            const double* __restrict__ vx, const int* __restrict__ min_index_in,
+                                                            double* __restrict__ steer, double* __restrict__ u_out,
+                                                            double* __restrict__ e_rr_out, double* __restrict__ k_r_out,
+                                                            int* __restrict__ min_index_out, double* __restrict__ pre_pro,
+                                                            double* __restrict__ H_out, double* __restrict__ f_out,
+                                                            int* __restrict__ iters_out, int* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int grp = lane / kNu, r = lane - grp * kNu;
+    const int gb = grp * kNu;
+    const int b = blockIdx.x * kGroupsPerWave + grp;
+    const bool live = b < B;
+    const int bb = live ? b : 0;
+    // ---- vehicle state (cal_vehicle_info, ref :758-776: no clamp on Vx)
+    double x = state[5 * bb], y = state[5 * bb + 1], fi = state[5 * bb + 2];
+    const double Vy = state[5 * bb + 3], fi_dot = state[5 * bb + 4], Vx = vx[bb];
+    // ---- continuous model (cal_A_B_C_fun, ref :778-809): Vx + 0.0001 everywhere, the C terms included
+    const double Vg = Vx + 0.0001;
+    M4 A;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) A.a[i][j] = 0.0;
+    A.a[0][1] = 1.0;
+    A.a[1][1] = (prm.Cf + prm.Cr) / (prm.m * Vg);
+    A.a[1][2] = -(prm.Cf + prm.Cr) / prm.m;
+    A.a[1][3] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.m * Vg);
+    A.a[2][3] = 1.0;
+    A.a[3][1] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.Iz * Vg);
+    A.a[3][2] = -(prm.a * prm.Cf - prm.b * prm.Cr) / prm.Iz;
+    A.a[3][3] = (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * Vg);
+    const V4 Bc{{0.0, -prm.Cf / prm.m, 0.0, -prm.a * prm.Cf / prm.Iz}};
+    const V4 Cc{{0.0, (prm.a * prm.Cf + prm.b * prm.Cr) / (prm.m * Vg) - Vg, 0.0,
+                 (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * Vg)}};
+    // ---- prediction and tracking error (cal_error_k_fun(ts = 0.1), ref :827-912) with the raw Vx
+    {
+        const double c = cos(fi), s = sin(fi);
+        const double xn = x + Vx * mpc::kTs * c - Vy * mpc::kTs * s;
+        const double yn = y + Vy * mpc::kTs * c + Vx * mpc::kTs * s;
+        x = xn;
+        y = yn;
+        fi = fi + fi_dot * mpc::kTs;
+    }
+    const double* path = target_path + (size_t)bb * max_path * 4;
+    const int np_ = min(n_path[bb], max_path);
+    int idx = min_index_in[bb];
+    {
+        double best = 10000.0;                                      // squared metres (ref :851)
+        int best_i = -1;
+        for (int i = r; i < np_; i += kNu) {
+            const double dx = path[4 * i] - x, dy = path[4 * i + 1] - y;
+            const double d = dx * dx + dy * dy;
+            if (d < best) {
+                best = d;
+                best_i = i;
+            }
+        }
+        double g_best = 10000.0;
+        int g_i = -1;
+#pragma unroll
+        for (int k = 0; k < kNu; ++k) {
+            const double dk = grp_bcast(best, gb, k);
+            const int ik = grp_bcast_int(best_i, gb, k);
+            if (ik >= 0 && (dk < g_best || (dk == g_best && ik < g_i))) {
+                g_best = dk;
+                g_i = ik;
+            }
+        }
+        if (g_i >= 0) idx = g_i;
+    }
+    const bool bad_index = live && (np_ < 1 || idx < 0 || idx >= np_);  // IndexError in the reference
+    if (bad_index || !live) idx = 0;
+    const double px = path[4 * idx], py = path[4 * idx + 1], pth = path[4 * idx + 2], pk = path[4 * idx + 3];
+    const double ct = cos(pth), st = sin(pth);
+    const double dvx = x - px, dvy = y - py;
+    const double e_d = -st * dvx + ct * dvy;
+    const double e_s = ct * dvx + st * dvy;
+    const double theta_r = pth + pk * e_s;
+    const double cd = cos(fi - theta_r), sd = sin(fi - theta_r);
+    const double e_d_dot = Vy * cd + Vx * sd;
+    const double e_fi = fi - theta_r;
+    const double S_dot = (Vx * cd - Vy * sd) / (1.0 - pk * e_d);
+    const double e_fi_dot = fi_dot - pk * S_dot;
+    const V4 e_rr{{e_d, e_d_dot, e_fi, e_fi_dot}};
+    // ---- bilinear discretisation (cal_discretized_matrix, ref :811-822)
+    M4 lhs, rhs, inv;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double e = (i == j) ? 1.0 : 0.0;
+            lhs.a[i][j] = e - (mpc::kTs * A.a[i][j]) / 2.0;
+            rhs.a[i][j] = e + (mpc::kTs * A.a[i][j]) / 2.0;
+        }
+    const bool inv_ok = mpc::inverse4(lhs, &inv);
+    M4 Ab;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            Ab.a[i][j] = ((inv.a[i][0] * rhs.a[0][j] + inv.a[i][1] * rhs.a[1][j]) + inv.a[i][2] * rhs.a[2][j]) + inv.a[i][3] * rhs.a[3][j];
+    V4 Bb = mpc::matvec(inv, Bc), Cb = mpc::matvec(inv, Cc);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        Bb.v[i] = Bb.v[i] * mpc::kTs;
+        Cb.v[i] = Cb.v[i] * mpc::kTs * pk * Vx;
+    }
+    // ---- condensed problem (cal_control_para_fun, ref :924-948): g_t = A_bar^t B_bar, w_i = A_bar^i e_rr + Cc_i
+    V4 g[kN];
+    g[0] = Bb;
+#pragma unroll
+    for (int t = 1; t < kN; ++t) g[t] = mpc::matvec(Ab, g[t - 1]);
+    V4 w[kN + 1];
+    {
+        V4 me = e_rr, cc{{0.0, 0.0, 0.0, 0.0}};
+        w[0] = me;
+#pragma unroll
+        for (int i = 1; i <= kN; ++i) {
+            me = mpc::matvec(Ab, me);
+            cc = mpc::matvec(Ab, cc);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                cc.v[q] += Cb.v[q];
+                w[i].v[q] = cc.v[q] + me.v[q];
+            }
+        }
+    }
+    const int jr = r / kP;
+    double h[kNu], f_r = 0.0;
+#pragma unroll
+    for (int c = 0; c < kNu; ++c) {
+        const int jc = c / kP;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 1; i <= kN; ++i) {
+            if (i - 1 - jr < 0 || i - 1 - jc < 0) continue;     // block row i of C: A_bar^(i-1-j) B_bar in step j < i
+            const double* wt = (i == kN) ? prm.f : prm.q;
+            const V4& ga = g[(i - 1 - jr) < 0 ? 0 : (i - 1 - jr)];
+            const V4& gc = g[i - 1 - jc];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc += ga.v[q] * wt[q] * gc.v[q];
+        }
+        if (c == r && r < kRegularised) acc += prm.r;
+        h[c] = 2.0 * acc;
+    }
+#pragma unroll
+    for (int i = 1; i <= kN; ++i) {
+        if (i - 1 - jr < 0) continue;
+        const double* wt = (i == kN) ? prm.f : prm.q;
+        const V4& ga = g[(i - 1 - jr) < 0 ? 0 : (i - 1 - jr)];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) f_r += ga.v[q] * wt[q] * w[i].v[q];
+    }
+    f_r = 2.0 * f_r;
+    // ---- box QP (ref :950-970) and outputs
+    const bool solvable = live && !bad_index && inv_ok;
+    double u = 0.0;
+    int it = 0;
+    const int rc = box_qp_full8(h, f_r, r, gb, solvable, &u, &it);
+    if (live) {
+        const bool ok = solvable && rc == 0;
+        if (H_out)
+#pragma unroll
+            for (int c = 0; c < kNu; ++c) H_out[((size_t)b * kNu + r) * kNu + c] = h[c];
+        if (f_out) f_out[(size_t)b * kNu + r] = f_r;
+        if (u_out) u_out[(size_t)b * kNu + r] = ok ? u : 0.0;
+        if (r == 0) {
+            steer[b] = ok ? u : 0.0;                              // ref :990: res['x'][0]
+            if (e_rr_out)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) e_rr_out[4 * b + q] = e_rr.v[q];
+            if (k_r_out) k_r_out[b] = pk;
+            min_index_out[b] = idx;
+            if (pre_pro) {
+                pre_pro[4 * b] = x;
+                pre_pro[4 * b + 1] = y;
+                pre_pro[4 * b + 2] = px + e_s * ct;
+                pre_pro[4 * b + 3] = py + e_s * st;
+            }
+            if (iters_out) iters_out[b] = it;
+            status[b] = bad_index ? kStSOutOfRange : ((!inv_ok || rc != 0) ? kStQpFailed : 0);
+        }
+    }
+}
+
+}  // namespace mpcff
 }  // namespace emp

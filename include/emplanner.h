@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define EMP_ABI_VERSION 11
+#define EMP_ABI_VERSION 12
 
 typedef struct emp_ctx emp_ctx;
 
@@ -600,6 +600,60 @@ int emp_lqr_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
                     const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
                     double* steer, double* K, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
                     int32_t* sweeps, int32_t* status, emp_mem where);
+
+/* ---- longitudinal PID, feed-forward MPC and the fused vehicle-control step (ABI 12) -------------------------------
+ * ref: controller/controller.py classes Longitudinal_PID_controller (:614-678), Vehicle_control (:680-724) and
+ * Lateral_MPC__with_feedforward_controller (:727-990).
+ *
+ * emp_pid_longitudinal: PID_control(target_speed) (:641-678) for B vehicles, bit-exact with the reference.  speed_kmh [B] is
+ * 3.6 * sqrt(x*x + y*y + z*z) of the vehicle's velocity, computed by the caller as the reference does (:647-649);
+ * target_speed [B].  The deque of the last errors is err [B][EMP_PID_BUFFER], oldest first, with n_err [B] entries (a count
+ * outside [0, EMP_PID_BUFFER] is clamped).  The error is appended before the separation test; with fewer than 2 entries the
+ * integral and derivative are 0; |error| > error_threshold sets the integral to 0 and clears the buffer (the derivative term
+ * stays).  command [B] = K_P e + K_I integral + K_D derivative.  err_out / n_err_out receive the buffer after the call (entries at
+ * and past n_err_out are 0) and MAY be the same arrays as err_in / n_err_in: with EMP_DEVICE a fleet keeps its PID state on
+ * the device across steps.  dt = 0 gives IEEE inf / NaN where the reference raises ZeroDivisionError. */
+#define EMP_PID_BUFFER 60
+typedef struct emp_pid_params {
+    double K_P, K_I, K_D, dt, error_threshold;     /* controller.py:622, :638: 1.15, 0, 0, 0.01, 1 */
+} emp_pid_params;
+void emp_pid_params_default(emp_pid_params* p);
+int emp_pid_longitudinal(emp_ctx* ctx, const emp_pid_params* p, int32_t B, const double* speed_kmh, const double* target_speed,
+                         const double* err_in, const int32_t* n_err_in, double* command, double* err_out, int32_t* n_err_out,
+                         emp_mem where);
+
+/* emp_mpc_ff_lateral: Lateral_MPC__with_feedforward_controller.MPC_control (:972-990) for B vehicles; inputs and status as
+ * emp_mpc_lateral, except that vx [B] is NOT clamped (cal_vehicle_info, :758-776) and min_index is only the fallback when
+ * no path point lies within 100 m (the search covers the whole path, :850-866).  N = 4 steps x P = 2 controls, ts = 0.1;
+ * the model uses Vx + 0.0001 (its C terms too), C_bar k_r times the raw Vx (:821), e_fi = fi - theta_r.  R_bar regularises
+ * only the first P steps' controls (:939-940), so H has a 2-D null space along u4 - u5 and u6 - u7: u0..u3 and the pair sums
+ * u4 + u5, u6 + u7 are determined, the split of a pair is the interior point's.  p->q_diag / f_diag / r are Q, F, R
+ * (emp_mpc_ff_params_default: (200, 1, 1, 1), (10, 10, 10, 10), 1; :974-979).  steer [B] = u[0] (:990); optional outputs (NULL to
+ * skip): u [B][8], e_rr [B][4], k_r [B], pre_pro [B][4], H [B][8][8], f [B][8], iters [B]. */
+#define EMP_MPC_FF_CONTROLS 8
+void emp_mpc_ff_params_default(emp_mpc_params* p);
+int emp_mpc_ff_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t max_path, const double* target_path,
+                       const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
+                       double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
+                       double* H, double* f, int32_t* iters, int32_t* status, emp_mem where);
+
+/* emp_vehicle_control: Vehicle_control.run_step(target_speed) (:680-724) for B vehicles in ONE kernel launch: the lateral law
+ * (lateral = EMP_LAT_MPC: emp_mpc_lateral, EMP_LAT_LQR: emp_lqr_lateral, with `lat` as their params and the same inputs),
+ * then emp_pid_longitudinal with `pid`, then the actuation: steer = min(1, s) if s >= 0 else max(-1, s); acc >= 0: throttle
+ * min(1, acc), brake 0; else throttle 0, brake max(1, acc) = 1 (the reference's expression, kept).  Python's min / max keep
+ * their first argument against NaN: a NaN steering command gives -1, a NaN acceleration throttle 0 and brake 1.
+ * control [B][3] = throttle, steer, brake; lat_command [B] is the raw lateral output, bit-identical to the stand-alone entry
+ * point's steer on the same inputs; lon_command [B] the PID command; min_index_out, e_rr [B][4], k_r, pre_pro [B][4] as there.
+ * A vehicle whose lateral status is non-zero gets zero controls, lon_command 0, and err_out / n_err_out = err_in / n_err_in
+ * unchanged (the reference raises in _control() before PID_control runs, :700-702).  err_out / n_err_out may alias err_in /
+ * n_err_in.  Optional outputs (NULL to skip): lat_command, lon_command, e_rr, k_r, pre_pro. */
+typedef enum emp_lateral_law { EMP_LAT_MPC = 0, EMP_LAT_LQR = 1 } emp_lateral_law;
+int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, int32_t B,
+                        int32_t max_path, const double* target_path, const int32_t* n_path, const double* state,
+                        const double* vx, const int32_t* min_index, const double* speed_kmh, const double* target_speed,
+                        const double* err_in, const int32_t* n_err_in, double* control, double* lat_command,
+                        double* lon_command, int32_t* min_index_out, double* e_rr, double* k_r, double* pre_pro,
+                        double* err_out, int32_t* n_err_out, int32_t* status, emp_mem where);
 
 /* ---- S-T speed DP (BASELINE config 5; reference planner/speed_planning_test.py) ----------------
  * The S-T grid is hard-coded in the reference (40 non-uniform s samples :114, 16 t samples :116); tables are
