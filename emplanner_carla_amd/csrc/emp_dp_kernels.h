@@ -1248,7 +1248,7 @@ __global__ void enrich_nodes_kernel(int B, int max_nodes, double res, const doub
     int n = 0;
     bool trunc = false;
     double end_s = s0, end_l = l0;
-    const int cols = n_nodes[b];
+    const int cols = min(max(n_nodes[b], 0), max_nodes);       // a count beyond the row's capacity is clamped, never followed
     for (int c = 0; c < cols; ++c) {
         end_s = node_s[(size_t)b * max_nodes + c];
         end_l = node_l[(size_t)b * max_nodes + c];

@@ -322,7 +322,7 @@ __global__ void heading_kappa_kernel(int B, int max_pts, const double* __restric
                                      double* __restrict__ theta, double* __restrict__ kappa) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int m = n_pts[b];
+    const int m = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
     if (m < 2) return;
     heading_kappa(xy + (size_t)b * max_pts * 2, 2, m, theta + (size_t)b * max_pts, 1, kappa + (size_t)b * max_pts, 1);
 }
@@ -397,7 +397,8 @@ __global__ void lmin_lmax_kernel(int B, int max_pts, int max_obs, const double* 
                                  double* __restrict__ l_min, double* __restrict__ l_max, int* __restrict__ status) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const bool ok = lmin_lmax(dp_s + (size_t)b * max_pts, dp_l + (size_t)b * max_pts, 1, n_pts[b],
+    const int n = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
+    const bool ok = lmin_lmax(dp_s + (size_t)b * max_pts, dp_l + (size_t)b * max_pts, 1, n,
                               obs_s + (size_t)b * max_obs, obs_l + (size_t)b * max_obs, min(max(n_obs[b], 0), max_obs), obs_length,
                               obs_width, l_min + (size_t)b * max_pts, l_max + (size_t)b * max_pts);
     status[b] = ok ? 0 : kStBoundIndex;
@@ -600,10 +601,12 @@ __global__ void path_to_xy_kernel(int B, int max_ref, int max_pts, const double*
                                   double* __restrict__ target_xy, int* __restrict__ n_out, int* __restrict__ status) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    const int P = min(max(n_ref[b], 0), max_ref);       // clamped to the row's capacity
+    const int n = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
     bool s_err, trunc;
-    const int m = frenet_path_to_xy(ref_line + (size_t)b * max_ref * 4, s_map + (size_t)b * max_ref, n_ref[b],
+    const int m = frenet_path_to_xy(ref_line + (size_t)b * max_ref * 4, s_map + (size_t)b * max_ref, P,
                                     begin_sl[2 * b], begin_sl[2 * b + 1], path_s + (size_t)b * max_pts,
-                                    path_l + (size_t)b * max_pts, n_pts[b], target_xy + (size_t)b * (max_pts + 1) * 2,
+                                    path_l + (size_t)b * max_pts, n, target_xy + (size_t)b * (max_pts + 1) * 2,
                                     max_pts + 1, &s_err, &trunc);
     n_out[b] = m;
     status[b] = (s_err ? kStSOutOfRange : 0) | (trunc ? kStTruncated : 0);
@@ -1155,12 +1158,15 @@ __global__ void s_map_kernel(int B, int max_ref, const double* __restrict__ ref_
                              const double* __restrict__ origin_xy, double* __restrict__ s_map) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    s_map_build(ref_line + (size_t)b * max_ref * 4, n_ref[b], origin_xy[2 * b], origin_xy[2 * b + 1],
-                s_map + (size_t)b * max_ref);
+    const int P = min(max(n_ref[b], 0), max_ref);       // a count beyond the row's capacity is clamped, never followed
+    if (P < 1) return;                                  // an empty line has no s_map (the reference raises IndexError)
+    s_map_build(ref_line + (size_t)b * max_ref * 4, P, origin_xy[2 * b], origin_xy[2 * b + 1], s_map + (size_t)b * max_ref);
 }
 
 // ref: cal_s_l_fun, planning_utils.py:475-509 (mode 0) and cal_projection_s_fun, :429-445 (mode 1: the caller
-// supplies the match indices and only s is produced)
+// supplies the match indices and only s is produced).  A match index outside [0, P) is not followed: that point's s and
+// l are NaN (l also where the scene's first index is out of range: every l projects on the first point's match); an
+// empty line (P = 0, where the reference raises IndexError) gives NaN for every point.
 __global__ void s_l_kernel(int B, int max_ref, int max_pts, const double* __restrict__ ref_line,
                            const double* __restrict__ s_map, const int* __restrict__ n_ref,
                            const double* __restrict__ xy, const int* __restrict__ n_pts,
@@ -1169,15 +1175,18 @@ __global__ void s_l_kernel(int B, int max_ref, int max_pts, const double* __rest
     if (b >= B) return;
     const double* line = ref_line + (size_t)b * max_ref * 4;
     const double* sm = s_map + (size_t)b * max_ref;
-    const int P = min(max(n_ref[b], 0), max_ref), k = n_pts[b];
+    const int P = min(max(n_ref[b], 0), max_ref);       // clamped to the row's capacity
+    const int k = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
+    const double qnan = __builtin_nan("");
     int m_first = 0;
     for (int j = 0; j < k; ++j) {
         const size_t o = (size_t)b * max_pts + j;
         const double x = xy[o * 2], y = xy[o * 2 + 1];
         const int m = match_in ? match_in[o] : match_scan(line, P, x, y, 0, 1, 50);
         if (j == 0) m_first = m;
-        out_s[o] = projection_s(node_at(line, m), sm[m], x, y);
-        if (out_l) out_l[o] = lateral_offset(project_on(node_at(line, m_first), x, y), x, y);
+        const bool ok = m >= 0 && m < P, ok_first = m_first >= 0 && m_first < P;
+        out_s[o] = ok ? projection_s(node_at(line, m), sm[m], x, y) : qnan;
+        if (out_l) out_l[o] = (ok && ok_first) ? lateral_offset(project_on(node_at(line, m_first), x, y), x, y) : qnan;
     }
 }
 
@@ -1190,17 +1199,22 @@ __global__ void s_l_deri_kernel(int B, int max_ref, int max_pts, const double* _
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const double* line = ref_line + (size_t)b * max_ref * 4;
-    const int P = min(max(n_ref[b], 0), max_ref), k = n_pts[b];
+    const int P = min(max(n_ref[b], 0), max_ref);       // clamped to the row's capacity
+    const int k = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
     int m_first = 0;
     for (int j = 0; j < k; ++j) {
         const size_t o = (size_t)b * max_pts + j;
+        double* r = out + o * 7;
+        if (P < 1) {                                    // empty line: the reference raises IndexError; no node is read
+            r[0] = r[1] = r[2] = r[3] = r[4] = r[5] = r[6] = __builtin_nan("");
+            continue;
+        }
         const double x = xy[o * 2], y = xy[o * 2 + 1];
         const int m = match_scan(line, P, x, y, 0, 1, 50);
         if (j == 0) m_first = m;
         const Node proj = project_on(node_at(line, m_first), x, y);
         const FrenetState f = frenet_state(proj, origin_xy[2 * b], origin_xy[2 * b + 1], vxy[o * 2], vxy[o * 2 + 1],
                                            axy[o * 2], axy[o * 2 + 1]);
-        double* r = out + o * 7;
         r[0] = f.l; r[1] = f.l_dot; r[2] = f.s_dot; r[3] = f.l_ddot; r[4] = f.dl_ds; r[5] = f.s_ddot; r[6] = f.ddl_ds;
     }
 }
@@ -1212,9 +1226,10 @@ __global__ void proj_point_kernel(int n, int max_ref, const double* __restrict__
                                   double* __restrict__ out, int* __restrict__ idx_out, int* __restrict__ status) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
+    const int P = min(max(n_ref[t], 0), max_ref);       // a count beyond the row's capacity is clamped, never followed
     int idx = pre_idx[t];
     Node pr{0, 0, 0, 0};
-    const bool ok = idx >= 0 && proj_point(ref_line + (size_t)t * max_ref * 4, s_map + (size_t)t * max_ref, n_ref[t], s[t], &idx, &pr);
+    const bool ok = idx >= 0 && proj_point(ref_line + (size_t)t * max_ref * 4, s_map + (size_t)t * max_ref, P, s[t], &idx, &pr);
     out[4 * t] = pr.x; out[4 * t + 1] = pr.y; out[4 * t + 2] = pr.theta; out[4 * t + 3] = pr.kappa;
     idx_out[t] = idx;
     status[t] = ok ? 0 : kStSOutOfRange;
@@ -1226,9 +1241,10 @@ __global__ void index2s_kernel(int B, int max_pts, const double* __restrict__ x,
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const size_t o = (size_t)b * max_pts;
+    const int n = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
     double acc = 0.0;
-    for (int i = 0; i < n_pts[b]; ++i) out[o + i] = 0.0;
-    for (int i = 1; i < n_pts[b]; ++i) {
+    for (int i = 0; i < n; ++i) out[o + i] = 0.0;
+    for (int i = 1; i < n; ++i) {
         if (x[o + i] != x[o + i]) break;
         const double dx = x[o + i] - x[o + i - 1], dy = y[o + i] - y[o + i - 1];
         acc += sqrt(dx * dx + dy * dy);
@@ -1247,10 +1263,11 @@ __global__ void frenet2cartesian_kernel(int B, int max_ref, int max_pts, const d
     const double* line = ref_line + (size_t)b * max_ref * 4;
     const double* sm = index2s + (size_t)b * max_ref;
     const int P = min(max(n_ref[b], 0), max_ref);       // clamped to the row's capacity
+    const int k = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
     const double qnan = __builtin_nan("");
     int st = 0;
     bool stopped = false;
-    for (int j = 0; j < n_pts[b]; ++j) {
+    for (int j = 0; j < k; ++j) {
         const double* v = sl + ((size_t)b * max_pts + j) * 4;
         double* o = out + ((size_t)b * max_pts + j) * 4;
         o[0] = o[1] = o[2] = o[3] = qnan;

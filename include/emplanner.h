@@ -12,6 +12,7 @@
  * Conventions
  *   - plain C, POD only; all floating point is IEEE-754 binary64, all indices int32.
  *   - every array is batch-major and padded: [B][max_x]... with a per-scene length array.
+ *   - per-scene counts beyond their row's capacity are clamped to [0, max_x], never followed.
  *   - `where` tells whether the DATA pointers of the call are host (EMP_HOST: the library
  *     stages them through its own device buffers) or device (EMP_DEVICE: used in place; e.g.
  *     torch tensors' data_ptr()).  Parameter structs are always host memory.
@@ -425,13 +426,14 @@ int emp_s_map(emp_ctx* ctx, int32_t B, int32_t max_ref, const double* ref_line, 
               const double* origin_xy, double* s_map, emp_mem where);
 
 /* ref: cal_s_l_fun (planning_utils.py:475-509) with a caller-supplied s_map: xy [B][max_pts][2] -> s, l [B][max_pts].
- * With match_index != NULL and l == NULL it is cal_projection_s_fun (:429-445): s from the given match indices. */
+ * With match_index != NULL and l == NULL it is cal_projection_s_fun (:429-445): s from the given match indices.  A match
+ * index outside [0, n_ref) is not followed: that point's s (and l) are NaN.  n_ref = 0 gives NaN for every point. */
 int emp_s_l(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_pts, const double* ref_line, const double* s_map,
             const int32_t* n_ref, const double* xy, const int32_t* n_pts, const int32_t* match_index,
             double* s, double* l, emp_mem where);
 
 /* ref: cal_s_l_deri_fun (planning_utils.py:512-588): xy, v_xy, a_xy [B][max_pts][2], origin_xy [B][2]
- * -> out [B][max_pts][7] = l, dl/dt, ds/dt, d2l/dt2, dl/ds, d2s/dt2, d2l/ds2 */
+ * -> out [B][max_pts][7] = l, dl/dt, ds/dt, d2l/dt2, dl/ds, d2s/dt2, d2l/ds2 (NaN rows where n_ref = 0) */
 int emp_s_l_deri(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_pts, const double* ref_line,
                  const int32_t* n_ref, const double* xy, const double* v_xy, const double* a_xy,
                  const int32_t* n_pts, const double* origin_xy, double* out, emp_mem where);
