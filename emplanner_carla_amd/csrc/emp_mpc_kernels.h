@@ -296,7 +296,7 @@ __global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Pa
         fi = fi + fi_dot * kTs;
     }
     const double* path = target_path + (size_t)bb * max_path * 4;
-    const int np_ = n_path[bb];
+    const int np_ = min(max(n_path[bb], 0), max_path);            // a count beyond the row is clamped, never followed
     int idx = min_index_in[bb];
     bool bad_index = live && (np_ < 1 || idx < 0 || idx >= np_);   // the reference raises IndexError at :224
     if (bad_index) idx = 0;
@@ -553,7 +553,7 @@ __global__ void lqr_lateral_kernel(int B, int max_path, mpc::Params prm, const d
         fi = fi + fi_dot * mpc::kTs;
     }
     const double* path = target_path + (size_t)b * max_path * 4;
-    const int np_ = n_path[b];
+    const int np_ = min(max(n_path[b], 0), max_path);             // a count beyond the row is clamped, never followed
     int idx = min_index_in[b];
     {
         double min_d = 10000.0;
@@ -799,7 +799,7 @@ __global__ __launch_bounds__(64) void mpc_ff_lateral_kernel(int B, int max_path,
         fi = fi + fi_dot * mpc::kTs;
     }
     const double* path = target_path + (size_t)bb * max_path * 4;
-    const int np_ = min(n_path[bb], max_path);
+    const int np_ = min(max(n_path[bb], 0), max_path);
     int idx = min_index_in[bb];
     {
         double best = 10000.0;                                      // squared metres (ref :851)

@@ -573,7 +573,9 @@ int emp_reference_line(emp_ctx* ctx, const emp_smooth_params* sp, int32_t B, int
  * reads the vehicle state from a live carla.Vehicle (cal_vehicle_info, :90-113); here the caller supplies
  * state [B][5] = x, y, yaw fi (rad), lateral velocity Vy, yaw rate fi_dot (rad/s) and vx [B] (the caller applies the
  * reference's |Vx| >= 0.005 clamp, :107-110).  target_path [B][max_path][4] = x, y, theta, kappa is the planner's
- * trajectory; min_index [B] the previous match (the search window is 50 points from it, :204).
+ * trajectory; min_index [B] the previous match (the search window is 50 points from it, :204).  n_path [B] is clamped to
+ * [0, max_path] (the convention above): a count beyond the row never reads the next vehicle's path.  The same holds for
+ * emp_lqr_lateral, emp_mpc_ff_lateral and emp_vehicle_control.
  * Chain: cal_A_B_C_fun (:115-148) -> cal_error_k_fun(ts = 0.1) (:170-251) -> cal_coefficient_of_discretion_fun (:151-168)
  * -> cal_control_para_fun (:253-311): condensed MPC with N = 6 steps x P = 2 controls, box |u| <= 1.
  * steer [B] = first control (res['x'][0]); optional outputs (NULL to skip): u [B][12], e_rr [B][4], k_r [B],

@@ -31,6 +31,7 @@ import pytest
 from emplanner_carla_amd import scenes as S
 from emplanner_carla_amd import _lib as L
 from oracle import ref_port as rp
+from tests.batch_check import Guarded
 from tests.conftest import assert_dp_l_vs_reference, assert_rel, make_planner
 
 pytestmark = pytest.mark.gpu
@@ -644,60 +645,6 @@ def test_empty_batch_writes_nothing(planner):
 # ---------------------------------------------------------------------------------------------------------------------
 # §2: the count contract on guarded device buffers
 # ---------------------------------------------------------------------------------------------------------------------
-F_GUARD = -7.25e77          # output guard sentinels
-I_GUARD = -777
-
-
-class Guarded:
-    """Raw EMP_DEVICE call on views into torch tensors with one guard row before and one after the batch.
-    spec: dict(fn=<emp_* name>, sig=[argument names and scalars in call order], ins={name: (array, guard fill)},
-    outs={name: (row shape, dtype)}, counts={name: capacity})."""
-
-    def __init__(self, pl, spec, B=None):
-        import torch
-        self.torch, self.pl, self.spec = torch, pl, spec
-        self.B = B if B is not None else next(iter(spec["ins"].values()))[0].shape[0]
-        self.t = {}
-        for name, (arr, fill) in spec["ins"].items():
-            arr = np.ascontiguousarray(arr[:self.B])
-            t = torch.empty((self.B + 2,) + arr.shape[1:], dtype=torch.from_numpy(arr).dtype, device="cuda")
-            t[0] = fill
-            t[-1] = fill
-            t[1:-1] = torch.from_numpy(arr).cuda()
-            self.t[name] = t
-        for name, (row, dt) in spec["outs"].items():
-            tdt = torch.float64 if dt == np.float64 else torch.int32
-            self.t[name] = torch.full((self.B + 2,) + tuple(row), F_GUARD if dt == np.float64 else I_GUARD, dtype=tdt,
-                                      device="cuda")
-        self.guard = {n: (self.t[n][0].clone(), self.t[n][-1].clone()) for n in spec["outs"]}
-
-    def set_count(self, name, values):
-        self.t[name][1:-1] = self.torch.from_numpy(np.ascontiguousarray(values, dtype=np.int32)).cuda()
-
-    def call(self):
-        args = []
-        for a in self.spec["sig"]:
-            if a == "B":
-                args.append(self.B)
-            elif isinstance(a, str):
-                args.append(self.t[a][1:].data_ptr())       # row 1 = scene 0 (B = 0: a pointer at the trailing guard)
-            else:
-                args.append(a)
-        self.torch.cuda.synchronize()
-        rc = getattr(self.pl._lib, self.spec["fn"])(self.pl._h, *args, L.EMP_DEVICE)
-        assert rc == 0, f"{self.spec['fn']}: rc {rc}"
-        self.pl.synchronize()
-        return {n: self.t[n][1:-1].cpu().numpy().copy() for n in self.spec["outs"]}
-
-    def check_guards(self, what):
-        for n, (g0, g1) in self.guard.items():
-            assert self.torch.equal(self.t[n][0], g0) and self.torch.equal(self.t[n][-1], g1), \
-                f"{what}: a guard row of {n} was written"
-        if self.B == 0:
-            for n in self.spec["outs"]:
-                assert self.torch.equal(self.t[n][1], self.guard[n][0]), f"{what}: B = 0 wrote {n}"
-
-
 def _spec_s_map(d):
     return dict(fn="emp_s_map", sig=["B", P, "ref", "n_ref", "origin", "s_map"],
                 ins={"ref": (d["ref"], NAN), "n_ref": (d["n_ref"], 0), "origin": (d["origin"], 0.0)},

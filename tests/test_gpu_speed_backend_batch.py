@@ -1,0 +1,305 @@
+"""The S-T speed back end of the C ABI - emp_speed_convex_space, emp_speed_qp, emp_speed_increase_points and
+emp_path_speed_merge - on whole batches of ragged scenes.
+
+test_back_end_fuzz_vs_port runs them with path_len either the valid count (zeros after it) or the whole row, and merge
+only with n_init = max_path, so a kernel that used the capacity instead of the count, or read its neighbour's row, could
+pass.  Here, at B = 64 and 151 (speed QP: two 32-lane scenes per block, so 151 leaves the last block half empty):
+
+- counts from 0, 1 and 2 up to the capacity (the capacity at scene 0 and at the last scene);
+- finite poison past every count: large ascending index2s and large kappa (which would tighten s_dot_ub if read), and
+  finite path arrays past n_init (a kernel that scanned them would find no NaN and take the wrong last slot);
+- every scene (not a sample) compared with oracle/st_backend.py on its valid slice: convex space and merge bit-exact
+  with statuses equal to the exception the port raises, speed QP at 1e-6, increase points as test_back_end_fuzz_vs_port;
+- batch invariance (tests/batch_check.invariant: alone, reversed, shifted by one, host == device), bit for bit;
+- the count contract of path_len and n_init (clamped to [0, max_path]) with raw guarded device calls.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+from emplanner_carla_amd import api as A
+from oracle import st_backend as be
+from tests.batch_check import Guarded, bits, check_count_contract, invariant, to_np
+from tests.conftest import assert_rel
+
+pytestmark = pytest.mark.gpu
+
+BATCHES = (64, 151)
+K = 12                      # obstacle slots
+P = 70                      # path capacity of the convex-space cases
+W = 80                      # path capacity of the merge cases
+NAN = np.nan
+LAT = 0.2 * 9.8
+
+
+@pytest.fixture(scope="module")
+def pl():
+    p = A.Planner(0)
+    yield p
+    p.close()
+
+
+def _ragged(rng, B, cap, lo):
+    n = rng.integers(lo, cap + 1, B).astype(np.int32)
+    n[1], n[2], n[3] = 0, 1, 2
+    n[0] = n[-1] = cap
+    return n
+
+
+def _code(fn, *args):
+    """(result, status) of a port call: the EMP_STB_* bit of the exception the reference raises."""
+    try:
+        return fn(*args), 0
+    except ValueError:
+        return None, A.STB_RANGE
+    except IndexError:
+        return None, A.STB_INDEX
+
+
+@functools.lru_cache(maxsize=None)
+def convex_inputs(B):
+    """DP profiles with 0 to 16 valid columns, ragged paths with poison past path_len, obstacle slots mixing NaN and
+    segments."""
+    rng = np.random.default_rng(900 + B)
+    ncol = _ragged(rng, B, 16, 0)
+    dp_s = np.full((B, 16), NAN)
+    dp_t = np.full((B, 16), NAN)
+    plen = _ragged(rng, B, P, 3)
+    idx2s = 1e4 + 10.0 * np.tile(np.arange(P, dtype=np.float64), (B, 1))
+    kappa = np.full((B, P), 50.0)
+    sets = [np.full((B, K), NAN) for _ in range(4)]
+    for b in range(B):
+        n = int(ncol[b])
+        v = rng.uniform(1.0, 9.0)
+        dp_t[b, :n] = 0.5 * (np.arange(n) + 1)
+        dp_s[b, :n] = np.cumsum(rng.uniform(0.3, 1.2, n) * v * 0.5)
+        m = int(plen[b])
+        idx2s[b, :m] = np.concatenate(([0.0], np.cumsum(rng.uniform(0.8, 1.6, max(m - 1, 0)))))[:m]
+        kappa[b, :m] = rng.normal(0, 0.02, m)
+        k = int(rng.integers(0, K + 1))
+        slots = rng.choice(K, k, replace=False)
+        t_in = rng.uniform(0.0, 7.0, k)
+        sets[2][b, slots] = t_in
+        sets[3][b, slots] = t_in + rng.uniform(0.3, 3.0, k)
+        s_in = rng.uniform(0.0, 50.0, k)
+        sets[0][b, slots] = s_in
+        sets[1][b, slots] = s_in + rng.uniform(-4.0, 12.0, k)
+    return [dp_s, dp_t, idx2s, kappa, plen] + sets
+
+
+CONVEX = ("s_lb", "s_ub", "s_dot_lb", "s_dot_ub", "status")
+
+
+def _convex_call(pl):
+    return lambda a, dev: dict(zip(CONVEX, (to_np(o) for o in pl.speed_convex_space(*a))))
+
+
+@pytest.mark.parametrize("B", BATCHES)
+def test_convex_space_batch(pl, B):
+    args = convex_inputs(B)
+    dp_s, dp_t, idx2s, kappa, plen, s_in, s_out, t_in, t_out = args
+    r = invariant(_convex_call(pl), args, "speed_convex_space")
+    seen = set()
+    for b in range(B):
+        n = int(plen[b])
+        want, code = _code(be.port_generate_convex_space, dp_s[b], dp_t[b], idx2s[b, :n], s_in[b], s_out[b], t_in[b],
+                           t_out[b], kappa[b, :n])
+        if np.isnan(dp_s[b, 0]):
+            code = A.STB_NO_PROFILE             # an empty DP profile: flagged (include/emplanner.h), the port returns +-inf
+        assert r["status"][b] == code, f"scene {b}: status {r['status'][b]}, the reference {code}"
+        seen.add(code)
+        got = np.stack([r[c][b] for c in CONVEX[:4]])
+        if code == 0:
+            assert bits(got) == bits(np.stack(want)), f"convex space of scene {b} (bit-exact expected)"
+        else:
+            assert np.isnan(got).all(), f"scene {b}: a flagged scene's bounds are NaN"
+    assert seen == {0, A.STB_RANGE, A.STB_INDEX, A.STB_NO_PROFILE}, seen
+
+
+@functools.lru_cache(maxsize=None)
+def qp_inputs(B):
+    """The convex-space scenes' profiles and bounds (+-inf where the convex space failed), start speeds and
+    accelerations."""
+    args = convex_inputs(B)
+    from emplanner_carla_amd.api import Planner
+    pl = Planner(0)
+    out = pl.speed_convex_space(*args)
+    pl.close()
+    st = out[4]
+    bounds = [np.where(st[:, None] == 0, o, inf) for o, inf in zip(out[:4], (-np.inf, np.inf, -np.inf, np.inf))]
+    rng = np.random.default_rng(950 + B)
+    return [rng.uniform(1.0, 9.0, B), rng.uniform(-1.0, 1.0, B), args[0], args[1]] + bounds
+
+
+QP = ("qp_s", "qp_s_dot", "qp_s_dot2", "relative_time", "iters", "status")
+
+
+@pytest.mark.parametrize("B", BATCHES)
+def test_speed_qp_batch(pl, B):
+    p = A.speed_qp_params()
+    args = qp_inputs(B)
+    r = invariant(lambda a, dev: dict(zip(QP, (to_np(o) for o in pl.speed_qp(p, *a)))), args, "speed_qp")
+    v0, a0, dp_s, dp_t = args[:4]
+    solved = 0
+    for b in range(B):
+        ncol = int((~np.isnan(dp_s[b])).sum())
+        st = r["status"][b]
+        if ncol in (0, 1, 16):
+            want = {0: A.STB_NO_PROFILE, 1: A.STB_QP_FAILED, 16: A.STB_INDEX}[ncol]
+            assert st == want and np.isnan(r["qp_s"][b]).all(), f"scene {b} ({ncol} columns): status {st}"
+            continue
+        (os_, ov, oa, ot), res, F = be.speed_qp(float(v0[b]), float(a0[b]), dp_s[b], dp_t[b], *(x[b] for x in args[4:]))
+        n, dt = F["qp_size"], F["dt"]
+        if res is None or res.status != "optimal":
+            assert st == A.STB_QP_FAILED, f"scene {b}: the oracle found no minimiser, the kernel reports {st}"
+            continue
+        assert st == 0 and r["iters"][b] > 0, f"scene {b}: status {st}"
+        np.testing.assert_array_equal(r["relative_time"][b, :n], np.arange(n) * dt)
+        for c in QP[:4]:
+            assert np.isnan(r[c][b, n:]).all(), f"scene {b}: {c} past the last station"
+        assert_rel(r["qp_s"][b, :n], os_[:n], 1e-6, f"qp_s of scene {b}")
+        assert_rel(r["qp_s_dot"][b, :n], ov[:n], 1e-6, f"qp_s_dot of scene {b}")
+        assert_rel(r["qp_s_dot2"][b, :n], oa[:n], 1e-6, f"qp_s_dot2 of scene {b}")
+        solved += 1
+    assert solved >= B // 4, solved
+
+
+def _profiles(rng, m):
+    """[B][4][17] speed profiles with m[b] valid stations, NaN behind them."""
+    B = len(m)
+    prof = np.full((B, 4, 17), NAN)
+    for b in range(B):
+        n = int(m[b])
+        dt = rng.uniform(0.3, 0.7)
+        a = rng.uniform(-2, 2, n)
+        v = np.maximum(0.2, 5 + np.cumsum(a) * dt)
+        prof[b, 0, :n] = np.concatenate(([0.0], np.cumsum(v[:-1] * dt)))[:n]
+        prof[b, 1, :n], prof[b, 2, :n], prof[b, 3, :n] = v, a, np.arange(n) * dt
+    return prof
+
+
+DENSE = ("s", "s_dot", "s_dot2", "relative_time", "status")
+
+
+def _dense_call(pl):
+    return lambda a, dev: dict(zip(DENSE, (to_np(o) for o in pl.speed_increase_points(*a))))
+
+
+@pytest.mark.parametrize("B", BATCHES)
+def test_increase_points_batch(pl, B):
+    m = _ragged(np.random.default_rng(31 + B), B, 17, 0)          # 17: no NaN tail
+    prof = _profiles(np.random.default_rng(32 + B), m)
+    r = invariant(_dense_call(pl), [prof[:, 0], prof[:, 1], prof[:, 2], prof[:, 3]], "speed_increase_points")
+    for b in range(B):
+        st = r["status"][b]
+        if m[b] == 0:
+            assert st == A.STB_NO_PROFILE, f"scene {b}: an empty profile, status {st}"
+            continue
+        if m[b] == 17:
+            assert st == A.STB_INDEX, f"scene {b}: a profile without NaN tail, status {st}"
+            continue
+        want = np.stack(be.port_increase_points(*prof[b]))
+        if m[b] >= 2:
+            assert st == 0, f"scene {b}: status {st}"
+        if st == 0:
+            assert bits(r["relative_time"][b]) == bits(want[3]), f"sample times of scene {b}"
+            got = np.stack([r[c][b] for c in DENSE[:3]])
+            assert np.array_equal(np.isnan(got), np.isnan(want[:3])), f"NaN pattern of scene {b}"    # one station: NaN
+            fin = ~np.isnan(want[:3])
+            if fin.any():
+                assert_rel(got[fin], want[:3][fin], 1e-12, f"samples of scene {b}", scale=1.0)
+
+
+@functools.lru_cache(maxsize=None)
+def merge_inputs(B):
+    """401-point speed samples of valid profiles; path arrays [B][W] with n_init from 0 to W.  Inside n_init the valid
+    points are followed by NaN where the reference expects it (none at all every seventh scene: IndexError; NaN from the
+    start every eleventh: no profile); past n_init finite poison that holds no NaN."""
+    rng = np.random.default_rng(970 + B)
+    prof = _profiles(rng, rng.integers(2, 17, B))
+    from emplanner_carla_amd.api import Planner
+    pl = Planner(0)
+    s, v, a, t, st = pl.speed_increase_points(prof[:, 0], prof[:, 1], prof[:, 2], prof[:, 3])
+    pl.close()
+    assert (st == 0).all()
+    n_init = _ragged(rng, B, W, 3)
+    ps = 1e6 + np.tile(np.arange(W, dtype=np.float64), (B, 1))
+    px, py, ph, pk = (np.full((B, W), 3e5) for _ in range(4))
+    for b in range(B):
+        n = int(n_init[b])
+        nv = n if b % 7 == 5 else (0 if b % 11 == 6 else int(rng.integers(min(3, n), n + 1)))
+        ps[b, :n] = np.concatenate(([0.0], np.cumsum(rng.uniform(0.5, 1.5, max(n - 1, 0)))))[:n]
+        px[b, :n], py[b, :n], ph[b, :n], pk[b, :n] = NAN, NAN, NAN, NAN
+        px[b, :nv], py[b, :nv], ph[b, :nv], pk[b, :nv] = rng.normal(size=(4, nv)).cumsum(axis=1)
+    now = rng.uniform(0, 50, B)
+    return [s, v, a, t, now, ps, px, py, ph, pk, n_init]
+
+
+@pytest.mark.parametrize("B", BATCHES)
+def test_path_speed_merge_batch(pl, B):
+    args = merge_inputs(B)
+    s, v, a, t, now, ps, px, py, ph, pk, n_init = args
+    r = invariant(lambda x, dev: dict(zip(("traj", "status"), (to_np(o) for o in pl.path_speed_merge(*x)))), args,
+                  "path_speed_merge")
+    seen = set()
+    for b in range(B):
+        n = int(n_init[b])
+        sl = lambda x: x[b, :n]
+        nv = int(np.argmax(np.isnan(px[b, :n]))) if np.isnan(px[b, :n]).any() else n
+        st = r["status"][b]
+        w = None
+        if nv == n:
+            want = A.STB_INDEX                                  # the reference's NaN scan runs off the array
+        elif nv == 0:
+            want = A.STB_NO_PROFILE
+        else:
+            w, want = _code(be.port_path_speed_merge, s[b], v[b], a[b], t[b], float(now[b]), sl(ps), sl(px), sl(py), sl(ph),
+                            sl(pk))
+        assert st == want, f"scene {b}: n_init {n}, {nv} valid points: status {st}, expected {want}"
+        seen.add(want)
+        if want == 0:
+            w = np.stack(w)
+            assert bits(r["traj"][b]) == bits(w), f"merge of scene {b} (bit-exact expected)"
+            assert np.isnan(r["traj"][b, :4, -1]).all(), f"scene {b}: the last slot is the last entry of [:n_init]"
+    assert seen == {0, A.STB_INDEX, A.STB_NO_PROFILE}, seen
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the count contract on guarded device buffers
+# ---------------------------------------------------------------------------------------------------------------------
+def _spec_convex(B):
+    dp_s, dp_t, idx2s, kappa, plen, s_in, s_out, t_in, t_out = convex_inputs(B)
+    return dict(fn="emp_speed_convex_space",
+                sig=["B", K, P, LAT, "dps", "dpt", "i2s", "kap", "plen", "si", "so", "ti", "to", "lb", "ub", "vlb", "vub", "st"],
+                ins={"dps": (dp_s, NAN), "dpt": (dp_t, NAN), "i2s": (idx2s, 1e4), "kap": (kappa, 50.0), "plen": (plen, 0),
+                     "si": (s_in, NAN), "so": (s_out, NAN), "ti": (t_in, NAN), "to": (t_out, NAN)},
+                outs={"lb": ((16,), np.float64), "ub": ((16,), np.float64), "vlb": ((16,), np.float64),
+                      "vub": ((16,), np.float64), "st": ((), np.int32)},
+                counts={"plen": P})
+
+
+def _spec_merge(B):
+    s, v, a, t, now, ps, px, py, ph, pk, n_init = merge_inputs(B)
+    return dict(fn="emp_path_speed_merge",
+                sig=["B", W, "s", "v", "a", "t", "now", "ps", "px", "py", "ph", "pk", "n", "traj", "st"],
+                ins={"s": (s, 0.0), "v": (v, 0.0), "a": (a, 0.0), "t": (t, 0.0), "now": (now, 0.0), "ps": (ps, 1e6),
+                     "px": (px, 3e5), "py": (py, 3e5), "ph": (ph, 3e5), "pk": (pk, 3e5), "n": (n_init, 0)},
+                outs={"traj": ((7, 401), np.float64), "st": ((), np.int32)},
+                counts={"n": W})
+
+
+SPECS = {"speed_convex_space": _spec_convex, "path_speed_merge": _spec_merge}
+
+
+@pytest.mark.parametrize("kernel", list(SPECS))
+def test_counts_beyond_capacity_are_clamped(pl, kernel):
+    B = 151
+    check_count_contract(pl, SPECS[kernel](B), (B // 2, B // 3), kernel)
+
+
+def test_empty_batch_writes_nothing(pl):
+    for name, spec in SPECS.items():
+        g = Guarded(pl, spec(64), B=0)
+        g.call()
+        g.check_guards(name)
