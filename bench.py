@@ -19,29 +19,36 @@ Other lines (one JSON line per invocation, same keys):
                        (s_k = 12 + 11 k +- 2, l_k = +-U(2.5, 5)), worst (all obstacles within reach
                        of the same columns)
     --dp-mode fused    the single-kernel DP (no HBM edge tensor; no sweep kernel, so `roofline` is null)
+    --full             everything beyond the headline (below); off by default
+
+A plain run (no --full) does only what the headline needs: it sets up, warms up and settles, times the steps, writes
+--dump-outputs, plans every resident input batch once more for `scenes_fully_planned_frac` (which `value` needs) and prints
+the line.  The figures marked [--full] below are measured by `--full` runs only; a plain run reports them as null (or leaves
+their keys out).
 
 Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
   roofline      the DP min-plus sweep kernel (HBM bound): algorithmic bytes / mean HIP-event duration of its
                 launches INSIDE the timed region (the only kernel bracketed by events there).  The timed region runs three
                 batches on three lanes: the sweep shares the chip with two other batches' edge-cost kernels, so `frac` is the
-                schedule's figure; `frac_alone` (diagnostic pass), `staged_leg` and `exclusive_sweep_leg` are the kernel's.
-                `traffic` = HBM bytes
+                schedule's figure; `frac_alone` (diagnostic pass), `staged_leg` and `exclusive_sweep_leg` are the kernel's
+                [--full].  `traffic` = HBM bytes
                 per launch from the rocprofv3 PMC passes named in `traffic_source`, or null when no profile of this
                 workload is committed
-  cpu_baseline  the reference-structured CPU port (oracle/ref_port.py), one core, bounded sample
-  cpu_baseline_pool   the same port on a pool of single-threaded processes (up to 64 host cores), whole-pool rate
-  kernels_ms    mean duration of every kernel of the cycle, from a short diagnostic pass after the timed region
+  cpu_baseline  [--full] the reference-structured CPU port (oracle/ref_port.py), one core, bounded sample
+  cpu_baseline_pool   [--full] the same port on a pool of single-threaded processes (up to 64 host cores), whole-pool rate
+  kernels_ms    [--full] mean duration of every kernel of the cycle, from a short diagnostic pass after the timed region
                 with every kernel bracketed by events, one batch in flight
-  roofline_dp_edge, dp_only   the FP64-issue-bound edge kernel (algorithmic flops of SURVEY.md 8d AND the executed
+  roofline_dp_edge, dp_only   [--full] the FP64-issue-bound edge kernel (algorithmic flops of SURVEY.md 8d AND the executed
                 wave-level instruction / active-lane counts of the committed SQ counter profile), and the DP alone
   value / all_scenes_cycles_per_s   `value` counts the scenes whose cycle ran to the end (scenes_fully_planned_frac of the batch;
                 the rest are refused at the end of the cycle: walls, blocked corridors, infeasible QPs - they were computed
                 too and cost the same time); all_scenes_cycles_per_s = scenes per step / ms_per_step
   roofline_step   the whole step against the chip's vector-issue capacity: sum over the step's kernels of their VALU-busy
                 quad-cycles (committed SQ counter pass, source named) / (1024 SIMDs x clock / 4 x ms_per_step), with the measured
-                cost of a wave64 FP64 instruction (tools/fp64_pipe_bench.hip: 4.3 cycles, not the 4 the counter charges)
+                cost of a wave64 FP64 instruction (tools/fp64_pipe_bench.hip: 4.3 cycles, not the 4 the counter charges); the
+                figures at the clock the chip held (its edge-cost kernel's clock probe, a few untimed steps) [--full]
   staged_leg, exclusive_sweep_leg, rccl_gather_leg, dram_leg, cfg5_leg, latency_leg, survey_leg, tight_corridor_leg, host_io_leg, gather_path_leg, dropin_leg
-                (default run only: N = 1, cfg2, 4096 scenes; --no-legs skips them) short secondary measurements after the
+                [--full] (default workload only: N = 1, cfg2, 4096 scenes; --no-legs skips them) short secondary measurements after the
                 headline: the staged pipeline of rounds 2-5 (two batches, front stage beside back stage: ~9 % longer steps, the
                 sweep beside the Cartesian tail only) and the same with the sweep held back behind the previous batch's path QP
                 (EMP_OPT_SWEEP_EXCLUSIVE = 2: the sweep's bandwidth at its best); 32768 scenes (the edge tensor streams from HBM instead of the
@@ -51,6 +58,9 @@ Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
                 per-step code of an N > 1 rank (record packing + gather streams) on this one GPU - without a process group
                 (gather_path_leg: the identity) and, in a process of its own, with a one-rank ProcessGroupNCCL whose dist.gather is a
                 real RCCL call every step (rccl_gather_leg)
+  gather        (N > 1, or --force-gather-path) the exchange's figures; the same steps without pack and gather,
+                ms_per_step_without_pack_and_gather and gather_hidden_behind_compute_frac [--full]
+  parity_sweeps_committed   [--full] what the committed large-sample parity runs of this build say (profiles/)
 """
 from __future__ import annotations
 
@@ -165,7 +175,8 @@ def latency_main(args):
     M = max_path_points(p)
     steps, warm = max(args.steps, 20), max(args.warmup, 5)
     out = {}
-    for name, inputs in (("device_resident_inputs", dev), ("host_arrays_in_and_out", host)):
+    # (the line's value first; --full: the same calls with NumPy arrays in and out, PCIe included)
+    for name, inputs in (("device_resident_inputs", dev), ("host_arrays_in_and_out", host))[:2 if args.full else 1]:
         for _ in range(warm):
             r = pl.plan_cycle(p, q, sp, max_pts=M, **inputs)
             pl.synchronize()
@@ -176,12 +187,14 @@ def latency_main(args):
         out[name] = (time.perf_counter() - t0) / steps * 1e3
         if name == "device_resident_inputs":      # the line's value: its last timed call is what --dump-outputs writes
             dumped = dump_outputs(args.dump_outputs, r) if args.dump_outputs else None
-    pl.set_timing(True)
-    for _ in range(5):
-        r = pl.plan_cycle(p, q, sp, max_pts=M, **dev)
-        pl.synchronize()
-    kernels = {n: round(pl.kernel_ms(n), 6) for n in ("project", "dp_edge", "dp_sweep", "dp_enrich", "path_qp", "to_cartesian")
-               if pl.kernel_ms(n) >= 0}
+    kernels = None
+    if args.full:
+        pl.set_timing(True)
+        for _ in range(5):
+            r = pl.plan_cycle(p, q, sp, max_pts=M, **dev)
+            pl.synchronize()
+        kernels = {n: round(pl.kernel_ms(n), 6) for n in ("project", "dp_edge", "dp_sweep", "dp_enrich", "path_qp", "to_cartesian")
+                   if pl.kernel_ms(n) >= 0}
     st = int(np.asarray(r.status.cpu() if hasattr(r.status, "cpu") else r.status)[0])
     line = {"metric": "planning cycle latency (DP+QP, 40x9 S-L lattice, 8 obs, ONE scene)", "value": round(out["device_resident_inputs"], 4),
             "unit": "ms per planning cycle", "n_gpus": 1, "steps": steps, "warmup": warm,
@@ -193,8 +206,8 @@ def latency_main(args):
             "roofline": None, "latency_ms": {k: round(v, 4) for k, v in out.items()}, "kernels_ms": kernels,
             "scene_status": st, "dumped_outputs": dumped,
             "note": "a single scene occupies one wavefront per kernel: the cycle is launch and dependent-instruction latency, "
-                    "no roofline applies"}
-    if not args.no_cpu_baseline:
+                    "no roofline applies", "cpu_baseline": None}
+    if args.full and not args.no_cpu_baseline:
         cb = cpu_baseline(cfg, 8, 7, scene_kwargs(args), budget_s=10.0)
         line["cpu_baseline"] = {**cb, "value": round(1e3 / cb["value"], 2), "unit": "ms per planning cycle"}
     print(json.dumps(line), flush=True)
@@ -314,7 +327,12 @@ def main():
                     help="arc radii of the reference lines: gentle = U(1500, 6000) m (default), survey = SURVEY 8(d)'s U(150, 1000) m")
     ap.add_argument("--latency", action="store_true", help="BASELINE configs[1]: one scene, synchronous calls")
     ap.add_argument("--dp-mode", choices=["two_kernel", "fused"], default="two_kernel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baselines, the secondary legs of the default "
+                         "workload, the per-kernel diagnostic pass, the clock probe, the steps without pack and gather of the "
+                         "exchange, the committed parity sweeps (--no-cpu-baseline and --no-legs still skip theirs); off by "
+                         "default: a plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--pipeline", default="auto", help="emp_set_pipeline mode: 'staged' (two batches, back stage of one over "
                     "the front stage of the next; the sweep keeps its bandwidth), 'off', or n >= 2 = n batches on n lanes "
                     "(more overlap: shorter steps, every kernel's own launches longer); 'auto' (default) = emp_set_pipeline(EMP_PIPELINE_AUTO): "
@@ -339,7 +357,7 @@ def main():
                     help="emp_set_option before the pipeline is set up (include/emplanner.h emp_option; names: "
                          "emplanner_carla_amd._lib.OPTIONS), e.g. --opt sweep_exclusive=2 --opt lane_edge_order=1; repeatable")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the secondary legs of the default run (N = 1, config cfg2, default batch): exclusive_sweep_leg "
+                    help="with --full: skip the secondary legs of the default workload (N = 1, config cfg2, default batch): exclusive_sweep_leg "
                          "(the same steps with the sweep held back behind the previous batch's path QP, --opt sweep_exclusive=2), "
                          "dram_leg (32768 scenes: the edge tensor streams from HBM), cfg5_leg (BASELINE configs[4], 4096 scenes), "
                          "latency_leg (configs[1], one scene per call), survey_leg / tight_corridor_leg (SURVEY 8(d)'s arc radii), "
@@ -579,38 +597,40 @@ def main():
             allr = [torch.zeros_like(mine) for _ in range(world)]
             dist.all_gather(allr, mine)
             per_rank = [float(x.item()) for x in allr]
-        # the same K steps WITHOUT pack and gather, between the same fences: what the exchange costs the step
-        fence()
-        pl.set_timing(False)
-        with_gather[0] = False
-        for _ in range(max(2, 2 * in_flight)):
-            step()
-        fence()
-        nogs = []
-        for _ in range(len(block_s)):                   # as many blocks as the timed region took, the median again
-            n0 = time.perf_counter()
-            for _ in range(args.steps):
+        # --full: the same K steps WITHOUT pack and gather, between the same fences: what the exchange costs the step
+        ms_with, ms_without = elapsed / args.steps * 1e3, None
+        if args.full:
+            fence()
+            pl.set_timing(False)
+            with_gather[0] = False
+            for _ in range(max(2, 2 * in_flight)):
                 step()
             fence()
-            nog = time.perf_counter() - n0
-            if world > 1:
-                el2 = torch.tensor([nog], dtype=torch.float64, device=device)
-                dist.all_reduce(el2, op=dist.ReduceOp.MAX)
-                nog = float(el2.item())
-            nogs.append(nog)
-        nog = float(np.median(nogs))
-        with_gather[0] = True
-        ms_with, ms_without = elapsed / args.steps * 1e3, nog / args.steps * 1e3
+            nogs = []
+            for _ in range(len(block_s)):                   # as many blocks as the timed region took, the median again
+                n0 = time.perf_counter()
+                for _ in range(args.steps):
+                    step()
+                fence()
+                nog = time.perf_counter() - n0
+                if world > 1:
+                    el2 = torch.tensor([nog], dtype=torch.float64, device=device)
+                    dist.all_reduce(el2, op=dist.ReduceOp.MAX)
+                    nog = float(el2.item())
+                nogs.append(nog)
+            nog = float(np.median(nogs))
+            with_gather[0] = True
+            ms_without = nog / args.steps * 1e3
         diag = {"backend": (dist.get_backend() if (world > 1 or pg_one) else "none (one process)"),
                 "world_size_seen_by_the_process_group": (dist.get_world_size() if (world > 1 or pg_one) else 1),
                 "ms_per_step_per_rank": [round(v, 4) for v in per_rank],
                 "ms_per_step_min_max_over_ranks": [round(min(per_rank), 4), round(max(per_rank), 4)],
                 # the destination rank takes in (N - 1) blocks per step on top of its own shard: what that costs it
                 "rank0_extra_ms_over_the_slowest_other_rank": (round(per_rank[0] - max(per_rank[1:]), 4) if len(per_rank) > 1 else None),
-                "ms_per_step_without_pack_and_gather": round(ms_without, 4),
+                "ms_per_step_without_pack_and_gather": None if ms_without is None else round(ms_without, 4),
                 "gather_ms_on_its_stream": None if gms is None else {"mean": round(gms[0], 4), "min": round(gms[1], 4), "max": round(gms[2], 4), "count": gms[3]},
                 "gather_hidden_behind_compute_frac": None}
-        if gms is not None and gms[0] > 0:
+        if gms is not None and gms[0] > 0 and ms_without is not None:
             exposed = max(0.0, ms_with - ms_without)
             diag["gather_hidden_behind_compute_frac"] = round(max(0.0, 1.0 - exposed / gms[0]), 3)
     # The other pipeline form, as a second, separately reported measurement (same steps, same fences; N = 1 only): the
@@ -640,7 +660,7 @@ def main():
     # counter reads per wavefront; untimed) - what roofline_step prices the step's vector-issue capacity at
     edge_clock_mhz = None
     probe_steps = 0
-    if args.dp_mode == "two_kernel" and pl.get_option("edge_form") == 0:
+    if args.full and args.dp_mode == "two_kernel" and pl.get_option("edge_form") == 0:
         fence()
         pl.set_timing(False)
         pl.set_option("edge_clock_probe", 1)
@@ -655,38 +675,40 @@ def main():
                 clocks.append(c)
         pl.set_option("edge_clock_probe", 0)
         edge_clock_mhz = float(np.median(clocks)) if clocks else None
-    # Per-kernel breakdown: a separate diagnostic pass AFTER the timed region, every kernel bracketed, one batch in
+    # --full: per-kernel breakdown, a separate diagnostic pass AFTER the timed region, every kernel bracketed, one batch in
     # flight (the durations of overlapping kernels would not add up to anything)
-    fence()
-    pl.set_pipeline(False)
-    for _ in range(2):
-        out, res = step()
-    fence()
-    pl.set_timing(True)
-    for _ in range(min(args.steps, 5)):
-        out, res = step()
-    fence()
     kernels = {}
-    for name in ("project", "dp_edge", "dp_sweep", "dp_fused", "dp_enrich", "path_qp", "to_cartesian", "heading", "st_graph",
-                 "speed_dp"):
-        ms = pl.kernel_ms(name)
-        if ms >= 0:
-            kernels[name] = round(ms, 6)
+    if args.full:
+        fence()
+        pl.set_pipeline(False)
+        for _ in range(2):
+            out, res = step()
+        fence()
+        pl.set_timing(True)
+        for _ in range(min(args.steps, 5)):
+            out, res = step()
+        fence()
+        for name in ("project", "dp_edge", "dp_sweep", "dp_fused", "dp_enrich", "path_qp", "to_cartesian", "heading", "st_graph",
+                     "speed_dp"):
+            ms = pl.kernel_ms(name)
+            if ms >= 0:
+                kernels[name] = round(ms, 6)
     pl.set_timing(False)
 
     # ---- secondary legs (N = 1, the default workload only): other workloads, observed by the same command, after the headline
     # and its diagnostic pass; each is a short measurement of its own and never touches the headline's numbers
     legs = {}
-    if (world == 1 and not gather_path and not wide and not args.no_legs and args.scenes_per_gpu in (0, 4096) and args.total_scenes in (0, 4096)
+    if (args.full and world == 1 and not gather_path and not wide and not args.no_legs and args.scenes_per_gpu in (0, 4096) and args.total_scenes in (0, 4096)
             and args.dp_mode == "two_kernel" and (auto_choice is not None or args.pipeline == DEFAULT_PIPELINE) and args.scene_dist == "corridor"):
         # (a) the staged pipeline of rounds 2-5 (two batches: the front stage of one beside the back stage of the other; the sweep
         # overlaps only the previous batch's Cartesian tail), with the library's default options and with the sweep held back
         # behind the previous batch's path QP (EMP_OPT_SWEEP_EXCLUSIVE = 2).  Each in a process of its own: which hardware queue
         # a stream lands on depends on the streams the process created before it, and a staged pipeline set up behind three lane
         # streams finds its two stages on one queue (0.43 ms a step instead of 0.22) - a fresh process is what a staged user has.
-        legs["staged_leg"] = staged_subprocess_leg(args.steps, {})
-        legs["exclusive_sweep_leg"] = staged_subprocess_leg(args.steps, {"sweep_exclusive": 2})
-        legs["rccl_gather_leg"] = rccl_gather_subprocess_leg(max(args.steps, 20))
+        # (their processes read frac_alone and the steps without pack and gather: --full figures)
+        legs["staged_leg"] = staged_subprocess_leg(args.steps, {}, ("--full",))
+        legs["exclusive_sweep_leg"] = staged_subprocess_leg(args.steps, {"sweep_exclusive": 2}, ("--full",))
+        legs["rccl_gather_leg"] = rccl_gather_subprocess_leg(max(args.steps, 20), ("--full",))
         legs["gather_path_leg"] = gather_path_leg(pl, torch, emp_dist, S.CFG2, 4096, max(args.steps, 20), device, scene_kw)
         legs["dram_leg"] = secondary_leg(pl, torch, S.CFG2, 32768, 10, 12, device, scene_kw)
         legs["cfg5_leg"] = secondary_leg(pl, torch, S.CFG5, 4096, 12, 6, device, scene_kw, speed=True)   # 55 ms timed: like the headline's blocks
@@ -702,9 +724,11 @@ def main():
         legs["dropin_leg"] = dropin_subprocess_leg(200)
 
     # outcome statistics (sanity: the work was really done): the planned fraction of every input batch the steps rotate through
-    # (one more pass each, untimed); every rank looks at its own shard and the fractions are averaged over the ranks
+    # (one more pass each, untimed, one batch in flight); every rank looks at its own shard and the fractions are averaged over
+    # the ranks
     fence()
     pl.set_timing(False)
+    pl.set_pipeline(False)
     oks = []
     for ib in range(n_in):
         with torch.cuda.stream(ts):
@@ -865,10 +889,10 @@ def main():
             "roofline": roof,
             "roofline_step": (roofline_step(cfg, count, args.scene_dist, elapsed / args.steps * 1e3, speed=wide, measured_clock_mhz=edge_clock_mhz) if pmode != 0 else None),
             **extra,
-            "kernels_ms": kernels,
+            "kernels_ms": kernels if args.full else None,
             "alt_pipeline": alt,
             "scenes_fully_planned_frac": round(ok_frac, 4),
-            "parity_sweeps_committed": committed_parity_sweeps() if (world == 1 and not args.no_legs) else None,
+            "parity_sweeps_committed": committed_parity_sweeps() if (args.full and world == 1 and not args.no_legs) else None,
             "options": {**{k: pl.get_option(k) for k in ("sweep_exclusive", "edge_after_enrich", "lane_edge_order", "path_qp_form", "edge_form")}, **options},
             **legs,
         }
@@ -881,7 +905,7 @@ def main():
         elif world > 1 or args.gather == "none":
             line["gather"] = {"mode": "none", "note": "no pack, no gather: compute scaling only",
                               "world_size_seen_by_the_process_group": (dist.get_world_size() if world > 1 else 1)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample if not wide else 2, 0, scene_kw)
             workers = usable_cores(64) if args.cpu_pool < 0 else args.cpu_pool
             if workers > 0 and not wide:

@@ -1,4 +1,4 @@
-"""bench_legs.py - the secondary measurements of bench.py's default run, and the step roofline.
+"""bench_legs.py - the secondary measurements of bench.py --full, and the step roofline.
 
 Imported by bench.py only (kept beside it so that bench.py itself stays the contract: arguments, the timed region, the JSON
 line, the CPU baselines).  Nothing here imports ``oracle/``: the CPU baselines are bench.py's.  Each leg is a short,
@@ -465,13 +465,14 @@ def roofline_step(cfg, count, scene_dist, ms_per_step, speed=False, measured_clo
 
 
 _BENCH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench.py")     # the legs below run it in processes of their own
-def rccl_gather_subprocess_leg(steps):
-    """`python bench.py --force-gather-path --one-rank-rccl --no-legs --no-cpu-baseline` in a fresh process, as a rank of an
-    N > 1 run is: the headline's step with its records packed and gathered to rank 0 by RCCL (one rank: the identity, through
-    ProcessGroupNCCL) on the gather stream, every step."""
+def rccl_gather_subprocess_leg(steps, bench_args=()):
+    """`python bench.py --force-gather-path --one-rank-rccl --no-legs --no-cpu-baseline [bench_args]` in a fresh process, as a
+    rank of an N > 1 run is: the headline's step with its records packed and gathered to rank 0 by RCCL (one rank: the identity,
+    through ProcessGroupNCCL) on the gather stream, every step.  `bench_args`: what the caller's bench.py needs for the figures
+    read below (bench.py --full passes --full)."""
     import subprocess
     t_leg = time.perf_counter()
-    cmd = [sys.executable, _BENCH, "--force-gather-path", "--one-rank-rccl", "--no-legs", "--no-cpu-baseline",
+    cmd = [sys.executable, _BENCH, *bench_args, "--force-gather-path", "--one-rank-rccl", "--no-legs", "--no-cpu-baseline",
            "--steps", str(steps), "--warmup", "5"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=os.path.dirname(_BENCH))
@@ -511,12 +512,13 @@ def dropin_subprocess_leg(requests=200):
         return {"error": f"{type(exc).__name__}: {exc}", "leg_wall_s": round(time.perf_counter() - t_leg, 2)}
 
 
-def staged_subprocess_leg(steps, options):
-    """`python bench.py --pipeline staged --no-legs --no-cpu-baseline [--opt ...]` in a fresh process (this one waits, its GPU
-    work fenced): the staged form's step time and its sweep's launches, as that command prints them."""
+def staged_subprocess_leg(steps, options, bench_args=()):
+    """`python bench.py --pipeline staged --no-legs --no-cpu-baseline [bench_args] [--opt ...]` in a fresh process (this one
+    waits, its GPU work fenced): the staged form's step time and its sweep's launches, as that command prints them
+    (`bench_args` as for rccl_gather_subprocess_leg)."""
     import subprocess
     t_leg = time.perf_counter()
-    cmd = [sys.executable, _BENCH, "--pipeline", "staged", "--no-legs", "--no-cpu-baseline", "--steps", str(steps),
+    cmd = [sys.executable, _BENCH, *bench_args, "--pipeline", "staged", "--no-legs", "--no-cpu-baseline", "--steps", str(steps),
            "--warmup", "5"]
     for k, v in options.items():
         cmd += ["--opt", f"{k}={v}"]

@@ -1,9 +1,11 @@
 """bench.py end to end on the GPU, short: the one-GPU line and the per-step code of an N > 1 rank (record packing on the
-result stream, gather on its own stream - the gather itself is the identity without a process group)."""
+result stream, gather on its own stream - the gather itself is the identity without a process group).  A plain run measures
+the headline only; the lines that check what else the benchmark measures run it with --full."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -19,12 +21,52 @@ def _auto_form(streams_beside_the_lanes):
     return queues, ("3 lanes" if queues >= 3 + streams_beside_the_lanes else "staged")
 
 
-def _run(*extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
-           *(() if "--legs" in extra else ("--no-legs",)), *[e for e in extra if e != "--legs"]]
+def _run(*extra, full=False):
+    """bench.py --steps 4 --warmup 2: a plain run, or with full=True a --full run without the CPU baselines (and without the
+    secondary legs unless "--legs" is among `extra`)."""
+    opts = ("--full", "--no-cpu-baseline", *(() if "--legs" in extra else ("--no-legs",))) if full else ()
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", *opts,
+           *[e for e in extra if e != "--legs"]]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_plain_run_measures_the_headline_only():
+    """`bench.py --steps K --warmup W` without --full: the contract's keys, the headline's own figures (the timed region's sweep
+    events, the planned fraction `value` needs) and nothing that takes a run of its own - no CPU baselines, no secondary legs,
+    no per-kernel diagnostic pass, no clock probe - so that the run spends little time outside its steps."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5"]
+    t0 = time.perf_counter()
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["timed_steps"] == 20 and d["timed_blocks"] == 1
+    assert d["unit"] == "planning cycles/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["value"] > 1e6
+    assert abs(d["value"] - d["all_scenes_cycles_per_s"] * d["scenes_fully_planned_frac"]) <= 1e-3 * d["value"]
+    assert 0.8 < d["scenes_fully_planned_frac"] < 0.95 and d["roofline"]["frac"] > 0.05 and d["roofline"]["frac_alone"] is None
+    assert d["cpu_baseline"] is None and "cpu_baseline_pool" not in d and d["kernels_ms"] is None
+    assert d["parity_sweeps_committed"] is None and d["untimed_steps_between_the_timed_region_and_the_diagnostic_pass"] == 0
+    assert not [k for k in d if k.endswith("_leg")] and "roofline_dp_edge" not in d and "dp_only" not in d
+    assert d["roofline_step"] is None or "frac_at_the_measured_clock" not in d["roofline_step"]
+    # the whole run, start to exit, less its warm-up and timed steps
+    assert wall - (20 + 5) * d["ms_per_step"] * 1e-3 < 30.0, wall
+
+
+def test_plain_run_with_the_gather_path():
+    """The per-step code of an N > 1 rank in a plain run: records packed and gathered every step and complete at the end;
+    the same steps without pack and gather are a --full figure."""
+    d = _run("--force-gather-path", "--scenes-per-gpu", "512")
+    g = d["gather"]
+    assert d["value"] > 1e5 and g["records_complete_on_rank0"] is True and g["doubles_per_scene"] == 179
+    assert g["gather_ms_on_its_stream"]["count"] == 4 and g["ms_per_step_without_pack_and_gather"] is None
+    assert g["gather_hidden_behind_compute_frac"] is None and d["kernels_ms"] is None and d["cpu_baseline"] is None
 
 
 @pytest.mark.parametrize("extra", [(), ("--no-pipeline",), ("--force-gather-path",), ("--force-gather-path", "--no-pipeline"),
@@ -32,7 +74,7 @@ def _run(*extra):
 def test_bench_line(extra):
     if "--alt-pipeline" in extra and _auto_form(2)[1] == "staged":
         extra = ("--alt-pipeline", "3")      # the headline is already the staged form on these queues: the other form is lanes
-    d = _run(*extra, "--min-timed-ms", "50")
+    d = _run(*extra, "--min-timed-ms", "50", full=True)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in d, key
@@ -79,7 +121,7 @@ def test_bench_line(extra):
 def test_other_bench_lines(extra, metric_part):
     """The other lines bench.py can print (BASELINE configs[1] and [4], the survey's and the worst-case scene layouts, the
     fused DP, the all-gather / trajectory-only exchange): each runs and carries the contract's keys."""
-    d = _run(*extra)
+    d = _run(*extra, full=True)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in d, key
@@ -101,11 +143,11 @@ def test_other_bench_lines(extra, metric_part):
 
 
 def test_default_run_carries_the_secondary_legs():
-    """The driver's one command (no flags beyond steps / warm-up) also observes the other workloads: the sweep held back behind
+    """The default workload's --full run also observes the other workloads: the sweep held back behind
     the previous batch's path QP, 32768 scenes (edge tensor from HBM), BASELINE configs[4] on 4096 scenes, configs[1], SURVEY
     8(d)'s arc radii with both obstacle layouts, the host path (NumPy in and out) and the N > 1 per-step code - each a short
     leg behind the headline, none of which may fail or change the headline's keys."""
-    d = _run("--legs")
+    d = _run("--legs", full=True)
     assert d["options"]["sweep_exclusive"] == 0 and d["options"]["edge_form"] == 0          # the library's defaults: the fastest step
     assert d["value_definition"].startswith("fully_planned") and d["fully_planned_cycles_per_s"] == d["value"]
     assert d["config"]["start_ahead_m"] == 2.7 and d["config"]["arc_radii_m"] == [1500.0, 6000.0]
@@ -197,7 +239,7 @@ def test_bench_two_ranks_on_one_gpu(extra):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--settle-steps", "4", "--scenes-per-gpu", "1024", "--no-cpu-baseline", *extra]
+           "--settle-steps", "4", "--scenes-per-gpu", "1024", "--full", "--no-cpu-baseline", *extra]
     env = dict(os.environ, EMP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -243,7 +285,7 @@ def test_bare_command_with_gpus_2_launches_two_ranks(size):
     bench.py re-executes itself under torch.distributed.run (gloo here: both ranks share the one GPU).  With --total-scenes the
     total is fixed and sharded (BASELINE configs[3] as written: strong scaling), ragged shards included."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--settle-steps", "4",
-           "--no-cpu-baseline", *size]
+           "--full", "--no-cpu-baseline", *size]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(EMP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)

@@ -5,7 +5,7 @@ mkdir -p $OUT
 for rep in 1 2; do
 for lib in "$@"; do
   cp variants/$lib emplanner_carla_amd/libemplanner.so
-  python bench.py --no-legs --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/b_${lib}_$rep.json 2> $OUT/e_${lib}_$rep.txt
+  python bench.py --full --no-legs --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/b_${lib}_$rep.json 2> $OUT/e_${lib}_$rep.txt
   python - <<PY
 import json
 try:

@@ -1,9 +1,9 @@
 #!/bin/bash
-# bench.py --no-legs --no-cpu-baseline under each --pipeline value: tools/pipe_ab.sh OUTDIR staged 2 3 4 ...
+# bench.py --full --no-legs --no-cpu-baseline under each --pipeline value: tools/pipe_ab.sh OUTDIR staged 2 3 4 ...
 OUT=$1; shift
 mkdir -p $OUT
 for p in "$@"; do
-  python bench.py --no-legs --no-cpu-baseline --pipeline $p ${BENCH_ARGS:-} > $OUT/bench_p$p.json 2> $OUT/err_p$p.txt
+  python bench.py --full --no-legs --no-cpu-baseline --pipeline $p ${BENCH_ARGS:-} > $OUT/bench_p$p.json 2> $OUT/err_p$p.txt
   python - <<PY
 import json
 try:

@@ -1,5 +1,5 @@
 #!/bin/bash
-# In-step A/B of edge-kernel options: bench.py --no-legs --no-cpu-baseline for each "name=value,name=value" argument.
+# In-step A/B of edge-kernel options: bench.py --full --no-legs --no-cpu-baseline for each "name=value,name=value" argument.
 # Usage: tools/step_ab.sh OUTDIR "edge_form=0,edge_block=128" "edge_form=1" ...
 OUT=$1; shift
 mkdir -p $OUT
@@ -7,7 +7,7 @@ for combo in "$@"; do
   args=""
   for kv in ${combo//,/ }; do args="$args --opt $kv"; done
   tag=${combo//,/_}; tag=${tag//=/}
-  python bench.py --no-legs --no-cpu-baseline ${BENCH_ARGS:-} $args > $OUT/bench_$tag.json 2> $OUT/err_$tag.txt
+  python bench.py --full --no-legs --no-cpu-baseline ${BENCH_ARGS:-} $args > $OUT/bench_$tag.json 2> $OUT/err_$tag.txt
   python - <<PY
 import json
 try:
