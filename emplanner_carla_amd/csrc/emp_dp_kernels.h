@@ -375,6 +375,13 @@ constexpr int kRingMaxCol = 32767;
 #ifndef EMP_EDGE_RING_BOUNDS
 #define EMP_EDGE_RING_BOUNDS __launch_bounds__(1024, EMP_EDGE_WAVES)
 #endif
+// Development measurement (-DEMP_DEV_HOOKS=1 -DEMP_EDGE_NO_SCAN=1 only): the ring kernel pops and stores its entries without
+// scanning their obstacles - the counters of such a build are the dense pass and the ring bookkeeping alone
+// (profiles/r07_edge/README.md).  The tensor it writes is wrong by design; a product build never compiles it in.
+#ifndef EMP_EDGE_NO_SCAN
+#define EMP_EDGE_NO_SCAN 0
+#endif
+constexpr bool kEdgeNoScan = EMP_DEV_HOOKS && EMP_EDGE_NO_SCAN;
 template <bool TILED, int ROW = 0, typename MASK = unsigned>
 __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* __restrict__ pair_tab,
                                                            const double* __restrict__ obs_s,
@@ -487,7 +494,8 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
             const double* o_s = t_obs_s + so * P.max_obs;
             const double* o_l = t_obs_l + so * P.max_obs;
             double coll = 0.0;
-            if (c == 0) {                                                     // exactly one obstacle in reach
+            if (kEdgeNoScan) {
+            } else if (c == 0) {                                              // exactly one obstacle in reach
                 const int m = (int)((code >> 6) & 63u);
                 coll = coll + obstacle_scan_dense(s0, t_smp, &tab[p], rr, o_s[m], o_l[m], P.w_coll);
             } else {
@@ -517,8 +525,9 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
         // the scene reads those verdicts out of ONE ballot per `row` obstacles (the scene's lanes are neighbours), where each
         // lane used to walk all the scene's obstacles itself (round 6: nob LDS reads and 4 nob instructions a column and lane;
         // its 6.5 m margin let through a few obstacles more, whose bands were empty all the same).
-        MASK near_s = 0;
+        MASK near_s = 0, near_w = 0;                                    // near_w: the union over the wavefront's scenes
         const int my_first_lane = sl * row;
+        const unsigned long long row_bits = (1ull << row) - 1;
         for (int m0 = 0; m0 < P.max_obs && m0 < kMaskBits; m0 += row) {      // wave-uniform trip count
             const int m = m0 + i;
             bool in_reach = false;
@@ -531,26 +540,51 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
                 my_band[2 * m] = in_reach ? ol - r : __builtin_inf();
                 my_band[2 * m + 1] = in_reach ? ol + r : -__builtin_inf();
             }
-            const unsigned long long verdicts = (__ballot(in_reach) >> my_first_lane) & ((1ull << row) - 1);   // obstacles m0 .. m0 + row - 1 of MY scene
+            const unsigned long long votes = __ballot(in_reach);
+            const unsigned long long verdicts = (votes >> my_first_lane) & row_bits;   // obstacles m0 .. m0 + row - 1 of MY scene
             near_s |= (MASK)((MASK)verdicts << m0);
+            unsigned long long any = 0;
+            for (int f = 0; f < lanes_used; f += row) any |= votes >> f;              // scalar: every scene's verdicts folded
+            near_w |= (MASK)((MASK)(any & row_bits) << m0);
         }
         if (!live) near_s = 0;
         __builtin_amdgcn_wave_barrier();
+        // Which obstacles an edge (k -> i) must scan: m with (l_hi > b_lo[m]) & (l_lo < b_hi[m]), l_hi / l_lo the pair table's
+        // fmax / fmin of l_k and l_i.  fmax and fmin return one of their operands (lattice values are never NaN), so exactly
+        //     l_hi > b_lo  <=>  (l_k > b_lo) | (l_i > b_lo)        l_lo < b_hi  <=>  (l_k < b_hi) | (l_i < b_hi)
+        // and the edge's mask is (A_k | A_i) & (B_k | B_i) & near_s with A_i = {m : l_i > b_lo[m]}, B_i = {m : l_i < b_hi[m]}.
+        // Every lane builds its own A and B once per column (one pass over the bands, wave-uniform: the obstacles in reach of
+        // ANY scene of the wavefront, the others masked by near_s); lane first_lane_of_scene + k holds A_k and B_k.  The same
+        // bits as testing every (edge, obstacle) pair - where the source row k walked near_s per lane, nine times a column.
+        MASK a_own = 0, b_own = 0;
+        {
+            const double l_own = tab[kF_LHI * rr + i * row + i];      // fmax(l_i, l_i): the pair table's own value of row i
+            for (MASK rest = near_w; rest; rest &= rest - 1) {
+                const int m = (kMaskBits == 32 ? __ffs((int)rest) : __ffsll((long long)rest)) - 1;
+                const double b_lo = my_band[2 * m], b_hi = my_band[2 * m + 1];
+                a_own |= (l_own > b_lo) ? (MASK)1 << m : (MASK)0;
+                b_own |= (l_own < b_hi) ? (MASK)1 << m : (MASK)0;
+            }
+        }
         const double F = jerk_unit_sum(t_smp, s0);                      // the column's jerk factor
         if (live && i == 0) f_tab[((j - j_begin - wave) / waves) * P.S + s] = F;
         for (int k = 0; k < row; ++k) {
             const int p = k * row + i;
-            MASK pass = 0;
-            double smooth = 0.0;
-            if (live) {
-                smooth = tab[kF_BASE * rr + p] + tab[kF_JERK * rr + p] * F;
-                const double l_lo = tab[kF_LLO * rr + p], l_hi = tab[kF_LHI * rr + p];
-                for (MASK rest = near_s; rest; rest &= rest - 1) {
-                    const int m = (kMaskBits == 32 ? __ffs((int)rest) : __ffsll((long long)rest)) - 1;
-                    const double b_lo = my_band[2 * m], b_hi = my_band[2 * m + 1];
-                    pass |= ((l_hi > b_lo) & (l_lo < b_hi)) ? (MASK)1 << m : (MASK)0;       // '&': no short-circuit branches
-                }
-                if (pass == 0) store_edge(j, k, lane, (smooth + 0.0) + tab[kF_REF * rr + p]);
+            const int src = (my_first_lane + k) << 2;                    // every lane of the wavefront is active here
+            MASK a_k, b_k;
+            if constexpr (kMaskBits == 32) {
+                a_k = (MASK)__builtin_amdgcn_ds_bpermute(src, (int)a_own);
+                b_k = (MASK)__builtin_amdgcn_ds_bpermute(src, (int)b_own);
+            } else {
+                a_k = ((MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)(a_own >> 32)) << 32) |
+                      (MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)a_own);
+                b_k = ((MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)(b_own >> 32)) << 32) |
+                      (MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)b_own);
+            }
+            const MASK pass = (a_k | a_own) & (b_k | b_own) & near_s;    // 0 on a dead lane (near_s = 0)
+            if (live && pass == 0) {
+                const double smooth = tab[kF_BASE * rr + p] + tab[kF_JERK * rr + p] * F;
+                store_edge(j, k, lane, (smooth + 0.0) + tab[kF_REF * rr + p]);
             }
             const bool one = pass != 0 && (pass & (pass - 1)) == 0;
             const bool many = pass != 0 && !one;
