@@ -234,7 +234,7 @@ static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
         const size_t waves_total = (size_t)grid.x * grid.y * wpb;
         const int grc = grow_buffer(ctx, ctx->edge_probe, waves_total * 4 * sizeof(unsigned long long));
         if (grc) return grc;
-        if (!ctx->edge_probe_done) EMP_HIP(ctx, hipEventCreateWithFlags(&ctx->edge_probe_done, hipEventDisableTiming));
+        if (const int rc = ctx->edge_probe_done.ensure(ctx, hipEventDisableTiming)) return rc;
         ctx->edge_probe_waves = (long)waves_total;
         if (const int rc = launch(ctx, "dp_edge", kern_ring, grid, block, lds, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
                                   cols_per_chunk, (unsigned long long*)ctx->edge_probe.p))
@@ -260,7 +260,7 @@ static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
     EMP_LAUNCH_CHECK(ctx);
     if (ordered) {
         emp_ctx::Lane& ln = ctx->lanes[ctx->active_lane];
-        if (!ln.ev_edge) EMP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_edge, hipEventDisableTiming));
+        if (const int rc = ln.ev_edge.ensure(ctx, hipEventDisableTiming)) return rc;
         ctx->lane_edge_done = ln.ev_edge;
         EMP_HIP(ctx, hipEventRecord(ctx->lane_edge_done, ctx->stream));
     }
@@ -308,11 +308,11 @@ static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, 
                                                    : (const void*)dp_sweep_kernel<R, PD, WPB, NT, true>,    \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
         if (const int rc = launch_gate(ctx)) return rc;                                                     \
-        if (ctx->capturing && defer) {      /* a stream capture records plain launches only */              \
+        if (ctx->cycle_graph.capturing && defer) {      /* a stream capture records plain launches only */  \
             hipLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT, false>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
                                ctx->stream, d, start_cost, edge, n_obs, rows, min_cost, status, bt_pre, bt_term, probe); \
             deferred = true;                                                                                \
-        } else if (ctx->capturing) {                                                                        \
+        } else if (ctx->cycle_graph.capturing) {                                                            \
             hipLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
                                ctx->stream, d, start_cost, edge, n_obs, rows, min_cost, status,             \
                                (unsigned char*)nullptr, (int*)nullptr, probe);                              \
@@ -363,7 +363,7 @@ static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, 
     }
     EMP_LAUNCH_CHECK(ctx);
     if (probe) {
-        if (!ctx->clock_probe_done) EMP_HIP(ctx, hipEventCreateWithFlags(&ctx->clock_probe_done, hipEventDisableTiming));
+        if (const int rc = ctx->clock_probe_done.ensure(ctx, hipEventDisableTiming)) return rc;
         EMP_HIP(ctx, hipEventRecord(ctx->clock_probe_done, ctx->stream));
     }
     return EMP_OK;
@@ -544,11 +544,11 @@ int emp_create(int device_id, emp_ctx** out) {
     emp_ctx* c = new emp_ctx();
     c->device = device_id;
     c->cu_count = prop.multiProcessorCount;
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
+    if (const int rc = c->main_stream.ensure(nullptr, hipStreamNonBlocking)) {
         delete c;
-        return fail(nullptr, EMP_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+        return rc;
     }
+    c->stream = c->main_stream;
     *out = c;
     return EMP_OK;
 }
@@ -556,48 +556,7 @@ int emp_create(int device_id, emp_ctx** out) {
 void emp_destroy(emp_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    (void)sync_all(ctx);
-    for (auto& b : ctx->pool)
-        if (b.p) (void)hipFree(b.p);
-    for (auto& ln : ctx->lanes) {
-        for (auto& b : ln.pool)
-            if (b.p) (void)hipFree(b.p);
-        if (ln.ev_in) (void)hipEventDestroy(ln.ev_in);
-        if (ln.ev_done) (void)hipEventDestroy(ln.ev_done);
-        if (ln.ev_front) (void)hipEventDestroy(ln.ev_front);
-        if (ln.ev_edge) (void)hipEventDestroy(ln.ev_edge);
-        if (ln.ev_tail) (void)hipEventDestroy(ln.ev_tail);
-        if (ln.ev_qp) (void)hipEventDestroy(ln.ev_qp);
-        if (ln.ev_enrich) (void)hipEventDestroy(ln.ev_enrich);
-        if (ln.ev_host) (void)hipEventDestroy(ln.ev_host);
-        if (ln.stream) (void)hipStreamDestroy(ln.stream);
-    }
-    if (ctx->cycle_graph) (void)hipGraphExecDestroy(ctx->cycle_graph);
-    if (ctx->back_stream) (void)hipStreamDestroy(ctx->back_stream);
-    if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    if (ctx->d2h_stream) (void)hipStreamDestroy(ctx->d2h_stream);
-    if (ctx->ev_h2d) (void)hipEventDestroy(ctx->ev_h2d);
-    if (ctx->ev_host_last) (void)hipEventDestroy(ctx->ev_host_last);
-    for (auto& hp : ctx->pinned) (void)hipHostFree(hp.p);
-    if (ctx->clock_probe.p) (void)hipFree(ctx->clock_probe.p);
-    if (ctx->clock_probe_done) (void)hipEventDestroy(ctx->clock_probe_done);
-    if (ctx->edge_probe.p) (void)hipFree(ctx->edge_probe.p);
-    if (ctx->edge_probe_done) (void)hipEventDestroy(ctx->edge_probe_done);
-    if (ctx->sweep_marker) (void)hipEventDestroy(ctx->sweep_marker);
-    for (auto& kv : ctx->pair_tables)
-        if (kv.second.buf.p) (void)hipFree(kv.second.buf.p);
-    for (auto& kv : ctx->named)
-        if (kv.second.p) (void)hipFree(kv.second.p);
-    if (ctx->arena_h_in) (void)hipHostFree(ctx->arena_h_in);
-    if (ctx->arena_h_out) (void)hipHostFree(ctx->arena_h_out);
-    if (ctx->arena_d_in) (void)hipFree(ctx->arena_d_in);
-    if (ctx->arena_d_out) (void)hipFree(ctx->arena_d_out);
-    for (auto& kv : ctx->events)
-        for (auto& pr : kv.second.pairs) {
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
-        }
-    (void)hipStreamDestroy(ctx->stream);
+    (void)sync_all(ctx);        // the owners release without synchronising
     delete ctx;
 }
 
@@ -609,7 +568,7 @@ int emp_synchronize(emp_ctx* ctx) {
     return EMP_OK;
 }
 
-void* emp_stream(emp_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+void* emp_stream(emp_ctx* ctx) { return ctx ? (void*)ctx->main_stream : nullptr; }
 
 void* emp_result_stream(emp_ctx* ctx) {
     if (!ctx) return nullptr;
@@ -733,32 +692,21 @@ int emp_set_pipeline(emp_ctx* ctx, int mode) {
     // few hardware queues, and a staged pipeline set up while three lane streams of an earlier mode were still alive found its
     // front and back stage on one queue - 0.43 ms a step instead of 0.22 (bench.py's staged legs behind the three-lane headline)
     for (size_t i = 0; i < ctx->lanes.size(); ++i)
-        if (ctx->lanes[i].stream && (m == EMP_PIPELINE_STAGED || (int)i >= m)) {
-            EMP_HIP(ctx, hipStreamDestroy(ctx->lanes[i].stream));
-            ctx->lanes[i].stream = nullptr;
-        }
-    if (m != EMP_PIPELINE_STAGED && ctx->back_stream) {
-        EMP_HIP(ctx, hipStreamDestroy(ctx->back_stream));
-        ctx->back_stream = nullptr;
-    }
+        if (m == EMP_PIPELINE_STAGED || (int)i >= m) EMP_HIP(ctx, ctx->lanes[i].stream.reset());
+    if (m != EMP_PIPELINE_STAGED) EMP_HIP(ctx, ctx->back_stream.reset());
     if ((int)ctx->lanes.size() < need) ctx->lanes.resize(need);
     for (int i = 0; i < need; ++i) {
         emp_ctx::Lane& ln = ctx->lanes[i];
-        if (m != EMP_PIPELINE_STAGED && !ln.stream) EMP_HIP(ctx, hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-        if (!ln.ev_in) EMP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_in, hipEventDisableTiming));
-        if (!ln.ev_front) EMP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_front, hipEventDisableTiming));
-        if (!ln.ev_tail) EMP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_tail, hipEventDisableTiming));
-        if (!ln.ev_done) EMP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_done, hipEventDisableTiming));
-        if (!ln.ev_qp) EMP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_qp, hipEventDisableTiming));
-        if (!ln.ev_enrich) EMP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_enrich, hipEventDisableTiming));
+        int rc = EMP_OK;
+        if (m != EMP_PIPELINE_STAGED && (rc = ln.stream.ensure(ctx, hipStreamNonBlocking))) return rc;
+        for (emp::Event* ev : {&ln.ev_in, &ln.ev_front, &ln.ev_tail, &ln.ev_done, &ln.ev_qp, &ln.ev_enrich})
+            if ((rc = ev->ensure(ctx, hipEventDisableTiming))) return rc;
     }
-    if (m == EMP_PIPELINE_STAGED && !ctx->back_stream) {
+    if (m == EMP_PIPELINE_STAGED) {
         // the back stage's kernels are short chains of dependent instructions on few wavefronts: their queue gets the
         // higher priority, so that they are dispatched (and, with s_setprio in the kernels, issued) ahead of the front
         // stage's bulk work they overlap with.  (Until round 6 an option confined this stream to a CU mask: never a gain.)
-        int prio_low = 0, prio_high = 0;
-        EMP_HIP(ctx, hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-        EMP_HIP(ctx, hipStreamCreateWithPriority(&ctx->back_stream, hipStreamNonBlocking, prio_high));
+        if (const int rc = ctx->back_stream.ensure(ctx, hipStreamNonBlocking, true)) return rc;
     }
     for (auto& ln : ctx->lanes) ln.done_valid = ln.qp_valid = ln.enrich_valid = false;       // everything was drained above
     ctx->lane_edge_done = nullptr;
@@ -1185,6 +1133,232 @@ static int dev_cycle_cartesian(emp_ctx* ctx, int B, int max_ref, int max_pts, in
                   begin_sl, path_s, path_l, path_len, traj, traj_len, status);
 }
 
+// ---- emp_plan_cycle's pipeline lane and cycle graph -------------------------------------------------------------------
+// Pipelined modes (device pointers only; emp_context.h).  LANES: the whole call runs on the next lane - its stream stands in
+// for ctx->stream and its pool for ctx->pool - behind whatever the caller has ordered on the main stream so far.  STAGED: the
+// call takes the pool of the next lane once the back stage that used it last is done; its front stage runs on the main
+// stream, its back stage on the back stream.
+// EMP_HOST_PINNED: the caller's arrays are page-locked; the call is pipelined like a device-pointer call, its inputs arrive
+// over the copy stream and its outputs leave over the d2h stream (emp_context.h Stage: async_host).
+// Outside pipelined mode (mode 0) a CycleLane orders nothing; done() still sends a pinned call's outputs home.
+class CycleLane {
+  public:
+    CycleLane(emp_ctx* c, int m, bool p) : ctx(c), mode(m), pinned(p) {}
+    ~CycleLane() {          // the main stream and pool stand in for the call's again
+        if (!ln) return;
+        ctx->stream = ctx->main_stream;
+        std::swap(ctx->pool, ln->pool);
+        ctx->active_lane = -1;
+    }
+
+    // The pinned path's streams and events, then the next lane is taken over and ordered.
+    int begin() {
+        if (pinned) {
+            if (const int rc = ctx->copy_stream.ensure(ctx, hipStreamNonBlocking)) return rc;
+            if (const int rc = ctx->d2h_stream.ensure(ctx, hipStreamNonBlocking)) return rc;
+            if (const int rc = ctx->ev_h2d.ensure(ctx, hipEventDisableTiming)) return rc;
+            if (const int rc = ctx->ev_host_last.ensure(ctx, hipEventDisableTiming)) return rc;
+        }
+        if (!mode) return EMP_OK;
+        ctx->lane = (ctx->lane + 1) % ctx->lanes_in_use();
+        ++ctx->cycle_calls;
+        ln = &ctx->lanes[ctx->lane];                  // (ln->ticket changes below, after the host-side wait for the lane's previous call)
+        std::swap(ctx->pool, ln->pool);
+        if (staged()) {
+            // the pool's previous user is four calls back: a host-side wait (emp_context.h, kStagedPools)
+            if (ln->done_valid) EMP_HIP(ctx, hipEventSynchronize(ln->ev_done));
+            if (ln->host_valid) EMP_HIP(ctx, hipEventSynchronize(ln->ev_host));   // ... and its outputs have left the pool
+        } else {
+            ctx->active_lane = ctx->lane;
+            ctx->stream = ln->stream;
+            if (ln->host_valid) EMP_HIP(ctx, hipEventSynchronize(ln->ev_host));
+            // The lane's previous occupant (call k - n) and whatever its caller queued behind it on the lane's stream (record
+            // packing) must be done before anything ordered on the main stream from here on may touch memory they use: the
+            // caller keeps a call's outputs alive only until this call is issued, and the NEXT call runs on another lane.
+            if (ln->done_valid) {
+                EMP_HIP(ctx, hipEventRecord(ln->ev_tail, ctx->stream));
+                EMP_HIP(ctx, hipStreamWaitEvent(ctx->main_stream, ln->ev_tail, 0));
+            }
+            EMP_HIP(ctx, hipEventRecord(ln->ev_in, ctx->main_stream));
+            EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ln->ev_in, 0));
+        }
+        // Only now - the previous occupant's outputs are in its caller's arrays - does the lane stop answering for the previous
+        // ticket: emp_wait_ticket(T) on another thread either still finds the lane under T with its event valid and waits for
+        // the same event, or finds no lane under T, which now MEANS that this thread has waited for T already (the advisor's
+        // round-5 finding: the ticket used to change before the wait, and a waiter in that window returned at once).
+        ln->host_valid = false;
+        ln->ticket = ctx->cycle_calls;
+        // A pinned call's inputs go into the lane's pool over the copy stream.  If the lane's previous occupant was an EMP_DEVICE
+        // cycle there has been no host-side wait for it: the copy stream waits for its kernels instead.
+        if (pinned && !staged() && ln->done_valid) EMP_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ln->ev_done, 0));
+        return EMP_OK;
+    }
+
+    // STAGED: what the front stage's launches signal and wait for (CycleSched).  `two_kernel`: the edge-cost kernel runs.
+    void front_waits(CycleSched& cs, bool two_kernel) const {
+        if (!staged()) return;
+        cs.front_stop = ln->ev_front;
+        // the previous call's back stage: its lane is the one before ours
+        const emp_ctx::Lane& prev = ctx->lanes[(ctx->lane + ctx->lanes_in_use() - 1) % ctx->lanes_in_use()];
+        // (EMP_OPT_SWEEP_EXCLUSIVE = 2: only its densification and path QP - the sweep runs beside the Cartesian tail)
+        if (ctx->opt[EMP_OPT_SWEEP_EXCLUSIVE] == 2 && prev.qp_valid) cs.sweep_wait = prev.ev_qp;
+        if (ctx->opt[EMP_OPT_SWEEP_EXCLUSIVE] == 1 && prev.done_valid) cs.sweep_wait = prev.ev_done;
+        if (ctx->opt[EMP_OPT_EDGE_AFTER_ENRICH] && two_kernel && prev.enrich_valid) cs.edge_wait = prev.ev_enrich;
+    }
+
+    // STAGED, behind the sweep: the back stage (short kernels that last as long as their slowest scene) goes to the back stream.
+    int to_back(const CycleSched& cs) {
+        if (!staged()) return EMP_OK;
+        // EMP_OPT_SWEEP_EXCLUSIVE: a marker behind the sweep on the front stream.  Measured, not understood: which of two
+        // regimes the two queues settle in depends on it.  With it the kernels keep the durations of the overlapped step (edge
+        // 198 us, path QP 140, Cartesian 70, sweep 19) and the step takes 0.264 ms (mode 2) / 0.277 (mode 1); without it the
+        // edge kernel runs at its stand-alone 147 us, starves the path QP beside it (250 us) and the step takes 0.32 - 0.35 ms
+        // (profiles/r04_sweep/README.md).  The clock probe's event did the same by accident, which is how this was found.
+        if (ctx->opt[EMP_OPT_SWEEP_EXCLUSIVE]) {
+            if (const int rc = ctx->sweep_marker.ensure(ctx, hipEventDisableTiming)) return rc;
+            EMP_HIP(ctx, hipEventRecord(ctx->sweep_marker, ctx->stream));
+        }
+        // behind the sweep's own completion event where the launch attached one (a marker packet behind the sweep costs the
+        // front queue ~5 us per step), else behind an event recorded here
+        hipEvent_t front_done = cs.front_attached;
+        if (!front_done) {
+            EMP_HIP(ctx, hipEventRecord(ln->ev_front, ctx->stream));
+            front_done = ln->ev_front;
+        }
+        EMP_HIP(ctx, hipStreamWaitEvent(ctx->back_stream, front_done, 0));
+        ctx->stream = ctx->back_stream;        // ~CycleLane puts the main stream back
+        return EMP_OK;
+    }
+
+    // STAGED: a back-stage kernel (`launch`) signals the lane's event `ev` for the NEXT call's front stage when `want`, and
+    // the lane's `valid` flag says whether it does.  The dispatch itself signals it where possible (CycleSched::attach_stop):
+    // a marker packet behind each idled the back queue ~6 us, and with the edge kernel's round-4 diet the back queue is what
+    // bounds the step.  Where the launch could not attach it, the event is recorded behind the kernel.
+    template <typename F>
+    int signal(CycleSched& cs, bool want, emp::Event emp_ctx::Lane::*ev, bool emp_ctx::Lane::*valid, F launch) {
+        want = want && staged();
+        cs.attach_stop = want ? (hipEvent_t)(ln->*ev) : nullptr;
+        cs.stop_attached = false;
+        if (const int rc = launch()) return rc;
+        if (want && !cs.stop_attached) EMP_HIP(ctx, hipEventRecord(ln->*ev, ctx->stream));
+        if (staged()) ln->*valid = want;
+        return EMP_OK;
+    }
+
+    // The end of the cycle: the lane's ev_done, then a pinned call's outputs go home on the d2h stream behind the cycle's last
+    // kernel.  Pipelined, nobody waits here (emp_wait_cycle, emp_synchronize, or the call that takes this pool over); not
+    // pipelined, the pool is the next call's, so the host waits.
+    int done(Stage& st) {
+        if (ln) {
+            EMP_HIP(ctx, hipEventRecord(ln->ev_done, ctx->stream));
+            ln->done_valid = true;
+        }
+        if (!st.async_host()) return EMP_OK;
+        if (ln) {
+            if (const int rc = ln->ev_host.ensure(ctx, hipEventDisableTiming)) return rc;
+            if (const int rc = st.finish_async(ln->ev_done, ln->ev_host)) return rc;
+            ln->host_valid = true;
+            return EMP_OK;
+        }
+        EMP_HIP(ctx, hipEventRecord(ctx->ev_h2d, ctx->stream));
+        if (const int rc = st.finish_async(ctx->ev_h2d, ctx->ev_host_last)) return rc;
+        EMP_HIP(ctx, hipEventSynchronize(ctx->ev_host_last));
+        return EMP_OK;
+    }
+
+  private:
+    bool staged() const { return mode == EMP_PIPELINE_STAGED; }
+    emp_ctx* ctx;
+    int mode;
+    bool pinned;
+    emp_ctx::Lane* ln = nullptr;       // the lane of this call (pipelined)
+};
+
+// EMP_OPT_CYCLE_GRAPH: one batch at a time on device pointers - the third consecutive call with one signature is captured,
+// the following ones are one hipGraphLaunch.  The signature is everything a launch argument is made of; the context's
+// allocation count says whether a temporary or a lattice table moved or changed since the capture.
+class CycleCapture {
+  public:
+    explicit CycleCapture(emp_ctx* c) : ctx(c) {}
+    ~CycleCapture() {
+        if (!active) return;            // (an early return inside the captured region: end the capture, keep nothing)
+        hipGraph_t g = nullptr;
+        (void)hipStreamEndCapture(ctx->stream, &g);
+        if (g) (void)hipGraphDestroy(g);
+        ctx->cycle_graph.capturing = false;
+    }
+
+    // A call that may use the graph replays it (and sets *replayed: that was the call's work) or, at its signature's third
+    // call in a row, begins a capture; any other call drops the graph.
+    int begin(int pmode, emp_mem where, int B, int max_ref, int max_obs, int max_pts, emp_dp_mode mode, const emp_dp_params* p,
+              const emp_qp_params* q, const emp_smooth_params* sp, const emp_cycle_io* io, bool* replayed) {
+        emp_ctx::CycleGraph& g = ctx->cycle_graph;
+        if (ctx->opt[EMP_OPT_CYCLE_GRAPH] != 1 || pmode != 0 || where != EMP_DEVICE || B <= 0 || ctx->timing ||
+            ctx->opt[EMP_OPT_SWEEP_CLOCK_PROBE] || ctx->opt[EMP_OPT_EDGE_CLOCK_PROBE]) {
+            if (g.exec) g.seen = 0;         // (a graph is dropped: its signature starts over)
+            (void)g.exec.reset();
+            return EMP_OK;
+        }
+        std::vector<unsigned long long> key;
+        auto add = [&](const void* ptr, size_t bytes) {
+            const unsigned char* b8 = (const unsigned char*)ptr;
+            for (size_t o = 0; o < bytes; o += 8) {
+                unsigned long long w = 0;
+                memcpy(&w, b8 + o, std::min<size_t>(8, bytes - o));
+                key.push_back(w);
+            }
+        };
+        const long long sizes[5] = {B, max_ref, max_obs, max_pts, (long long)mode};
+        add(sizes, sizeof(sizes));
+        add(p, sizeof(*p));
+        add(q, sizeof(*q));
+        add(sp, sizeof(*sp));
+        add(io, sizeof(*io));
+        add(ctx->opt, sizeof(ctx->opt));
+        if (g.exec && key == g.key && ctx->alloc_gen == g.gen) {
+            EMP_HIP(ctx, hipGraphLaunch(g.exec, ctx->stream));
+            ++g.replays;
+            *replayed = true;
+            return EMP_OK;
+        }
+        (void)g.exec.reset();               // another signature, or the buffers moved: the graph is stale
+        g.seen = (key == g.seen_key) ? g.seen + 1 : 1;
+        g.seen_key = key;
+        if (g.seen >= 3) {                  // the two calls before this one allocated and built whatever this signature needs
+            g.gen = ctx->alloc_gen;
+            EMP_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
+            active = g.capturing = true;
+        }
+        return EMP_OK;
+    }
+
+    // The capture (if any) ends: the graph is kept unless the context's buffers changed inside it, and launched - the captured
+    // launches have not run yet: this is the call's work.
+    int end() {
+        if (!active) return EMP_OK;
+        emp_ctx::CycleGraph& g = ctx->cycle_graph;
+        active = g.capturing = false;
+        hipGraph_t graph = nullptr;
+        EMP_HIP(ctx, hipStreamEndCapture(ctx->stream, &graph));
+        emp::GraphExec exec;
+        const hipError_t ie = hipGraphInstantiate(&exec.h, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        EMP_HIP(ctx, ie);
+        if (ctx->alloc_gen != g.gen) {      // something was allocated or rebuilt inside the capture after all
+            g.seen = 0;
+            return emp::fail(ctx, EMP_ERR_HIP, "EMP_OPT_CYCLE_GRAPH: the context's buffers changed inside a capture");
+        }
+        g.exec = std::move(exec);
+        g.key = g.seen_key;
+        EMP_HIP(ctx, hipGraphLaunch(g.exec, ctx->stream));
+        return EMP_OK;
+    }
+
+  private:
+    emp_ctx* ctx;
+    bool active = false;
+};
+
 }  // namespace emp
 
 extern "C" {
@@ -1420,127 +1594,15 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
     EMP_REQUIRE(ctx, io->traj && io->traj_len && io->status, "traj, traj_len and status are required outputs");
     EMP_REQUIRE(ctx, q->ds > 0, "ds must be > 0");
     EMP_HIP(ctx, hipSetDevice(ctx->device));
-    // Pipelined modes (device pointers only; emp_context.h).  LANES: the whole call runs on the next lane - its stream
-    // stands in for ctx->stream and its pool for ctx->pool - behind whatever the caller has ordered on the main stream so
-    // far.  STAGED: the call takes the pool of the next of two lanes once the back stage that used it last is done; its
-    // front stage runs on the main stream.
-    // EMP_HOST_PINNED: the caller's arrays are page-locked; the call is pipelined like a device-pointer call, its inputs
-    // arrive over the copy stream and its outputs leave over the d2h stream (emp_context.h Stage: async_host)
     const bool pinned = where == EMP_HOST_PINNED;
-    if (pinned && !ctx->copy_stream) {
-        EMP_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-        EMP_HIP(ctx, hipStreamCreateWithFlags(&ctx->d2h_stream, hipStreamNonBlocking));
-        EMP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_h2d, hipEventDisableTiming));
-        EMP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_host_last, hipEventDisableTiming));
-    }
     const int pmode = ((where == EMP_DEVICE || pinned) && B > 0) ? ctx->pipe_mode : 0;
-    const bool piped = pmode != 0, staged = pmode == EMP_PIPELINE_STAGED;
-    struct LaneSwap {
-        emp_ctx* c;
-        emp_ctx::Lane* ln = nullptr;
-        hipStream_t main_stream;
-        LaneSwap(emp_ctx* c_, int mode) : c(c_), main_stream(c_->stream) {
-            if (!mode) return;
-            c->lane = (c->lane + 1) % c->lanes_in_use();
-            ++c->cycle_calls;
-            ln = &c->lanes[c->lane];                 // (ln->ticket changes below, after the host-side wait for the lane's previous call)
-            std::swap(c->pool, ln->pool);
-            if (mode != EMP_PIPELINE_STAGED) {
-                c->active_lane = c->lane;
-                c->stream = ln->stream;
-            }
-        }
-        ~LaneSwap() {
-            if (!ln) return;
-            c->stream = main_stream;
-            std::swap(c->pool, ln->pool);
-            c->active_lane = -1;
-        }
-    } lane(ctx, pmode);
-    if (staged) {
-        // the pool's previous user is four calls back: a host-side wait (emp_context.h, kStagedPools)
-        if (lane.ln->done_valid) EMP_HIP(ctx, hipEventSynchronize(lane.ln->ev_done));
-        if (lane.ln->host_valid) EMP_HIP(ctx, hipEventSynchronize(lane.ln->ev_host));   // ... and its outputs have left the pool
-    } else if (piped) {
-        if (lane.ln->host_valid) EMP_HIP(ctx, hipEventSynchronize(lane.ln->ev_host));
-        // The lane's previous occupant (call k - n) and whatever its caller queued behind it on the lane's stream (record
-        // packing) must be done before anything ordered on the main stream from here on may touch memory they use: the
-        // caller keeps a call's outputs alive only until this call is issued, and the NEXT call runs on another lane.
-        if (lane.ln->done_valid) {
-            EMP_HIP(ctx, hipEventRecord(lane.ln->ev_tail, ctx->stream));
-            EMP_HIP(ctx, hipStreamWaitEvent(lane.main_stream, lane.ln->ev_tail, 0));
-        }
-        EMP_HIP(ctx, hipEventRecord(lane.ln->ev_in, lane.main_stream));
-        EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, lane.ln->ev_in, 0));
-    }
-    if (piped) {
-        // Only now - the previous occupant's outputs are in its caller's arrays - does the lane stop answering for the previous
-        // ticket: emp_wait_ticket(T) on another thread either still finds the lane under T with its event valid and waits for
-        // the same event, or finds no lane under T, which now MEANS that this thread has waited for T already (the advisor's
-        // round-5 finding: the ticket used to change before the wait, and a waiter in that window returned at once).
-        lane.ln->host_valid = false;
-        lane.ln->ticket = ctx->cycle_calls;
-        // A pinned call's inputs go into the lane's pool over the copy stream.  If the lane's previous occupant was an EMP_DEVICE
-        // cycle there has been no host-side wait for it: the copy stream waits for its kernels instead.
-        if (pinned && !staged && lane.ln->done_valid) EMP_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, lane.ln->ev_done, 0));
-    }
-    // EMP_OPT_CYCLE_GRAPH: one batch at a time on device pointers - the third consecutive call with one signature is captured,
-    // the following ones are one hipGraphLaunch.  The signature is everything a launch argument is made of; the context's
-    // allocation count says whether a temporary or a lattice table moved or changed since the capture.
-    struct CaptureGuard {
-        emp_ctx* c;
-        bool active = false;
-        ~CaptureGuard() {
-            if (!active) return;            // (an early return inside the captured region: end the capture, keep nothing)
-            hipGraph_t g = nullptr;
-            (void)hipStreamEndCapture(c->stream, &g);
-            if (g) (void)hipGraphDestroy(g);
-            c->capturing = false;
-        }
-    } capture{ctx};
-    const bool graph_ok = ctx->opt[EMP_OPT_CYCLE_GRAPH] == 1 && pmode == 0 && where == EMP_DEVICE && B > 0 && !ctx->timing &&
-                          !ctx->opt[EMP_OPT_SWEEP_CLOCK_PROBE] && !ctx->opt[EMP_OPT_EDGE_CLOCK_PROBE];
-    if (graph_ok) {
-        std::vector<unsigned long long> key;
-        auto add = [&](const void* ptr, size_t bytes) {
-            const unsigned char* b8 = (const unsigned char*)ptr;
-            for (size_t o = 0; o < bytes; o += 8) {
-                unsigned long long w = 0;
-                memcpy(&w, b8 + o, std::min<size_t>(8, bytes - o));
-                key.push_back(w);
-            }
-        };
-        const long long sizes[5] = {B, max_ref, max_obs, max_pts, (long long)mode};
-        add(sizes, sizeof(sizes));
-        add(p, sizeof(*p));
-        add(q, sizeof(*q));
-        add(sp, sizeof(*sp));
-        add(io, sizeof(*io));
-        add(ctx->opt, sizeof(ctx->opt));
-        if (ctx->cycle_graph && key == ctx->cycle_graph_key && ctx->alloc_gen == ctx->cycle_graph_gen) {
-            EMP_HIP(ctx, hipGraphLaunch(ctx->cycle_graph, ctx->stream));
-            ++ctx->cycle_graph_replays;
-            return EMP_OK;
-        }
-        if (ctx->cycle_graph) {             // another signature, or the buffers moved: the graph is stale
-            (void)hipGraphExecDestroy(ctx->cycle_graph);
-            ctx->cycle_graph = nullptr;
-        }
-        ctx->cycle_seen = (key == ctx->cycle_seen_key) ? ctx->cycle_seen + 1 : 1;
-        ctx->cycle_seen_key = key;
-        if (ctx->cycle_seen >= 3) {         // the two calls before this one allocated and built whatever this signature needs
-            ctx->cycle_graph_gen = ctx->alloc_gen;
-            EMP_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
-            capture.active = true;
-            ctx->capturing = true;
-        }
-    } else if (ctx->cycle_graph) {
-        (void)hipGraphExecDestroy(ctx->cycle_graph);
-        ctx->cycle_graph = nullptr;
-        ctx->cycle_seen = 0;
-    }
+    CycleLane lane(ctx, pmode, pinned);
+    if ((rc = lane.begin())) return rc;
+    CycleCapture graph(ctx);
+    bool replayed = false;
+    if ((rc = graph.begin(pmode, where, B, max_ref, max_obs, max_pts, mode, p, q, sp, io, &replayed)) || replayed) return rc;
     // (the slot form of in() / out(): with EMP_HOST_PINNED the device pointers are known only at inputs_ready() / outputs_ready())
-    Stage st(ctx, where, piped, pinned);
+    Stage st(ctx, where, pmode != 0, pinned);
     const double *d_ref = nullptr, *d_o, *d_sxy, *d_v, *d_a, *d_oxy, *d_dyn, *d_glob = nullptr;
     const int *d_nr = nullptr, *d_no, *d_nglob = nullptr, *d_prem = nullptr;
     if (front) {
@@ -1563,20 +1625,13 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
     // rows completely, padding included
     double *d_rows, *d_dps, *d_dpl, *d_ps, *d_pl, *d_traj;
     int *d_dplen, *d_plen, *d_tlen, *d_st, *d_match = nullptr, *d_rst = nullptr;
-    st.out(io->dp_rows, (size_t)B * d.col, &d_rows, false);
-    if (!d_rows) d_rows = st.tmp<double>((size_t)B * d.col);
-    st.out(io->dp_s, (size_t)B * max_pts, &d_dps, false);
-    if (!d_dps) d_dps = st.tmp<double>((size_t)B * max_pts);
-    st.out(io->dp_l, (size_t)B * max_pts, &d_dpl, false);
-    if (!d_dpl) d_dpl = st.tmp<double>((size_t)B * max_pts);
-    st.out(io->dp_len, (size_t)B, &d_dplen, false);
-    if (!d_dplen) d_dplen = st.tmp<int>((size_t)B);
-    st.out(io->path_s, (size_t)B * max_pts, &d_ps, false);
-    if (!d_ps) d_ps = st.tmp<double>((size_t)B * max_pts);
-    st.out(io->path_l, (size_t)B * max_pts, &d_pl, false);
-    if (!d_pl) d_pl = st.tmp<double>((size_t)B * max_pts);
-    st.out(io->path_len, (size_t)B, &d_plen, false);
-    if (!d_plen) d_plen = st.tmp<int>((size_t)B);
+    st.out_or_tmp(io->dp_rows, (size_t)B * d.col, &d_rows);
+    st.out_or_tmp(io->dp_s, (size_t)B * max_pts, &d_dps);
+    st.out_or_tmp(io->dp_l, (size_t)B * max_pts, &d_dpl);
+    st.out_or_tmp(io->dp_len, (size_t)B, &d_dplen);
+    st.out_or_tmp(io->path_s, (size_t)B * max_pts, &d_ps);
+    st.out_or_tmp(io->path_l, (size_t)B * max_pts, &d_pl);
+    st.out_or_tmp(io->path_len, (size_t)B, &d_plen);
     st.out(io->traj, (size_t)B * (max_pts + 1) * 4, &d_traj, false);
     st.out(io->traj_len, (size_t)B, &d_tlen, false);
     st.out(io->status, (size_t)B, &d_st, false);
@@ -1610,113 +1665,37 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
         return rc;
     if (has_dyn) d_no = d_ntot;                            // downstream stages see the projected + virtual obstacles
     CycleSched cs;
+    const bool two_kernel = mode == EMP_DP_TWO_KERNEL && !wide(d);
     // the sweep may leave the backtrack to the densification kernel (emp_dp_kernels.h, BT == false): two temporaries for it
-    if (mode == EMP_DP_TWO_KERNEL && !wide(d)) {
+    if (two_kernel) {
         cs.bt_pre = st.tmp<unsigned char>((size_t)d.tiles * d.col * 64);
         cs.bt_term = st.tmp<int>((size_t)B);
         if ((rc = st.ready())) return rc;        // (staged behind the projection launch: checked here)
     }
-    if (staged) cs.front_stop = lane.ln->ev_front;
-    if (staged && ctx->opt[EMP_OPT_SWEEP_EXCLUSIVE]) {       // the previous call's back stage: its lane is the one before ours
-        emp_ctx::Lane& prev = ctx->lanes[(ctx->lane + ctx->lanes_in_use() - 1) % ctx->lanes_in_use()];
-        if (ctx->opt[EMP_OPT_SWEEP_EXCLUSIVE] == 2) {        // ... only its densification and path QP: the sweep runs beside the Cartesian tail
-            if (prev.qp_valid) cs.sweep_wait = prev.ev_qp;
-        } else if (prev.done_valid) {
-            cs.sweep_wait = prev.ev_done;
-        }
-    }
-    if (staged && ctx->opt[EMP_OPT_EDGE_AFTER_ENRICH] && mode == EMP_DP_TWO_KERNEL && !wide(d)) {
-        emp_ctx::Lane& prev = ctx->lanes[(ctx->lane + ctx->lanes_in_use() - 1) % ctx->lanes_in_use()];
-        if (prev.enrich_valid) cs.edge_wait = prev.ev_enrich;
-    }
+    lane.front_waits(cs, two_kernel);
     if ((rc = dev_dp_plan(ctx, d, d_os, d_ol, d_no, d_start, mode, d_rows, nullptr, d_st, &cs))) return rc;
     const QpDev Q = make_qp_dev(q);
-    // EMP_OPT_SWEEP_EXCLUSIVE: a marker behind the sweep on the front stream.  Measured, not understood: which of two
-    // regimes the two queues settle in depends on it.  With it the kernels keep the durations of the overlapped step (edge
-    // 198 us, path QP 140, Cartesian 70, sweep 19) and the step takes 0.264 ms (mode 2) / 0.277 (mode 1); without it the
-    // edge kernel runs at its stand-alone 147 us, starves the path QP beside it (250 us) and the step takes 0.32 - 0.35 ms
-    // (profiles/r04_sweep/README.md).  The clock probe's event did the same by accident, which is how this was found.
-    if (staged && ctx->opt[EMP_OPT_SWEEP_EXCLUSIVE]) {
-        if (!ctx->sweep_marker) EMP_HIP(ctx, hipEventCreateWithFlags(&ctx->sweep_marker, hipEventDisableTiming));
-        EMP_HIP(ctx, hipEventRecord(ctx->sweep_marker, ctx->stream));
-    }
-    if (staged) {      // the back stage (short kernels that last as long as their slowest scene) goes to the back stream
-        // behind the sweep's own completion event where the launch attached one (a marker packet behind the sweep costs the
-        // front queue ~5 us per step), else behind an event recorded here
-        hipEvent_t front_done = cs.front_attached;
-        if (!front_done) {
-            EMP_HIP(ctx, hipEventRecord(lane.ln->ev_front, ctx->stream));
-            front_done = lane.ln->ev_front;
-        }
-        EMP_HIP(ctx, hipStreamWaitEvent(ctx->back_stream, front_done, 0));
-        ctx->stream = ctx->back_stream;        // ~LaneSwap puts the main stream back
-    }
-    // The two events the NEXT call's front stage waits for (densification done, path QP done) are signalled by the dispatches
-    // themselves where possible: a marker packet behind each idled the back queue ~6 us, and with the edge kernel's round-4 diet
-    // the back queue is what bounds the step.
-    const bool want_enrich_ev = staged && ctx->opt[EMP_OPT_EDGE_AFTER_ENRICH] != 0;
-    cs.attach_stop = want_enrich_ev ? lane.ln->ev_enrich : nullptr;
-    if ((rc = dev_dp_enrich(ctx, d, d_rows, d_start, max_pts, d_dps, d_dpl, d_dplen, d_st, 1, &cs, cs.bt_deferred ? cs.bt_pre : nullptr,
-                            cs.bt_deferred ? cs.bt_term : nullptr, d_no, d_rows)))
-        return rc;
-    if (want_enrich_ev) {
-        if (!cs.stop_attached) EMP_HIP(ctx, hipEventRecord(lane.ln->ev_enrich, ctx->stream));
-        lane.ln->enrich_valid = true;
-    } else if (staged) {
-        lane.ln->enrich_valid = false;
-    }
-    cs.attach_stop = staged ? lane.ln->ev_qp : nullptr;
-    cs.stop_attached = false;
-    if ((rc = dev_cycle_qp(ctx, B, max_pts, mo, Q, d_dps, d_dpl, d_dplen, d_os, d_ol, d_no, d_start, d_ps, d_pl, d_plen, d_st, &cs)))
-        return rc;
-    if (staged) {
-        if (!cs.stop_attached) EMP_HIP(ctx, hipEventRecord(lane.ln->ev_qp, ctx->stream));
-        lane.ln->qp_valid = true;
-    }
+    if ((rc = lane.to_back(cs))) return rc;
+    auto enrich = [&] {
+        return dev_dp_enrich(ctx, d, d_rows, d_start, max_pts, d_dps, d_dpl, d_dplen, d_st, 1, &cs, cs.bt_deferred ? cs.bt_pre : nullptr,
+                             cs.bt_deferred ? cs.bt_term : nullptr, d_no, d_rows);
+    };
+    auto path_qp = [&] {
+        return dev_cycle_qp(ctx, B, max_pts, mo, Q, d_dps, d_dpl, d_dplen, d_os, d_ol, d_no, d_start, d_ps, d_pl, d_plen, d_st, &cs);
+    };
+    if ((rc = lane.signal(cs, ctx->opt[EMP_OPT_EDGE_AFTER_ENRICH] != 0, &emp_ctx::Lane::ev_enrich, &emp_ctx::Lane::enrich_valid, enrich))) return rc;
+    if ((rc = lane.signal(cs, true, &emp_ctx::Lane::ev_qp, &emp_ctx::Lane::qp_valid, path_qp))) return rc;
     const int path_cap = (max_pts + Q.decimate - 1) / Q.decimate + (Q.midpoint ? 1 : 0);
     if ((rc = dev_cycle_cartesian(ctx, B, max_ref, max_pts, path_cap, sp, d_ref, d_sm, d_nr, d_bsl, d_ps, d_pl, d_plen,
                                   d_traj, d_tlen, d_st)))
         return rc;
-    if (piped) {
-        EMP_HIP(ctx, hipEventRecord(lane.ln->ev_done, ctx->stream));
-        lane.ln->done_valid = true;
-    }
-    if (st.async_host()) {
-        // outputs go home on the d2h stream behind the cycle's last kernel; pipelined: nobody waits here (emp_wait_cycle,
-        // emp_synchronize, or the call that takes this pool over); not pipelined: the pool is the next call's, so wait
-        if (piped) {
-            if (!lane.ln->ev_host) EMP_HIP(ctx, hipEventCreateWithFlags(&lane.ln->ev_host, hipEventDisableTiming));
-            if ((rc = st.finish_async(lane.ln->ev_done, lane.ln->ev_host))) return rc;
-            lane.ln->host_valid = true;
-            return EMP_OK;
-        }
-        EMP_HIP(ctx, hipEventRecord(ctx->ev_h2d, ctx->stream));
-        if ((rc = st.finish_async(ctx->ev_h2d, ctx->ev_host_last))) return rc;
-        EMP_HIP(ctx, hipEventSynchronize(ctx->ev_host_last));
-        return EMP_OK;
-    }
-    if (capture.active) {
-        hipGraph_t g = nullptr;
-        capture.active = false;
-        ctx->capturing = false;
-        EMP_HIP(ctx, hipStreamEndCapture(ctx->stream, &g));
-        hipGraphExec_t exec = nullptr;
-        const hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        EMP_HIP(ctx, ie);
-        if (ctx->alloc_gen != ctx->cycle_graph_gen) {      // something was allocated or rebuilt inside the capture after all
-            (void)hipGraphExecDestroy(exec);
-            ctx->cycle_seen = 0;
-            return emp::fail(ctx, EMP_ERR_HIP, "EMP_OPT_CYCLE_GRAPH: the context's buffers changed inside a capture");
-        }
-        ctx->cycle_graph = exec;
-        ctx->cycle_graph_key = ctx->cycle_seen_key;
-        EMP_HIP(ctx, hipGraphLaunch(exec, ctx->stream));       // the captured launches have not run yet: this is the call's work
-    }
+    if ((rc = lane.done(st))) return rc;
+    if (st.async_host()) return EMP_OK;            // (finish_async has sent the outputs)
+    if ((rc = graph.end())) return rc;
     return st.finish();
 }
 
-int64_t emp_cycle_graph_replays(emp_ctx* ctx) { return ctx ? (int64_t)ctx->cycle_graph_replays : -1; }
+int64_t emp_cycle_graph_replays(emp_ctx* ctx) { return ctx ? (int64_t)ctx->cycle_graph.replays : -1; }
 
 uint64_t emp_cycle_ticket(emp_ctx* ctx) { return ctx ? ctx->cycle_calls : 0; }
 
@@ -1748,18 +1727,18 @@ int emp_wait_ticket(emp_ctx* ctx, uint64_t ticket) {
 int emp_host_alloc(emp_ctx* ctx, uint64_t bytes, void** out) {
     EMP_REQUIRE(ctx, ctx && out, "NULL argument");
     EMP_HIP(ctx, hipSetDevice(ctx->device));
-    void* p = nullptr;
-    EMP_HIP(ctx, hipHostMalloc(&p, bytes ? bytes : 8, hipHostMallocDefault));
-    ctx->pinned.push_back({p, (size_t)(bytes ? bytes : 8)});
-    *out = p;
+    emp_ctx::HostBlock hb;
+    if (const int rc = hb.ensure(ctx, bytes ? bytes : 8)) return rc;
+    *out = hb.p;
+    ctx->pinned.push_back(std::move(hb));
     return EMP_OK;
 }
 int emp_host_free(emp_ctx* ctx, void* ptr) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
-    auto it = std::find_if(ctx->pinned.begin(), ctx->pinned.end(), [&](const emp_ctx::Pinned& a) { return a.p == ptr; });
+    auto it = std::find_if(ctx->pinned.begin(), ctx->pinned.end(), [&](const emp_ctx::HostBlock& a) { return a.p == ptr; });
     EMP_REQUIRE(ctx, it != ctx->pinned.end(), "not an emp_host_alloc pointer of this context");
     EMP_HIP(ctx, (hipError_t)sync_all(ctx));
-    EMP_HIP(ctx, hipHostFree(ptr));
+    EMP_HIP(ctx, it->reset());
     ctx->pinned.erase(it);
     return EMP_OK;
 }

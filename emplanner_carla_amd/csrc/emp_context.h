@@ -16,27 +16,79 @@
 
 #include "../../include/emplanner.h"
 
-// an atomic that a std::vector element may hold (copyable: the copy is a plain load / store, made only while no other thread
+// an atomic that a std::vector element may hold (movable: the move is a plain load / store, made only while no other thread
 // can be looking - emp_set_pipeline resizing the lanes)
 template <typename T>
 struct Shared {
     std::atomic<T> v;
     Shared(T x = T()) : v(x) {}
-    Shared(const Shared& o) : v(o.v.load()) {}
-    Shared& operator=(const Shared& o) { v.store(o.v.load()); return *this; }
+    Shared(Shared&& o) noexcept : v(o.v.load()) {}
     Shared& operator=(T x) { v.store(x, std::memory_order_release); return *this; }
     operator T() const { return v.load(std::memory_order_acquire); }
 };
 
+struct emp_ctx;
+
+namespace emp {
+
+// Owners of the context's HIP resources: move-only, one handle each, released by the destructor.  A destructor never
+// synchronises: what releases a resource that queued work may still use drains first (emp_destroy, grow_buffer).
+template <typename H, hipError_t (*Release)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Handle& operator=(Handle&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Handle() { (void)reset(); }
+    operator H() const { return h; }
+    hipError_t reset() {
+        const hipError_t e = h ? Release(h) : hipSuccess;
+        h = nullptr;
+        return e;
+    }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    int ensure(emp_ctx* ctx, unsigned flags);                               // created on first use
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+    int ensure(emp_ctx* ctx, unsigned flags, bool high_priority = false);   // created on first use
+};
+using GraphExec = Handle<hipGraphExec_t, hipGraphExecDestroy>;
+
+// device memory (hipMalloc) or, kHost, page-locked host memory (hipHostMalloc), and its size
+template <bool kHost>
+struct Mem {
+    void* p = nullptr;
+    size_t bytes = 0;
+    Mem() = default;
+    Mem(Mem&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    Mem& operator=(Mem&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~Mem() { (void)reset(); }
+    hipError_t reset() {
+        const hipError_t e = !p ? hipSuccess : kHost ? hipHostFree(p) : hipFree(p);
+        p = nullptr;
+        bytes = 0;
+        return e;
+    }
+    int ensure(emp_ctx* ctx, size_t n);                                     // n bytes, allocated on first use
+};
+
+}  // namespace emp
+
 struct emp_ctx {
+    using Buf = emp::Mem<false>;
+    using HostBlock = emp::Mem<true>;
     int device = 0;
+    emp::Stream main_stream;            // the first owner: released last
+    // the stream the launchers issue to: the main stream, or what stands in for it during a call (a lane's stream, the back
+    // stream, the result stream)
     hipStream_t stream = nullptr;
     std::string err;
     // grow-only pool of device buffers, handed out in call order and recycled by the next call
-    struct Buf {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
     std::vector<Buf> pool;
     size_t cursor = 0;
     // persistent named scratch (survives across the staged buffers of one call)
@@ -53,7 +105,7 @@ struct emp_ctx {
     // per-kernel timing
     bool timing = false;
     struct Ev {
-        std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;   // one pair per launch since timing was enabled
+        std::vector<std::pair<emp::Event, emp::Event>> pairs;   // one pair per launch since timing was enabled
         size_t used = 0;
     };
     std::map<std::string, Ev> events;
@@ -73,41 +125,35 @@ struct emp_ctx {
     // queued behind it on the lane, still runs (the lanes are ordered behind the main stream, not against each other).
     // ev_done: end of the lane's latest cycle - what the next user of the lane's pool and every other entry point wait for.
     struct Lane {
-        hipStream_t stream = nullptr;
-        hipEvent_t ev_in = nullptr, ev_front = nullptr, ev_done = nullptr, ev_tail = nullptr;
-        hipEvent_t ev_host = nullptr;   // EMP_HOST_PINNED cycles: the lane's latest cycle's outputs have reached the caller's host arrays
+        emp::Stream stream;
+        emp::Event ev_in, ev_front, ev_done, ev_tail;
+        emp::Event ev_host;             // EMP_HOST_PINNED cycles: the lane's latest cycle's outputs have reached the caller's host arrays
         // `ticket` and `host_valid` are the two fields emp_wait_ticket reads from ANOTHER thread while a call is in progress:
         // atomics, and a call that takes the lane over changes them only AFTER its own host-side wait for the previous
         // occupant's outputs (emp_plan_cycle) - until then the lane still answers for the previous ticket
         Shared<bool> host_valid{false};
         Shared<uint64_t> ticket{0};     // emp_cycle_ticket of the lane's latest cycle
-        hipEvent_t ev_qp = nullptr;     // STAGED: end of the cycle's path QP on the back stream (EMP_OPT_SWEEP_EXCLUSIVE = 2)
-        hipEvent_t ev_enrich = nullptr; // STAGED: end of the cycle's densification kernel on the back stream (EMP_OPT_EDGE_AFTER_ENRICH)
-        hipEvent_t ev_edge = nullptr;   // LANES: end of the cycle's edge-cost kernel (EMP_OPT_LANE_EDGE_ORDER)
+        emp::Event ev_qp;               // STAGED: end of the cycle's path QP on the back stream (EMP_OPT_SWEEP_EXCLUSIVE = 2)
+        emp::Event ev_enrich;           // STAGED: end of the cycle's densification kernel on the back stream (EMP_OPT_EDGE_AFTER_ENRICH)
+        emp::Event ev_edge;             // LANES: end of the cycle's edge-cost kernel (EMP_OPT_LANE_EDGE_ORDER)
         bool done_valid = false, qp_valid = false, enrich_valid = false;
         std::vector<Buf> pool;
     };
     std::vector<Lane> lanes;            // created on demand, kept until emp_destroy
-    hipStream_t back_stream = nullptr;  // STAGED: the back stages (highest queue priority)
+    emp::Stream back_stream;            // STAGED: the back stages (highest queue priority)
     // EMP_HOST_PINNED (emp_plan_cycle): inputs go host -> device on copy_stream while the previous call computes, outputs device ->
     // host on d2h_stream behind the cycle's last kernel - neither ever sits on a queue that carries kernels.  Created on first use.
-    hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
-    hipEvent_t ev_h2d = nullptr;        // the latest call's inputs have arrived
-    hipEvent_t ev_host_last = nullptr;  // non-pipelined pinned call: outputs have reached the host
-    struct Pinned {
-        void* p;
-        size_t bytes;
-    };
-    std::vector<Pinned> pinned;         // emp_host_alloc allocations still alive (freed by emp_destroy)
+    emp::Stream copy_stream, d2h_stream;
+    emp::Event ev_h2d;                  // the latest call's inputs have arrived
+    emp::Event ev_host_last;            // non-pipelined pinned call: outputs have reached the host
+    std::vector<HostBlock> pinned;      // emp_host_alloc allocations still alive
     // Small EMP_HOST calls (round 6): ONE page-locked arena and one device arena per direction.  The arrays of a synchronous call
     // with host pointers are packed into the input arena by the host and cross PCIe as one copy; the outputs come back as one
     // copy and are unpacked by the host (Stage).  A copy command costs 4-14 us whatever its size and a call of the reference's
     // function surface has three to twenty small arrays: emp_lmin_lmax went from 100 to ~60 us (profiles/r06_call_cost_probe.txt).
     static constexpr size_t kArena = 256 * 1024, kArenaArray = 64 * 1024;
-    char* arena_h_in = nullptr;         // page-locked, kArena bytes each
-    char* arena_h_out = nullptr;
-    char* arena_d_in = nullptr;         // device, kArena bytes each
-    char* arena_d_out = nullptr;
+    HostBlock arena_h_in, arena_h_out;  // kArena bytes each
+    Buf arena_d_in, arena_d_out;
     bool arena_failed = false;          // an allocation failed once: the per-array path from then on
     bool stage_open = false;            // a Stage is in its input phase: kernel launches are refused until its ready()
     int pipe_mode = 0;                  // 0 off, 1 STAGED, n >= 2 LANES with n lanes
@@ -118,26 +164,29 @@ struct emp_ctx {
     // emp_set_option (include/emplanner.h): per-context tuning / A-B / test-hook values; the library reads no environment
     int32_t opt[EMP_OPT_COUNT] = {0, 0, 0, 0, 0, 0, /* EDGE_AFTER_ENRICH */ 1, /* LANE_EDGE_ORDER */ 2, 0, 0, 0, /* FOREIGN_STREAMS */ 1};
     int auto_queues = 0, auto_streams = 0;   // what the latest emp_set_pipeline(EMP_PIPELINE_AUTO) saw (emp_pipeline_form)
-    // EMP_OPT_CYCLE_GRAPH: the launches of one emp_plan_cycle call as an executable graph, the call signature it belongs to, how
-    // often that signature has been seen in a row, and the allocation count (grow_buffer) it was captured under
-    hipGraphExec_t cycle_graph = nullptr;
-    std::vector<unsigned long long> cycle_graph_key, cycle_seen_key;
-    int cycle_seen = 0;
-    long long cycle_graph_replays = 0;
-    unsigned long long alloc_gen = 0, cycle_graph_gen = 0;
-    bool capturing = false;             // launchers avoid what a stream capture cannot record (hipExtLaunchKernelGGL)
+    // EMP_OPT_CYCLE_GRAPH (emp_api.hip CycleCapture): the launches of one emp_plan_cycle call as an executable graph, the call
+    // signature it belongs to, how often that signature has been seen in a row, and the allocation count it was captured under
+    struct CycleGraph {
+        emp::GraphExec exec;
+        std::vector<unsigned long long> key, seen_key;
+        int seen = 0;
+        long long replays = 0;
+        unsigned long long gen = 0;
+        bool capturing = false;         // launchers avoid what a stream capture cannot record (hipExtLaunchKernelGGL)
+    } cycle_graph;
+    unsigned long long alloc_gen = 0;   // buffers (grow_buffer) and pair tables made so far
     hipEvent_t lane_edge_done = nullptr; // EMP_OPT_LANE_EDGE_ORDER: recorded behind the latest edge-cost launch of a lane-mode call (a lane's ev_edge)
-    hipEvent_t sweep_marker = nullptr;  // EMP_OPT_SWEEP_EXCLUSIVE: recorded on the front stream behind the sweep (emp_api.hip)
+    emp::Event sweep_marker;            // EMP_OPT_SWEEP_EXCLUSIVE: recorded on the front stream behind the sweep (emp_api.hip)
     // EMP_OPT_SWEEP_CLOCK_PROBE: a ring of kProbeSlots launches x [tiles][4] ticks (shader-clock begin / end, reference
     // begin / end); probe_launches counts the launches recorded since the option was last switched on
     static constexpr int kProbeSlots = 32;
     Buf clock_probe;
     Buf edge_probe;                     // EMP_OPT_EDGE_CLOCK_PROBE: [wavefronts of the latest edge launch][2] reference ticks
     long edge_probe_waves = 0;
-    hipEvent_t edge_probe_done = nullptr;
+    emp::Event edge_probe_done;
     int clock_probe_tiles = 0;
     long probe_launches = 0;
-    hipEvent_t clock_probe_done = nullptr;
+    emp::Event clock_probe_done;
     bool pipelined() const { return pipe_mode != 0; }
     // STAGED rotates kStagedPools pools of temporaries although only two calls overlap on the GPU: call k reuses the pool
     // of call k - 4 and the HOST waits for that call's back stage (long finished unless the host runs more than four
@@ -147,7 +196,7 @@ struct emp_ctx {
     static constexpr int kStagedPools = 4;
     int lanes_in_use() const { return pipe_mode == 1 ? kStagedPools : pipe_mode; }
     hipStream_t result_stream() const {
-        return pipe_mode == 0 ? stream : pipe_mode == 1 ? back_stream : lanes[lane].stream;
+        return pipe_mode == 0 ? main_stream.h : pipe_mode == 1 ? back_stream.h : lanes[lane].stream.h;
     }
 };
 
@@ -178,14 +227,36 @@ inline int hip_error(emp_ctx* ctx, hipError_t e, const char* what) {
         if (!(cond)) return emp::fail((ctx), EMP_ERR_INVALID, std::string(msg));                   \
     } while (0)
 
+inline int Event::ensure(emp_ctx* ctx, unsigned flags) {
+    return h ? EMP_OK : hip_error(ctx, hipEventCreateWithFlags(&h, flags), "hipEventCreateWithFlags");
+}
+
+// high_priority: the device's highest stream priority (the STAGED back stream)
+inline int Stream::ensure(emp_ctx* ctx, unsigned flags, bool high_priority) {
+    if (h) return EMP_OK;
+    if (!high_priority) return hip_error(ctx, hipStreamCreateWithFlags(&h, flags), "hipStreamCreateWithFlags");
+    int prio_low = 0, prio_high = 0;
+    EMP_HIP(ctx, hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
+    return hip_error(ctx, hipStreamCreateWithPriority(&h, flags, prio_high), "hipStreamCreateWithPriority");
+}
+
+template <bool kHost>
+inline int Mem<kHost>::ensure(emp_ctx* ctx, size_t n) {
+    if (p) return EMP_OK;
+    const hipError_t e = kHost ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n);
+    if (const int rc = hip_error(ctx, e, kHost ? "hipHostMalloc" : "hipMalloc")) return rc;
+    bytes = n;
+    return EMP_OK;
+}
+
 // Waits for everything queued on the context's streams (the main one and every lane).
 inline int sync_all(emp_ctx* ctx) {
-    hipError_t e = hipStreamSynchronize(ctx->stream);
+    hipError_t e = hipStreamSynchronize(ctx->main_stream);
     for (auto& ln : ctx->lanes) {
         const hipError_t e2 = ln.stream ? hipStreamSynchronize(ln.stream) : hipSuccess;
         if (e == hipSuccess) e = e2;
     }
-    for (hipStream_t st : {ctx->back_stream, ctx->copy_stream, ctx->d2h_stream}) {
+    for (hipStream_t st : {ctx->back_stream.h, ctx->copy_stream.h, ctx->d2h_stream.h}) {
         if (!st) continue;
         const hipError_t e2 = hipStreamSynchronize(st);
         if (e == hipSuccess) e = e2;
@@ -199,13 +270,9 @@ inline int grow_buffer(emp_ctx* ctx, emp_ctx::Buf& b, size_t bytes) {
     if (b.bytes >= bytes) return EMP_OK;
     if (b.p) {
         EMP_HIP(ctx, (hipError_t)sync_all(ctx));
-        EMP_HIP(ctx, hipFree(b.p));
+        EMP_HIP(ctx, b.reset());
     }
-    b.p = nullptr;
-    b.bytes = 0;
-    const size_t want = bytes + bytes / 4;
-    EMP_HIP(ctx, hipMalloc(&b.p, want));
-    b.bytes = want;
+    if (const int rc = b.ensure(ctx, bytes + bytes / 4)) return rc;
     ++ctx->alloc_gen;
     return EMP_OK;
 }
@@ -241,7 +308,7 @@ class Stage {
         : ctx_(c), dev_(where == EMP_DEVICE), async_(async_host && where != EMP_DEVICE) {
         c->cursor = 0;
         c->stage_open = true;
-        arena_ = !dev_ && !async_ && where == EMP_HOST && !c->capturing;
+        arena_ = !dev_ && !async_ && where == EMP_HOST && !c->cycle_graph.capturing;
         if (!in_cycle && c->pipelined() && c->fence)
             for (auto& ln : c->lanes)
                 if (ln.done_valid) (void)hipStreamWaitEvent(c->stream, ln.ev_done, 0);
@@ -269,6 +336,12 @@ class Stage {
         void* v = get(n * sizeof(T));
         if (v && zero && n) EMP_KEEP(hipMemsetAsync(v, 0, n * sizeof(T), ctx_->stream));
         return rc_ ? nullptr : (T*)v;
+    }
+    // an optional output (not zero-filled): the caller's array, or a device temporary where the caller passed none
+    template <typename T>
+    void out_or_tmp(T* host, size_t n, T** slot) {
+        out(host, n, slot, false);
+        if (!*slot) *slot = tmp<T>(n);
     }
     // async_host: every input of the call is known.  Arrays that lie side by side in host memory (a HostRing slot is ONE
     // page-locked block: api.py) get one device block at the same offsets and cross PCIe as ONE copy - a copy command costs
@@ -306,10 +379,10 @@ class Stage {
         if (rc_) return rc_;
         for (auto& b : backs_)
             if (b.bytes) EMP_HIP(ctx_, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, ctx_->stream));
-        if (out_used_) EMP_HIP(ctx_, hipMemcpyAsync(ctx_->arena_h_out, ctx_->arena_d_out, out_used_, hipMemcpyDeviceToHost, ctx_->stream));
+        if (out_used_) EMP_HIP(ctx_, hipMemcpyAsync(ctx_->arena_h_out.p, ctx_->arena_d_out.p, out_used_, hipMemcpyDeviceToHost, ctx_->stream));
         if (!dev_) EMP_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
         for (size_t i = 0; i < arena_backs_.size(); ++i)
-            if (arena_backs_[i].bytes) memcpy(arena_backs_[i].host, ctx_->arena_h_out + arena_offs_[i], arena_backs_[i].bytes);
+            if (arena_backs_[i].bytes) memcpy(arena_backs_[i].host, (char*)ctx_->arena_h_out.p + arena_offs_[i], arena_backs_[i].bytes);
         return EMP_OK;
     }
 
@@ -350,8 +423,8 @@ class Stage {
         if (async_) return defer(ins_, (void*)host, bytes, slot);
         if (arena_ && arena_take(bytes, &in_used_)) {      // packed: one copy for all small inputs (flush_inputs)
             const size_t off = in_used_ - arena_round(bytes);
-            if (bytes) memcpy(ctx_->arena_h_in + off, host, bytes);
-            return ctx_->arena_d_in + off;
+            if (bytes) memcpy((char*)ctx_->arena_h_in.p + off, host, bytes);
+            return (char*)ctx_->arena_d_in.p + off;
         }
         void* d = get(bytes);
         if (d && bytes) EMP_KEEP(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, ctx_->stream));
@@ -365,12 +438,12 @@ class Stage {
             if (arena_ && arena_take(bytes, &out_used_)) {       // packed: one zero fill, one copy back (finish)
                 const size_t off = out_used_ - arena_round(bytes);
                 if (!out_zeroed_) {      // the whole output arena once per call instead of a memset per array
-                    if (!EMP_KEEP(hipMemsetAsync(ctx_->arena_d_out, 0, emp_ctx::kArena, ctx_->stream))) return nullptr;
+                    if (!EMP_KEEP(hipMemsetAsync(ctx_->arena_d_out.p, 0, emp_ctx::kArena, ctx_->stream))) return nullptr;
                     out_zeroed_ = true;
                 }
                 arena_backs_.push_back({host, nullptr, bytes, nullptr});
                 arena_offs_.push_back(off);
-                return ctx_->arena_d_out + off;
+                return (char*)ctx_->arena_d_out.p + off;
             }
             if (!(d = get(bytes))) return nullptr;
             backs_.push_back({host, d, bytes, nullptr});
@@ -382,7 +455,7 @@ class Stage {
     // and by ready().  False once the call has failed.
     bool flush_inputs() {
         if (!rc_ && in_used_ > in_sent_) {
-            if (!EMP_KEEP(hipMemcpyAsync(ctx_->arena_d_in + in_sent_, ctx_->arena_h_in + in_sent_, in_used_ - in_sent_,
+            if (!EMP_KEEP(hipMemcpyAsync((char*)ctx_->arena_d_in.p + in_sent_, (char*)ctx_->arena_h_in.p + in_sent_, in_used_ - in_sent_,
                                          hipMemcpyHostToDevice, ctx_->stream)))
                 return false;
             in_sent_ = in_used_;
@@ -443,26 +516,14 @@ class Stage {
     }
     static size_t arena_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     // room for `bytes` in an arena whose fill mark is *used?  Creates the four arenas on first use; false = take the per-array path
-    // (an array of more than kArenaArray bytes - a host memcpy of that size costs more than the copy command it saves - or a full arena)
+    // (an array of more than kArenaArray bytes - a host memcpy of that size costs more than the copy command it saves - or a full
+    // arena, or an arena that could not be allocated: what was allocated stays with the context, unused)
     bool arena_take(size_t bytes, size_t* used) {
         if (bytes > emp_ctx::kArenaArray || *used + arena_round(bytes) > emp_ctx::kArena || ctx_->arena_failed) return false;
-        if (!ctx_->arena_h_in) {
-            void *hi = nullptr, *ho = nullptr, *di = nullptr, *dout = nullptr;
-            if (hipHostMalloc(&hi, emp_ctx::kArena, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc(&ho, emp_ctx::kArena, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&di, emp_ctx::kArena) != hipSuccess || hipMalloc(&dout, emp_ctx::kArena) != hipSuccess) {
-                (void)hipGetLastError();
-                if (hi) (void)hipHostFree(hi);
-                if (ho) (void)hipHostFree(ho);
-                if (di) (void)hipFree(di);
-                if (dout) (void)hipFree(dout);
-                ctx_->arena_failed = true;
-                return false;
-            }
-            ctx_->arena_h_in = (char*)hi;
-            ctx_->arena_h_out = (char*)ho;
-            ctx_->arena_d_in = (char*)di;
-            ctx_->arena_d_out = (char*)dout;
+        if (ctx_->arena_h_in.ensure(ctx_, emp_ctx::kArena) || ctx_->arena_h_out.ensure(ctx_, emp_ctx::kArena) ||
+            ctx_->arena_d_in.ensure(ctx_, emp_ctx::kArena) || ctx_->arena_d_out.ensure(ctx_, emp_ctx::kArena)) {
+            ctx_->arena_failed = true;
+            return false;
         }
         *used += arena_round(bytes);
         return true;
@@ -493,9 +554,9 @@ struct KernelTimer {
         if (!c->timing_filter.empty() && c->timing_filter != name) return;
         emp_ctx::Ev& e = c->events[name];
         if (e.used == e.pairs.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-            e.pairs.push_back({a, b});
+            std::pair<Event, Event> pr;
+            if (hipEventCreate(&pr.first.h) != hipSuccess || hipEventCreate(&pr.second.h) != hipSuccess) return;
+            e.pairs.push_back(std::move(pr));
         }
         auto& pr = e.pairs[e.used++];
         start = pr.first;
