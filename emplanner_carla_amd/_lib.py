@@ -34,6 +34,8 @@ def hw_queues() -> int:
         return 4
 
 
+ABI_VERSION = 13                   # EMP_ABI_VERSION of include/emplanner.h this binding speaks
+
 EMP_HOST, EMP_DEVICE, EMP_HOST_PINNED = 0, 1, 2
 EMP_EDGE_CANONICAL, EMP_EDGE_TILED = 0, 1
 EMP_DP_FUSED, EMP_DP_TWO_KERNEL = 0, 1
@@ -115,6 +117,13 @@ class CycleIO(C.Structure):
         "dyn_dis_speed",
         # the optional front end (ABI 11): the cycle starts from the global path
         "global_path", "n_global", "pre_match_index", "match_index", "ref_status")] + [("max_global", C.c_int32), ("reserved_io", C.c_int32)]
+
+
+class SpeedIO(C.Structure):
+    """emp_speed_io (ABI 13): the speed half of emp_plan_trajectory."""
+    _fields_ = [(n, _vp) for n in (
+        "dyn_obs", "n_dyn", "start_heading", "plan_start_time", "dyn_pre_match",
+        "trajectory", "speed_status", "path_index2s", "st_segments", "dp_speed", "speed_profile")] + [("reserved", C.c_int32)]
 
 
 # name -> (restype, argtypes); data pointers are void* so numpy arrays and raw device addresses both fit
@@ -207,6 +216,9 @@ PROTOTYPES = {
     "emp_speed_qp": (C.c_int, [_vp, C.POINTER(SpeedQpParams), _i32] + [_vp] * 14 + [C.c_int]),
     "emp_speed_increase_points": (C.c_int, [_vp, _i32] + [_vp] * 9 + [C.c_int]),
     "emp_path_speed_merge": (C.c_int, [_vp, _i32, _i32] + [_vp] * 13 + [C.c_int]),
+    "emp_plan_trajectory": (C.c_int, [_vp, C.POINTER(DpParams), C.POINTER(QpParams), C.POINTER(SmoothParams),
+                                      C.POINTER(SpeedDpParams), C.POINTER(SpeedQpParams), _i32, _i32, _i32, _i32, _i32,
+                                      C.c_int, C.POINTER(CycleIO), C.POINTER(SpeedIO), C.c_int]),
 }
 
 _lib = None
@@ -234,7 +246,7 @@ def load():
         fn = getattr(lib, name)   # AttributeError here means header and library disagree
         fn.restype = res
         fn.argtypes = args
-    if lib.emp_abi_version() != 12:
+    if lib.emp_abi_version() != ABI_VERSION:
         raise RuntimeError("libemplanner.so ABI version mismatch")
     _lib = lib
     return lib

@@ -393,6 +393,31 @@ class CycleResult:
     status: object       # (B,) int32 bit mask
     match_index: object = None   # (B,) int32 - only from a cycle that started at the global path (front end fused in)
     ref_status: object = None    # (B,) int32 - the front end's own status (OR it into ``status``)
+    speed: "TrajectoryResult" = None   # only from ``plan_cycle(..., speed=TrajectoryInputs(...))``
+
+
+@dataclass
+class TrajectoryInputs:
+    """The speed half of ``plan_cycle(..., speed=...)`` (emp_plan_trajectory; reference test_10.py:233-340): the dynamic
+    obstacles are projected onto the planned trajectory and the S-T speed planner turns it into a timed trajectory."""
+    dp: SpeedDpParams              # speed_dp_params()
+    qp: SpeedQpParams              # speed_qp_params()
+    dyn_obs: object                # (B, K, 4) x, y, vx, vy of the dynamic obstacles, 1 <= K <= 64
+    n_dyn: object                  # (B,) int32
+    plan_start_time: object        # (B,) the merge's current_time (test_10.py:325: cur_time + 0.1)
+    start_heading: object = None   # (B,) default: atan2(start_v[:, 1], start_v[:, 0]) (test_10.py:247)
+    dyn_pre_match: object = None   # (B,) int32 pre_match_index of the obstacles' match on the trajectory; None = 0
+    intermediates: bool = True     # also return path_index2s, st_segments, dp_speed and speed_profile
+
+
+@dataclass
+class TrajectoryResult:
+    trajectory: object             # (B, 7, 401) x, y, heading, kappa, speed, accel, time
+    speed_status: object           # (B,) int32 EMP_STB_* bits (STB_*; never ORed with the path's ``status``)
+    path_index2s: object = None    # (B, max_pts + 2) trajectory_index2s of the NaN-padded rows
+    st_segments: object = None     # (4, B, K) s_in, s_out, t_in, t_out
+    dp_speed: object = None        # (2, B, 16) speed_s, speed_t of the speed DP
+    speed_profile: object = None   # (4, B, 17) qp_s, qp_s_dot, qp_s_dot2, relative_time of the speed QP
 
 
 class Planner:
@@ -1129,7 +1154,8 @@ class Planner:
 
     def plan_cycle(self, p: DpParams, q: QpParams, sp: SmoothParams, ref_line, n_ref, origin_xy, start_xy, start_v,
                    start_a, obs_xy, n_obs, max_pts=None, mode=L.EMP_DP_TWO_KERNEL, dyn_dis_speed=None, slot=None,
-                   out: "CycleResult" = None, global_path=None, n_global=None, pre_match_index=None) -> CycleResult:
+                   out: "CycleResult" = None, global_path=None, n_global=None, pre_match_index=None,
+                   speed: "TrajectoryInputs" = None) -> CycleResult:
         """ref motion_planning body, test_9.py:113-218, for a batch of scenes.  dyn_dis_speed (B,2): distance and speed
         of each scene's first dynamic obstacle (NaN = none) for the virtual obstacles of test_9.py:137-169.
         ``slot``: a ``HostRing`` slot whose page-locked arrays ARE the inputs (the array arguments are then ignored) and
@@ -1140,9 +1166,26 @@ class Planner:
         ``global_path`` (B,G,4), ``n_global`` (B,), ``pre_match_index`` (B,): the cycle starts from the GLOBAL path - the
         reference's find_match_points / sampling / smooth_reference_line (test_9.py:99-110, ``reference_line``) run in front of it
         in the same call, the 51-point line stays on the device, ``start_xy`` is the predicted location; ``ref_line`` and ``n_ref``
-        are then ignored (pass None) and the result carries ``match_index`` and ``ref_status``."""
+        are then ignored (pass None) and the result carries ``match_index`` and ``ref_status``.
+        ``speed``: a ``TrajectoryInputs`` - the S-T speed planner runs behind the path in the same call (emp_plan_trajectory,
+        reference test_10.py:99-340) and ``result.speed`` is a ``TrajectoryResult``; the path outputs are the same bits as
+        without it.  Not with ``slot``."""
         if slot is not None:
+            if speed is not None:
+                raise ValueError("speed= cannot be combined with slot=: HostRing slots carry the cycle's arrays only")
             return self._plan_cycle_pinned(p, q, sp, slot, mode)
+        heading = None
+        if speed is not None:
+            heading = speed.start_heading
+            if heading is None:                  # test_10.py:247, before _Args orders the planner's stream behind the caller's
+                # from the float64 values the path half receives
+                if _is_torch(start_v):
+                    import torch
+                    v64 = start_v.to(torch.float64)
+                    heading = torch.atan2(v64[:, 1], v64[:, 0])
+                else:
+                    v64 = np.asarray(start_v, np.float64)
+                    heading = np.arctan2(v64[:, 1], v64[:, 0])
         front = global_path is not None
         a = self._args(global_path if front else ref_line, origin_xy)
         a.cycle = True               # pipelined mode: the outputs become complete on the result stream (see _Args.done)
@@ -1176,8 +1219,31 @@ class Planner:
             arr, ptr = a.out(shape, dt, getattr(out, name) if out is not None else None)
             res[name] = arr
             setattr(io, name, ptr)
-        self._check(self._lib.emp_plan_cycle(self._h, C.byref(p), C.byref(q), C.byref(sp), B, P, mo, M, int(mode),
-                                             C.byref(io), a.where))
+        if speed is None:
+            self._check(self._lib.emp_plan_cycle(self._h, C.byref(p), C.byref(q), C.byref(sp), B, P, mo, M, int(mode),
+                                                 C.byref(io), a.where))
+        else:
+            K = int(speed.dyn_obs.shape[1])
+            sio = L.SpeedIO()
+            sio.dyn_obs = a.inp(speed.dyn_obs, np.float64, (B, K, 4))
+            sio.n_dyn = a.inp(speed.n_dyn, np.int32, (B,))
+            sio.start_heading = a.inp(heading, np.float64, (B,))
+            sio.plan_start_time = a.inp(speed.plan_start_time, np.float64, (B,))
+            sio.dyn_pre_match = a.inp(speed.dyn_pre_match, np.int32, (B,))
+            sres = {}
+            shapes = (("trajectory", (B, 7, SPEED_DENSE_POINTS), np.float64), ("speed_status", (B,), np.int32))
+            if speed.intermediates:
+                shapes += (("path_index2s", (B, M + 2), np.float64), ("st_segments", (4, B, K), np.float64),
+                           ("dp_speed", (2, B, SPEED_DP_COLS), np.float64),
+                           ("speed_profile", (4, B, SPEED_QP_POINTS), np.float64))
+            for name, shape, dt in shapes:
+                arr, ptr = a.out(shape, dt)
+                sres[name] = arr
+                setattr(sio, name, ptr)
+            self._check(self._lib.emp_plan_trajectory(self._h, C.byref(p), C.byref(q), C.byref(sp), C.byref(speed.dp),
+                                                      C.byref(speed.qp), B, P, mo, M, K, int(mode), C.byref(io), C.byref(sio),
+                                                      a.where))
+            res["speed"] = TrajectoryResult(**sres)
         if self.pipelined and a.torch:
             # The outputs of the calls in flight stay referenced here even if the caller drops them at once: their
             # memory must not come back from torch's allocator into a later call's outputs while this call, or a
@@ -1186,7 +1252,7 @@ class Planner:
             # (emp_plan_cycle, lane mode) first orders the main stream behind the tail of its lane, i.e. behind call k
             # and its consumers, and every later call is ordered behind the main stream.  (Staged mode: call
             # k + emp_pipeline_depth() is not issued before the back stage of call k is done.)
-            self._inflight.append((list(res.values()), a.keep))
+            self._inflight.append((list(res.values()) + (list(vars(res["speed"]).values()) if "speed" in res else []), a.keep))
             if len(self._inflight) > self._retain:
                 self._inflight.pop(0)
         return CycleResult(**res)

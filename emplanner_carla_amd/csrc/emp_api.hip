@@ -17,6 +17,7 @@
 #include "emp_st_backend_kernels.h"
 #include "emp_tail_kernels.h"
 #include "emp_mpc_kernels.h"
+#include "emp_speed_front_kernels.h"
 
 namespace emp {
 thread_local std::string g_create_error;
@@ -1570,9 +1571,32 @@ int emp_frenet_path_to_xy(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_
     return st.finish();
 }
 
-int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q, const emp_smooth_params* sp, int32_t B,
-                   int32_t max_ref, int32_t max_obs, int32_t max_pts, emp_dp_mode mode, const emp_cycle_io* io,
-                   emp_mem where) {
+}  // extern "C"
+
+namespace emp {
+// The speed half of emp_plan_trajectory (ref test_10.py:233-340): its arrays are staged with the cycle's, and run() launches it
+// on the cycle's stream - the lane's in lane mode, the back stream in staged mode - behind the Cartesian tail, with the lane's
+// temporaries.  Member bodies after the S-T entry points (make_st_dev).
+struct SpeedHalf {
+    const emp_speed_dp_params* dp;
+    const emp_speed_qp_params* qp;
+    const emp_speed_io* io;
+    int max_dyn;
+    const double *dyn = nullptr, *heading = nullptr, *t0 = nullptr;
+    const int *n_dyn = nullptr, *pre = nullptr;
+    double *traj = nullptr, *i2s = nullptr, *seg = nullptr, *dp_speed = nullptr, *profile = nullptr;
+    int* status = nullptr;
+    void ins(Stage& st, int B);
+    void outs(Stage& st, int B, int max_pts);
+    int run(emp_ctx* ctx, Stage& st, int B, int max_pts, const double* d_traj, const int* d_tlen, const double* d_v,
+            const double* d_a);
+};
+}  // namespace emp
+
+// emp_plan_cycle's body; with `speed` (emp_plan_trajectory) the speed half runs behind the Cartesian tail, before the lane is done
+static int plan_cycle_impl(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q, const emp_smooth_params* sp, int32_t B,
+                           int32_t max_ref, int32_t max_obs, int32_t max_pts, emp_dp_mode mode, const emp_cycle_io* io,
+                           emp_mem where, SpeedHalf* speed) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p && q && sp && io, "NULL parameter struct");
     EMP_REQUIRE(ctx, qp_reserved_ok(q), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
@@ -1600,7 +1624,8 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
     if ((rc = lane.begin())) return rc;
     CycleCapture graph(ctx);
     bool replayed = false;
-    if ((rc = graph.begin(pmode, where, B, max_ref, max_obs, max_pts, mode, p, q, sp, io, &replayed)) || replayed) return rc;
+    // (the trajectory call is never captured: plain launches)
+    if (!speed && ((rc = graph.begin(pmode, where, B, max_ref, max_obs, max_pts, mode, p, q, sp, io, &replayed)) || replayed)) return rc;
     // (the slot form of in() / out(): with EMP_HOST_PINNED the device pointers are known only at inputs_ready() / outputs_ready())
     Stage st(ctx, where, pmode != 0, pinned);
     const double *d_ref = nullptr, *d_o, *d_sxy, *d_v, *d_a, *d_oxy, *d_dyn, *d_glob = nullptr;
@@ -1620,6 +1645,7 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
     st.in(io->obs_xy, (size_t)B * max_obs * 2, &d_oxy);
     st.in(io->n_obs, (size_t)B, &d_no);
     st.in(io->dyn_dis_speed, (size_t)B * 2, &d_dyn);
+    if (speed) speed->ins(st, B);
     st.inputs_ready();
     // outputs (optional ones fall back to device temporaries); no memsets: every kernel of the cycle writes its
     // rows completely, padding included
@@ -1639,6 +1665,7 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
         st.out(io->match_index, (size_t)B, &d_match, false);
         st.out(io->ref_status, (size_t)B, &d_rst, false);
     }
+    if (speed) speed->outs(st, B, max_pts);
     st.outputs_ready();
     // intermediates
     const int mo = obs_cap > 0 ? obs_cap : 1;
@@ -1689,10 +1716,19 @@ int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q,
     if ((rc = dev_cycle_cartesian(ctx, B, max_ref, max_pts, path_cap, sp, d_ref, d_sm, d_nr, d_bsl, d_ps, d_pl, d_plen,
                                   d_traj, d_tlen, d_st)))
         return rc;
+    if (speed && (rc = speed->run(ctx, st, B, max_pts, d_traj, d_tlen, d_v, d_a))) return rc;
     if ((rc = lane.done(st))) return rc;
     if (st.async_host()) return EMP_OK;            // (finish_async has sent the outputs)
     if ((rc = graph.end())) return rc;
     return st.finish();
+}
+
+extern "C" {
+
+int emp_plan_cycle(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q, const emp_smooth_params* sp, int32_t B,
+                   int32_t max_ref, int32_t max_obs, int32_t max_pts, emp_dp_mode mode, const emp_cycle_io* io,
+                   emp_mem where) {
+    return plan_cycle_impl(ctx, p, q, sp, B, max_ref, max_obs, max_pts, mode, io, where, nullptr);
 }
 
 int64_t emp_cycle_graph_replays(emp_ctx* ctx) { return ctx ? (int64_t)ctx->cycle_graph.replays : -1; }
@@ -2224,6 +2260,121 @@ int emp_path_speed_merge(emp_ctx* ctx, int32_t B, int32_t max_path, const double
 }
 
 }  // extern "C"
+
+// ---- path cycle + S-T speed planner in one call (reference test_10.py:99-340) ---------------------
+namespace emp {
+
+void SpeedHalf::ins(Stage& st, int B) {
+    dyn = st.in(io->dyn_obs, (size_t)B * max_dyn * 4);
+    n_dyn = st.in(io->n_dyn, (size_t)B);
+    heading = st.in(io->start_heading, (size_t)B);
+    t0 = st.in(io->plan_start_time, (size_t)B);
+    pre = st.in(io->dyn_pre_match, (size_t)B);
+}
+
+void SpeedHalf::outs(Stage& st, int B, int max_pts) {
+    const size_t W = (size_t)max_pts + 2;
+    traj = st.out(io->trajectory, (size_t)B * 7 * stb::kDense, false);
+    status = st.out(io->speed_status, (size_t)B, false);
+    st.out_or_tmp(io->path_index2s, (size_t)B * W, &i2s);
+    st.out_or_tmp(io->st_segments, (size_t)B * 4 * max_dyn, &seg);
+    st.out_or_tmp(io->dp_speed, (size_t)B * 2 * stb::kDp, &dp_speed);
+    st.out_or_tmp(io->speed_profile, (size_t)B * 4 * stb::kQp, &profile);
+}
+
+int SpeedHalf::run(emp_ctx* ctx, Stage& st, int B, int max_pts, const double* d_traj, const int* d_tlen, const double* d_v,
+                   const double* d_a) {
+    const int W = max_pts + 2;
+    const size_t nb = (size_t)B, bw = nb * W;
+    double* rows = st.tmp<double>(4 * bw);
+    double* v0 = st.tmp<double>(nb);
+    double* a0 = st.tmp<double>(nb);
+    int* width = st.tmp<int>(nb);
+    int* st_front = st.tmp<int>(nb);
+    int* end_node = st.tmp<int>(2 * nb);
+    double* cs = st.tmp<double>(4 * nb * stb::kDp);
+    int* st_cs = st.tmp<int>(nb);
+    double* qp4 = profile;
+    int* st_qp = st.tmp<int>(nb);
+    double* dense = st.tmp<double>(4 * nb * stb::kDense);
+    int* st_dense = st.tmp<int>(nb);
+    int* st_merge = st.tmp<int>(nb);
+    // emp_speed_dp's heaviest-first order beyond 512 scenes (emp_st_kernels.h: st_count_kernel)
+    const bool order = B > 512;
+    int* d_order = order ? st.tmp<int>(nb) : nullptr;
+    unsigned char* d_key = order ? st.tmp<unsigned char>(nb) : nullptr;
+    int* d_hist = order ? st.tmp<int>(2 * (size_t)kStKeys, true) : nullptr;
+    if (const int rc = st.ready()) return rc;          // (temporaries staged behind the cycle's launches: checked here)
+    const size_t sp = nb * max_dyn;
+    double *si = seg, *so = seg + sp, *ti = seg + 2 * sp, *to = seg + 3 * sp;
+    double *ds = dp_speed, *dt = dp_speed + nb * stb::kDp;
+    if (const int rc = launch(ctx, "speed_front", speed_front_wave_kernel, dim3(B), dim3(64), 2 * (size_t)W * sizeof(double), B,
+                              max_pts, W, max_dyn, d_traj, d_tlen, d_v, d_a, heading, dyn, n_dyn, pre, rows, i2s, v0, a0, seg,
+                              width, st_front))
+        return rc;
+    if (order) {
+        if (const int rc = launch_gate(ctx)) return rc;
+        KernelTimer t(ctx, "speed_dp_order");
+        hipLaunchKernelGGL(st_count_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, max_dyn, (const double*)si, d_key, d_hist);
+        hipLaunchKernelGGL(st_scatter_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, (const unsigned char*)d_key,
+                           (const int*)d_hist, d_hist + kStKeys, d_order);
+        EMP_LAUNCH_CHECK(ctx);
+    }
+    if (const int rc = launch(ctx, "speed_dp", max_dyn <= 32 ? speed_dp_kernel<uint32_t> : speed_dp_kernel<uint64_t>, dim3(B),
+                              dim3(kStBlock), speed_dp_lds_bytes(max_dyn), make_st_dev(dp, B, max_dyn), (const double*)si,
+                              (const double*)so, (const double*)ti, (const double*)to, (const double*)v0, (double*)nullptr,
+                              (double*)nullptr, (int*)nullptr, end_node, ds, dt, (const int*)d_order))
+        return rc;
+    // generate_convex_space on the W-wide rows (the reference's default max_lateral_accel = 0.2 * 9.8, speed_planning_test.py:309);
+    // path_len = merge width: W, or 0 for a scene that already raised
+    const double* kappa = rows + 3 * bw;
+    if (const int rc = launch(ctx, "speed_convex_space", stb::convex_space_kernel, grid1(B, 64), dim3(64), 0, B, max_dyn, W, 0.2 * 9.8,
+                              (const double*)ds, (const double*)dt, (const double*)i2s, kappa, (const int*)width, (const double*)si,
+                              (const double*)so, (const double*)ti, (const double*)to, cs, cs + nb * stb::kDp, cs + 2 * nb * stb::kDp,
+                              cs + 3 * nb * stb::kDp, st_cs))
+        return rc;
+    const stb::SpeedQpParams prm{qp->w_cost_s_dot2, qp->w_cost_v_ref, qp->w_cost_jerk, qp->reference_speed};
+    const size_t qlds = 2 * (size_t)(stb::speed_qp_words(stb::kQp) + 1) * sizeof(double);
+    const size_t q17 = nb * stb::kQp, d401 = nb * stb::kDense;
+    if (const int rc = launch(ctx, "speed_qp", stb::speed_qp_kernel<32>, dim3((B + 1) / 2), dim3(64), qlds, B, prm, (const double*)v0,
+                              (const double*)a0, (const double*)ds, (const double*)dt, (const double*)cs,
+                              (const double*)(cs + nb * stb::kDp), (const double*)(cs + 2 * nb * stb::kDp),
+                              (const double*)(cs + 3 * nb * stb::kDp), qp4, qp4 + q17, qp4 + 2 * q17, qp4 + 3 * q17, (int*)nullptr,
+                              st_qp))
+        return rc;
+    if (const int rc = launch(ctx, "speed_increase_points", stb::densify_kernel, dim3(B), dim3(64), 0, B, (const double*)qp4,
+                              (const double*)(qp4 + q17), (const double*)(qp4 + 2 * q17), (const double*)(qp4 + 3 * q17), dense,
+                              dense + d401, dense + 2 * d401, dense + 3 * d401, st_dense))
+        return rc;
+    if (const int rc = launch(ctx, "path_speed_merge", stb::merge_kernel, dim3(B), dim3(64), 5 * (size_t)W * sizeof(double), B, W,
+                              (const double*)dense, (const double*)(dense + d401), (const double*)(dense + 2 * d401),
+                              (const double*)(dense + 3 * d401), t0, (const double*)i2s, (const double*)rows,
+                              (const double*)(rows + bw), (const double*)(rows + 2 * bw), kappa, (const int*)width, traj, st_merge))
+        return rc;
+    return launch(ctx, "speed_status", speed_status_kernel, grid1(B, 64), dim3(64), 0, B, (const int*)st_front, (const int*)st_cs,
+                  (const int*)st_qp, (const int*)st_dense, (const int*)st_merge, status);
+}
+
+}  // namespace emp
+
+extern "C" int emp_plan_trajectory(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q, const emp_smooth_params* sp,
+                                   const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp, int32_t B, int32_t max_ref,
+                                   int32_t max_obs, int32_t max_pts, int32_t max_dyn, emp_dp_mode mode, const emp_cycle_io* io,
+                                   const emp_speed_io* sio, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, sdp && sqp && sio, "NULL speed parameter struct or emp_speed_io");
+    EMP_REQUIRE(ctx, sio->reserved == 0, "emp_speed_io.reserved must be 0");
+    EMP_REQUIRE(ctx, max_dyn >= 1 && max_dyn <= st::kMaxObs, "max_dyn must be in [1, 64] (the speed DP's obstacle slots)");
+    EMP_REQUIRE(ctx, where != EMP_HOST_PINNED, "emp_plan_trajectory does not take EMP_HOST_PINNED arrays (HostRing slots carry the "
+                                               "cycle's layout only): use EMP_HOST or EMP_DEVICE");
+    EMP_REQUIRE(ctx, sio->dyn_obs && sio->n_dyn && sio->start_heading && sio->plan_start_time,
+                "dyn_obs, n_dyn, start_heading and plan_start_time are required inputs");
+    EMP_REQUIRE(ctx, sio->trajectory && sio->speed_status, "trajectory and speed_status are required outputs");
+    EMP_REQUIRE(ctx, !(sdp->w_cost_obs < 0.0), "w_cost_obs must not be negative");
+    EMP_REQUIRE(ctx, sqp->w_cost_s_dot2 > 0 && sqp->w_cost_v_ref > 0 && sqp->w_cost_jerk >= 0, "speed QP weights must be positive");
+    SpeedHalf speed{sdp, sqp, sio, (int)max_dyn};
+    return plan_cycle_impl(ctx, p, q, sp, B, max_ref, max_obs, max_pts, mode, io, where, &speed);
+}
 
 // ---- lateral MPC controller (reference controller/controller.py:65-337) -------------------------
 extern "C" {

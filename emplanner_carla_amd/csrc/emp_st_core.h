@@ -325,6 +325,27 @@ EMP_HD double edge_cost(const Weights& w, double s0, double t0, double v0, doubl
     return (obs + acc) + ref;
 }
 
+// ref :53-94 for one live slot (its s is not NaN) of generate_st_graph: the four outputs hold NaN on entry and keep it where
+// the obstacle is ignored
+EMP_HD void st_graph_slot(double s, double l, double s_dot, double l_dot, double* s_in, double* s_out, double* t_in, double* t_out) {
+    if (fabs(l_dot) < 0.3) return;             // ref :53-66: slow lateral movers are ignored either way
+    const double t_zero = -l / l_dot;
+    const double b1 = 2.0 / l_dot + t_zero;
+    const double b2 = -2.0 / l_dot + t_zero;
+    const double t_max = b1 > b2 ? b1 : b2;
+    const double t_min = b1 > b2 ? b2 : b1;
+    if (t_max < 1.0 || t_min > 8.0) return;    // ref :79-83
+    if (t_min < 0.0 && t_max > 0.0) {          // ref :84-90: already inside the +-2 m band
+        *s_in = s;
+        *t_in = 0.0;
+    } else {
+        *s_in = s + s_dot * t_min;
+        *t_in = t_min;
+    }
+    *s_out = s + s_dot * t_max;
+    *t_out = t_max;
+}
+
 // ref :38-98 (generate_st_graph) for one scene; arrays of n slots
 EMP_HD void st_graph(int n, const double* obs_s, const double* obs_l, const double* obs_s_dot, const double* obs_l_dot,
                      double* s_in, double* s_out, double* t_in, double* t_out) {
@@ -337,22 +358,7 @@ EMP_HD void st_graph(int n, const double* obs_s, const double* obs_l, const doub
             alive = false;
             continue;
         }
-        if (fabs(obs_l_dot[i]) < 0.3) continue;  // ref :53-66: slow lateral movers are ignored either way
-        const double t_zero = -obs_l[i] / obs_l_dot[i];
-        const double b1 = 2.0 / obs_l_dot[i] + t_zero;
-        const double b2 = -2.0 / obs_l_dot[i] + t_zero;
-        const double t_max = b1 > b2 ? b1 : b2;
-        const double t_min = b1 > b2 ? b2 : b1;
-        if (t_max < 1.0 || t_min > 8.0) continue;  // ref :79-83
-        if (t_min < 0.0 && t_max > 0.0) {          // ref :84-90: already inside the +-2 m band
-            s_in[i] = obs_s[i];
-            t_in[i] = 0.0;
-        } else {
-            s_in[i] = obs_s[i] + obs_s_dot[i] * t_min;
-            t_in[i] = t_min;
-        }
-        s_out[i] = obs_s[i] + obs_s_dot[i] * t_max;
-        t_out[i] = t_max;
+        st_graph_slot(obs_s[i], obs_l[i], obs_s_dot[i], obs_l_dot[i], &s_in[i], &s_out[i], &t_in[i], &t_out[i]);
     }
 }
 

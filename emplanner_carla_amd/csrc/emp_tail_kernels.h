@@ -272,6 +272,15 @@ __global__ __launch_bounds__(64) void frenet_project_wave_kernel(
     }
 }
 
+// ref: find_match_points (planning_utils.py:72-92 unwindowed, :123-167 windowed from pre_match_index `st`, which the caller
+// has checked to lie in [0, P)) / match_projection_points (:383-402): the match index of one point
+__device__ inline int find_match_one(const double* line, int P, double x, double y, bool windowed, int st) {
+    if (!windowed) return match_scan(line, P, x, y, 0, 1, 50);
+    const Node pm = node_at(line, st);
+    const double flag = dot2(x - pm.x, y - pm.y, cos(pm.theta), sin(pm.theta));   // ref :139 np.dot
+    return match_scan(line, P, x, y, st, flag > 0.0 ? 1 : -1, 5);
+}
+
 // ref: match_projection_points (mode 0) / find_match_points (mode 1), one lane per scene, points in order
 __global__ void match_points_kernel(int B, int max_ref, int max_pts, const double* __restrict__ ref_line,
                                     const int* __restrict__ n_ref, const double* __restrict__ xy,
@@ -298,15 +307,7 @@ __global__ void match_points_kernel(int B, int max_ref, int max_pts, const doubl
     }
     for (int j = 0; j < k; ++j) {
         const double x = xy[((size_t)b * max_pts + j) * 2], y = xy[((size_t)b * max_pts + j) * 2 + 1];
-        int m;
-        if (!windowed) {
-            m = match_scan(line, P, x, y, 0, 1, 50);                               // ref planning_utils.py:72-92 / :383-402
-        } else {
-            const int st = pre_match_index[b];                                     // ref :123-167
-            const Node pm = node_at(line, st);
-            const double flag = dot2(x - pm.x, y - pm.y, cos(pm.theta), sin(pm.theta));   // ref :139 np.dot
-            m = match_scan(line, P, x, y, st, flag > 0.0 ? 1 : -1, 5);
-        }
+        const int m = find_match_one(line, P, x, y, windowed, windowed ? pre_match_index[b] : 0);
         if (j == 0) m_first = m;
         match_index[(size_t)b * max_pts + j] = m;
         const Node pr = project_on(node_at(line, m_first), x, y);                  // quirk: first point's match (:103/:169/:413)
@@ -1163,6 +1164,16 @@ __global__ void s_map_kernel(int B, int max_ref, const double* __restrict__ ref_
     s_map_build(ref_line + (size_t)b * max_ref * 4, P, origin_xy[2 * b], origin_xy[2 * b + 1], s_map + (size_t)b * max_ref);
 }
 
+// ref: cal_s_l_fun, planning_utils.py:496-507, for one point matched at `m`, its l on the FIRST point's match `m_first` (quirk :413);
+// an index outside [0, P) gives NaN.  l may be null.
+__device__ inline void s_l_point(const double* line, const double* sm, int P, int m, int m_first, double x, double y, double* s,
+                                 double* l) {
+    const double qnan = __builtin_nan("");
+    const bool ok = m >= 0 && m < P, ok_first = m_first >= 0 && m_first < P;
+    *s = ok ? projection_s(node_at(line, m), sm[m], x, y) : qnan;
+    if (l) *l = (ok && ok_first) ? lateral_offset(project_on(node_at(line, m_first), x, y), x, y) : qnan;
+}
+
 // ref: cal_s_l_fun, planning_utils.py:475-509 (mode 0) and cal_projection_s_fun, :429-445 (mode 1: the caller
 // supplies the match indices and only s is produced).  A match index outside [0, P) is not followed: that point's s and
 // l are NaN (l also where the scene's first index is out of range: every l projects on the first point's match); an
@@ -1177,16 +1188,16 @@ __global__ void s_l_kernel(int B, int max_ref, int max_pts, const double* __rest
     const double* sm = s_map + (size_t)b * max_ref;
     const int P = min(max(n_ref[b], 0), max_ref);       // clamped to the row's capacity
     const int k = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
-    const double qnan = __builtin_nan("");
     int m_first = 0;
     for (int j = 0; j < k; ++j) {
         const size_t o = (size_t)b * max_pts + j;
         const double x = xy[o * 2], y = xy[o * 2 + 1];
         const int m = match_in ? match_in[o] : match_scan(line, P, x, y, 0, 1, 50);
         if (j == 0) m_first = m;
-        const bool ok = m >= 0 && m < P, ok_first = m_first >= 0 && m_first < P;
-        out_s[o] = ok ? projection_s(node_at(line, m), sm[m], x, y) : qnan;
-        if (out_l) out_l[o] = (ok && ok_first) ? lateral_offset(project_on(node_at(line, m_first), x, y), x, y) : qnan;
+        double s, l;
+        s_l_point(line, sm, P, m, m_first, x, y, &s, out_l ? &l : nullptr);
+        out_s[o] = s;
+        if (out_l) out_l[o] = l;
     }
 }
 
@@ -1235,6 +1246,12 @@ __global__ void proj_point_kernel(int n, int max_ref, const double* __restrict__
     status[t] = ok ? 0 : kStSOutOfRange;
 }
 
+// ref: trajectory_index2s, planning_utils.py:776: one chord (the caller sums them left to right)
+__device__ inline double chord_length(double x0, double y0, double x1, double y1) {
+    const double dx = x1 - x0, dy = y1 - y0;
+    return sqrt(dx * dx + dy * dy);
+}
+
 // ref: trajectory_index2s, planning_utils.py:758-780: cumulative chord length until the first NaN x
 __global__ void index2s_kernel(int B, int max_pts, const double* __restrict__ x, const double* __restrict__ y,
                                const int* __restrict__ n_pts, double* __restrict__ out) {
@@ -1246,8 +1263,7 @@ __global__ void index2s_kernel(int B, int max_pts, const double* __restrict__ x,
     for (int i = 0; i < n; ++i) out[o + i] = 0.0;
     for (int i = 1; i < n; ++i) {
         if (x[o + i] != x[o + i]) break;
-        const double dx = x[o + i] - x[o + i - 1], dy = y[o + i] - y[o + i - 1];
-        acc += sqrt(dx * dx + dy * dy);
+        acc += chord_length(x[o + i - 1], y[o + i - 1], x[o + i], y[o + i]);
         out[o + i] = acc;
     }
 }
@@ -1301,16 +1317,21 @@ __global__ void frenet2cartesian_kernel(int B, int max_ref, int max_pts, const d
     status[b] = st;
 }
 
+// ref: cal_dy_obs_deri, planning_utils.py:795-806 for one obstacle: l, velocity, projected heading and kappa -> s_dot, l_dot, dl/ds
+__device__ inline void dy_obs_deri_one(double l, double vx, double vy, double hd, double k, double* s_dot_out, double* l_dot_out,
+                                       double* dl_out) {
+    const double l_dot = dot2(vx, vy, -sin(hd), cos(hd));                 // np.dot, :799-800
+    const double s_dot = dot2(vx, vy, cos(hd), sin(hd)) / (1.0 - k * l);
+    *s_dot_out = s_dot;
+    *l_dot_out = l_dot;
+    *dl_out = (fabs(s_dot) < 1e-6) ? 0.0 : l_dot / s_dot;
+}
+
 // ref: cal_dy_obs_deri, planning_utils.py:783-808: in [n][5] = l, vx, vy, heading, kappa -> out [n][3] = s_dot, l_dot, dl
 __global__ void dy_obs_deri_kernel(int n, const double* __restrict__ in, double* __restrict__ out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const double l = in[5 * t], vx = in[5 * t + 1], vy = in[5 * t + 2], hd = in[5 * t + 3], k = in[5 * t + 4];
-    const double l_dot = dot2(vx, vy, -sin(hd), cos(hd));                 // np.dot, :799-800
-    const double s_dot = dot2(vx, vy, cos(hd), sin(hd)) / (1.0 - k * l);
-    out[3 * t] = s_dot;
-    out[3 * t + 1] = l_dot;
-    out[3 * t + 2] = (fabs(s_dot) < 1e-6) ? 0.0 : l_dot / s_dot;
+    dy_obs_deri_one(in[5 * t], in[5 * t + 1], in[5 * t + 2], in[5 * t + 3], in[5 * t + 4], &out[3 * t], &out[3 * t + 1], &out[3 * t + 2]);
 }
 
 // small utilities ---------------------------------------------------------------------------------

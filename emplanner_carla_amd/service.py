@@ -17,10 +17,12 @@ static obstacles count only if the nearest is within 30 m (test_9.py:117), only 
 from __future__ import annotations
 
 import logging
+import math
 
 import numpy as np
 
-from .api import Planner, dp_params, max_path_points, qp_params, smooth_params
+from .api import (Planner, TrajectoryInputs, dp_params, max_path_points, qp_params, smooth_params, speed_dp_params,
+                  speed_qp_params)
 
 log = logging.getLogger("emplanner_carla_amd.service")
 
@@ -278,6 +280,72 @@ def plan_requests(planner: Planner, requests, dp=None, qp=None, sp=None, stages=
         traj = [tuple(float(x) for x in row) for row in res.traj[b, :m]]
         out.append(((traj, [int(match[b])], [float(x) for x in res.path_s[b, :k]], [float(x) for x in res.path_l[b, :k]]),
                     status))
+    return out
+
+
+def as_test9_request(request):
+    """A test_10-shaped request (test_10.py:100-102: test_9's eight fields with dynamic obstacles as (x, y, vx, vy, ax, ay, dis,
+    speed), then cur_time) in test_9 form: dynamic obstacles as (x, y, dis, speed), no cur_time.  test_10.py:136 unpacks the
+    8-tuples as 4-tuples; the distance and speed its path half means are fields 6 and 7."""
+    static, dynamic, vehicle_loc, pred_loc, vehicle_v, vehicle_a, path, match_list = request[:8]
+    dyn9 = [(o[0], o[1], o[6], o[7]) for o in dynamic]
+    return (static, dyn9, vehicle_loc, pred_loc, vehicle_v, vehicle_a, path, match_list)
+
+
+def pack_trajectory_requests(requests, max_dyn=None):
+    """The arrays of ``pack_requests`` for test_10-shaped requests (its ``dyn`` from fields 6 and 7 of the first dynamic
+    obstacle), plus the speed half's: dyn_obs (B, K, 4) x, y, vx, vy, n_dyn (B,), plan_start_time (B,) = cur_time + 0.1
+    (test_10.py:325), start_heading (B,) = atan2(vy, vx) of the vehicle's velocity (test_10.py:247)."""
+    a = pack_requests([as_test9_request(r) for r in requests])
+    B = len(requests)
+    n = [len(r[1]) for r in requests]
+    K = int(max_dyn) if max_dyn else max(1, max(n, default=1))
+    if K > 64 or max(n, default=0) > K:
+        raise ValueError(f"at most min(max_dyn, 64) dynamic obstacles per request (got {max(n, default=0)}, max_dyn {K})")
+    a["dyn_obs"] = np.zeros((B, K, 4))
+    a["n_dyn"] = np.asarray(n, np.int32).reshape(B)
+    for b, r in enumerate(requests):
+        if n[b]:
+            a["dyn_obs"][b, :n[b]] = [(float(o[0]), float(o[1]), float(o[2]), float(o[3])) for o in r[1]]
+    a["plan_start_time"] = np.asarray([float(r[8]) + 0.1 for r in requests], np.float64).reshape(B)
+    a["start_heading"] = np.asarray([math.atan2(float(r[4][1]), float(r[4][0])) for r in requests], np.float64).reshape(B)
+    return a
+
+
+def plan_trajectory_requests(planner: Planner, requests, dp=None, qp=None, sp=None, speed_dp=None, speed_qp=None, max_dyn=None):
+    """test_10's ``motion_planning`` body (test_10.py:99-340) for a batch of test_10-shaped requests, in ONE device call
+    (``plan_cycle(..., speed=...)``, emp_plan_trajectory).  Returns per request (reply, trajectory, status, speed_status):
+    reply is the 4-tuple of test_10.py:350 with the GLOBAL-path match index (as ``plan_requests``: the driver feeds it back as the
+    next pre_match_index on the global path), trajectory the seven lists x, y, heading, kappa, speed, accel, time of
+    path_speed_merge.  reply is None where ``plan_requests`` refuses the path; trajectory is None there too (the reference
+    raises in its path half and never reaches the speed planner) and where the speed planner has a non-zero status (the
+    reference raises there, or its speed QP fails).  The obstacles' match on the trajectory starts at
+    index 0 (emp_speed_io.dyn_pre_match: the reference hands it the global-path index, test_10.py:268-271)."""
+    B = len(requests)
+    if B == 0:
+        return []
+    dp = dp or dp_params()
+    qp = qp or qp_params()
+    sp = sp or smooth_params()
+    a = pack_trajectory_requests(requests, max_dyn)
+    M = max_path_points(dp)
+    speed = TrajectoryInputs(speed_dp or speed_dp_params(), speed_qp or speed_qp_params(), a["dyn_obs"], a["n_dyn"],
+                             a["plan_start_time"], start_heading=a["start_heading"], intermediates=False)
+    res = planner.plan_cycle(dp, qp, sp, None, None, max_pts=M, origin_xy=a["veh"], start_xy=a["pred"], start_v=a["v"],
+                             start_a=a["a"], obs_xy=a["obs_xy"], n_obs=a["n_obs"], dyn_dis_speed=a["dyn"],
+                             global_path=a["global_path"], n_global=a["n_global"], pre_match_index=a["pre_match"], speed=speed)
+    out = []
+    for b in range(B):
+        st_ref, st_path = int(res.ref_status[b]), int(res.status[b])
+        status, speed_status = st_ref | st_path, int(res.speed.speed_status[b])
+        reply = None
+        if st_ref == 0 and (st_path & ~1) == 0:
+            m, k = int(res.traj_len[b]), int(res.path_len[b])
+            reply = ([tuple(float(x) for x in row) for row in res.traj[b, :m]], [int(res.match_index[b])],
+                     [float(x) for x in res.path_s[b, :k]], [float(x) for x in res.path_l[b, :k]])
+        # the reference raises in the path half before it reaches the speed planner: no trajectory behind a refused path
+        lists = None if (reply is None or speed_status) else tuple([float(x) for x in row] for row in res.speed.trajectory[b])
+        out.append((reply, lists, status, speed_status))
     return out
 
 

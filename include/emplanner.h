@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define EMP_ABI_VERSION 12
+/* ABI 13 (migration from 12): adds emp_speed_io and emp_plan_trajectory - the path cycle and the S-T speed planner in one call.
+ * Nothing of ABI 12 changed: a caller that does not use the new entry point only updates its version check. */
+#define EMP_ABI_VERSION 13
 
 typedef struct emp_ctx emp_ctx;
 
@@ -752,6 +754,67 @@ int emp_path_speed_merge(emp_ctx* ctx, int32_t B, int32_t max_path, const double
                          const double* path_s, const double* x_init, const double* y_init, const double* heading_init,
                          const double* kappa_init, const int32_t* n_init, double* trajectory, int32_t* status,
                          emp_mem where);
+
+/* ---- path cycle + S-T speed planner in one call (ABI 13) ---------------------------------------------------------------
+ * ref: motion_planning of test_10.py:99-340 - the reference's most complete planning loop: plan the path (emp_plan_cycle exactly:
+ * every emp_cycle_io output, the front end included, equals emp_plan_cycle's bit for bit), project the DYNAMIC obstacles onto the
+ * planned trajectory, run the speed planner; the result is a timed trajectory.  Per scene, on the device, no host round trip:
+ *   1. rows x, y, heading, kappa of width W = max_pts + 2 from traj / traj_len, NaN from traj_len on (the reference's
+ *      trajectory_index2s and path_speed_merge are MATLAB transliterations that need a NaN behind the valid points: W
+ *      guarantees one)
+ *   2. trajectory_index2s on those rows (the chords summed left to right, as emp_trajectory_index2s)
+ *   3. calc_speed_planning_start_condition(start_v, start_a, start_heading)
+ *   4. find_match_points(dyn xy, traj[:traj_len], is_first_run = False, dyn_pre_match); every projected node is taken at the
+ *      FIRST obstacle's match (planning_utils.py:169)
+ *   5. cal_s_l_fun(dyn xy, traj[:traj_len], s_map = path_index2s)
+ *   6. cal_dy_obs_deri with the projected heading and kappa (it stops at the first NaN l)
+ *   7. generate_st_graph; slots at or beyond n_dyn are NaN in all four inputs
+ *   8. speed_DP, generate_convex_space (path = the W-wide rows, max_lateral_accel = 0.2 * 9.8, the reference's default),
+ *      speed_QP, increase_points, path_speed_merge(current_time = plan_start_time)
+ * Steps 1-7 are one wavefront per scene (speed_front_wave_kernel); 8 are the kernels of the stand-alone entry points with their
+ * launch configurations - the values equal the chain emp_trajectory_index2s -> emp_speed_start_condition -> emp_find_match_points
+ * -> emp_s_l -> emp_dy_obs_deri -> emp_st_graph -> emp_speed_dp -> emp_speed_convex_space -> emp_speed_qp ->
+ * emp_speed_increase_points -> emp_path_speed_merge on the same arrays, bit for bit.
+ * Statuses stay separate: io->status keeps the path's EMP_ST_* bits, speed_status takes the OR of the speed stages' EMP_STB_* bits
+ * (the two sets overlap: 2, 4 and 8 mean different things).  The speed half runs for every scene whatever its path status.  A
+ * scene with n_dyn > 0 whose obstacle match cannot start inside [0, traj_len) (dyn_pre_match outside it, or an empty trajectory:
+ * the reference's IndexError, planning_utils.py:132) gets speed_status = EMP_STB_INDEX alone and an all-NaN trajectory; its
+ * st_segments are NaN and its dp_speed is the DP of that empty graph.  With n_dyn == 0 the match loop never runs: no error.
+ * Decisions pinned on test_10's defects:
+ *   - :136 unpacks the 8-tuples its driver sends (:521) as 4-tuples: the path half's io->dyn_dis_speed is the caller's, and the
+ *     request packer (service.plan_trajectory_requests) takes fields 6 and 7 (dis, speed) of the first dynamic obstacle
+ *   - :234-238 and :244 use undefined or chained-assigned names: the trajectory arrays are the columns of the cycle's traj
+ *   - :268-271 hand the GLOBAL path's match index to a search on the ~60-point local trajectory, an IndexError in every cycle
+ *     with a dynamic obstacle once the vehicle is more than a trajectory's length of nodes along its path: dyn_pre_match makes
+ *     the index explicit (NULL = 0, the Python default; the global index reproduces the reference literally)
+ *   - :350 replies with the obstacles' match list where test_9 sends the global-path match index, which the driver feeds back as
+ *     the next pre_match_index on the global path: the reply carries the global-path match index, as plan_requests does
+ *   - the last of the 401 samples takes the arrays' last slots (speed_planning_test.py:608-611), NaN when padded: kept
+ * Limits: 1 <= max_dyn <= 64 (the speed DP's), and the emp_plan_cycle limits.  EMP_HOST_PINNED is refused (HostRing slots carry
+ * the cycle's layout only); with EMP_OPT_CYCLE_GRAPH set the call is not captured and runs as plain launches.  B == 0: EMP_OK.
+ * Pipelined, the speed half runs on the call's lane (staged: its back stream) behind the Cartesian tail: its outputs are complete
+ * on emp_result_stream() like the path's. */
+typedef struct emp_speed_io {
+    /* inputs */
+    const double* dyn_obs;          /* [B][max_dyn][4] x, y, vx, vy of the dynamic obstacles (test_10.py:258-265) */
+    const int32_t* n_dyn;           /* [B] (clamped to [0, max_dyn]) */
+    const double* start_heading;    /* [B] plan_start_heading (test_10.py:247: atan2(vy, vx) of start_v, computed by the caller) */
+    const double* plan_start_time;  /* [B] the merge's current_time (test_10.py:325: cur_time + 0.1, added by the caller) */
+    const int32_t* dyn_pre_match;   /* [B] pre_match_index of the obstacles' find_match_points on the trajectory; NULL = 0 */
+    /* outputs */
+    double* trajectory;             /* [B][7][401] x, y, heading, kappa, speed, accel, time  (required) */
+    int32_t* speed_status;          /* [B] EMP_STB_* bits (required) */
+    double* path_index2s;           /* [B][max_pts + 2] trajectory_index2s of the rows, optional */
+    double* st_segments;            /* [4][B][max_dyn] s_in, s_out, t_in, t_out (plane-major, as emp_speed_dp takes them), optional */
+    double* dp_speed;               /* [2][B][16] speed_s, speed_t of the speed DP, optional */
+    double* speed_profile;          /* [4][B][17] qp_s, qp_s_dot, qp_s_dot2, relative_time of the speed QP, optional */
+    int32_t reserved;               /* must be 0 */
+} emp_speed_io;
+
+int emp_plan_trajectory(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q, const emp_smooth_params* sp,
+                        const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp, int32_t B, int32_t max_ref,
+                        int32_t max_obs, int32_t max_pts, int32_t max_dyn, emp_dp_mode mode, const emp_cycle_io* io,
+                        const emp_speed_io* sio, emp_mem where);
 
 #ifdef __cplusplus
 }
