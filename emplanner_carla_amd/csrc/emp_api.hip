@@ -21,7 +21,6 @@
 
 namespace emp {
 thread_local std::string g_create_error;
-constexpr int kMaxTiledRow = 32;       // the tiled kernels (scenes packed into wavefronts, pair table in LDS) up to here
 
 // Asked by every launch of this file before it is issued: none while the call's Stage still takes inputs (packed inputs may not
 // have been sent yet - emp_context.h Stage::ready()).
@@ -38,6 +37,16 @@ static int launch(emp_ctx* ctx, const char* name, K kern, dim3 grid, dim3 block,
     KernelTimer t(ctx, name);
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, args...);
     EMP_LAUNCH_CHECK(ctx);
+    return EMP_OK;
+}
+
+constexpr const char* kQpTooLarge = "problem too large for the LDS-resident QP solver";
+// Dynamic LDS of a kernel: refused with the caller's own text beyond a compute unit's 160 KB, opted in beyond the default 48 KB.
+template <typename K>
+static int set_lds(emp_ctx* ctx, K kernel, size_t bytes, const char* too_large) {
+    EMP_REQUIRE(ctx, bytes <= 160 * 1024, too_large);
+    if (bytes > 48 * 1024)
+        EMP_HIP(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return EMP_OK;
 }
 
@@ -71,8 +80,8 @@ static int make_dp_dev(emp_ctx* ctx, const emp_dp_params* p, int B, int max_obs,
     EMP_REQUIRE(ctx, p->sample_s > 0 && p->sample_l > 0 && p->sampling_res > 0, "sample_s, sample_l, sampling_res must be > 0");
     d->row = p->row;
     d->col = p->col;
-    d->S = p->row <= kMaxTiledRow ? 64 / p->row : 1;      // wider lattices: one scene per block, canonical edge tensor
-    d->tiles = (B + d->S - 1) / d->S;
+    d->S = dp_tiling(p->row, B).S;
+    d->tiles = dp_tiling(p->row, B).tiles;
     d->B = B;
     d->max_obs = max_obs > 0 ? max_obs : 1;
     d->sample_s = p->sample_s;
@@ -86,12 +95,10 @@ static int make_dp_dev(emp_ctx* ctx, const emp_dp_params* p, int B, int max_obs,
     return EMP_OK;
 }
 
-static bool wide(const DpDev& d) { return d.row > kMaxTiledRow; }
-// elements of the edge tensor the DP kernels exchange: tiled up to 32 rows, canonical [B][col-1][row][row] beyond
-static size_t tiled_elems(const DpDev& d) {
-    if (wide(d)) return (size_t)d.B * (size_t)(d.col - 1) * d.row * d.row;
-    return (size_t)d.tiles * (size_t)(d.col - 1) * d.row * 64;
-}
+// elements of the edge tensor the DP kernels exchange between themselves: tiled up to 32 rows, canonical beyond (emp_dp_launch.h)
+static size_t tiled_elems(const DpDev& d) { return edge_tensor_elems(d.row, d.col, d.B, true); }
+// a plan emp_dp_launch.h refused, as the call's error
+static int plan_refused(emp_ctx* ctx, const char* error) { return error ? fail(ctx, EMP_ERR_INVALID, error) : EMP_OK; }
 
 // ---- device-level stage launchers (all pointers are device memory; nothing synchronises) -----
 // pair table of the lattice (emp_dp_kernels.h dp_pair_table_kernel): rebuilt only when the lattice parameters change,
@@ -116,114 +123,40 @@ static int dp_pair_table(emp_ctx* ctx, const DpDev& d, const double** out) {
     return EMP_OK;
 }
 
+// The tiled edge-cost kernels of one layout and mask width, by the plan's row_inst
+struct EdgeKernels {
+    decltype(&dp_edge_ring_kernel<true>) ring;
+    decltype(&dp_edge_kernel<true>) lockstep;
+};
+template <bool TILED, typename MASK>
+static EdgeKernels edge_kernels(int row_inst) {
+    switch (row_inst) {
+        case 5: return {dp_edge_ring_kernel<TILED, 5, MASK>, dp_edge_kernel<TILED, 5, MASK>};
+        case 9: return {dp_edge_ring_kernel<TILED, 9, MASK>, dp_edge_kernel<TILED, 9, MASK>};
+        case 12: return {dp_edge_ring_kernel<TILED, 12, MASK>, dp_edge_kernel<TILED, 12, MASK>};
+        case 21: return {dp_edge_ring_kernel<TILED, 21, MASK>, dp_edge_kernel<TILED, 21, MASK>};
+        default: return {dp_edge_ring_kernel<TILED, 0, MASK>, dp_edge_kernel<TILED, 0, MASK>};
+    }
+}
+
+// Edge costs: plan (emp_dp_launch.h plan_edge), pick the kernel, wait, one launch, signal.
 static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const double* obs_l, const int* n_obs,
                        const double* start, double* start_cost, double* edge, bool tiled, CycleSched* cs) {
     if (d.B == 0) return EMP_OK;
-    if (wide(d)) {          // more than 32 rows: generic kernel, canonical tensor whatever `tiled` says (emp_dp_kernels.h)
-        const double* pair_tab = nullptr;
-        { const int prc = dp_pair_table(ctx, d, &pair_tab); if (prc) return prc; }
-        EMP_REQUIRE(ctx, d.B <= 0x7fffffff && d.col - 1 <= 65535, "batch or lattice too large for the wide-row edge kernel's grid");
-        return launch(ctx, "dp_edge", dp_edge_wide_kernel, dim3(d.B, d.col > 1 ? d.col - 1 : 1), dim3(std::min(((d.row + 63) / 64) * 64, 256)), 0,
-                      d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge);
-    }
-    // per block: pair table, the tile's obstacles, sample offsets; per wavefront: the longitudinal box terms of its column
-    // ([S][mask width] doubles, emp_dp_kernels.h: box_dx2)
-    // EMP_OPT_EDGE_FORM: 0 (default) the work-ring kernel (emp_dp_kernels.h dp_edge_ring_kernel: edges with obstacles in reach are
-    // queued per wavefront and scanned one entry per lane), 1 the lockstep kernel of rounds 1-4 - bit-identical tensors.  The ring
-    // form needs every obstacle of a row inside one 64-bit mask and the column index inside 15 bits; anything else is lockstep.
-    const bool ring = ctx->opt[EMP_OPT_EDGE_FORM] == 0 && d.max_obs <= 64 && d.col <= kRingMaxCol;
-    const bool m32 = d.max_obs <= 32;          // every obstacle of a row fits a 32-bit reach mask
-    const size_t lds_fixed = (ring ? ((size_t)kTableFields * d.row * d.row + 2 * (size_t)d.S * d.max_obs + ((d.S + 1) & ~1)) * sizeof(double)
-                                   : ((size_t)kTableFields * d.row * d.row + 2 * (size_t)d.S * d.max_obs + kTableTail) * sizeof(double)) + EMP_EDGE_LDS_PAD;
-    const size_t lds_wave = ring ? 2 * (size_t)d.S * d.max_obs * sizeof(double) + (size_t)edge_ring_bytes(d.max_obs) + 4 * (size_t)d.S * sizeof(double)
-                                 : (size_t)d.S * (d.max_obs <= 32 ? d.max_obs : (d.max_obs < 64 ? d.max_obs : 64)) * sizeof(double);
-    size_t lds = lds_fixed + 2 * lds_wave;        // the block-size rule below prices a two-wavefront block; the launch its own
-    EMP_REQUIRE(ctx, lds <= 160 * 1024, "lattice too wide for the LDS pair table");
-    int ncol = d.col - 1;
-    int chunks = 1;
-    // Block size: as many wavefronts per block as it takes to fill a CU's twenty wavefront slots (five per SIMD) with the
-    // blocks its LDS holds - and no more, because a block needs a free slot on as many SIMDs as it has wavefronts at the same
-    // moment: beside the previous batch's path-QP wavefronts (staged pipeline) a two-wavefront block of the 40 x 9 lattice
-    // (12 KB of LDS: 13 blocks per CU) finds room where a four-wavefront block does not (step 0.322 -> 0.289 ms), while the
-    // 120 x 21 lattice's 60 KB table allows two blocks per CU, which therefore carry ten wavefronts each.
-    // EMP_OPT_EDGE_BLOCK (emp_set_option) overrides it.
-    const int eb_env = ctx->opt[EMP_OPT_EDGE_BLOCK];
-    int wpb = 4;
-    if (!ring) {
-        const int blocks_per_cu = (int)((160 * 1024) / (lds > 0 ? lds : 1));
-        wpb = (20 + blocks_per_cu - 1) / (blocks_per_cu > 0 ? blocks_per_cu : 1);
-        if (wpb < 2) wpb = 2;
-        if (wpb > 16) wpb = 16;
-    } else {
-        // the ring form's wavefronts carry ~3 KB of LDS each: the smallest block that puts sixteen wavefronts on a CU (or as many
-        // as the LDS allows).  Small blocks matter in the staged step, where a block must find all its slots free at once beside
-        // the previous batch's path-QP wavefronts: at 40 x 9 two-wavefront blocks give 0.241 ms per step, three 0.258, four 0.266,
-        // eight 0.293 - although ALONE the kernel is fastest with four (profiles/r05_edge/README.md)
-        // (LDS is allocated in 1280-byte granules, 128 of them a CU)
-        auto blocks_per_cu = [](size_t l) { return (size_t)128 / ((l + 1279) / 1280); };
-        int best = 0;
-        for (int w = 2; w <= 16; ++w) {
-            const size_t l = lds_fixed + (size_t)w * lds_wave;
-            if (l > 160 * 1024) break;
-            best = std::max(best, (int)std::min<size_t>(blocks_per_cu(l) * w, 20));
-        }
-        for (int w = 2; w <= 16; ++w) {
-            const size_t l = lds_fixed + (size_t)w * lds_wave;
-            if (l > 160 * 1024) break;
-            if ((int)std::min<size_t>(blocks_per_cu(l) * w, 20) >= std::min(best, 16)) {
-                wpb = w;
-                break;
-            }
-        }
-    }
-    // (a tensor beyond the 256 MiB Infinity Cache - 32768 scenes of the 40 x 9 lattice - keeps four wavefronts per block: the
-    // faster front stage otherwise leaves the sweep, which then streams from DRAM for 150 us, beside the previous batch's
-    // path QP: 0.75 of the roofline against 0.61)
-    if (tiled && tiled_elems(d) * sizeof(double) > ((size_t)256 << 20) && wpb < 4) wpb = 4;
-    if (eb_env) wpb = eb_env / 64;
-    // (the rule above prices a two-wavefront block; a wide table with wide obstacle rows - 32 rows, 254+ obstacle slots: one block
-    // of sixteen wavefronts per CU - may not hold sixteen per-wavefront scratch areas: fewer wavefronts, not a refusal)
-    while (wpb > 1 && lds_fixed + (size_t)wpb * lds_wave > 160 * 1024) --wpb;
-    const int eb = wpb * 64;
-    lds = lds_fixed + (size_t)wpb * lds_wave;
-    EMP_REQUIRE(ctx, lds <= 160 * 1024, "edge-cost block too large for the LDS");
-    // each of the block's wavefronts takes whole columns: two per wavefront, or one while that leaves the chip short of blocks
-    // (a single scene: 29 us with one column per wavefront, 44 with two); chunk sizes multiples of the wavefront count
-    if (ncol > 0) {
-        int cpw = ((long long)d.tiles * ((ncol + 2 * wpb - 1) / (2 * wpb)) >= 1024) ? 2 : 1;
-        // (ring form: a wavefront drains its rings once, at the end of its columns - four columns per wavefront while that
-        // still leaves several thousand blocks: 120 x 21 at 4096 scenes 2.18 -> 2.01 ms)
-        if (ring && (long long)d.tiles * ((ncol + 4 * wpb - 1) / (4 * wpb)) >= 4096) cpw = 4;
-        chunks = (ncol + cpw * wpb - 1) / (cpw * wpb);
-        if (chunks < 1) chunks = 1;
-    }
-    int cols_per_chunk = ncol > 0 ? (ncol + chunks - 1) / chunks : 1;
-    cols_per_chunk = cols_per_chunk >= wpb ? (cols_per_chunk / wpb) * wpb : wpb;
-    chunks = ncol > 0 ? (ncol + cols_per_chunk - 1) / cols_per_chunk : 1;
-    if (ring) {       // the ring form's jerk-factor table: [columns per wavefront][S] per wavefront (priced above with four columns, the most the rule below gives a wavefront)
-        const size_t cpw_final = (size_t)(cols_per_chunk + wpb - 1) / wpb;
-        lds = lds_fixed + (size_t)wpb * (lds_wave - 4 * (size_t)d.S * sizeof(double) + cpw_final * d.S * sizeof(double));
-        EMP_REQUIRE(ctx, lds <= 160 * 1024, "edge-cost block too large for the LDS");
-    }
-    dim3 grid(d.tiles, chunks), block(eb);
+    const EdgePlan p = plan_edge(d, tiled, ctx->opt[EMP_OPT_EDGE_FORM], ctx->opt[EMP_OPT_EDGE_BLOCK], EMP_EDGE_LDS_PAD);
+    if (const int rc = plan_refused(ctx, p.error)) return rc;
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
     const double* pair_tab = nullptr;
-    { const int prc = dp_pair_table(ctx, d, &pair_tab); if (prc) return prc; }
-    // the benchmark lattices' row counts are compiled in (emp_dp_kernels.h: dp_edge_column<ROW>), as in the sweep; any other takes
-    // the generic instantiation - the same operations either way
+    if (const int rc = dp_pair_table(ctx, d, &pair_tab)) return rc;
+    if (p.wide)
+        return launch(ctx, "dp_edge", dp_edge_wide_kernel, grid, block, 0, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge);
     using M32 = unsigned int;
     using M64 = unsigned long long;
-#define EMP_EDGE_PICK(K, T)                                                                                           \
-    (d.row == 9 ? (m32 ? K<T, 9, M32> : K<T, 9, M64>)                                                                 \
-     : d.row == 21 ? (m32 ? K<T, 21, M32> : K<T, 21, M64>)                                                            \
-     : d.row == 12 ? (m32 ? K<T, 12, M32> : K<T, 12, M64>)                                                            \
-     : d.row == 5 ? (m32 ? K<T, 5, M32> : K<T, 5, M64>)                                                               \
-                  : (m32 ? K<T, 0, M32> : K<T, 0, M64>))
-    auto kern_ring = tiled ? EMP_EDGE_PICK(dp_edge_ring_kernel, true) : EMP_EDGE_PICK(dp_edge_ring_kernel, false);
-    auto kern = tiled ? EMP_EDGE_PICK(dp_edge_kernel, true) : EMP_EDGE_PICK(dp_edge_kernel, false);
-#undef EMP_EDGE_PICK
-    if (lds > 48 * 1024)
-        EMP_HIP(ctx, hipFuncSetAttribute(ring ? (const void*)kern_ring : (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
+    const EdgeKernels k = tiled ? (p.m32 ? edge_kernels<true, M32>(p.row_inst) : edge_kernels<true, M64>(p.row_inst))
+                                : (p.m32 ? edge_kernels<false, M32>(p.row_inst) : edge_kernels<false, M64>(p.row_inst));
+    if (const int rc = p.ring ? set_lds(ctx, k.ring, p.lds, "edge-cost block too large for the LDS")
+                              : set_lds(ctx, k.lockstep, p.lds, "edge-cost block too large for the LDS"))
+        return rc;
     // EMP_OPT_EDGE_AFTER_ENRICH (staged pipeline): the edge kernel starts behind the previous call's densification kernel,
     // so that the path QP that follows it on the back queue is dispatched BEFORE this kernel's sixteen-wavefront blocks
     // take the compute units (emp_plan_cycle)
@@ -231,39 +164,72 @@ static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
         EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, cs->edge_wait, 0));
         cs->edge_wait = nullptr;
     }
-    if (ring && ctx->opt[EMP_OPT_EDGE_CLOCK_PROBE]) {          // measurement: two reference ticks per wavefront of this launch
-        const size_t waves_total = (size_t)grid.x * grid.y * wpb;
+    // EMP_OPT_EDGE_CLOCK_PROBE (measurement, ring form): two reference ticks per wavefront of this launch
+    const bool probed = p.ring && ctx->opt[EMP_OPT_EDGE_CLOCK_PROBE];
+    if (probed) {
+        const size_t waves_total = (size_t)grid.x * grid.y * p.wpb;
         const int grc = grow_buffer(ctx, ctx->edge_probe, waves_total * 4 * sizeof(unsigned long long));
         if (grc) return grc;
         if (const int rc = ctx->edge_probe_done.ensure(ctx, hipEventDisableTiming)) return rc;
         ctx->edge_probe_waves = (long)waves_total;
-        if (const int rc = launch(ctx, "dp_edge", kern_ring, grid, block, lds, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
-                                  cols_per_chunk, (unsigned long long*)ctx->edge_probe.p))
-            return rc;
-        EMP_HIP(ctx, hipEventRecord(ctx->edge_probe_done, ctx->stream));
-        return EMP_OK;
     }
     // EMP_OPT_LANE_EDGE_ORDER (lane mode): this edge kernel starts when the previous call's, on another lane, is done - the
     // lanes' FP64-bound kernels take turns instead of running two or three at a time, and the HBM-bound sweep behind each of them
     // has one of them beside it, not two (measured: include/emplanner.h).  Pure ordering: results do not depend on it.
+    // A probed launch takes no part in it: neither the wait nor the record.
     const int leo = ctx->opt[EMP_OPT_LANE_EDGE_ORDER];
-    const bool ordered = ctx->pipe_mode >= 2 && ctx->active_lane >= 0 && (leo == 1 || (leo == 2 && d.B >= 8192));
+    const bool ordered = !probed && ctx->pipe_mode >= 2 && ctx->active_lane >= 0 && (leo == 1 || (leo == 2 && d.B >= 8192));
     if (ordered && ctx->lane_edge_done) EMP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->lane_edge_done, 0));
     if (const int rc = launch_gate(ctx)) return rc;
-    KernelTimer t(ctx, "dp_edge");       // (open until the event below is recorded)
-    if (ring) {
-        hipLaunchKernelGGL(kern_ring, grid, block, lds, ctx->stream, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
-                           cols_per_chunk, (unsigned long long*)nullptr);
-    } else {
-        hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
-                           cols_per_chunk);
+    {
+        KernelTimer t(ctx, "dp_edge");       // (open until the lane's event is recorded)
+        if (p.ring) {
+            hipLaunchKernelGGL(k.ring, grid, block, p.lds, ctx->stream, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
+                               p.cols_per_chunk, probed ? (unsigned long long*)ctx->edge_probe.p : nullptr);
+        } else {
+            hipLaunchKernelGGL(k.lockstep, grid, block, p.lds, ctx->stream, d, pair_tab, obs_s, obs_l, n_obs, start, start_cost, edge,
+                               p.cols_per_chunk);
+        }
+        EMP_LAUNCH_CHECK(ctx);
+        if (ordered) {
+            emp_ctx::Lane& ln = ctx->lanes[ctx->active_lane];
+            if (const int rc = ln.ev_edge.ensure(ctx, hipEventDisableTiming)) return rc;
+            ctx->lane_edge_done = ln.ev_edge;
+            EMP_HIP(ctx, hipEventRecord(ctx->lane_edge_done, ctx->stream));
+        }
     }
-    EMP_LAUNCH_CHECK(ctx);
-    if (ordered) {
-        emp_ctx::Lane& ln = ctx->lanes[ctx->active_lane];
-        if (const int rc = ln.ev_edge.ensure(ctx, hipEventDisableTiming)) return rc;
-        ctx->lane_edge_done = ln.ev_edge;
-        EMP_HIP(ctx, hipEventRecord(ctx->lane_edge_done, ctx->stream));
+    if (probed) EMP_HIP(ctx, hipEventRecord(ctx->edge_probe_done, ctx->stream));      // behind the kernel (and its timing event)
+    return EMP_OK;
+}
+
+// What a sweep launch carries besides its plan: the dispatch's events and dp_sweep_kernel's arguments.
+struct SweepCall {
+    hipEvent_t start, stop;
+    bool defer;       // the backtrack is left to the densification kernel (BT == false), which reads bt_pre / bt_term
+    const DpDev& d;
+    const double *start_cost, *edge;
+    const int* n_obs;
+    double *rows, *min_cost;
+    int* status;
+    unsigned char* bt_pre;
+    int* bt_term;
+    unsigned long long* probe;
+};
+
+// The one launch of dp_sweep_kernel<R, PD, 1, NT, BT>.  A stream capture records plain launches only; otherwise the dispatch
+// itself stamps c.start and signals c.stop (hipExtLaunchKernelGGL: no marker packets around the roofline kernel).
+template <int R, int PD, bool NT>
+static int launch_sweep(emp_ctx* ctx, const SweepPlan& p, const SweepCall& c) {
+    if (p.row_inst != R || p.pd != PD || p.nt != NT) return fail(ctx, EMP_ERR_INVALID, "internal: sweep instantiation differs from its plan");
+    const auto kern = c.defer ? dp_sweep_kernel<R, PD, 1, NT, false> : dp_sweep_kernel<R, PD, 1, NT, true>;
+    if (const int rc = set_lds(ctx, kern, p.lds, "too many columns for the predecessor table in LDS")) return rc;
+    if (const int rc = launch_gate(ctx)) return rc;
+    if (ctx->cycle_graph.capturing) {
+        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, ctx->stream, c.d, c.start_cost, c.edge, c.n_obs, c.rows, c.min_cost,
+                           c.status, c.bt_pre, c.bt_term, c.probe);
+    } else {
+        hipExtLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, ctx->stream, c.start, c.stop, 0, c.d, c.start_cost, c.edge, c.n_obs,
+                              c.rows, c.min_cost, c.status, c.bt_pre, c.bt_term, c.probe);
     }
     return EMP_OK;
 }
@@ -271,12 +237,14 @@ static int dev_dp_edge(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
 static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, const double* edge,
                         const int* n_obs, double* rows, double* min_cost, int* status, CycleSched* cs) {
     if (d.B == 0) return EMP_OK;
-    if (wide(d)) {          // more than 32 rows: one block per scene, predecessors in device memory
+    const SweepPlan p = plan_sweep(d);
+    if (const int rc = plan_refused(ctx, p.error)) return rc;
+    if (dp_wide(d)) {          // more than 32 rows: one block per scene, predecessors in device memory
         emp_ctx::Buf& pre = ctx->named["dp_wide_pre_" + std::to_string(ctx->active_lane)];
         const int grc = grow_buffer(ctx, pre, (size_t)d.B * d.col * d.row * sizeof(unsigned short));
         if (grc) return grc;
-        return launch(ctx, "dp_sweep", dp_sweep_wide_kernel, dim3(d.B), dim3(std::min(((d.row + 63) / 64) * 64, 256)),
-                      2 * (size_t)d.row * sizeof(double), d, start_cost, edge, n_obs, (unsigned short*)pre.p, rows, min_cost, status);
+        return launch(ctx, "dp_sweep", dp_sweep_wide_kernel, dim3(p.grid), dim3(p.block), p.lds, d, start_cost, edge, n_obs,
+                      (unsigned short*)pre.p, rows, min_cost, status);
     }
     // EMP_OPT_SWEEP_EXCLUSIVE (staged pipeline): the sweep starts once the previous call's back stage is done
     if (cs && cs->sweep_wait) {
@@ -294,73 +262,23 @@ static int dev_dp_sweep(emp_ctx* ctx, const DpDev& d, const double* start_cost, 
         ctx->probe_launches++;
     }
     KernelTimer t(ctx, "dp_sweep", true);   // the roofline kernel: events stamped by the dispatch itself
-    unsigned char* const bt_pre = cs ? cs->bt_pre : nullptr;
-    int* const bt_term = cs ? cs->bt_term : nullptr;
-    bool deferred = false;
-    hipEvent_t stop_ev = t.stop ? t.stop : cs ? cs->front_stop : nullptr;
-#define EMP_SWEEP(R, PD, WPB) EMP_SWEEP_NT(R, PD, WPB, false)
-#define EMP_SWEEP_NT(R, PD, WPB, NT)                                                                        \
-    do {                                                                                                    \
-        const size_t lds = (size_t)(WPB) * (d.col * 64 + 64 * sizeof(double));                              \
-        EMP_REQUIRE(ctx, lds <= 160 * 1024, "too many columns for the predecessor table in LDS");           \
-        const bool defer = (R) > 0 && bt_pre && bt_term;                                                    \
-        if (lds > 48 * 1024)                                                                                \
-            EMP_HIP(ctx, hipFuncSetAttribute(defer ? (const void*)dp_sweep_kernel<R, PD, WPB, NT, false>    \
-                                                   : (const void*)dp_sweep_kernel<R, PD, WPB, NT, true>,    \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
-        if (const int rc = launch_gate(ctx)) return rc;                                                     \
-        if (ctx->cycle_graph.capturing && defer) {      /* a stream capture records plain launches only */  \
-            hipLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT, false>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
-                               ctx->stream, d, start_cost, edge, n_obs, rows, min_cost, status, bt_pre, bt_term, probe); \
-            deferred = true;                                                                                \
-        } else if (ctx->cycle_graph.capturing) {                                                            \
-            hipLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
-                               ctx->stream, d, start_cost, edge, n_obs, rows, min_cost, status,             \
-                               (unsigned char*)nullptr, (int*)nullptr, probe);                              \
-        } else if (defer) {                                                                                 \
-            hipExtLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT, false>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
-                                  ctx->stream, t.start, stop_ev, 0, d, start_cost, edge, n_obs, rows, min_cost, status, \
-                                  bt_pre, bt_term, probe);                                                  \
-            deferred = true;                                                                                \
-        } else {                                                                                            \
-            hipExtLaunchKernelGGL((dp_sweep_kernel<R, PD, WPB, NT>), dim3((d.tiles + (WPB) - 1) / (WPB)), dim3(64 * (WPB)), lds, \
-                                  ctx->stream, t.start, stop_ev, 0, d, start_cost, edge, n_obs, rows, min_cost, status, \
-                                  (unsigned char*)nullptr, (int*)nullptr, probe);                           \
-        }                                                                                                   \
-    } while (0)
-    // Ring depth PD (columns in flight per wavefront), measured at 4096 scenes: 2 is best for rows 5..12 (row 9:
-    // 20.4 us against 23.2 at PD = 8, 21.4 at PD = 1), 3 for the 21-row lattice; nontemporal loads change nothing.
-    // Load policy, measured on the 40x9 lattice (sweep alone, TB/s of algorithmic bytes; plain / nontemporal): 4096 scenes
-    // (105 MB tensor) 5.45 / 4.74, 8192 (226 MB) 6.47 / 6.21, 12288 (331 MB) 5.04 / 6.45, 16384 4.47 / 6.40, 32768 (883 MB)
-    // 4.52 / 6.03.  A tensor that fits the 256 MiB Infinity Cache is still there when the sweep follows the edge kernel
-    // that wrote it, and plain loads hit it; a larger one streams from HBM, where plain loads also drag every line through
-    // the cache hierarchy they will never hit again: nontemporal from 256 MiB on.
-    const bool nt = tiled_elems(d) * sizeof(double) > ((size_t)256 << 20);
-#define EMP_SWEEP_AUTO(R, PD)                      \
-    do {                                           \
-        if (nt) EMP_SWEEP_NT(R, PD, 1, true);      \
-        else EMP_SWEEP_NT(R, PD, 1, false);        \
-    } while (0)
-    switch (d.row) {
-        case 5: EMP_SWEEP_AUTO(5, 2); break;
-        case 9:
-            // (round 5: three columns in flight instead of two.  Alone the two are within noise of each other - 0.72-0.77 of the
-            // peak either way; beside the previous batch's Cartesian tail, where the sweep runs since EMP_OPT_SWEEP_EXCLUSIVE
-            // defaults to 0, the deeper ring holds 0.67-0.68 where the shallow one holds 0.65: six A/B pairs, tools/step_ab.sh)
-            // (ring depths 4 and 8 and the other load policy were option values until round 6: HISTORY.md 3.2 has their numbers)
-            if (nt) EMP_SWEEP_NT(9, 2, 1, true);         // from DRAM (32768 scenes) the shallow ring keeps 0.697 against 0.692
-            else EMP_SWEEP_NT(9, 3, 1, false);
-            break;
-        case 12: EMP_SWEEP_AUTO(12, 2); break;
-        case 21: EMP_SWEEP_AUTO(21, 3); break;
-        default: EMP_SWEEP(0, 1, 1); break;
+    const hipEvent_t stop_ev = t.stop ? t.stop : cs ? cs->front_stop : nullptr;
+    // the caller's two buffers are used by the compiled row counts only
+    const bool defer = p.row_inst > 0 && cs && cs->bt_pre && cs->bt_term;
+    const SweepCall c{t.start, stop_ev, defer, d, start_cost, edge, n_obs, rows, min_cost, status,
+                      defer ? cs->bt_pre : nullptr, defer ? cs->bt_term : nullptr, probe};
+    int lrc;
+    switch (p.row_inst) {          // the plan's (row_inst, pd, nt) become template arguments here
+        case 5: lrc = p.nt ? launch_sweep<5, 2, true>(ctx, p, c) : launch_sweep<5, 2, false>(ctx, p, c); break;
+        case 9: lrc = p.nt ? launch_sweep<9, 2, true>(ctx, p, c) : launch_sweep<9, 3, false>(ctx, p, c); break;
+        case 12: lrc = p.nt ? launch_sweep<12, 2, true>(ctx, p, c) : launch_sweep<12, 2, false>(ctx, p, c); break;
+        case 21: lrc = p.nt ? launch_sweep<21, 3, true>(ctx, p, c) : launch_sweep<21, 3, false>(ctx, p, c); break;
+        default: lrc = launch_sweep<0, 1, false>(ctx, p, c); break;
     }
-#undef EMP_SWEEP_AUTO
-#undef EMP_SWEEP
-#undef EMP_SWEEP_NT
+    if (lrc) return lrc;
     if (cs) {
         cs->front_attached = stop_ev;
-        cs->bt_deferred = deferred;
+        cs->bt_deferred = defer;
     }
     EMP_LAUNCH_CHECK(ctx);
     if (probe) {
@@ -390,12 +308,11 @@ static int dev_dp_enrich(emp_ctx* ctx, const DpDev& d, const double* rows, const
                          const unsigned char* pre = nullptr, const int* term = nullptr, const int* n_obs = nullptr,
                          double* rows_out = nullptr) {
     if (d.B == 0) return EMP_OK;
-    const size_t lds = (size_t)d.col * sizeof(double) + (pre ? (size_t)d.col * d.row : 0);      // the rows [col], + the predecessor bytes
-    EMP_REQUIRE(ctx, lds <= 160 * 1024, "too many columns for the densification kernel's predecessor table in LDS");
-    if (lds > 48 * 1024)
-        EMP_HIP(ctx, hipFuncSetAttribute((const void*)dp_enrich_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const EnrichPlan p = plan_enrich(d, pre != nullptr);
+    if (const int rc = plan_refused(ctx, p.error)) return rc;
+    if (const int rc = set_lds(ctx, dp_enrich_wave_kernel, p.lds, "too many columns for the densification kernel's predecessor table in LDS")) return rc;
     KernelTimer t(ctx, "dp_enrich");
-    return launch_attaching(ctx, cs, t.stop != nullptr, dp_enrich_wave_kernel, dim3(d.B), dim3(64), lds, d, rows, start, max_pts, path_s,
+    return launch_attaching(ctx, cs, t.stop != nullptr, dp_enrich_wave_kernel, dim3(d.B), dim3(64), p.lds, d, rows, start, max_pts, path_s,
                             path_l, path_len, status, or_status, pre, term, n_obs, rows_out);
 }
 
@@ -417,33 +334,16 @@ static int dp_edge_tensor(emp_ctx* ctx, const DpDev& d, double** edge, double** 
 static int dev_dp_fused(emp_ctx* ctx, const DpDev& d, const double* obs_s, const double* obs_l, const int* n_obs,
                         const double* start, double* rows, double* min_cost, int* status) {
     if (d.B == 0) return EMP_OK;
+    const FusedPlan p = plan_fused(d);
+    if (const int rc = plan_refused(ctx, p.error)) return rc;
     const double* pair_tab = nullptr;
-    int rc = dp_pair_table(ctx, d, &pair_tab);
-    if (rc) return rc;
-    // columns per chunk: 4 (one per wavefront) while two buffers of them leave room for three blocks per CU, fewer on wide
-    // lattices whose pair table fills the LDS
-    int nc = 4;
-    while (nc > 1 && fused_lds(d.row, d.col, d.S, d.max_obs, nc).total > 53 * 1024) nc /= 2;
-    const size_t lds = (size_t)fused_lds(d.row, d.col, d.S, d.max_obs, nc).total;
-    EMP_REQUIRE(ctx, lds <= 160 * 1024, "lattice too wide for the fused DP kernel's LDS working set");
+    if (const int rc = dp_pair_table(ctx, d, &pair_tab)) return rc;
+    const int r = dp_row_inst(d.row);
+    const auto kern = r == 5 ? dp_fused_kernel<5> : r == 9 ? dp_fused_kernel<9> : r == 12 ? dp_fused_kernel<12> : r == 21 ? dp_fused_kernel<21> : dp_fused_kernel<0>;
     KernelTimer t(ctx, "dp_fused");
-#define EMP_FUSED(R)                                                                                                  \
-    do {                                                                                                              \
-        if (lds > 48 * 1024)                                                                                          \
-            EMP_HIP(ctx, hipFuncSetAttribute((const void*)dp_fused_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                             (int)lds));                                                              \
-        if (const int rc_ = launch_gate(ctx)) return rc_;                                                             \
-        hipLaunchKernelGGL(dp_fused_kernel<R>, dim3(d.tiles), dim3(256), lds, ctx->stream, d, pair_tab, obs_s, obs_l,   \
-                           n_obs, start, rows, min_cost, status, nc);                                                 \
-    } while (0)
-    switch (d.row) {
-        case 5: EMP_FUSED(5); break;
-        case 9: EMP_FUSED(9); break;
-        case 12: EMP_FUSED(12); break;
-        case 21: EMP_FUSED(21); break;
-        default: EMP_FUSED(0); break;
-    }
-#undef EMP_FUSED
+    if (const int rc = set_lds(ctx, kern, p.lds, "lattice too wide for the fused DP kernel's LDS working set")) return rc;
+    if (const int rc = launch_gate(ctx)) return rc;
+    hipLaunchKernelGGL(kern, dim3(d.tiles), dim3(256), p.lds, ctx->stream, d, pair_tab, obs_s, obs_l, n_obs, start, rows, min_cost, status, p.nc);
     EMP_LAUNCH_CHECK(ctx);
     return EMP_OK;
 }
@@ -453,7 +353,7 @@ static int dev_dp_plan(emp_ctx* ctx, const DpDev& d, const double* obs_s, const 
                        const double* start, emp_dp_mode mode, double* rows, double* min_cost, int* status, CycleSched* cs) {
     if (d.B == 0) return EMP_OK;
     // the single-kernel form lives on the tiled layout: lattices wider than 32 rows take the two-kernel form either way
-    if (mode == EMP_DP_FUSED && !wide(d)) return dev_dp_fused(ctx, d, obs_s, obs_l, n_obs, start, rows, min_cost, status);
+    if (mode == EMP_DP_FUSED && !dp_wide(d)) return dev_dp_fused(ctx, d, obs_s, obs_l, n_obs, start, rows, min_cost, status);
     double *edge, *start_cost;
     int rc = dp_edge_tensor(ctx, d, &edge, &start_cost);
     if (rc) return rc;
@@ -920,10 +820,7 @@ int emp_kernel_samples(emp_ctx* ctx, const char* kernel, double* ms, int32_t cap
 // ---- DP ----------------------------------------------------------------------------------
 uint64_t emp_edge_tensor_elems(const emp_dp_params* p, int32_t B, emp_edge_layout layout) {
     if (!p || p->row < 1 || p->row > emp::kMaxWideRow || p->col < 1 || B < 0) return 0;
-    if (layout == EMP_EDGE_CANONICAL || p->row > emp::kMaxTiledRow) return (uint64_t)B * (p->col - 1) * p->row * p->row;
-    const int S = 64 / p->row;
-    const uint64_t tiles = ((uint64_t)B + S - 1) / S;
-    return tiles * (uint64_t)(p->col - 1) * p->row * 64;
+    return (uint64_t)emp::edge_tensor_elems(p->row, p->col, B, layout != EMP_EDGE_CANONICAL);
 }
 
 int emp_dp_edge_costs(emp_ctx* ctx, const emp_dp_params* p, int32_t B, int32_t max_obs, const double* obs_s,
@@ -1040,21 +937,10 @@ static int dev_project(emp_ctx* ctx, int B, int max_ref, int max_obs, const doub
                        int* n_obs_out = nullptr) {
     if (B == 0) return EMP_OK;
     const size_t lds = (size_t)7 * max_ref * sizeof(double);
-    EMP_REQUIRE(ctx, lds <= 160 * 1024, "reference line too long for the LDS-resident projection kernel");
-    if (lds > 48 * 1024)
-        EMP_HIP(ctx, hipFuncSetAttribute((const void*)frenet_project_wave_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (const int rc = set_lds(ctx, frenet_project_wave_kernel, lds, "reference line too long for the LDS-resident projection kernel")) return rc;
     return launch(ctx, "project", frenet_project_wave_kernel, dim3(B), dim3(64), lds, B, max_ref, max_obs, ref_line, n_ref, origin_xy,
                   start_xy, start_v, start_a, obs_xy, n_obs, s_map, obs_s, obs_l, begin_sl, start, obs_cap < 0 ? max_obs : obs_cap, dyn,
                   n_obs_out);
-}
-
-template <typename K>
-static int set_lds(emp_ctx* ctx, K kernel, size_t bytes) {
-    EMP_REQUIRE(ctx, bytes <= 160 * 1024, "problem too large for the LDS-resident QP solver");
-    if (bytes > 48 * 1024)
-        EMP_HIP(ctx, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return EMP_OK;
 }
 
 // smooth_reference_line, one wavefront per scene (emp_reference_line, and the front end of emp_plan_cycle)
@@ -1065,7 +951,7 @@ static int dev_reference_line(emp_ctx* ctx, const emp_smooth_params* sp, int B, 
     const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
     const size_t lds = (2 * (size_t)kRefLinePoints + 2 * (size_t)BoxRangeQp::words(kRefLinePoints, kRefLinePoints) +
                         (size_t)kRefLinePoints) * sizeof(double);
-    if (const int rc = set_lds(ctx, reference_line_wave_kernel, lds)) return rc;
+    if (const int rc = set_lds(ctx, reference_line_wave_kernel, lds, kQpTooLarge)) return rc;
     return launch(ctx, "reference_line", reference_line_wave_kernel, dim3(B), dim3(64), lds, B, max_global, sx, sy, args...);
 }
 
@@ -1091,18 +977,18 @@ static int dev_cycle_qp(emp_ctx* ctx, int B, int max_pts, int max_obs, const QpD
                                                                                                 : cycle_qp_group_words<16, 4>(cap, max_obs);
         const size_t per_wave = (size_t)(64 / gp) * words * sizeof(double) + EMP_QP_LDS_PAD;
         auto kern = cap <= 26 ? cycle_qp_rows_kernel<8, 3> : cap <= 34 ? cycle_qp_rows_kernel<8, 4> : cycle_qp_rows_kernel<16, 4>;
-        if ((rc = set_lds(ctx, kern, per_wave))) return rc;
+        if ((rc = set_lds(ctx, kern, per_wave, kQpTooLarge))) return rc;
         const int spw = 64 / gp;
         return launch_attaching(ctx, cs, t.stop != nullptr, kern, dim3((B + spw - 1) / spw), dim3(64), per_wave, B, max_pts,
                                 max_obs, cap, Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
     } else if (cap <= 34) {                                           // N, ns <= 32: two scenes per wavefront
         const size_t per_pair = 2 * ((size_t)5 * cap + 4 * (size_t)max_obs + path_qp_words_pair()) * sizeof(double);
         auto kern = cycle_qp_wave_kernel<32>;
-        if ((rc = set_lds(ctx, kern, per_pair))) return rc;
+        if ((rc = set_lds(ctx, kern, per_pair, kQpTooLarge))) return rc;
         return launch_attaching(ctx, cs, t.stop != nullptr, kern, dim3((B + 1) / 2), dim3(64), per_pair, B, max_pts,
                                 max_obs, cap, Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
     }
-    if ((rc = set_lds(ctx, cycle_qp_wave_kernel<64>, per_group))) return rc;
+    if ((rc = set_lds(ctx, cycle_qp_wave_kernel<64>, per_group, kQpTooLarge))) return rc;
     return launch_attaching(ctx, cs, t.stop != nullptr, cycle_qp_wave_kernel<64>, dim3(B), dim3(64), per_group, B, max_pts, max_obs, cap,
                             Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
 }
@@ -1123,13 +1009,13 @@ static int dev_cycle_cartesian(emp_ctx* ctx, int B, int max_ref, int max_pts, in
         const int spw = cap <= 32 ? 4 : 2;
         const size_t lds4 = ((size_t)spw * ((size_t)max_ref + 5 * (size_t)cap) + 2 * (size_t)BoxRangeQp::words(cap, cap)) * sizeof(double);
         auto k4 = cap <= 24 ? cycle_cartesian_rows_kernel<8, 3> : cap <= 32 ? cycle_cartesian_rows_kernel<8, 4> : cycle_cartesian_rows_kernel<16, 4>;
-        if (const int rc = set_lds(ctx, k4, lds4)) return rc;
+        if (const int rc = set_lds(ctx, k4, lds4, kQpTooLarge)) return rc;
         const int force_fb = ctx->opt[EMP_OPT_SMOOTH_FORCE_FALLBACK] ? 1 : 0;                        // test hook
         return launch(ctx, "to_cartesian", k4, dim3((B + spw - 1) / spw), dim3(64), lds4, B, max_ref, max_pts, cap, sx, sy, ref_line,
                       s_map, n_ref, begin_sl, path_s, path_l, path_len, traj, traj_len, status, force_fb);
     }
     auto kern = cap > 32 ? cycle_cartesian_wave_kernel_wide : cycle_cartesian_wave_kernel_narrow;
-    if (const int rc = set_lds(ctx, kern, lds)) return rc;
+    if (const int rc = set_lds(ctx, kern, lds, kQpTooLarge)) return rc;
     return launch(ctx, "to_cartesian", kern, dim3(B), dim3(64), lds, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref,
                   begin_sl, path_s, path_l, path_len, traj, traj_len, status);
 }
@@ -1488,7 +1374,7 @@ int emp_path_qp(emp_ctx* ctx, const emp_qp_params* q, int32_t B, int32_t max_pts
     if (const int rc = st.ready()) return rc;
     if (B) {
         const size_t lds = (size_t)path_qp_words(max_pts) * sizeof(double);
-        if (const int rc = set_lds(ctx, path_qp_wave_kernel, lds)) return rc;
+        if (const int rc = set_lds(ctx, path_qp_wave_kernel, lds, kQpTooLarge)) return rc;
         if (const int rc = launch(ctx, "path_qp", path_qp_wave_kernel, dim3(B), dim3(64), lds, B, max_pts, max_pts, make_qp_dev(q),
                                   d_lo, d_hi, d_np, d_s3, d_l, d_dl, d_ddl, d_it, d_st))
             return rc;
@@ -1513,7 +1399,7 @@ int emp_smooth_line(emp_ctx* ctx, const emp_smooth_params* sp, int32_t B, int32_
         const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
         const size_t lds = (2 * (size_t)BoxRangeQp::words(max_pts, max_pts) + (size_t)max_pts) * sizeof(double);
         auto kern = max_pts > 32 ? smooth_wave_kernel<true> : smooth_wave_kernel<false>;
-        if (const int rc = set_lds(ctx, kern, lds)) return rc;
+        if (const int rc = set_lds(ctx, kern, lds, kQpTooLarge)) return rc;
         if (const int rc = launch(ctx, "smooth", kern, dim3(B), dim3(64), lds, B, max_pts, max_pts, sx, sy, d_xy, d_np, d_out, d_it, d_st))
             return rc;
     }
@@ -1692,7 +1578,7 @@ static int plan_cycle_impl(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_pa
         return rc;
     if (has_dyn) d_no = d_ntot;                            // downstream stages see the projected + virtual obstacles
     CycleSched cs;
-    const bool two_kernel = mode == EMP_DP_TWO_KERNEL && !wide(d);
+    const bool two_kernel = mode == EMP_DP_TWO_KERNEL && !dp_wide(d);
     // the sweep may leave the backtrack to the densification kernel (emp_dp_kernels.h, BT == false): two temporaries for it
     if (two_kernel) {
         cs.bt_pre = st.tmp<unsigned char>((size_t)d.tiles * d.col * 64);

@@ -19,31 +19,9 @@
 #include <hip/hip_runtime.h>
 
 #include "emp_core.h"
+#include "emp_dp_launch.h"     // DpDev, the pair table's fields, the LDS carve-ups host and device share, the launch plans
 
 namespace emp {
-
-struct DpDev {
-    int row, col;
-    int S;       // scenes per wavefront tile = 64 / row
-    int tiles;   // ceil(B / S)
-    int B;
-    int max_obs;
-    double sample_s, sample_l, res;
-    double w_coll, w0, w1, w2, w_ref;
-};
-
-// Pair-table fields behind the kSamples lateral samples (round 5: the three quintic coefficients gave way to ONE jerk
-// weight - see kF_JERK - which takes the table from 17 to 15 fields: 53 instead of 60 KB of LDS at 21 rows)
-constexpr int kF_JERK = kSamples + 0;     // w2 (h h), h = l_cur - l_pre: the quirked jerk term of the edge is this times F(s0)
-constexpr int kF_BASE = kSamples + 1;     // w0 sum dl^2 + w1 sum ddl^2
-constexpr int kF_REF = kSamples + 2;      // w_ref sum l^2
-constexpr int kF_LLO = kSamples + 3;      // min(l_pre, l_cur)
-constexpr int kF_LHI = kSamples + 4;      // max(l_pre, l_cur)
-constexpr int kTableFields = kSamples + 5;
-// behind the fields: the kSamples sample offsets t_n, their two moments (emp_core.h sample_moments) and the UNIT quintic's
-// a3, a4, a5 (the coefficients of the neighbour edge with h = 1)
-constexpr int kUnitQuintic = 3;
-constexpr int kTableTail = kSamples + kSampleMoments + kUnitQuintic;
 
 // The quirked jerk sum of a NEIGHBOUR edge, factorised (round 5).  A neighbour edge starts with dl = ddl = 0, so its
 // shifted coefficients are h times the unit quintic's (a3, a4, a5) = h (u3, u4, u5), h = l_cur - l_pre; the absolute-s
@@ -358,20 +336,7 @@ __global__ __launch_bounds__(1024, EMP_EDGE_WAVES) void dp_edge_kernel(DpDev P, 
 // Edges without an obstacle in reach are stored from the dense part (coalesced, the other lanes masked); ring entries are
 // stored by the lane that scanned them, 8 bytes each - the entries of a round are neighbours in (j, k, lane) order, so the
 // stores of a round still fall into two or three 512-byte rows of the tiled tensor.
-// Capacity: a ring never holds more than 63 left-over + 64 pushed entries = 127 < kRingSlots.
-constexpr int kRingSlots = 128;
-
-// Per wavefront, in LDS: code[2][kRingSlots] (32 bits an entry: column j << 17 | source row k << 12 | obstacle m << 6 | owner
-// lane - the one-obstacle ring's entry IS its obstacle, it has no mask) and, for the several-obstacle ring only, one mask per
-// slot as wide as the scene's obstacle count needs (1, 2, 4 or 8 bytes: ascending bit = ascending m).  The edge's smoothness
-// term is recomputed by the lane that pops the entry.  LDS is what decides how many edge blocks sit beside the previous batch's
-// path-QP wavefronts in the staged step (allocated in 1280-byte granules, 128 a CU): the 40 x 9 lattice's two-wavefront block
-// is 14.4 KB = 12 granules, six of them fit beside two path-QP wavefronts (profiles/r05_edge/README.md 8).
-EMP_HD constexpr int edge_ring_mask_bytes(int max_obs) { return max_obs <= 8 ? 1 : max_obs <= 16 ? 2 : max_obs <= 32 ? 4 : 8; }
-EMP_HD constexpr int edge_ring_bytes(int max_obs) { return 2 * kRingSlots * 4 + kRingSlots * edge_ring_mask_bytes(max_obs); }
-// the code's fields: 32 rows (5 bits of k), 64 obstacles, 64 lanes, columns below 2^15
-constexpr int kRingMaxCol = 32767;
-
+// (kRingSlots, the ring's bytes per wavefront and kRingMaxCol: emp_dp_launch.h)
 #ifndef EMP_EDGE_RING_BOUNDS
 #define EMP_EDGE_RING_BOUNDS __launch_bounds__(1024, EMP_EDGE_WAVES)
 #endif
@@ -847,8 +812,6 @@ __global__ __launch_bounds__(64 * WPB) void dp_sweep_kernel(DpDev P, const doubl
 // bit-identical to what the tiled kernels would compute - with the edge tensor in the canonical layout
 // [B][col-1][i][k] (k fastest): correctness for every `row` up to kMaxWideRow, not speed (the reference's own
 // default is 12 rows; BASELINE's widest lattice has 21).
-constexpr int kMaxWideRow = 1024;      // (round 5: predecessors of the wide sweep are 16-bit; until round 4 a byte, 256 rows.  The pair
-                                       // table is 15 row^2 doubles - 126 MB at 1024 rows - and the tensor (col - 1) row^2 doubles per scene)
 
 // grid = (B, max(col - 1, 1)), block = row rounded up to a wavefront (<= 256 threads): thread i costs the `row` edges
 // from column j-1 into row i of column j; pair table, sample offsets and obstacles are read from device memory.
@@ -963,22 +926,7 @@ __global__ __launch_bounds__(256) void dp_sweep_wide_kernel(DpDev P, const doubl
 // lowest-k predecessor, first-minimum terminal), so rows, min_cost and status are bit-identical to the two-kernel
 // path.  Trade: no 8 E bytes per scene written and read back, against one block per tile - 586 blocks at 4096
 // scenes 40x9, two or three per CU instead of the edge kernel's sixteen wavefronts per CU (HISTORY.md section 3.2).
-struct FusedLds {
-    int off_smp, off_obs_s, off_obs_l, off_buf, off_front, off_pre, off_ctr, total;   // bytes
-};
-__host__ __device__ inline FusedLds fused_lds(int row, int col, int S, int max_obs, int nc) {
-    FusedLds L;
-    int o = kTableFields * row * row * 8;
-    L.off_smp = o;   o += kTableTail * 8;
-    L.off_obs_s = o; o += S * max_obs * 8;
-    L.off_obs_l = o; o += S * max_obs * 8;
-    L.off_buf = o;   o += 2 * nc * row * 64 * 8;
-    L.off_front = o; o += 64 * 8;
-    L.off_pre = o;   o += ((col * 64 + 7) / 8) * 8;
-    L.off_ctr = o;   o += 8;
-    L.total = o;
-    return L;
-}
+// (FusedLds, fused_lds: the kernel's LDS carve-up, emp_dp_launch.h)
 
 template <int ROW>
 __global__ __launch_bounds__(256, 4) void dp_fused_kernel(DpDev P, const double* __restrict__ pair_tab,

@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "..", "..", "emplanner_carla_amd", "csrc")
 
 
 def load():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("emp_core.h", "emp_frenet_core.h", "emp_qp_core.h", "emp_st_core.h", "emp_st_backend_core.h")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("emp_core.h", "emp_dp_launch.h", "emp_frenet_core.h", "emp_qp_core.h", "emp_st_core.h", "emp_st_backend_core.h")]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", SRC, "-o", OUT],
@@ -53,4 +53,16 @@ def load():
     lib.hc_stb_increase_points.argtypes = [p] * 8
     lib.hc_stb_np_interp.restype = d
     lib.hc_stb_np_interp.argtypes = [p, p, i, d]
+    lib.hc_plan_edge.restype = C.c_char_p
+    lib.hc_plan_edge.argtypes = [i] * 7 + [p]
+    lib.hc_plan_sweep.restype = C.c_char_p
+    lib.hc_plan_sweep.argtypes = [i] * 4 + [p]
+    lib.hc_plan_fused.restype = C.c_char_p
+    lib.hc_plan_fused.argtypes = [i] * 4 + [p]
+    lib.hc_plan_enrich.restype = C.c_char_p
+    lib.hc_plan_enrich.argtypes = [i] * 5 + [p]
+    lib.hc_edge_tensor_elems.restype = C.c_longlong
+    lib.hc_edge_tensor_elems.argtypes = [i] * 4
+    lib.hc_edge_ring_constants.restype = None
+    lib.hc_edge_ring_constants.argtypes = [i, p]
     return lib

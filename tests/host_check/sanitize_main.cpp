@@ -1,6 +1,6 @@
 // sanitize_main.cpp - the host-side logic of the library (the scalar cores the kernels are built from: emp_core.h,
-// emp_frenet_core.h, emp_qp_core.h, emp_st_core.h, emp_st_backend_core.h, reached through host_check.cpp's entry
-// points) driven with deterministic random and hostile inputs under -fsanitize=address,undefined.  Test tool only:
+// emp_frenet_core.h, emp_qp_core.h, emp_st_core.h, emp_st_backend_core.h, and the launch plans of emp_dp_launch.h, reached
+// through host_check.cpp's entry points) driven with deterministic random and hostile inputs under -fsanitize=address,undefined.  Test tool only:
 // tests/test_host_logic.py builds and runs it; any sanitizer report makes it exit non-zero.
 //
 // Inputs: sizes at and beside every compile-time capacity (0, 1, 2, 3, 31..34, 63..65, 255, 256, 257), empty and
@@ -30,6 +30,11 @@ int hc_stb_speed_qp(const double*, const double*, double, double, const double*,
                     const double*, double*, double*, double*, double*, int*);
 int hc_stb_increase_points(const double*, const double*, const double*, const double*, double*, double*, double*, double*);
 double hc_stb_np_interp(const double*, const double*, int, double);
+const char* hc_plan_edge(int, int, int, int, int, int, int, long long*);
+const char* hc_plan_sweep(int, int, int, int, long long*);
+const char* hc_plan_fused(int, int, int, int, long long*);
+const char* hc_plan_enrich(int, int, int, int, int, long long*);
+long long hc_edge_tensor_elems(int, int, int, int);
 }
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ull;
@@ -140,6 +145,21 @@ int main() {
         for (int q = 0; q < 50; ++q) sink += hc_stb_np_interp(idx2s, kap, plen, hostile(uni(-5, 220))) > 0;
         calls += 5;
     }
+    // ---- launch geometry of the lattice-DP kernels (emp_dp_launch.h): the size_t and int arithmetic of every plan over the
+    // grid tests/golden/dp_launch_plans.npz pins, and at the API's own limits (4080 columns, 2^31 - 1 scenes)
+    for (int row : {1, 5, 9, 12, 21, 32, 33, 64, 1024})
+        for (int col : {1, 2, 9, 21, 40, 120, 4080})
+            for (int B : {1, 7, 64, 4096, 32768, 2147483647})
+                for (int mo : {0, 8, 32, 33, 64, 65, 254, 256}) {
+                    long long out[10];
+                    for (int v = 0; v < 12; ++v) sink += hc_plan_edge(row, col, B, mo, v & 1, (v >> 1) & 1, (v >> 2) * 128, out) != nullptr;
+                    sink += hc_plan_sweep(row, col, B, mo, out) != nullptr;
+                    sink += hc_plan_fused(row, col, B, mo, out) != nullptr;
+                    sink += hc_plan_enrich(row, col, B, mo, 0, out) != nullptr;
+                    sink += hc_plan_enrich(row, col, B, mo, 1, out) != nullptr;
+                    sink += (double)(hc_edge_tensor_elems(row, col, B, 0) & 1) + (double)(hc_edge_tensor_elems(row, col, B, 1) & 1);
+                    calls += 18;
+                }
     std::printf("sanitize_main: %ld calls, checksum %d\n", calls, (int)std::fmod(std::fabs(sink), 1000.0));
     return 0;
 }

@@ -402,3 +402,100 @@ def test_projection_dot_product_rounds_like_numpy(hc):
     if (dots == plain).all():
         pytest.skip("this host's numpy rounds 2-vector dot products the plain way")
     np.testing.assert_array_equal(out, dots)
+
+
+# ---- launch geometry of the lattice-DP kernels (csrc/emp_dp_launch.h) --------------------------------------------------
+def _dp_plan_row(hc, row, col, B, max_obs, tiled, form, block, messages):
+    """One row of tests/golden/dp_launch_plans.npz, recomputed: the inputs, then every plan (refusal as 1 + its index in
+    `messages`, the plan's fields zero beside it)."""
+    code = lambda m: 0 if m is None else 1 + messages.index(m.decode())
+    e, s, f, n = (np.zeros(k, dtype=np.int64) for k in (10, 6, 2, 1))
+    out = [row, col, B, max_obs, tiled, form, block]
+    out += [code(hc.hc_plan_edge(row, col, B, max_obs, tiled, form, block, e.ctypes.data)), *e]
+    out += [code(hc.hc_plan_sweep(row, col, B, max_obs, s.ctypes.data)), *s]
+    out += [code(hc.hc_plan_fused(row, col, B, max_obs, f.ctypes.data)), *f]
+    for pre in (0, 1):
+        out += [code(hc.hc_plan_enrich(row, col, B, max_obs, pre, n.ctypes.data)), n[0]]
+    out.append(hc.hc_edge_tensor_elems(row, col, B, tiled))
+    return out
+
+
+def test_dp_launch_plans_match_the_pinned_table(hc):
+    """Every launch plan of emp_dp_launch.h (edge-cost, sweep, fused, densification, and the edge tensor's size) on the
+    25 920 points of tests/golden/dp_launch_plans.npz: row {1, 5, 9, 12, 21, 32, 33, 64, 1024} x col {1, 2, 9, 21, 40,
+    120} x B {1, 7, 64, 4096, 32768} x max_obs {0, 8, 32, 33, 64, 65, 254, 256} x both layouts x edge_form {0, 1} x
+    edge_block {0, 128, 256}; all fields compared, refusals with their text.  The table holds what the launchers computed
+    inline before the plans existed (commit b1fe952: those lines, unchanged, behind a stub context): the numbers were tuned
+    on the GPU, and no parity test notices a slip in them - the kernels are bit-identical for any geometry."""
+    g = load_golden("dp_launch_plans.npz")
+    plans, messages = g["plans"], [str(m) for m in g["messages"]]
+    assert plans.shape == (9 * 6 * 5 * 8 * 2 * 2 * 3, len(g["columns"]))
+    got = np.array([_dp_plan_row(hc, *(int(v) for v in p[:7]), messages) for p in plans], dtype=np.int64)
+    bad = np.nonzero((got != plans).any(axis=1))[0]
+    assert bad.size == 0, (f"{bad.size} points differ; first: inputs {plans[bad[0], :7].tolist()} "
+                           f"fields {[str(c) for c in g['columns'][got[bad[0]] != plans[bad[0]]]]}")
+
+
+def test_dp_edge_plan_invariants(hc):
+    """What every good edge-cost plan on the pinned grid must satisfy, whatever the tuning: the block fits the LDS and is
+    its wavefronts; the chunks are whole wavefront rounds and cover the lattice; the ring form only where its entry code
+    holds the scene (64 obstacles, 15 bits of column); and the ring form's LDS is exactly what dp_edge_ring_kernel carves
+    up (emp_dp_kernels.h: the pointer arithmetic from `tab` to `f_all`)."""
+    g = load_golden("dp_launch_plans.npz")
+    LDS = 160 * 1024
+    n_ring = n_shrunk = 0
+    for row, col, B, max_obs, tiled, form, block in np.unique(g["plans"][:, :7], axis=0).tolist():
+        e = np.zeros(10, dtype=np.int64)
+        if hc.hc_plan_edge(row, col, B, max_obs, tiled, form, block, e.ctypes.data) is not None:
+            continue
+        wide, ring, m32, row_inst, wpb, cpc, gx, gy, threads, lds = e.tolist()
+        what = f"row {row} col {col} B {B} max_obs {max_obs} tiled {tiled} form {form} block {block}"
+        assert wide == (row > 32), what
+        assert 0 <= lds <= LDS and threads == 64 * wpb and gx >= 1 and 1 <= gy <= 65535, what
+        assert gy * cpc >= col - 1, what
+        if wide:
+            assert (gx, gy, lds) == (B, max(col - 1, 1), 0) and threads <= 256, what
+            continue
+        mo = max(max_obs, 1)                                     # make_dp_dev: at least one slot
+        S = 64 // row
+        assert gx == (B + S - 1) // S and cpc % wpb == 0 and m32 == (mo <= 32), what
+        assert row_inst == (row if row in (5, 9, 12, 21) else 0), what
+        c = np.zeros(4, dtype=np.int64)
+        hc.hc_edge_ring_constants(mo, c.ctypes.data)
+        fields, ring_slots, ring_max_col, ring_bytes = c.tolist()
+        assert ring_bytes == 2 * ring_slots * 4 + ring_slots * (1 if mo <= 8 else 2 if mo <= 16 else 4 if mo <= 32 else 8)
+        if ring:
+            assert form == 0 and mo <= 64 and col <= ring_max_col, what
+            # dp_edge_ring_kernel: tab [fields][row^2], t_obs_s and t_obs_l [S][max_obs], t_ps [S rounded up to even] doubles;
+            # per wavefront the reach bands [2][S][max_obs] doubles, then the two rings, then the jerk factors
+            # [columns per wavefront][S] doubles with columns per wavefront = ceil(cols_per_chunk / wavefronts)
+            cpw = (cpc + wpb - 1) // wpb
+            per_wave = 2 * S * mo * 8 + ring_bytes + cpw * S * 8
+            assert lds == (fields * row * row + 2 * S * mo + ((S + 1) & ~1)) * 8 + wpb * per_wave, what
+            n_ring += 1
+        else:
+            # dp_edge_kernel: the table and the obstacles as above, the fields + 5 doubles of the table's tail; per wavefront
+            # the box terms [S][min(max_obs, 64)]
+            per_wave = S * min(mo, 64) * 8
+            assert lds == (fields * row * row + 2 * S * mo + fields) * 8 + wpb * per_wave, what
+        if block:
+            assert wpb <= block // 64, what                      # overridden: as asked, or shrunk to what the LDS holds
+        else:
+            assert wpb <= 16, what
+        if wpb < (block // 64 if block else 2):                  # shrunk: one more wavefront would not have fitted
+            assert lds + per_wave > LDS, what
+            n_shrunk += 1
+    assert n_ring > 1000 and n_shrunk > 0                        # the grid reaches both (32 rows with 254 obstacle slots shrinks)
+
+
+def test_edge_tensor_elems_is_the_size_of_the_tiled_tensor(hc):
+    """emp_dp_launch.h edge_tensor_elems against the package's own host-side tiling (api.tile_edges) and the canonical
+    shape, on small lattices either side of every scenes-per-wavefront count."""
+    from emplanner_carla_amd.api import tile_edges
+    for row in (1, 5, 9, 12, 21, 31, 32):
+        for col in (2, 3, 6):
+            for B in (1, 2, 3, 7, 13, 64, 65):
+                canonical = np.zeros((B, col - 1, row, row))
+                assert hc.hc_edge_tensor_elems(row, col, B, 1) == tile_edges(canonical, row).size
+                assert hc.hc_edge_tensor_elems(row, col, B, 0) == canonical.size
+    assert hc.hc_edge_tensor_elems(33, 4, 5, 1) == 5 * 3 * 33 * 33         # beyond 32 rows: canonical whatever is asked
