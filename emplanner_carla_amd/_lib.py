@@ -91,6 +91,14 @@ class PidParams(C.Structure):
                 ("error_threshold", C.c_double)]
 
 
+class VehicleParams(C.Structure):
+    """emp_vehicle_params: the project's vehicle model (include/emplanner.h states it in full)."""
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("Cf", C.c_double), ("Cr", C.c_double), ("m", C.c_double),
+                ("Iz", C.c_double), ("dt", C.c_double), ("steer_gain", C.c_double), ("throttle_accel", C.c_double),
+                ("brake_decel", C.c_double), ("drag", C.c_double), ("reserved", C.c_int32)]
+
+
+ROLLOUT_MAX_TICKS = 65536          # EMP_ROLLOUT_MAX_TICKS
 PID_BUFFER = 60                    # EMP_PID_BUFFER: the error deque's maxlen (controller.py:637)
 MPC_FF_CONTROLS = 8                # EMP_MPC_FF_CONTROLS
 EMP_LAT_MPC, EMP_LAT_LQR = 0, 1
@@ -205,6 +213,10 @@ PROTOTYPES = {
     "emp_mpc_ff_lateral": (C.c_int, [_vp, C.POINTER(MpcParams), _i32, _i32] + [_vp] * 15 + [C.c_int]),
     "emp_vehicle_control": (C.c_int, [_vp, _i32, C.POINTER(MpcParams), C.POINTER(PidParams), _i32, _i32] + [_vp] * 19
                             + [C.c_int]),
+    "emp_vehicle_params_default": (None, [C.POINTER(VehicleParams)]),
+    "emp_vehicle_step": (C.c_int, [_vp, C.POINTER(VehicleParams), _i32] + [_vp] * 6 + [C.c_int]),
+    "emp_rollout": (C.c_int, [_vp, _i32, C.POINTER(MpcParams), C.POINTER(PidParams), C.POINTER(VehicleParams), _i32, _i32]
+                    + [_vp] * 7 + [_i32, _i32] + [_vp] * 10 + [C.c_int]),
     "emp_speed_dp_params_default": (None, [C.POINTER(SpeedDpParams)]),
     "emp_st_graph": (C.c_int, [_vp, _i32, _i32] + [_vp] * 8 + [C.c_int]),
     "emp_speed_dp": (C.c_int, [_vp, C.POINTER(SpeedDpParams), _i32, _i32] + [_vp] * 11 + [C.c_int]),

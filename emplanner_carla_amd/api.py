@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from ._lib import DpParams, QpParams, SmoothParams, SpeedDpParams, SpeedQpParams, MpcParams, PidParams, EmpError
+from ._lib import DpParams, QpParams, SmoothParams, SpeedDpParams, SpeedQpParams, MpcParams, PidParams, VehicleParams, EmpError
 
 
 def dp_params(row=12, col=6, sample_s=15, sample_l=1.5, sampling_res=2, w_collision_cost=1e12,
@@ -82,6 +82,39 @@ def mpc_ff_params(vehicle_para=(1.015, 2.910 - 1.015, 1412, -148970, -82204, 153
 def pid_params(K_P=1.15, K_I=0.0, K_D=0.0, dt=0.01, error_threshold=1.0) -> PidParams:
     """Gains of Longitudinal_PID_controller (controller.py:622-638; its defaults)."""
     return PidParams(float(K_P), float(K_I), float(K_D), float(dt), float(error_threshold))
+
+
+def vehicle_params(vehicle_para=(1.015, 2.910 - 1.015, 1412, -148970, -82204, 1537), dt=0.01, steer_gain=1.0, throttle_accel=3.0,
+                   brake_decel=6.0, drag=0.0) -> VehicleParams:
+    """Parameters of the project's vehicle model (include/emplanner.h: emp_vehicle_step states it in full; the reference has
+    none, its plant is CARLA).  vehicle_para is unpacked as in mpc_params; dt is the PID's tick."""
+    p = VehicleParams()
+    p.a, p.b, p.Cf, p.Cr, p.m, p.Iz = (float(v) for v in vehicle_para)
+    p.dt, p.steer_gain, p.throttle_accel = float(dt), float(steer_gain), float(throttle_accel)
+    p.brake_decel, p.drag, p.reserved = float(brake_decel), float(drag), 0
+    return p
+
+
+@dataclass
+class VehicleStepResult:
+    state: object        # (B, 6) x, y, fi, Vy, fi_dot, Vx after the tick
+    ctl_state: object    # (B, 5) x, y, fi, Vy, fi_dot: vehicle_control's ``state``
+    vx_ctl: object       # (B,) Vx with the reference's |Vx| >= 0.005 clamp: vehicle_control's ``vx``
+    speed_kmh: object    # (B,) 3.6 * sqrt(Vx^2 + Vy^2): vehicle_control's ``speed_kmh``
+
+
+@dataclass
+class RolloutResult:
+    state: object        # (B, 6) after T ticks
+    min_index: object    # (B,) int32 the last tick's match: the next rollout's min_index
+    err: object          # (B, 60) PID error buffer after the rollout
+    n_err: object        # (B,) int32
+    status: object       # (B,) int32 OR of the ticks' lateral statuses
+    fail_tick: object    # (B,) int32 first tick with a non-zero status, -1 if none
+    log_state: object    # (n_log, B, 6) the state the controller saw at ticks 0, log_every, ...; None without logs
+    log_control: object  # (n_log, B, 3) throttle, steer, brake
+    log_err: object      # (n_log, B, 4) e_rr
+    log_index: object    # (n_log, B) int32 the tick's match index
 
 
 @dataclass
@@ -928,6 +961,62 @@ class Planner:
         self._check(self._lib.emp_vehicle_control(
             self._h, law, C.byref(lat), C.byref(pid), B, M, *ins, ctp, lcp, ocp, mip, ep, kp, ppp, eop, nop, stp, a.where))
         return VehicleControlResult(ctl, lc, oc, mi, e, k, pp, eo, no, st)
+
+    # ---- the vehicle model and the closed loop (the project's own plant; the reference's is CARLA) ------------------
+    def vehicle_step(self, vp: VehicleParams, state, control, in_place=False) -> VehicleStepResult:
+        """One tick of the vehicle model for B vehicles: state (B, 6) = x, y, fi, Vy, fi_dot, Vx and control (B, 3) = throttle,
+        steer, brake (vehicle_control's) -> the next state and the next vehicle_control call's inputs.  in_place=True writes the
+        next state into ``state``."""
+        a = self._args(state, control)
+        B = int(state.shape[0])
+        so, sop = a.out((B, 6), np.float64, into=_same_array(state, np.float64) if in_place else None)
+        cs, csp = a.out((B, 5), np.float64)
+        vx, vxp = a.out((B,), np.float64)
+        kmh, kmhp = a.out((B,), np.float64)
+        self._check(self._lib.emp_vehicle_step(self._h, C.byref(vp), B, a.inp(state, np.float64, (B, 6)),
+                                               a.inp(control, np.float64, (B, 3)), sop, csp, vxp, kmhp, a.where))
+        return VehicleStepResult(so, cs, vx, kmh)
+
+    def rollout(self, lat: MpcParams, pid: PidParams, vp: VehicleParams, target_path, n_path, state, min_index, target_speed,
+                err, n_err, T, lateral="mpc", log_every=None, in_place=False) -> RolloutResult:
+        """T closed-loop ticks (vehicle_control, then vehicle_step) of B vehicles in ONE kernel launch, bit-identical to the
+        chain of the 2 T separate calls.  target_path (B, M, 4) / n_path (B,) may be ``CycleResult.traj`` / ``traj_len`` as
+        plan_cycle left them on the device (M = max_pts + 1).  state (B, 6), min_index (B,), target_speed (B,), err (B, 60),
+        n_err (B,).  log_every=k records ticks 0, k, 2k, ... (None: no logs).  in_place=True updates ``state``, ``min_index``,
+        ``err`` and ``n_err`` where they live.  With lateral="lqr" keep the fleet moving: a creeping vehicle costs up to 5000
+        Riccati sweeps per tick."""
+        law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
+        if law is None:
+            raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+        T = int(T)
+        if not 1 <= T <= L.ROLLOUT_MAX_TICKS:
+            raise ValueError(f"T must be in [1, {L.ROLLOUT_MAX_TICKS}]")
+        if log_every is not None and int(log_every) < 1:
+            raise ValueError("log_every must be at least 1")
+        a = self._args(target_path, state, err)
+        B, M = int(target_path.shape[0]), int(target_path.shape[1])
+        nb = L.PID_BUFFER
+        ins = [a.inp(target_path, np.float64, (B, M, 4)), a.inp(n_path, np.int32, (B,)), a.inp(state, np.float64, (B, 6)),
+               a.inp(min_index, np.int32, (B,)), a.inp(target_speed, np.float64, (B,)), a.inp(err, np.float64, (B, nb)),
+               a.inp(n_err, np.int32, (B,))]
+        same = (lambda x, dt: _same_array(x, dt)) if in_place else (lambda x, dt: None)
+        so, sop = a.out((B, 6), np.float64, into=same(state, np.float64))
+        mi, mip = a.out((B,), np.int32, into=same(min_index, np.int32))
+        eo, eop = a.out((B, nb), np.float64, into=same(err, np.float64))
+        no, nop = a.out((B,), np.int32, into=same(n_err, np.int32))
+        st, stp = a.out((B,), np.int32)
+        ft, ftp = a.out((B,), np.int32)
+        if log_every is None:
+            every, logs, logp = 1, [None] * 4, [None] * 4
+        else:
+            every = int(log_every)
+            n_log = (T + every - 1) // every
+            pairs = [a.out((n_log, B, 6), np.float64), a.out((n_log, B, 3), np.float64), a.out((n_log, B, 4), np.float64),
+                     a.out((n_log, B), np.int32)]
+            logs, logp = [q[0] for q in pairs], [q[1] for q in pairs]
+        self._check(self._lib.emp_rollout(self._h, law, C.byref(lat), C.byref(pid), C.byref(vp), B, M, *ins, T, every, sop, mip, eop,
+                                          nop, stp, ftp, *logp, a.where))
+        return RolloutResult(so, mi, eo, no, st, ft, *logs)
 
     # ---- S-T speed DP (reference planner/speed_planning_test.py) ------------------------------
     def st_graph(self, obs_s, obs_l, obs_s_dot, obs_l_dot):

@@ -17,6 +17,7 @@
 #include "emp_st_backend_kernels.h"
 #include "emp_tail_kernels.h"
 #include "emp_mpc_kernels.h"
+#include "emp_rollout_kernels.h"
 #include "emp_speed_front_kernels.h"
 
 namespace emp {
@@ -2499,6 +2500,103 @@ int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat
         if (const int rc = launch(ctx, "vehicle_control", lqr::lqr_lateral_kernel<true>, grid1(B, 64), dim3(64), 0, B, max_path,
                                   mpc_params(lat), d_path, d_np, d_state, d_vx, d_mi, d_lat, (double*)nullptr, d_e, d_k, d_mo, d_pp,
                                   (int*)nullptr, d_st, io))
+            return rc;
+    }
+    return st.finish();
+}
+
+}  // extern "C"
+
+// ---- the vehicle model and the closed-loop rollout (the project's own plant: the reference's is CARLA) ---------------------
+namespace {
+
+ctl::VehicleParams vehicle_params(const emp_vehicle_params* p) {
+    return ctl::VehicleParams{p->a, p->b, p->Cf, p->Cr, p->m, p->Iz, p->dt, p->steer_gain, p->throttle_accel, p->brake_decel, p->drag};
+}
+
+}  // namespace
+
+extern "C" {
+
+void emp_vehicle_params_default(emp_vehicle_params* p) {
+    if (!p) return;
+    emp_mpc_params vp;
+    emp_mpc_params_default(&vp);                            // vehicle_para as the controllers take it
+    p->a = vp.a; p->b = vp.b; p->Cf = vp.Cf; p->Cr = vp.Cr; p->m = vp.m; p->Iz = vp.Iz;
+    p->dt = 0.01;                                           // the PID's (ref controller.py:622)
+    p->steer_gain = 1.0;
+    p->throttle_accel = 3.0;
+    p->brake_decel = 6.0;
+    p->drag = 0.0;
+    p->reserved = 0;
+}
+
+int emp_vehicle_step(emp_ctx* ctx, const emp_vehicle_params* vp, int32_t B, const double* state, const double* control,
+                     double* state_out, double* ctl_state, double* vx_ctl, double* speed_kmh, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, vp && B >= 0, "bad sizes");
+    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    EMP_REQUIRE(ctx, state && control && state_out, "NULL argument");
+    EMP_STAGE(st, where);
+    const double* d_state = st.in(state, (size_t)B * 6);
+    const double* d_ctl = st.in(control, (size_t)B * 3);
+    double* d_out = st.out(state_out, (size_t)B * 6, false);
+    double* d_cs = st.out(ctl_state, (size_t)B * 5, false);
+    double* d_vx = st.out(vx_ctl, (size_t)B, false);
+    double* d_kmh = st.out(speed_kmh, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "vehicle_step", rollout::vehicle_step_kernel, grid1(B, 256), dim3(256), 0, B, vehicle_params(vp),
+                              d_state, d_ctl, d_out, d_cs, d_vx, d_kmh))
+        return rc;
+    return st.finish();
+}
+
+int emp_rollout(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, const emp_vehicle_params* vp,
+                int32_t B, int32_t max_path, const double* target_path, const int32_t* n_path, const double* state,
+                const int32_t* min_index, const double* target_speed, const double* err_in, const int32_t* n_err_in, int32_t T,
+                int32_t log_every, double* state_out, int32_t* min_index_out, double* err_out, int32_t* n_err_out, int32_t* status,
+                int32_t* fail_tick, double* log_state, double* log_control, double* log_err, int32_t* log_index, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, lateral == EMP_LAT_MPC || lateral == EMP_LAT_LQR, "lateral must be EMP_LAT_MPC or EMP_LAT_LQR");
+    EMP_REQUIRE(ctx, lat && pid && vp && B >= 0 && max_path >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    EMP_REQUIRE(ctx, T >= 1 && T <= EMP_ROLLOUT_MAX_TICKS, "T must be in [1, 65536]");
+    EMP_REQUIRE(ctx, log_every >= 1, "log_every must be at least 1");
+    EMP_REQUIRE(ctx, target_path && n_path && state && min_index && target_speed && err_in && n_err_in && state_out &&
+                         min_index_out && err_out && n_err_out && status && fail_tick,
+                "NULL argument");
+    const size_t n_log = ((size_t)T + (size_t)log_every - 1) / (size_t)log_every;
+    EMP_STAGE(st, where);
+    const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
+    const int* d_np = st.in(n_path, (size_t)B);
+    rollout::IO io{};
+    io.pid = pid_params(pid);
+    io.vp = vehicle_params(vp);
+    io.T = T;
+    io.log_every = log_every;
+    io.state_in = st.in(state, (size_t)B * 6);
+    io.min_index_in = st.in(min_index, (size_t)B);
+    io.target_speed = st.in(target_speed, (size_t)B);
+    io.err_in = st.in(err_in, (size_t)B * ctl::kPidBuffer);
+    io.n_err_in = st.in(n_err_in, (size_t)B);
+    io.state_out = st.out(state_out, (size_t)B * 6, false);
+    io.min_index_out = st.out(min_index_out, (size_t)B, false);
+    io.err_out = st.out(err_out, (size_t)B * ctl::kPidBuffer, false);
+    io.n_err_out = st.out(n_err_out, (size_t)B, false);
+    io.status = st.out(status, (size_t)B, false);
+    io.fail_tick = st.out(fail_tick, (size_t)B, false);
+    io.log_state = st.out(log_state, n_log * B * 6, false);
+    io.log_control = st.out(log_control, n_log * B * 3, false);
+    io.log_err = st.out(log_err, n_log * B * 4, false);
+    io.log_index = st.out(log_index, n_log * B, false);
+    if (const int rc = st.ready()) return rc;
+    if (lateral == EMP_LAT_MPC) {
+        if (const int rc = launch(ctx, "rollout", rollout::mpc_rollout_kernel, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave),
+                                  dim3(64), 0, B, max_path, mpc_params(lat), d_path, d_np, io))
+            return rc;
+    } else {
+        if (const int rc = launch(ctx, "rollout", rollout::lqr_rollout_kernel, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(lat),
+                                  d_path, d_np, io))
             return rc;
     }
     return st.finish();

@@ -1,5 +1,6 @@
-// emp_control_core.h - the longitudinal PID step and the actuation mapping of the reference's Vehicle_control, as plain
-// functions that hipcc (device code of the fused control kernels) and g++ (tests/host_check/control_check.cpp) both compile.
+// emp_control_core.h - the longitudinal PID step and the actuation mapping of the reference's Vehicle_control, and the
+// project's vehicle model (vehicle_step, below), as plain functions that hipcc (device code of the fused control and rollout
+// kernels) and g++ (tests/host_check/control_check.cpp, tests/host_check/vehicle_check.cpp) both compile.
 // ref: controller/controller.py class Longitudinal_PID_controller (:614-678) and Vehicle_control.run_step (:680-724).
 //
 // Arithmetic contract: bit-exact with the reference's Python floats.  Every expression is evaluated in the written order with
@@ -86,6 +87,69 @@ EMP_HD void actuate(double steer_cmd, double acc_cmd, double* throttle, double* 
         *throttle = 0.0;
         *brake = (acc_cmd > 1.0) ? acc_cmd : 1.0;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The vehicle model of emp_vehicle_step / emp_rollout.  THIS IS THE PROJECT'S DEFINITION, NOT THE REFERENCE'S: the reference has
+// no vehicle model (CARLA's physics is its plant).  It is the dynamic bicycle model that the controllers' own cal_A_B_C_fun
+// (ref controller.py:115-148) linearises, stepped with the bilinear rule the controllers discretise it with (:159-165), so the
+// plant and the controllers' prediction agree by construction.  Same arithmetic contract as above: written order, separately
+// rounded operations, IEEE `/`; only the pose uses libm (sin, cos) and speed_kmh sqrt.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct VehicleParams {
+    double a, b, Cf, Cr, m, Iz;                // vehicle_para as the controllers unpack it (ref :132)
+    double dt;                                 // tick (0.01: the PID's)
+    double steer_gain;                         // wheel angle [rad] per unit steer (1: the MPC treats u as the wheel angle)
+    double throttle_accel, brake_decel, drag;  // m/s^2 per unit throttle / brake; 1/s
+};
+
+struct VehicleState {
+    double x, y, fi, Vy, fi_dot, Vx;           // pose, body-frame lateral velocity, yaw rate, body-frame longitudinal velocity
+};
+
+// cal_vehicle_info's sign-preserving clamp |Vx| >= 0.005 (ref :106-109), Python's max(a, b): `a` unless b is strictly larger
+EMP_HD double clamp_vx(double Vx) {
+    if (Vx < 0.0) {
+        const double av = fabs(Vx);
+        return -((0.005 > av) ? 0.005 : av);
+    }
+    return (0.005 > Vx) ? 0.005 : Vx;
+}
+
+// 3.6 * |velocity| as the PID reads it (ref :647-649), from the body-frame components
+EMP_HD double speed_kmh_of(double Vx, double Vy) { return 3.6 * sqrt(Vx * Vx + Vy * Vy); }
+
+// One tick.  delta = steer_gain * steer; ax = throttle_accel * throttle - brake_decel * brake - drag * Vx.  The lateral pair
+// z = (Vy, fi_dot) solves (I - dt/2 A) z+ = (I + dt/2 A) z + dt * bv * delta by Cramer's rule, with
+//   A = [[(Cf+Cr)/(m Vxc), (a Cf - b Cr)/(m Vxc) - Vxc], [(a Cf - b Cr)/(Iz Vxc), (a^2 Cf + b^2 Cr)/(Iz Vxc)]], Vxc = clamp_vx(Vx),
+//   bv = (-Cf/m, -a Cf/Iz)
+// (A-stable: no speed makes the step blow up where the continuous model decays).  The pose steps from the OLD values; Vx+ =
+// max(Vx + dt * ax, 0): the model does not reverse (a NaN speed becomes 0).
+EMP_HD VehicleState vehicle_step(const VehicleParams& p, const VehicleState& s, double throttle, double steer, double brake) {
+    const double delta = p.steer_gain * steer;
+    const double ax = (p.throttle_accel * throttle - p.brake_decel * brake) - p.drag * s.Vx;
+    const double Vxc = clamp_vx(s.Vx);
+    const double a11 = (p.Cf + p.Cr) / (p.m * Vxc);
+    const double a12 = (p.a * p.Cf - p.b * p.Cr) / (p.m * Vxc) - Vxc;
+    const double a21 = (p.a * p.Cf - p.b * p.Cr) / (p.Iz * Vxc);
+    const double a22 = (p.a * p.a * p.Cf + p.b * p.b * p.Cr) / (p.Iz * Vxc);
+    const double bv1 = -p.Cf / p.m, bv2 = -p.a * p.Cf / p.Iz;
+    const double h = p.dt / 2.0;
+    const double m11 = h * a11, m12 = h * a12, m21 = h * a21, m22 = h * a22;
+    const double l11 = 1.0 - m11, l12 = -m12, l21 = -m21, l22 = 1.0 - m22;
+    const double r1 = ((1.0 + m11) * s.Vy + m12 * s.fi_dot) + (p.dt * bv1) * delta;
+    const double r2 = (m21 * s.Vy + (1.0 + m22) * s.fi_dot) + (p.dt * bv2) * delta;
+    const double det = l11 * l22 - l12 * l21;
+    VehicleState n;
+    n.Vy = (r1 * l22 - l12 * r2) / det;
+    n.fi_dot = (l11 * r2 - l21 * r1) / det;
+    const double c = cos(s.fi), sn = sin(s.fi);
+    n.x = s.x + p.dt * (s.Vx * c - s.Vy * sn);
+    n.y = s.y + p.dt * (s.Vx * sn + s.Vy * c);
+    n.fi = s.fi + p.dt * s.fi_dot;
+    const double v = s.Vx + p.dt * ax;
+    n.Vx = (v > 0.0) ? v : 0.0;
+    return n;
 }
 
 }  // namespace ctl

@@ -248,27 +248,22 @@ __device__ inline void control_epilogue(const CtlIO& io, int b, int lat_status, 
     }
 }
 
-// ref: Lateral_MPC_controller._control (:313-337) for B vehicles; grid = ceil(B / 5), block = 64.  kFused: then the longitudinal
-// half of Vehicle_control.run_step (control_epilogue) on the lane that holds u[0] - emp_vehicle_control in one launch; the
-// lateral arithmetic is the same in both instantiations.
-template <bool kFused>
-__global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Params prm, const double* __restrict__ target_path,
-                                                         const int* __restrict__ n_path, const double* __restrict__ state,
-                                                         const double* __restrict__ vx, const int* __restrict__ min_index_in,
-                                                         double* __restrict__ steer, double* __restrict__ u_out,
-                                                         double* __restrict__ e_rr_out, double* __restrict__ k_r_out,
-                                                         int* __restrict__ min_index_out, double* __restrict__ pre_pro,
-                                                         double* __restrict__ H_out, double* __restrict__ f_out,
-                                                         int* __restrict__ iters_out, int* __restrict__ status, CtlIO io) {
-    const int lane = threadIdx.x & 63;
-    const int grp = lane / kNu, r = lane - grp * kNu;
-    const int gb = grp * kNu;
-    const int b = blockIdx.x * kGroupsPerWave + grp;
-    const bool live = grp < kGroupsPerWave && b < B;
-    const int bb = live ? b : 0;
-    // ---- vehicle state (what cal_vehicle_info provides, ref :90-113)
-    double x = state[5 * bb], y = state[5 * bb + 1], fi = state[5 * bb + 2];
-    const double Vy = state[5 * bb + 3], fi_dot = state[5 * bb + 4], Vx = vx[bb];
+// What one evaluation of a lateral law leaves in registers: the kernels below write it out, the rollout kernels feed it to the
+// vehicle model.
+struct LatResult {
+    double steer;                  // the command; 0 where status != 0
+    V4 e_rr;
+    double pk;                     // k_r
+    double pre[4];                 // predicted x, y and projected x, y
+    int idx, iters, status;        // match index, QP iterations / Riccati sweeps, status bits
+};
+
+// ref: Lateral_MPC_controller._control (:313-337) for the vehicle of MY 12-lane group (lane r of the group at lane gb), from its
+// state in registers: the body of mpc_lateral_kernel and of a tick of mpc_rollout_kernel.  `path` is the vehicle's row, np_ its
+// clamped count, idx the previous match.  h, *f_r_out, *u_out: row r of H, f_r and control r (lane-local); *o is group-uniform.
+__device__ __forceinline__ void mpc_lateral_core(const Params& prm, const double* __restrict__ path, int np_, double x, double y,
+                                                 double fi, double Vy, double fi_dot, double Vx, int idx, bool live, int r, int gb,
+                                                 double (&h)[kNu], double* f_r_out, double* u_out, LatResult* o) {
     // ---- continuous error model (ref :115-148)
     M4 A;
 #pragma unroll
@@ -295,11 +290,8 @@ __global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Pa
         y = yn;
         fi = fi + fi_dot * kTs;
     }
-    const double* path = target_path + (size_t)bb * max_path * 4;
-    const int np_ = min(max(n_path[bb], 0), max_path);            // a count beyond the row is clamped, never followed
-    int idx = min_index_in[bb];
     bool bad_index = live && (np_ < 1 || idx < 0 || idx >= np_);   // the reference raises IndexError at :224
-    if (bad_index) idx = 0;
+    if (bad_index || !live) idx = 0;                               // (an idle group follows no index at all)
     {
         double min_d = 10000.0;                                     // squared metres (ref :201): farther than 100 m
         const int first = idx, last = min(first + kWindow, np_);    // keeps the previous match
@@ -368,7 +360,7 @@ __global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Pa
         }
     }
     const int jr = r / kP;
-    double h[kNu], f_r = 0.0;
+    double f_r = 0.0;
 #pragma unroll
     for (int c = 0; c < kNu; ++c) {
         const int jc = c / kP;
@@ -400,29 +392,64 @@ __global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Pa
     double u = 0.0;
     int it = 0;
     const int rc = box_qp_full12(h, f_r, r, gb, solvable, &u, &it);
+    const bool ok = solvable && rc == 0;
+    *f_r_out = f_r;
+    *u_out = ok ? u : 0.0;
+    o->steer = grp_bcast(ok ? u : 0.0, gb, 0);                    // ref :311: res['x'][0]
+    o->e_rr = e_rr;
+    o->pk = pk;
+    o->pre[0] = x;
+    o->pre[1] = y;
+    o->pre[2] = px + e_s * ct;
+    o->pre[3] = py + e_s * st;
+    o->idx = idx;
+    o->iters = it;
+    o->status = bad_index ? kStSOutOfRange : ((!inv_ok || rc != 0) ? kStQpFailed : 0);
+}
+
+// ref: Lateral_MPC_controller._control (:313-337) for B vehicles; grid = ceil(B / 5), block = 64.  kFused: then the longitudinal
+// half of Vehicle_control.run_step (control_epilogue) on the lane that holds u[0] - emp_vehicle_control in one launch; the
+// lateral arithmetic is the same in both instantiations.
+template <bool kFused>
+__global__ __launch_bounds__(64) void mpc_lateral_kernel(int B, int max_path, Params prm, const double* __restrict__ target_path,
+                                                         const int* __restrict__ n_path, const double* __restrict__ state,
+                                                         const double* __restrict__ vx, const int* __restrict__ min_index_in,
+                                                         double* __restrict__ steer, double* __restrict__ u_out,
+                                                         double* __restrict__ e_rr_out, double* __restrict__ k_r_out,
+                                                         int* __restrict__ min_index_out, double* __restrict__ pre_pro,
+                                                         double* __restrict__ H_out, double* __restrict__ f_out,
+                                                         int* __restrict__ iters_out, int* __restrict__ status, CtlIO io) {
+    const int lane = threadIdx.x & 63;
+    const int grp = lane / kNu, r = lane - grp * kNu;
+    const int gb = grp * kNu;
+    const int b = blockIdx.x * kGroupsPerWave + grp;
+    const bool live = grp < kGroupsPerWave && b < B;
+    const int bb = live ? b : 0;
+    double h[kNu], f_r, u;
+    LatResult o;
+    // vehicle state: what cal_vehicle_info provides (ref :90-113); a count beyond the path's row is clamped, never followed
+    mpc_lateral_core(prm, target_path + (size_t)bb * max_path * 4, min(max(n_path[bb], 0), max_path), state[5 * bb],
+                     state[5 * bb + 1], state[5 * bb + 2], state[5 * bb + 3], state[5 * bb + 4], vx[bb], min_index_in[bb], live, r, gb,
+                     h, &f_r, &u, &o);
     if (live) {
         if (H_out)
 #pragma unroll
             for (int c = 0; c < kNu; ++c) H_out[((size_t)b * kNu + r) * kNu + c] = h[c];
         if (f_out) f_out[(size_t)b * kNu + r] = f_r;
-        if (u_out) u_out[(size_t)b * kNu + r] = (solvable && rc == 0) ? u : 0.0;
+        if (u_out) u_out[(size_t)b * kNu + r] = u;
         if (r == 0) {
-            steer[b] = (solvable && rc == 0) ? u : 0.0;           // ref :311: res['x'][0]
+            steer[b] = o.steer;
             if (e_rr_out)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) e_rr_out[4 * b + q] = e_rr.v[q];
-            if (k_r_out) k_r_out[b] = pk;
-            min_index_out[b] = idx;
-            if (pre_pro) {
-                pre_pro[4 * b] = x;
-                pre_pro[4 * b + 1] = y;
-                pre_pro[4 * b + 2] = px + e_s * ct;
-                pre_pro[4 * b + 3] = py + e_s * st;
-            }
-            if (iters_out) iters_out[b] = it;
-            const int stat = bad_index ? kStSOutOfRange : ((!inv_ok || rc != 0) ? kStQpFailed : 0);
-            status[b] = stat;
-            if constexpr (kFused) control_epilogue(io, b, stat, steer[b]);
+                for (int q = 0; q < 4; ++q) e_rr_out[4 * b + q] = o.e_rr.v[q];
+            if (k_r_out) k_r_out[b] = o.pk;
+            min_index_out[b] = o.idx;
+            if (pre_pro)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pre_pro[4 * b + q] = o.pre[q];
+            if (iters_out) iters_out[b] = o.iters;
+            status[b] = o.status;
+            if constexpr (kFused) control_epilogue(io, b, o.status, o.steer);
         }
     }
 }
@@ -451,19 +478,11 @@ __device__ __forceinline__ M4 matmul(const M4& A, const M4& B) {
     return C;
 }
 
-// kFused: as mpc_lateral_kernel<true> - one vehicle per lane, so every lane runs its own epilogue.
-template <bool kFused>
-__global__ void lqr_lateral_kernel(int B, int max_path, mpc::Params prm, const double* __restrict__ target_path,
-                                   const int* __restrict__ n_path, const double* __restrict__ state,
-                                   const double* __restrict__ vx, const int* __restrict__ min_index_in,
-                                   double* __restrict__ steer, double* __restrict__ K_out, double* __restrict__ e_rr_out,
-                                   double* __restrict__ k_r_out, int* __restrict__ min_index_out,
-                                   double* __restrict__ pre_pro, int* __restrict__ sweeps_out, int* __restrict__ status,
-                                   mpc::CtlIO io) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    double x = state[5 * b], y = state[5 * b + 1], fi = state[5 * b + 2];
-    const double Vy = state[5 * b + 3], fi_dot = state[5 * b + 4], Vx = vx[b];
+// ref: Lateral_LQR_controller._control (:374-611) for ONE vehicle from its state in registers: the body of lqr_lateral_kernel and
+// of a tick of lqr_rollout_kernel.  `path` is the vehicle's row, np_ its clamped count, idx the fallback match.
+__device__ __forceinline__ void lqr_lateral_core(const mpc::Params& prm, const double* __restrict__ path, int np_, double x, double y,
+                                                 double fi, double Vy, double fi_dot, double Vx, int idx, V4* K_out,
+                                                 mpc::LatResult* o) {
     // ---- continuous model (ref :424-455): Vx + 0.0001 guards the divisions
     const double Vg = Vx + 0.0001;
     M4 A;
@@ -552,9 +571,6 @@ __global__ void lqr_lateral_kernel(int B, int max_path, mpc::Params prm, const d
         y = yn;
         fi = fi + fi_dot * mpc::kTs;
     }
-    const double* path = target_path + (size_t)b * max_path * 4;
-    const int np_ = min(max(n_path[b], 0), max_path);             // a count beyond the row is clamped, never followed
-    int idx = min_index_in[b];
     {
         double min_d = 10000.0;
         for (int i = 0; i < np_; ++i) {
@@ -586,28 +602,50 @@ __global__ void lqr_lateral_kernel(int B, int max_path, mpc::Params prm, const d
     delta_f = delta_f * 3.141592653589793 / 180.0;
     const double u = -(((K.v[0] * e_d + K.v[1] * e_d_dot) + K.v[2] * e_fi) + K.v[3] * e_fi_dot) + delta_f;
     const bool ok = inv_ok && !bad_index;
-    steer[b] = ok ? u : 0.0;
+    o->steer = ok ? u : 0.0;
+    *K_out = K;
+    o->e_rr = V4{{e_d, e_d_dot, e_fi, e_fi_dot}};
+    o->pk = pk;
+    o->pre[0] = x;
+    o->pre[1] = y;
+    o->pre[2] = px + e_s * ct;
+    o->pre[3] = py + e_s * st;
+    o->idx = idx;
+    o->iters = sweeps;
+    o->status = bad_index ? kStSOutOfRange : (inv_ok ? 0 : kStQpFailed);
+}
+
+// kFused: as mpc_lateral_kernel<true> - one vehicle per lane, so every lane runs its own epilogue.
+template <bool kFused>
+__global__ void lqr_lateral_kernel(int B, int max_path, mpc::Params prm, const double* __restrict__ target_path,
+                                   const int* __restrict__ n_path, const double* __restrict__ state,
+                                   const double* __restrict__ vx, const int* __restrict__ min_index_in,
+                                   double* __restrict__ steer, double* __restrict__ K_out, double* __restrict__ e_rr_out,
+                                   double* __restrict__ k_r_out, int* __restrict__ min_index_out,
+                                   double* __restrict__ pre_pro, int* __restrict__ sweeps_out, int* __restrict__ status,
+                                   mpc::CtlIO io) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    V4 K;
+    mpc::LatResult o;
+    // a count beyond the path's row is clamped, never followed
+    lqr_lateral_core(prm, target_path + (size_t)b * max_path * 4, min(max(n_path[b], 0), max_path), state[5 * b], state[5 * b + 1],
+                     state[5 * b + 2], state[5 * b + 3], state[5 * b + 4], vx[b], min_index_in[b], &K, &o);
+    steer[b] = o.steer;
     if (K_out)
 #pragma unroll
         for (int j = 0; j < 4; ++j) K_out[4 * b + j] = K.v[j];
-    if (e_rr_out) {
-        e_rr_out[4 * b] = e_d;
-        e_rr_out[4 * b + 1] = e_d_dot;
-        e_rr_out[4 * b + 2] = e_fi;
-        e_rr_out[4 * b + 3] = e_fi_dot;
-    }
-    if (k_r_out) k_r_out[b] = pk;
-    min_index_out[b] = idx;
-    if (pre_pro) {
-        pre_pro[4 * b] = x;
-        pre_pro[4 * b + 1] = y;
-        pre_pro[4 * b + 2] = px + e_s * ct;
-        pre_pro[4 * b + 3] = py + e_s * st;
-    }
-    if (sweeps_out) sweeps_out[b] = sweeps;
-    const int stat = bad_index ? kStSOutOfRange : (inv_ok ? 0 : kStQpFailed);
-    status[b] = stat;
-    if constexpr (kFused) mpc::control_epilogue(io, b, stat, steer[b]);
+    if (e_rr_out)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) e_rr_out[4 * b + q] = o.e_rr.v[q];
+    if (k_r_out) k_r_out[b] = o.pk;
+    min_index_out[b] = o.idx;
+    if (pre_pro)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pre_pro[4 * b + q] = o.pre[q];
+    if (sweeps_out) sweeps_out[b] = o.iters;
+    status[b] = o.status;
+    if constexpr (kFused) mpc::control_epilogue(io, b, o.status, o.steer);
 }
 
 }  // namespace lqr

@@ -661,6 +661,68 @@ int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat
                         double* lon_command, int32_t* min_index_out, double* e_rr, double* k_r, double* pre_pro,
                         double* err_out, int32_t* n_err_out, int32_t* status, emp_mem where);
 
+/* ---- the vehicle model and the closed-loop rollout ------------------------------------------------------------------
+ * THE MODEL IS THIS PROJECT'S DEFINITION, NOT THE REFERENCE'S.  The reference has no vehicle model: its main loop
+ * (test_9.py:336-436) runs Vehicle_control.run_step 100 times per planning cycle against CARLA's physics.  Ours is the dynamic
+ * bicycle model that the controllers' own cal_A_B_C_fun (controller.py:115-148) linearises, stepped with the bilinear rule the
+ * controllers discretise it with (:159-165).  New with ABI 13's library; adding functions does not change EMP_ABI_VERSION.
+ *
+ * emp_vehicle_step: one tick of B vehicles.  state [B][6] = x, y, fi, Vy, fi_dot, Vx (pose; body-frame lateral velocity, yaw
+ * rate and longitudinal velocity); control [B][3] = throttle, steer, brake, as emp_vehicle_control writes them.  In this order,
+ * every operation rounded separately (no contraction), `/` IEEE division:
+ *   delta = steer_gain * steer;   ax = (throttle_accel * throttle - brake_decel * brake) - drag * Vx
+ *   Vxc = Vx with the reference's sign-preserving clamp |Vxc| >= 0.005 (controller.py:106-109)
+ *   a11 = (Cf + Cr) / (m * Vxc)                 a12 = (a * Cf - b * Cr) / (m * Vxc) - Vxc
+ *   a21 = (a * Cf - b * Cr) / (Iz * Vxc)        a22 = (a * a * Cf + b * b * Cr) / (Iz * Vxc)
+ *   bv1 = -Cf / m,  bv2 = -a * Cf / Iz,  h = dt / 2,  mij = h * aij
+ *   the lateral pair z = (Vy, fi_dot) solves (I - h A) z+ = (I + h A) z + dt * bv * delta by Cramer's rule:
+ *     l11 = 1 - m11, l12 = -m12, l21 = -m21, l22 = 1 - m22
+ *     r1 = ((1 + m11) * Vy + m12 * fi_dot) + (dt * bv1) * delta;   r2 = (m21 * Vy + (1 + m22) * fi_dot) + (dt * bv2) * delta
+ *     det = l11 * l22 - l12 * l21;   Vy+ = (r1 * l22 - l12 * r2) / det;   fi_dot+ = (l11 * r2 - l21 * r1) / det
+ *   (the rule is A-stable: no speed makes the step blow up where the continuous model decays)
+ *   the pose steps from the OLD values: x+ = x + dt * (Vx * cos fi - Vy * sin fi), y+ = y + dt * (Vx * sin fi + Vy * cos fi),
+ *   fi+ = fi + dt * fi_dot;   Vx+ = max(Vx + dt * ax, 0): the model does not reverse.
+ * Optional outputs (NULL to skip) are the next emp_vehicle_control call's inputs, so a chain of calls never leaves the device:
+ * ctl_state [B][5] = x, y, fi, Vy, fi_dot; vx_ctl [B] = the clamped Vx+; speed_kmh [B] = 3.6 * sqrt(Vx+ * Vx+ + Vy+ * Vy+).
+ * state_out may alias state.  vp->reserved must be 0.
+ * With the controllers' default vehicle_para (the reference drivers' tuple, unpacked in the controllers' order) a radian of wheel
+ * angle yields about 0.03 rad/s of yaw rate at 10 m/s: this plant follows straight and very gently curved paths only. */
+typedef struct emp_vehicle_params {
+    double a, b, Cf, Cr, m, Iz;            /* as emp_mpc_params (the controllers' defaults) */
+    double dt;                             /* tick, 0.01 s: the PID's */
+    double steer_gain;                     /* wheel angle [rad] per unit steer, 1.0: the MPC treats u as the wheel angle */
+    double throttle_accel, brake_decel;    /* m/s^2 per unit throttle / brake: 3.0, 6.0 */
+    double drag;                           /* 1/s, 0.0 */
+    int32_t reserved;                      /* must be 0 */
+} emp_vehicle_params;
+void emp_vehicle_params_default(emp_vehicle_params* p);
+int emp_vehicle_step(emp_ctx* ctx, const emp_vehicle_params* vp, int32_t B, const double* state, const double* control,
+                     double* state_out, double* ctl_state, double* vx_ctl, double* speed_kmh, emp_mem where);
+
+/* emp_rollout: T closed-loop ticks of B vehicles in ONE kernel launch.  Tick t is exactly emp_vehicle_control (lateral law
+ * `lateral` with `lat`, PID `pid`) on (ctl_state, vx_ctl, speed_kmh, min_index, PID state), followed by emp_vehicle_step with `vp`
+ * on its controls; the next tick takes emp_vehicle_step's ctl_state / vx_ctl / speed_kmh, emp_vehicle_control's min_index_out and
+ * err_out / n_err_out.  Tick 0's ctl_state, vx_ctl and speed_kmh come from state [B][6] by emp_vehicle_step's own formulas (the
+ * first five values, the clamp, 3.6 * sqrt(Vx * Vx + Vy * Vy)).  There are no special cases: a vehicle whose lateral status is
+ * non-zero in a tick gets zero controls, keeps its PID state and coasts through that tick (emp_vehicle_control's rule), and
+ * takes part in the next tick like any other (its min_index_out may have become valid).  EVERY OUTPUT EQUALS, BIT FOR BIT, T
+ * iterations of the two stand-alone calls on the same arrays.
+ * Inputs as emp_vehicle_control (target_path [B][max_path][4], n_path [B] clamped to [0, max_path], min_index [B],
+ * target_speed [B], err_in [B][EMP_PID_BUFFER], n_err_in [B]); T in [1, EMP_ROLLOUT_MAX_TICKS], log_every >= 1.
+ * Outputs: state_out [B][6], min_index_out [B], err_out / n_err_out (each may alias its input); status [B] = OR of the ticks'
+ * lateral statuses; fail_tick [B] = first tick with a non-zero status, -1 if none.  Optional logs (NULL to skip) have
+ * n_log = ceil(T / log_every) rows, tick-major; tick t is logged when t % log_every == 0: log_state [n_log][B][6] (the state the
+ * controller saw), log_control [n_log][B][3], log_err [n_log][B][4] (e_rr), log_index [n_log][B] (the tick's min_index_out).
+ * As in emp_vehicle_control, e_rr of a tick whose status is non-zero is computed from path slot 0 whatever n_path says.
+ * Cost: EMP_LAT_LQR's Riccati iteration may take 5000 sweeps for a creeping vehicle (controller.py:470-481), a wavefront runs
+ * as long as its slowest lane, and the rollout multiplies that by T: keep LQR fleets moving. */
+#define EMP_ROLLOUT_MAX_TICKS 65536
+int emp_rollout(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, const emp_vehicle_params* vp,
+                int32_t B, int32_t max_path, const double* target_path, const int32_t* n_path, const double* state,
+                const int32_t* min_index, const double* target_speed, const double* err_in, const int32_t* n_err_in, int32_t T,
+                int32_t log_every, double* state_out, int32_t* min_index_out, double* err_out, int32_t* n_err_out, int32_t* status,
+                int32_t* fail_tick, double* log_state, double* log_control, double* log_err, int32_t* log_index, emp_mem where);
+
 /* ---- S-T speed DP (BASELINE config 5; reference planner/speed_planning_test.py) ----------------
  * The S-T grid is hard-coded in the reference (40 non-uniform s samples :114, 16 t samples :116); tables are
  * [B][EMP_ST_ROWS][EMP_ST_COLS], row 0 = largest s (CalcSTCoordinate, :287-305).  Obstacle slots hold NaN when
