@@ -98,6 +98,15 @@ class VehicleParams(C.Structure):
                 ("brake_decel", C.c_double), ("drag", C.c_double), ("reserved", C.c_int32)]
 
 
+class DriveParams(C.Structure):
+    """emp_drive_params: the thresholds of the driver's get_actor_from_world / predict_block (test_9.py:48-89, :335, :377)."""
+    _fields_ = [("dis_limitation", C.c_double), ("lateral_band", C.c_double), ("behind", C.c_double),
+                ("dynamic_speed", C.c_double), ("static_gate", C.c_double), ("pred_ts", C.c_double), ("advance_s", C.c_double),
+                ("reserved", C.c_int32)]
+
+
+DRIVE_MAX_PERIODS = 4096           # EMP_DRIVE_MAX_PERIODS
+DRV_TRUNCATED = 1                  # EMP_DRV_TRUNCATED
 ROLLOUT_MAX_TICKS = 65536          # EMP_ROLLOUT_MAX_TICKS
 PID_BUFFER = 60                    # EMP_PID_BUFFER: the error deque's maxlen (controller.py:637)
 MPC_FF_CONTROLS = 8                # EMP_MPC_FF_CONTROLS
@@ -132,6 +141,14 @@ class SpeedIO(C.Structure):
     _fields_ = [(n, _vp) for n in (
         "dyn_obs", "n_dyn", "start_heading", "plan_start_time", "dyn_pre_match",
         "trajectory", "speed_status", "path_index2s", "st_segments", "dp_speed", "speed_profile")] + [("reserved", C.c_int32)]
+
+
+class DriveIO(C.Structure):
+    """emp_drive_io: the arrays of emp_drive - inputs, the in/out state's outputs, per-period logs."""
+    _fields_ = [(n, _vp) for n in (
+        "global_path", "n_global", "state", "accel", "actors", "n_act", "pre_match_index", "track", "track_len", "held",
+        "state_out", "accel_out", "actors_out", "pre_match_index_out", "track_out", "track_len_out", "held_out",
+        "log_state", "log_plan_status", "log_roll_status", "log_held", "log_counts", "log_traj", "log_traj_len")] + [("reserved", C.c_int32)]
 
 
 # name -> (restype, argtypes); data pointers are void* so numpy arrays and raw device addresses both fit
@@ -217,6 +234,11 @@ PROTOTYPES = {
     "emp_vehicle_step": (C.c_int, [_vp, C.POINTER(VehicleParams), _i32] + [_vp] * 6 + [C.c_int]),
     "emp_rollout": (C.c_int, [_vp, _i32, C.POINTER(MpcParams), C.POINTER(PidParams), C.POINTER(VehicleParams), _i32, _i32]
                     + [_vp] * 7 + [_i32, _i32] + [_vp] * 10 + [C.c_int]),
+    "emp_drive_params_default": (None, [C.POINTER(DriveParams)]),
+    "emp_drive_request": (C.c_int, [_vp, C.POINTER(DriveParams), _i32, _i32, _i32, _i32] + [_vp] * 18 + [C.c_int]),
+    "emp_drive": (C.c_int, [_vp, C.POINTER(DpParams), C.POINTER(QpParams), C.POINTER(SmoothParams), C.POINTER(DriveParams), _i32,
+                            C.POINTER(MpcParams), C.POINTER(PidParams), C.POINTER(VehicleParams)] + [_i32] * 8
+                  + [_vp, C.POINTER(DriveIO), C.c_int]),
     "emp_speed_dp_params_default": (None, [C.POINTER(SpeedDpParams)]),
     "emp_st_graph": (C.c_int, [_vp, _i32, _i32] + [_vp] * 8 + [C.c_int]),
     "emp_speed_dp": (C.c_int, [_vp, C.POINTER(SpeedDpParams), _i32, _i32] + [_vp] * 11 + [C.c_int]),

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from ._lib import DpParams, QpParams, SmoothParams, SpeedDpParams, SpeedQpParams, MpcParams, PidParams, VehicleParams, EmpError
+from ._lib import DpParams, QpParams, SmoothParams, SpeedDpParams, SpeedQpParams, MpcParams, PidParams, VehicleParams, DriveParams, EmpError
 
 
 def dp_params(row=12, col=6, sample_s=15, sample_l=1.5, sampling_res=2, w_collision_cost=1e12,
@@ -115,6 +115,52 @@ class RolloutResult:
     log_control: object  # (n_log, B, 3) throttle, steer, brake
     log_err: object      # (n_log, B, 4) e_rr
     log_index: object    # (n_log, B) int32 the tick's match index
+
+
+def drive_params(dis_limitation=50.0, lateral_band=5.0, behind=-10.0, dynamic_speed=1.0, static_gate=30.0, pred_ts=0.2,
+                 advance_s=0.0) -> DriveParams:
+    """Thresholds of the driver's get_actor_from_world and predict_block (test_9.py:48-89, :116, :335, :377; its values).
+    advance_s: seconds the actors move in a stand-alone ``drive_request``; ``drive`` uses T * dt instead."""
+    return DriveParams(float(dis_limitation), float(lateral_band), float(behind), float(dynamic_speed), float(static_gate),
+                       float(pred_ts), float(advance_s), 0)
+
+
+@dataclass
+class DriveRequest:
+    """What ``Planner.drive_request`` makes of fleet state and actors: the inputs of ``plan_cycle(global_path=...)``."""
+    static_xy: object      # (B, max_obs, 2) the nearest static actors, nearest first: plan_cycle's obs_xy
+    n_static: object       # (B,) int32
+    static_dis: object     # (B, max_obs)
+    dyn: object            # (B, max_dyn, 4) x, y, dis, speed of the nearest dynamic actors
+    n_dyn: object          # (B,) int32
+    dyn_dis_speed: object  # (B, 2) the first dynamic's (dis, speed), NaN without one: plan_cycle's dyn_dis_speed
+    n_obs: object          # (B,) int32 n_static behind the planner's 30 m gate (test_9.py:116): plan_cycle's n_obs
+    origin_xy: object      # (B, 2)
+    start_xy: object       # (B, 2) predict_block's location
+    pred_fi: object        # (B,)
+    start_v: object        # (B, 2) world-frame velocity
+    start_a: object        # (B, 2) the caller's accel
+    req_status: object     # (B,) int32 DRV_TRUNCATED when more actors were kept than max_obs / max_dyn hold
+    actors_next: object    # (B, max_act, 4) the actors advance_s later, or None
+
+
+@dataclass
+class DriveResult:
+    """Outputs of ``Planner.drive`` in emp_drive_io's order: the in/out state after K periods, then the per-period logs."""
+    state: object            # (B, 6)
+    accel: object            # (B, 2) world-frame acceleration over the last tick: the next call's accel
+    actors: object           # (B, max_act, 4)
+    pre_match_index: object  # (B,) int32 the last cycle's match_index
+    track: object            # (B, max_pts + 1, 4) the trajectory being tracked
+    track_len: object        # (B,) int32
+    held: object             # (B,) int32 periods since the track was last replaced by a valid plan
+    log_state: object        # (K, B, 6) state at the start of each period; None without logs
+    log_plan_status: object  # (K, B) int32 status | ref_status of the period's plan
+    log_roll_status: object  # (K, B) int32
+    log_held: object         # (K, B) int32
+    log_counts: object       # (K, B, 2) int32 n_obs, n_dyn
+    log_traj: object         # (K, B, max_pts + 1, 4) the period's plan, adopted or not
+    log_traj_len: object     # (K, B) int32
 
 
 @dataclass
@@ -1017,6 +1063,81 @@ class Planner:
         self._check(self._lib.emp_rollout(self._h, law, C.byref(lat), C.byref(pid), C.byref(vp), B, M, *ins, T, every, sop, mip, eop,
                                           nop, stp, ftp, *logp, a.where))
         return RolloutResult(so, mi, eo, no, st, ft, *logs)
+
+    # ---- the fleet loop (the reference driver's main loop, test_9.py:336-436) ---------------------------------------
+    def drive_request(self, dp: DriveParams, state, accel, actors, n_act, max_obs: int, max_dyn: int = 8,
+                      advance=False, in_place=False) -> DriveRequest:
+        """Fleet state (B, 6) and actors (B, A, 4) = x, y, vx, vy with n_act (B,) -> the next ``plan_cycle(global_path=...)``
+        call's inputs (get_actor_from_world, predict_block, the 30 m gate; include/emplanner.h states the arithmetic).  accel
+        (B, 2) or None (zeros) is passed through as start_a.  advance=True also returns the actors dp.advance_s later;
+        with in_place=True they are written into ``actors``."""
+        a = self._args(state, actors)
+        B, A = int(actors.shape[0]), int(actors.shape[1])
+        mo, md = int(max_obs), int(max_dyn)
+        ins = [a.inp(state, np.float64, (B, 6)), a.inp(accel, np.float64, (B, 2)), a.inp(actors, np.float64, (B, A, 4)),
+               a.inp(n_act, np.int32, (B,))]
+        outs = [a.out(shape, dt) for shape, dt in (
+            ((B, mo, 2), np.float64), ((B,), np.int32), ((B, mo), np.float64), ((B, md, 4), np.float64), ((B,), np.int32),
+            ((B, 2), np.float64), ((B,), np.int32), ((B, 2), np.float64), ((B, 2), np.float64), ((B,), np.float64),
+            ((B, 2), np.float64), ((B, 2), np.float64), ((B,), np.int32))]
+        nxt, nxtp = (None, None)
+        if advance or in_place:
+            nxt, nxtp = a.out((B, A, 4), np.float64, into=_same_array(actors, np.float64) if in_place else None)
+        self._check(self._lib.emp_drive_request(self._h, C.byref(dp), B, A, mo, md, *ins, *[o[1] for o in outs], nxtp, a.where))
+        return DriveRequest(*[o[0] for o in outs], nxt)
+
+    def drive(self, p: DpParams, q: QpParams, sp: SmoothParams, dp: DriveParams, lat: MpcParams, pid: PidParams, vp: VehicleParams,
+              global_path, n_global, state, accel, actors, n_act, pre_match_index, track, track_len, held, target_speed,
+              K, T, max_obs: int, max_dyn: int = 8, max_pts=None, lateral="mpc", logs=True, in_place=False) -> DriveResult:
+        """K planning periods of a fleet in ONE call, nothing leaving the device in between: per period ``drive_request`` (the
+        actors move T * vp.dt in place), ``plan_cycle(global_path=...)``, adopt the plan if it is valid (else hold the track and
+        count in ``held``), ``rollout`` of T ticks on the track with a new controller, and the acceleration over the last tick.
+        global_path (B, G, 4), n_global (B,), state (B, 6), accel (B, 2) or None, actors (B, A, 4), n_act (B,), pre_match_index
+        (B,), track (B, max_pts + 1, 4), track_len (B,), held (B,), target_speed (B,).  A vehicle with track_len 0 and no valid
+        plan coasts.  logs=False skips the per-period logs.  in_place=True updates state, actors, pre_match_index, track,
+        track_len and held (and accel, when given) where they live.  Equals the chain of the separate calls bit for bit."""
+        law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
+        if law is None:
+            raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+        K, T = int(K), int(T)
+        a = self._args(global_path, state, actors, track)
+        B, G, A = int(global_path.shape[0]), int(global_path.shape[1]), int(actors.shape[1])
+        M = int(max_pts) if max_pts else max_path_points(p)
+        io = L.DriveIO()
+        io.global_path = a.inp(global_path, np.float64, (B, G, 4))
+        io.n_global = a.inp(n_global, np.int32, (B,))
+        io.state = a.inp(state, np.float64, (B, 6))
+        io.accel = a.inp(accel, np.float64, (B, 2))
+        io.actors = a.inp(actors, np.float64, (B, A, 4))
+        io.n_act = a.inp(n_act, np.int32, (B,))
+        io.pre_match_index = a.inp(pre_match_index, np.int32, (B,))
+        io.track = a.inp(track, np.float64, (B, M + 1, 4))
+        io.track_len = a.inp(track_len, np.int32, (B,))
+        io.held = a.inp(held, np.int32, (B,))
+        tsp = a.inp(target_speed, np.float64, (B,))
+        same = (lambda x, dt: _same_array(x, dt) if x is not None else None) if in_place else (lambda x, dt: None)
+        res = []
+        for name, src, shape, dt in (("state_out", state, (B, 6), np.float64), ("accel_out", accel, (B, 2), np.float64),
+                                     ("actors_out", actors, (B, A, 4), np.float64),
+                                     ("pre_match_index_out", pre_match_index, (B,), np.int32),
+                                     ("track_out", track, (B, M + 1, 4), np.float64), ("track_len_out", track_len, (B,), np.int32),
+                                     ("held_out", held, (B,), np.int32)):
+            arr, ptr = a.out(shape, dt, into=same(src, dt))
+            res.append(arr)
+            setattr(io, name, ptr)
+        for name, shape, dt in (("log_state", (K, B, 6), np.float64), ("log_plan_status", (K, B), np.int32),
+                                ("log_roll_status", (K, B), np.int32), ("log_held", (K, B), np.int32),
+                                ("log_counts", (K, B, 2), np.int32), ("log_traj", (K, B, M + 1, 4), np.float64),
+                                ("log_traj_len", (K, B), np.int32)):
+            if logs and K >= 1:
+                arr, ptr = a.out(shape, dt)
+                setattr(io, name, ptr)
+            else:
+                arr = None
+            res.append(arr)
+        self._check(self._lib.emp_drive(self._h, C.byref(p), C.byref(q), C.byref(sp), C.byref(dp), law, C.byref(lat), C.byref(pid),
+                                        C.byref(vp), B, G, int(max_obs), M, A, int(max_dyn), K, T, tsp, C.byref(io), a.where))
+        return DriveResult(*res)
 
     # ---- S-T speed DP (reference planner/speed_planning_test.py) ------------------------------
     def st_graph(self, obs_s, obs_l, obs_s_dot, obs_l_dot):

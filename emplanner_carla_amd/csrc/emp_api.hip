@@ -19,6 +19,7 @@
 #include "emp_mpc_kernels.h"
 #include "emp_rollout_kernels.h"
 #include "emp_speed_front_kernels.h"
+#include "emp_drive_kernels.h"
 
 namespace emp {
 thread_local std::string g_create_error;
@@ -1480,10 +1481,11 @@ struct SpeedHalf {
 };
 }  // namespace emp
 
-// emp_plan_cycle's body; with `speed` (emp_plan_trajectory) the speed half runs behind the Cartesian tail, before the lane is done
+// emp_plan_cycle's body; with `speed` (emp_plan_trajectory) the speed half runs behind the Cartesian tail, before the lane is done;
+// `plain` (emp_drive): EMP_OPT_CYCLE_GRAPH is neither used nor touched
 static int plan_cycle_impl(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q, const emp_smooth_params* sp, int32_t B,
                            int32_t max_ref, int32_t max_obs, int32_t max_pts, emp_dp_mode mode, const emp_cycle_io* io,
-                           emp_mem where, SpeedHalf* speed) {
+                           emp_mem where, SpeedHalf* speed, bool plain = false) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p && q && sp && io, "NULL parameter struct");
     EMP_REQUIRE(ctx, qp_reserved_ok(q), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
@@ -1512,7 +1514,7 @@ static int plan_cycle_impl(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_pa
     CycleCapture graph(ctx);
     bool replayed = false;
     // (the trajectory call is never captured: plain launches)
-    if (!speed && ((rc = graph.begin(pmode, where, B, max_ref, max_obs, max_pts, mode, p, q, sp, io, &replayed)) || replayed)) return rc;
+    if (!speed && !plain && ((rc = graph.begin(pmode, where, B, max_ref, max_obs, max_pts, mode, p, q, sp, io, &replayed)) || replayed)) return rc;
     // (the slot form of in() / out(): with EMP_HOST_PINNED the device pointers are known only at inputs_ready() / outputs_ready())
     Stage st(ctx, where, pmode != 0, pinned);
     const double *d_ref = nullptr, *d_o, *d_sxy, *d_v, *d_a, *d_oxy, *d_dyn, *d_glob = nullptr;
@@ -2514,6 +2516,15 @@ ctl::VehicleParams vehicle_params(const emp_vehicle_params* p) {
     return ctl::VehicleParams{p->a, p->b, p->Cf, p->Cr, p->m, p->Iz, p->dt, p->steer_gain, p->throttle_accel, p->brake_decel, p->drag};
 }
 
+// the one launch of emp_rollout (and of every period of emp_drive): the lateral kernels' mappings
+int launch_rollout(emp_ctx* ctx, int lateral, const emp_mpc_params* lat, int B, int max_path, const double* d_path, const int* d_np,
+                   const rollout::IO& io) {
+    if (lateral == EMP_LAT_MPC)
+        return launch(ctx, "rollout", rollout::mpc_rollout_kernel, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave), dim3(64), 0,
+                      B, max_path, mpc_params(lat), d_path, d_np, io);
+    return launch(ctx, "rollout", rollout::lqr_rollout_kernel, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(lat), d_path, d_np, io);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2590,15 +2601,254 @@ int emp_rollout(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const 
     io.log_err = st.out(log_err, n_log * B * 4, false);
     io.log_index = st.out(log_index, n_log * B, false);
     if (const int rc = st.ready()) return rc;
-    if (lateral == EMP_LAT_MPC) {
-        if (const int rc = launch(ctx, "rollout", rollout::mpc_rollout_kernel, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave),
-                                  dim3(64), 0, B, max_path, mpc_params(lat), d_path, d_np, io))
+    if (const int rc = launch_rollout(ctx, lateral, lat, B, max_path, d_path, d_np, io)) return rc;
+    return st.finish();
+}
+
+}  // extern "C"
+
+// ---- the fleet loop (reference driver test_9.py:336-436): request, plan, adopt, T ticks - K periods, nothing leaves the device ----
+namespace {
+
+drive::Params drive_params(const emp_drive_params* p, double advance_s) {
+    return drive::Params{p->dis_limitation, p->lateral_band, p->behind, p->dynamic_speed, p->static_gate, p->pred_ts, advance_s};
+}
+
+int launch_drive_request(emp_ctx* ctx, int B, int max_act, int max_obs, int max_dyn, const drive::Params& prm, const drive::RequestIO& io) {
+    const DriveRequestPlan p = plan_drive_request(B);
+    if (const int rc = plan_refused(ctx, p.error)) return rc;
+    return launch(ctx, "drive_request", drive::drive_request_kernel, dim3(p.grid), dim3(p.block), 0, B, max_act, max_obs, max_dyn, prm, io);
+}
+
+// While emp_drive stages its arrays the context's pool is the drive pool; while its periods run, the pipeline setting is off.
+// Both are put back however the call ends.
+struct DriveScope {
+    emp_ctx* ctx;
+    int pipe_mode;
+    bool own_pool = false;
+    explicit DriveScope(emp_ctx* c) : ctx(c), pipe_mode(c->pipe_mode) { swap_pool(); }
+    ~DriveScope() {
+        ctx->pipe_mode = pipe_mode;
+        if (own_pool) swap_pool();
+    }
+    void swap_pool() {
+        std::swap(ctx->pool, ctx->drive_pool);
+        own_pool = !own_pool;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+void emp_drive_params_default(emp_drive_params* p) {
+    if (!p) return;
+    p->dis_limitation = 50.0;       // ref test_9.py:377
+    p->lateral_band = 5.0;          // :77
+    p->behind = -10.0;              // :78
+    p->dynamic_speed = 1.0;         // :81
+    p->static_gate = 30.0;          // :116
+    p->pred_ts = 0.2;               // :335
+    p->advance_s = 0.0;
+    p->reserved = 0;
+}
+
+int emp_drive_request(emp_ctx* ctx, const emp_drive_params* p, int32_t B, int32_t max_act, int32_t max_obs, int32_t max_dyn,
+                      const double* state, const double* accel, const double* actors, const int32_t* n_act, double* static_xy,
+                      int32_t* n_static, double* static_dis, double* dyn, int32_t* n_dyn, double* dyn_dis_speed, int32_t* n_obs,
+                      double* origin_xy, double* start_xy, double* pred_fi, double* start_v, double* start_a,
+                      int32_t* req_status, double* actors_next, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, p && B >= 0, "bad sizes");
+    EMP_REQUIRE(ctx, p->reserved == 0, "emp_drive_params.reserved must be 0");
+    EMP_REQUIRE(ctx, max_act >= 1 && max_act <= 64, "max_act must be in [1, 64]");
+    EMP_REQUIRE(ctx, max_obs >= 1 && max_obs <= 256 && max_dyn >= 1 && max_dyn <= 64, "max_obs must be in [1, 256], max_dyn in [1, 64]");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "EMP_HOST_PINNED is emp_plan_cycle's");
+    EMP_REQUIRE(ctx, state && actors && n_act && static_xy && n_static && static_dis && dyn && n_dyn && dyn_dis_speed && n_obs &&
+                         origin_xy && start_xy && pred_fi && start_v && start_a && req_status,
+                "NULL argument");
+    EMP_STAGE(st, where);
+    drive::RequestIO io{};
+    io.state = st.in(state, (size_t)B * 6);
+    io.accel = st.in(accel, (size_t)B * 2);
+    io.actors = st.in(actors, (size_t)B * max_act * 4);
+    io.n_act = st.in(n_act, (size_t)B);
+    io.static_xy = st.out(static_xy, (size_t)B * max_obs * 2, false);
+    io.n_static = st.out(n_static, (size_t)B, false);
+    io.static_dis = st.out(static_dis, (size_t)B * max_obs, false);
+    io.dyn = st.out(dyn, (size_t)B * max_dyn * 4, false);
+    io.n_dyn = st.out(n_dyn, (size_t)B, false);
+    io.dyn_dis_speed = st.out(dyn_dis_speed, (size_t)B * 2, false);
+    io.n_obs = st.out(n_obs, (size_t)B, false);
+    io.origin_xy = st.out(origin_xy, (size_t)B * 2, false);
+    io.start_xy = st.out(start_xy, (size_t)B * 2, false);
+    io.pred_fi = st.out(pred_fi, (size_t)B, false);
+    io.start_v = st.out(start_v, (size_t)B * 2, false);
+    io.start_a = st.out(start_a, (size_t)B * 2, false);
+    io.req_status = st.out(req_status, (size_t)B, false);
+    io.actors_next = st.out(actors_next, (size_t)B * max_act * 4, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch_drive_request(ctx, B, max_act, max_obs, max_dyn, drive_params(p, p->advance_s), io)) return rc;
+    return st.finish();
+}
+
+int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
+              const emp_drive_params* drv, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
+              const emp_vehicle_params* vp, int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act,
+              int32_t max_dyn, int32_t K, int32_t T, const double* target_speed, const emp_drive_io* io, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, dp && qp && smooth && drv && lat && pid && vp && io, "NULL parameter struct");
+    EMP_REQUIRE(ctx, drv->reserved == 0, "emp_drive_params.reserved must be 0");
+    EMP_REQUIRE(ctx, io->reserved == 0, "emp_drive_io.reserved must be 0");
+    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    EMP_REQUIRE(ctx, qp_reserved_ok(qp), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_drive takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, lateral == EMP_LAT_MPC || lateral == EMP_LAT_LQR, "lateral must be EMP_LAT_MPC or EMP_LAT_LQR");
+    EMP_REQUIRE(ctx, B >= 0 && max_global >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, K >= 1 && K <= EMP_DRIVE_MAX_PERIODS, "K must be in [1, 4096]");
+    EMP_REQUIRE(ctx, T >= 1 && T <= EMP_ROLLOUT_MAX_TICKS, "T must be in [1, 65536]");
+    EMP_REQUIRE(ctx, max_act >= 1 && max_act <= 64, "max_act must be in [1, 64]");
+    EMP_REQUIRE(ctx, max_obs >= 1 && max_obs <= 253 && max_dyn >= 1 && max_dyn <= 64, "max_obs must be in [1, 253], max_dyn in [1, 64]");
+    EMP_REQUIRE(ctx, max_pts >= 2 && max_pts <= 255, "2 <= max_pts <= 255 required");
+    EMP_REQUIRE(ctx, qp->ds > 0, "ds must be > 0");
+    EMP_REQUIRE(ctx, target_speed && io->global_path && io->n_global && io->state && io->actors && io->n_act && io->pre_match_index &&
+                         io->track && io->track_len && io->held,
+                "NULL input array");
+    EMP_REQUIRE(ctx, io->state_out && io->accel_out && io->actors_out && io->pre_match_index_out && io->track_out && io->track_len_out &&
+                         io->held_out,
+                "NULL output array");
+    {   // the lattice parameters are checked here, before anything is staged or launched, by the cycle's own rule; the DpDev
+        // is not kept (plan_cycle_impl makes its own every period).  max_obs + 3: the cycle adds up to three virtual obstacles
+        // for the dynamic one and holds 256 in all, hence this call's limit of 253 against emp_drive_request's 256
+        DpDev d;
+        if (const int rc = make_dp_dev(ctx, dp, B, max_obs + 3, &d)) return rc;
+    }
+    EMP_HIP(ctx, hipSetDevice(ctx->device));
+    DriveScope scope(ctx);
+    Stage st(ctx, where);                       // (with a pipeline set: the main stream waits for the cycles in flight)
+    const size_t nB = (size_t)B, row = (size_t)(max_pts + 1) * 4, nK = (size_t)K;
+    const double* d_glob = st.in(io->global_path, nB * max_global * 4);
+    const int* d_nglob = st.in(io->n_global, nB);
+    const double* d_state = st.in(io->state, nB * 6);
+    const double* d_accel = st.in(io->accel, nB * 2);
+    const double* d_actors = st.in(io->actors, nB * max_act * 4);
+    const int* d_nact = st.in(io->n_act, nB);
+    const int* d_prem = st.in(io->pre_match_index, nB);
+    const double* d_track = st.in(io->track, nB * row);
+    const int* d_tlen = st.in(io->track_len, nB);
+    const int* d_held = st.in(io->held, nB);
+    const double* d_target = st.in(target_speed, nB);
+    double* o_state = st.out(io->state_out, nB * 6, false);
+    double* o_accel = st.out(io->accel_out, nB * 2, false);
+    double* o_actors = st.out(io->actors_out, nB * max_act * 4, false);
+    int* o_prem = st.out(io->pre_match_index_out, nB, false);
+    double* o_track = st.out(io->track_out, nB * row, false);
+    int* o_tlen = st.out(io->track_len_out, nB, false);
+    int* o_held = st.out(io->held_out, nB, false);
+    double* l_state = st.out(io->log_state, nK * nB * 6, false);
+    int* l_plan = st.out(io->log_plan_status, nK * nB, false);
+    int* l_roll = st.out(io->log_roll_status, nK * nB, false);
+    int* l_held = st.out(io->log_held, nK * nB, false);
+    int* l_counts = st.out(io->log_counts, nK * nB * 2, false);
+    double* l_traj = st.out(io->log_traj, nK * nB * row, false);
+    int* l_tlen = st.out(io->log_traj_len, nK * nB, false);
+    // the request's outputs, the cycle's, the rollout's: temporaries of the drive pool, the same for every period
+    drive::RequestIO rq{};
+    rq.n_act = d_nact;
+    rq.static_xy = st.tmp<double>(nB * max_obs * 2);
+    rq.n_static = st.tmp<int>(nB);
+    rq.static_dis = st.tmp<double>(nB * max_obs);
+    rq.dyn = st.tmp<double>(nB * max_dyn * 4);
+    rq.n_dyn = st.tmp<int>(nB);
+    rq.dyn_dis_speed = st.tmp<double>(nB * 2);
+    rq.n_obs = st.tmp<int>(nB);
+    rq.origin_xy = st.tmp<double>(nB * 2);
+    rq.start_xy = st.tmp<double>(nB * 2);
+    rq.pred_fi = st.tmp<double>(nB);
+    rq.start_v = st.tmp<double>(nB * 2);
+    rq.start_a = st.tmp<double>(nB * 2);
+    rq.req_status = st.tmp<int>(nB);
+    rq.actors_next = o_actors;
+    emp_cycle_io cio{};
+    cio.global_path = d_glob;
+    cio.n_global = d_nglob;
+    cio.max_global = max_global;
+    cio.origin_xy = rq.origin_xy;
+    cio.start_xy = rq.start_xy;
+    cio.start_v = rq.start_v;
+    cio.start_a = rq.start_a;
+    cio.obs_xy = rq.static_xy;
+    cio.n_obs = rq.n_obs;
+    cio.dyn_dis_speed = rq.dyn_dis_speed;
+    cio.traj = st.tmp<double>(nB * row);
+    cio.traj_len = st.tmp<int>(nB);
+    cio.status = st.tmp<int>(nB);
+    cio.match_index = st.tmp<int>(nB);
+    cio.ref_status = st.tmp<int>(nB);
+    drive::AdoptIO ad{};
+    ad.traj = cio.traj;
+    ad.traj_len = cio.traj_len;
+    ad.status = cio.status;
+    ad.ref_status = cio.ref_status;
+    ad.match_index = cio.match_index;
+    ad.track_out = o_track;
+    ad.track_len_out = o_tlen;
+    ad.held_out = o_held;
+    ad.pre_match_out = o_prem;
+    // the rollout: a new controller every period (min_index 0, an empty PID deque); its tick-(T - 1) log row feeds the acceleration
+    const int log_every = std::max(T - 1, 1);
+    const size_t n_log = ((size_t)T + log_every - 1) / log_every;
+    rollout::IO ro{};
+    ro.pid = pid_params(pid);
+    ro.vp = vehicle_params(vp);
+    ro.T = T;
+    ro.log_every = log_every;
+    ro.min_index_in = st.tmp<int>(nB, true);
+    ro.target_speed = d_target;
+    ro.err_in = st.tmp<double>(nB * ctl::kPidBuffer, true);
+    ro.n_err_in = st.tmp<int>(nB, true);
+    ro.state_out = o_state;
+    ro.min_index_out = st.tmp<int>(nB);
+    ro.err_out = st.tmp<double>(nB * ctl::kPidBuffer);
+    ro.n_err_out = st.tmp<int>(nB);
+    int* t_roll = st.tmp<int>(nB);
+    ro.fail_tick = st.tmp<int>(nB);
+    ro.log_state = st.tmp<double>(n_log * nB * 6);
+    const double* last_seen = ro.log_state + (T == 1 ? 0 : 1) * nB * 6;
+    if (const int rc = st.ready()) return rc;
+    if (B == 0) return st.finish();
+    scope.swap_pool();                          // the cycles recycle the context's pool as ever
+    ctx->pipe_mode = 0;                         // ... and run one batch at a time on the main stream
+    const drive::Params prm = drive_params(drv, (double)T * vp->dt);
+    const DriveRequestPlan wp = plan_drive_request(B);
+    for (int k = 0; k < K; ++k) {
+        const size_t kB = (size_t)k * nB;
+        rq.state = k ? o_state : d_state;
+        rq.accel = k ? o_accel : d_accel;
+        rq.actors = k ? o_actors : d_actors;
+        rq.log_state = l_state ? l_state + kB * 6 : nullptr;
+        rq.log_counts = l_counts ? l_counts + kB * 2 : nullptr;
+        if (const int rc = launch_drive_request(ctx, B, max_act, max_obs, max_dyn, prm, rq)) return rc;
+        cio.pre_match_index = k ? o_prem : d_prem;
+        if (const int rc = plan_cycle_impl(ctx, dp, qp, smooth, B, kRefLinePoints, max_obs, max_pts, EMP_DP_TWO_KERNEL, &cio, EMP_DEVICE,
+                                           nullptr, true))
             return rc;
-    } else {
-        if (const int rc = launch(ctx, "rollout", rollout::lqr_rollout_kernel, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(lat),
-                                  d_path, d_np, io))
+        ad.track_in = k ? o_track : d_track;
+        ad.track_len_in = k ? o_tlen : d_tlen;
+        ad.held_in = k ? o_held : d_held;
+        ad.log_plan_status = l_plan ? l_plan + kB : nullptr;
+        ad.log_held = l_held ? l_held + kB : nullptr;
+        ad.log_traj = l_traj ? l_traj + kB * row : nullptr;
+        ad.log_traj_len = l_tlen ? l_tlen + kB : nullptr;
+        if (const int rc = launch(ctx, "drive_adopt", drive::drive_adopt_kernel, dim3(wp.grid), dim3(wp.block), 0, B, max_pts, ad)) return rc;
+        ro.state_in = rq.state;
+        ro.status = l_roll ? l_roll + kB : t_roll;
+        if (const int rc = launch_rollout(ctx, lateral, lat, B, max_pts + 1, o_track, o_tlen, ro)) return rc;
+        if (const int rc = launch(ctx, "drive_accel", drive::drive_accel_kernel, grid1(B, 256), dim3(256), 0, B, vp->dt, (const double*)o_state,
+                                  last_seen, o_accel))
             return rc;
     }
+    ctx->pipe_mode = scope.pipe_mode;
     return st.finish();
 }
 

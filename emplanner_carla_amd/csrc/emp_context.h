@@ -91,6 +91,8 @@ struct emp_ctx {
     // grow-only pool of device buffers, handed out in call order and recycled by the next call
     std::vector<Buf> pool;
     size_t cursor = 0;
+    // emp_drive's own pool: its staged arrays and temporaries live through the K cycles of the call, each of which recycles `pool`
+    std::vector<Buf> drive_pool;
     // persistent named scratch (survives across the staged buffers of one call)
     std::map<std::string, Buf> named;
     std::string timing_filter;   // non-empty: only this kernel name is bracketed by events

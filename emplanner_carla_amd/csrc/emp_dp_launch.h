@@ -296,4 +296,25 @@ static inline EnrichPlan plan_enrich(const DpDev& d, bool with_pre) {
     return p;
 }
 
+// ---- the fleet loop's wave-per-vehicle kernels (emp_drive_kernels.h: drive_request_kernel, drive_adopt_kernel) --------------
+struct DriveRequestPlan {
+    int wpb = 0;                // wavefronts (vehicles) per block
+    int grid = 0, block = 0;
+    const char* error = nullptr;
+};
+
+// One wavefront per vehicle: a block per vehicle while the fleet is smaller than a wavefront's worth of vehicles (the few
+// wavefronts spread over the compute units), four to a block from there on.  Not tuned: the kernels take microseconds either way.
+static inline DriveRequestPlan plan_drive_request(int B) {
+    DriveRequestPlan p;
+    if (B < 0) {
+        p.error = "negative batch";
+        return p;
+    }
+    p.wpb = B >= 64 ? 4 : 1;
+    p.block = 64 * p.wpb;
+    p.grid = (int)(((long long)B + p.wpb - 1) / p.wpb);
+    return p;
+}
+
 }  // namespace emp

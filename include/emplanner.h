@@ -878,6 +878,116 @@ int emp_plan_trajectory(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_param
                         int32_t max_obs, int32_t max_pts, int32_t max_dyn, emp_dp_mode mode, const emp_cycle_io* io,
                         const emp_speed_io* sio, emp_mem where);
 
+/* ---- the fleet loop: perceive, predict, plan, adopt, track - K periods on the device (additions: the ABI stays 13) -----------
+ * ref: the driver's main loop, test_9.py:336-436.  emp_drive_request is what the driver does between two planning requests:
+ * get_actor_from_world (test_9.py:48-89), predict_block (planning_utils.py:591-614), the planner's gate on the nearest static
+ * obstacle (test_9.py:116) and the first dynamic obstacle's (dis, speed).  One wavefront per vehicle, one actor per lane.
+ * Arithmetic, per vehicle with state = x, y, fi, Vy, fi_dot, Vx (emp_vehicle_step's; fi in radians - the reference's degrees-to-
+ * radians factor is the caller's), every operation rounded separately, IEEE division and sqrt, c = cos fi, s = sin fi:
+ *   wx = Vx c - Vy s,  wy = Vx s + Vy c                               the ego's world-frame velocity
+ * per actor (x_a, y_a, vx_a, vy_a in the world frame, z = 0):
+ *   dis   = sqrt((x - x_a)^2 + (y - y_a)^2 + 0)
+ *   v1    = (x_a - x, y_a - y)
+ *   lat   = v1x (-s) + v1y c
+ *   along = v1x wx + v1y wy
+ *   speed = sqrt(vx_a^2 + vy_a^2 + 0)
+ *   kept    when dis < dis_limitation and -lateral_band < lat < lateral_band and along > behind  (NaN compares false: dropped)
+ *   dynamic when kept and speed > dynamic_speed, else static
+ * Each class is ordered by dis ascending, equal dis in actor-index order (Python's stable list.sort).  Then
+ *   n_obs = n_static if n_static > 0 and static_dis[0] <= static_gate, else 0          (the cycle's static count, test_9.py:116)
+ *   dyn_dis_speed = the first dynamic's (dis, speed), (NaN, NaN) without one            (the cycle's io->dyn_dis_speed)
+ *   V = sqrt(wx^2 + wy^2 + 0),  beta = atan2(wy, wx) - fi,  V_y = V sin beta,  V_x = V cos beta,  ts = pred_ts
+ *   start_xy = (x + V_x ts c - V_y ts s,  y + V_y ts c + V_x ts s)                     products left to right, as the Python
+ *   pred_fi = fi + fi_dot ts,  origin_xy = (x, y),  start_v = (wx, wy),  start_a = accel (NULL: zeros)
+ *   actors_next = (x_a + vx_a advance_s, y_a + vy_a advance_s, vx_a, vy_a): the product rounded, then the sum; slots at or
+ *                 beyond n_act copied unchanged; optional, may be `actors`
+ * n_act is clamped to [0, max_act] and slots at or beyond it are never read.  Unused output slots are 0.  static_xy / static_dis
+ * hold the max_obs nearest statics and dyn the max_dyn nearest dynamics; req_status is EMP_DRV_TRUNCATED when more were kept.
+ * Limits: 1 <= max_act <= 64, 1 <= max_obs <= 256, 1 <= max_dyn <= 64. */
+#define EMP_DRV_TRUNCATED 1
+#define EMP_DRIVE_MAX_PERIODS 4096
+
+typedef struct emp_drive_params {
+    double dis_limitation;      /* 50  (test_9.py:377) */
+    double lateral_band;        /* 5   (:77) */
+    double behind;              /* -10 (:78) */
+    double dynamic_speed;       /* 1   (:81) */
+    double static_gate;         /* 30  (:116) */
+    double pred_ts;             /* 0.2 (:335) */
+    double advance_s;           /* seconds the actors move per call; 0.  emp_drive uses the double product T * dt instead */
+    int32_t reserved;           /* must be 0 */
+} emp_drive_params;
+void emp_drive_params_default(emp_drive_params* p);
+
+/* state [B][6], accel [B][2] or NULL, actors [B][max_act][4], n_act [B] -> static_xy [B][max_obs][2], n_static [B],
+ * static_dis [B][max_obs], dyn [B][max_dyn][4] = x, y, dis, speed, n_dyn [B], dyn_dis_speed [B][2], n_obs [B], origin_xy [B][2],
+ * start_xy [B][2], pred_fi [B], start_v [B][2], start_a [B][2], req_status [B]; actors_next [B][max_act][4] or NULL. */
+int emp_drive_request(emp_ctx* ctx, const emp_drive_params* p, int32_t B, int32_t max_act, int32_t max_obs, int32_t max_dyn,
+                      const double* state, const double* accel, const double* actors, const int32_t* n_act, double* static_xy,
+                      int32_t* n_static, double* static_dis, double* dyn, int32_t* n_dyn, double* dyn_dis_speed, int32_t* n_obs,
+                      double* origin_xy, double* start_xy, double* pred_fi, double* start_v, double* start_a,
+                      int32_t* req_status, double* actors_next, emp_mem where);
+
+/* emp_drive: K periods of [request, plan, adopt, T ticks] on emp_stream(), stream-ordered, without a host synchronisation or a
+ * copy between them (the host waits only where emp_plan_cycle itself does).  Period k:
+ *   1. the request above on state / accel / actors, advance_s = T * vp->dt (actors move in place)
+ *   2. emp_plan_cycle exactly as it runs with io->global_path set (EMP_DP_TWO_KERNEL, one batch at a time) on the request's
+ *      arrays: obs_xy = static_xy, n_obs, dyn_dis_speed, origin_xy, start_xy, start_v, start_a; pre_match_index of period k + 1 is
+ *      this period's match_index
+ *   3. adopt: a plan is valid when ref_status == 0 and (status & ~EMP_ST_DP_INFEASIBLE) == 0 (the service's rule).  Valid: its
+ *      traj[0..traj_len) becomes the track, track_len = traj_len, held = 0.  Otherwise track / track_len stay and held += 1 (the
+ *      service's "previous" policy; the counter is the report).  A vehicle that never had a valid plan has track_len == 0: the
+ *      rollout flags it and it coasts
+ *   4. emp_rollout's kernel, unchanged: T ticks on track / track_len, min_index = 0 and an empty PID deque (the reference builds a
+ *      new Vehicle_control every period, test_9.py:415), the caller's target_speed [B]
+ *   5. accel = (w(state after the period) - w(state the controller saw at tick T - 1)) / vp->dt, w as above, in a trailing
+ *      one-lane-per-vehicle kernel
+ * In/out arrays: each *_out may be the memory of its input.  Logs are optional (NULL), one row per period.
+ * Decisions pinned on the reference:
+ *   - the reference tracks the reply to the PREVIOUS request (a blocking recv sits right behind the send, test_9.py:390-395); here
+ *     the plan of period k drives period k.  The one-period lag is the reference's way of hiding a 0.3 s planner: not reproduced
+ *   - the reference's plant is CARLA; ours is emp_vehicle_step, and its caveat stands: gentle paths only
+ *   - the speed planner (emp_plan_trajectory) is not part of the loop: target_speed is the caller's constant, as test_9.py:420
+ * Limits: 1 <= K <= EMP_DRIVE_MAX_PERIODS, T as emp_rollout, max_obs <= 253, the emp_plan_cycle and emp_drive_request limits.
+ * B == 0: EMP_OK.  EMP_HOST_PINNED is refused.  With a pipeline set the call fences like every non-cycle entry point, runs its
+ * periods one at a time and leaves the setting as it found it; EMP_OPT_CYCLE_GRAPH is ignored (plain launches).  With
+ * lateral = EMP_LAT_LQR keep the fleet at 5 m/s and above (emp_rollout's cost note). */
+typedef struct emp_drive_io {
+    /* inputs */
+    const double* global_path;      /* [B][max_global][4] */
+    const int32_t* n_global;        /* [B] */
+    const double* state;            /* [B][6] */
+    const double* accel;            /* [B][2] world-frame acceleration, NULL = zeros */
+    const double* actors;           /* [B][max_act][4] */
+    const int32_t* n_act;           /* [B] */
+    const int32_t* pre_match_index; /* [B] */
+    const double* track;            /* [B][max_pts + 1][4] */
+    const int32_t* track_len;       /* [B] */
+    const int32_t* held;            /* [B] */
+    /* outputs (required; each may alias the input of its name) */
+    double* state_out;
+    double* accel_out;
+    double* actors_out;
+    int32_t* pre_match_index_out;
+    double* track_out;
+    int32_t* track_len_out;
+    int32_t* held_out;
+    /* per-period logs, NULL to skip */
+    double* log_state;              /* [K][B][6] state at the start of the period */
+    int32_t* log_plan_status;       /* [K][B] status | ref_status */
+    int32_t* log_roll_status;       /* [K][B] */
+    int32_t* log_held;              /* [K][B] */
+    int32_t* log_counts;            /* [K][B][2] n_obs, n_dyn */
+    double* log_traj;               /* [K][B][max_pts + 1][4] the period's plan, adopted or not */
+    int32_t* log_traj_len;          /* [K][B] */
+    int32_t reserved;               /* must be 0 */
+} emp_drive_io;
+
+int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
+              const emp_drive_params* drive_params, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
+              const emp_vehicle_params* vp, int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act,
+              int32_t max_dyn, int32_t K, int32_t T, const double* target_speed, const emp_drive_io* io, emp_mem where);
+
 #ifdef __cplusplus
 }
 #endif
