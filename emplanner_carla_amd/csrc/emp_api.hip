@@ -931,6 +931,8 @@ static QpDev make_qp_dev(const emp_qp_params* q) {
 }
 
 static inline dim3 grid1(int n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
+// one 64-lane block per wavefront of `per_wave` vehicle groups (the lateral MPCs' mapping)
+static inline dim3 grid_groups(int B, int per_wave) { return grid1(B, per_wave); }
 
 static int dev_project(emp_ctx* ctx, int B, int max_ref, int max_obs, const double* ref_line, const int* n_ref,
                        const double* origin_xy, const double* start_xy, const double* start_v, const double* start_a,
@@ -2297,13 +2299,16 @@ static mpc::Params mpc_params(const emp_mpc_params* p) {
     return prm;
 }
 
-int emp_mpc_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t max_path, const double* target_path,
-                    const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
-                    double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
-                    double* H, double* f, int32_t* iters, int32_t* status, emp_mem where) {
-    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
-    EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
-    EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
+}  // extern "C"
+
+// Stage and launch a lateral law of the MPC shape (emp_mpc_lateral, emp_mpc_ff_lateral): one vehicle per group of nu lanes, 64 / nu
+// groups per wavefront, nu controls and an nu x nu Hessian out.  `tail` is what the kernel takes after status (the fused
+// epilogue's CtlIO, or nothing).
+template <typename K, typename... Tail>
+static int mpc_shaped_lateral(emp_ctx* ctx, const char* name, K kern, int nu, const emp_mpc_params* p, int B, int max_path,
+                              const double* target_path, const int32_t* n_path, const double* state, const double* vx,
+                              const int32_t* min_index, double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out,
+                              double* pre_pro, double* H, double* f, int32_t* iters, int32_t* status, emp_mem where, Tail... tail) {
     EMP_STAGE(st, where);
     const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
     const int* d_np = st.in(n_path, (size_t)B);
@@ -2311,21 +2316,33 @@ int emp_mpc_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
     const double* d_vx = st.in(vx, (size_t)B);
     const int* d_mi = st.in(min_index, (size_t)B);
     double* d_steer = st.out(steer, (size_t)B, false);
-    double* d_u = st.out(u, (size_t)B * mpc::kNu, false);
+    double* d_u = st.out(u, (size_t)B * nu, false);
     double* d_e = st.out(e_rr, (size_t)B * 4, false);
     double* d_k = st.out(k_r, (size_t)B, false);
     int* d_mo = st.out(min_index_out, (size_t)B, false);
     double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
-    double* d_H = st.out(H, (size_t)B * mpc::kNu * mpc::kNu, false);
-    double* d_f = st.out(f, (size_t)B * mpc::kNu, false);
+    double* d_H = st.out(H, (size_t)B * nu * nu, false);
+    double* d_f = st.out(f, (size_t)B * nu, false);
     int* d_it = st.out(iters, (size_t)B, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, "mpc_lateral", mpc::mpc_lateral_kernel<false>, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave),
-                              dim3(64), 0, B, max_path, mpc_params(p), d_path, d_np, d_state, d_vx, d_mi, d_steer, d_u, d_e, d_k, d_mo,
-                              d_pp, d_H, d_f, d_it, d_st, mpc::CtlIO{}))
+    if (const int rc = launch(ctx, name, kern, grid_groups(B, 64 / nu), dim3(64), 0, B, max_path, mpc_params(p), d_path, d_np, d_state,
+                              d_vx, d_mi, d_steer, d_u, d_e, d_k, d_mo, d_pp, d_H, d_f, d_it, d_st, tail...))
         return rc;
     return st.finish();
+}
+
+extern "C" {
+
+int emp_mpc_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t max_path, const double* target_path,
+                    const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
+                    double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
+                    double* H, double* f, int32_t* iters, int32_t* status, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
+    return mpc_shaped_lateral(ctx, "mpc_lateral", mpc::mpc_lateral_kernel<false>, mpc::kNu, p, B, max_path, target_path, n_path, state, vx,
+                              min_index, steer, u, e_rr, k_r, min_index_out, pre_pro, H, f, iters, status, where, mpc::CtlIO{});
 }
 
 void emp_lqr_params_default(emp_mpc_params* p) {
@@ -2434,28 +2451,8 @@ int emp_mpc_ff_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
     EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
-    EMP_STAGE(st, where);
-    const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
-    const int* d_np = st.in(n_path, (size_t)B);
-    const double* d_state = st.in(state, (size_t)B * 5);
-    const double* d_vx = st.in(vx, (size_t)B);
-    const int* d_mi = st.in(min_index, (size_t)B);
-    double* d_steer = st.out(steer, (size_t)B, false);
-    double* d_u = st.out(u, (size_t)B * mpcff::kNu, false);
-    double* d_e = st.out(e_rr, (size_t)B * 4, false);
-    double* d_k = st.out(k_r, (size_t)B, false);
-    int* d_mo = st.out(min_index_out, (size_t)B, false);
-    double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
-    double* d_H = st.out(H, (size_t)B * mpcff::kNu * mpcff::kNu, false);
-    double* d_f = st.out(f, (size_t)B * mpcff::kNu, false);
-    int* d_it = st.out(iters, (size_t)B, false);
-    int* d_st = st.out(status, (size_t)B, false);
-    if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, "mpc_ff_lateral", mpcff::mpc_ff_lateral_kernel,
-                              dim3((B + mpcff::kGroupsPerWave - 1) / mpcff::kGroupsPerWave), dim3(64), 0, B, max_path, mpc_params(p),
-                              d_path, d_np, d_state, d_vx, d_mi, d_steer, d_u, d_e, d_k, d_mo, d_pp, d_H, d_f, d_it, d_st))
-        return rc;
-    return st.finish();
+    return mpc_shaped_lateral(ctx, "mpc_ff_lateral", mpcff::mpc_ff_lateral_kernel, mpcff::kNu, p, B, max_path, target_path, n_path, state,
+                              vx, min_index, steer, u, e_rr, k_r, min_index_out, pre_pro, H, f, iters, status, where);
 }
 
 int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, int32_t B,
@@ -2494,9 +2491,9 @@ int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat
     if (const int rc = st.ready()) return rc;
     if (lateral == EMP_LAT_MPC) {
         if (const int rc = launch(ctx, "vehicle_control", mpc::mpc_lateral_kernel<true>,
-                                  dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave), dim3(64), 0, B, max_path, mpc_params(lat),
-                                  d_path, d_np, d_state, d_vx, d_mi, d_lat, (double*)nullptr, d_e, d_k, d_mo, d_pp, (double*)nullptr,
-                                  (double*)nullptr, (int*)nullptr, d_st, io))
+                                  grid_groups(B, mpc::kGroupsPerWave), dim3(64), 0, B, max_path, mpc_params(lat), d_path, d_np, d_state,
+                                  d_vx, d_mi, d_lat, (double*)nullptr, d_e, d_k, d_mo, d_pp, (double*)nullptr, (double*)nullptr,
+                                  (int*)nullptr, d_st, io))
             return rc;
     } else {
         if (const int rc = launch(ctx, "vehicle_control", lqr::lqr_lateral_kernel<true>, grid1(B, 64), dim3(64), 0, B, max_path,
@@ -2520,8 +2517,8 @@ ctl::VehicleParams vehicle_params(const emp_vehicle_params* p) {
 int launch_rollout(emp_ctx* ctx, int lateral, const emp_mpc_params* lat, int B, int max_path, const double* d_path, const int* d_np,
                    const rollout::IO& io) {
     if (lateral == EMP_LAT_MPC)
-        return launch(ctx, "rollout", rollout::mpc_rollout_kernel, dim3((B + mpc::kGroupsPerWave - 1) / mpc::kGroupsPerWave), dim3(64), 0,
-                      B, max_path, mpc_params(lat), d_path, d_np, io);
+        return launch(ctx, "rollout", rollout::mpc_rollout_kernel, grid_groups(B, mpc::kGroupsPerWave), dim3(64), 0, B, max_path,
+                      mpc_params(lat), d_path, d_np, io);
     return launch(ctx, "rollout", rollout::lqr_rollout_kernel, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(lat), d_path, d_np, io);
 }
 

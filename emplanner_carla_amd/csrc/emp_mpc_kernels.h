@@ -88,7 +88,7 @@ __device__ inline bool inverse4(const M4& A, M4* out) {
     return true;
 }
 
-// value of lane `k` of MY 12-lane group
+// value of lane `k` of MY group (the group whose first lane is group_base)
 __device__ __forceinline__ double grp_bcast(double v, int group_base, int k) {
     union { double d; int i[2]; } a, r;
     a.d = v;
@@ -97,25 +97,31 @@ __device__ __forceinline__ double grp_bcast(double v, int group_base, int k) {
     r.i[1] = __builtin_amdgcn_ds_bpermute(src, a.i[1]);
     return r.d;
 }
-template <class Op>
+__device__ __forceinline__ int grp_bcast_int(int v, int group_base, int k) {
+    return __builtin_amdgcn_ds_bpermute((group_base + k) << 2, v);
+}
+// over the NU lanes of MY group, in lane order
+template <int NU, class Op>
 __device__ __forceinline__ double grp_reduce(double v, int group_base, Op op) {
     double acc = grp_bcast(v, group_base, 0);
 #pragma unroll
-    for (int k = 1; k < kNu; ++k) acc = op(acc, grp_bcast(v, group_base, k));
+    for (int k = 1; k < NU; ++k) acc = op(acc, grp_bcast(v, group_base, k));
     return acc;
 }
 
-// Dense box QP  min 1/2 u'Hu + f'u, -1 <= u <= 1  on one 12-lane group: lane r holds row r of H (h[]) and f_r.
-// Same interior point as smooth_pair_lanes (emp_qp_wave.h): G = I, so a row IS its unknown.
+// Dense box QP  min 1/2 u'Hu + f'u, -1 <= u <= 1  on one group of NU lanes: lane r holds row r of H (h[]) and f_r.
+// Same interior point as smooth_pair_lanes (emp_qp_wave.h): G = I, so a row IS its unknown.  H may be singular (the
+// feed-forward law's is): M = H + diag(wu + wl) stays positive definite because the barrier weights are.
 // Returns 0 ok / 2 failed (group-uniform); u_out = this lane's control.
-__device__ inline int box_qp_full12(const double (&h)[kNu], double f_r, int r, int gb, bool live, double* u_out, int* iters_out) {
+template <int NU>
+__device__ inline int box_qp_full(const double (&h)[NU], double f_r, int r, int gb, bool live, double* u_out, int* iters_out) {
     const double eps_p = 1e-10, eps_mu = 1e-13, eps_d_rel = 1e-10;
     const double lo = -1.0, hi = 1.0;
     double u = 0.0, su = 1.0, sl = 1.0, zu = 1.0, zl = 1.0;          // slacks of the centre of the box are already 1
-    const double qscale = fmax(1.0, grp_reduce(fabs(f_r), gb, [](double a, double b) { return fmax(a, b); }));
+    const double qscale = fmax(1.0, grp_reduce<NU>(fabs(f_r), gb, [](double a, double b) { return fmax(a, b); }));
     int state = live ? 1 : 0, iters = 0;
     bool acceptable = false;
-    const int rows = 2 * kNu;
+    const int rows = 2 * NU;
     while (__any(state == 1)) {
         const bool run = state == 1;
         const double rpu = u - hi + su, rpl = lo - u + sl;
@@ -123,12 +129,12 @@ __device__ inline int box_qp_full12(const double (&h)[kNu], double f_r, int r, i
         const double wu = zu * isu, wl = zl * isl;
         double hu = 0.0;
 #pragma unroll
-        for (int c = 0; c < kNu; ++c) hu = __builtin_fma(h[c], grp_bcast(u, gb, c), hu);
+        for (int c = 0; c < NU; ++c) hu = __builtin_fma(h[c], grp_bcast(u, gb, c), hu);
         const double rd = (hu + f_r) + (zu - zl);
-        const double rd_max = grp_reduce(fabs(rd), gb, [](double a, double b) { return fmax(a, b); });
-        const double rp_max = grp_reduce(fmax(fabs(rpu), fabs(rpl)), gb, [](double a, double b) { return fmax(a, b); });
-        const double zmax = grp_reduce(fmax(zu, zl), gb, [](double a, double b) { return fmax(a, b); });
-        const double mu = grp_reduce(su * zu + sl * zl, gb, [](double a, double b) { return a + b; }) / (double)rows;
+        const double rd_max = grp_reduce<NU>(fabs(rd), gb, [](double a, double b) { return fmax(a, b); });
+        const double rp_max = grp_reduce<NU>(fmax(fabs(rpu), fabs(rpl)), gb, [](double a, double b) { return fmax(a, b); });
+        const double zmax = grp_reduce<NU>(fmax(zu, zl), gb, [](double a, double b) { return fmax(a, b); });
+        const double mu = grp_reduce<NU>(su * zu + sl * zl, gb, [](double a, double b) { return a + b; }) / (double)rows;
         if (run) {
             const double dscale = fmax(qscale, zmax);
             if (rd_max <= eps_d_rel * dscale && rp_max <= eps_p && mu <= eps_mu) state = 0;
@@ -139,24 +145,24 @@ __device__ inline int box_qp_full12(const double (&h)[kNu], double f_r, int r, i
         const bool go = state == 1;
         // ---- dense Cholesky of M = H + diag(wu + wl): lane r keeps row r; after step k its entry k is L[r][k]
         // (r > k) and lane k's entries j > k are U[k][j] = L[j][k]
-        double a[kNu], rinv = 1.0;
+        double a[NU], rinv = 1.0;
 #pragma unroll
-        for (int c = 0; c < kNu; ++c) a[c] = go ? h[c] : ((c == r) ? 1.0 : 0.0);
+        for (int c = 0; c < NU; ++c) a[c] = go ? h[c] : ((c == r) ? 1.0 : 0.0);
 #pragma unroll
-        for (int c = 0; c < kNu; ++c)
+        for (int c = 0; c < NU; ++c)
             if (c == r && go) a[c] += wu + wl;
         bool bad = false;
 #pragma unroll
-        for (int k = 0; k < kNu; ++k) {
-            double rowk[kNu];
+        for (int k = 0; k < NU; ++k) {
+            double rowk[NU];
 #pragma unroll
-            for (int j = k; j < kNu; ++j) rowk[j] = grp_bcast(a[j], gb, k);
+            for (int j = k; j < NU; ++j) rowk[j] = grp_bcast(a[j], gb, k);
             const double piv = rowk[k];
             if (!(piv > 0.0)) bad = true;
             const double rs = fast_rsqrt(piv > 0.0 ? piv : 1.0);
             const double lik = a[k] * rs;                       // column-k entry of my row, scaled (symmetry: = U[k][r])
 #pragma unroll
-            for (int j = k + 1; j < kNu; ++j) {
+            for (int j = k + 1; j < NU; ++j) {
                 const double ukj = rowk[j] * rs;
                 if (r > k) a[j] = __builtin_fma(-lik, ukj, a[j]);
                 else if (r == k) a[j] = ukj;
@@ -168,13 +174,13 @@ __device__ inline int box_qp_full12(const double (&h)[kNu], double f_r, int r, i
         const bool go2 = state == 1;
         auto solve = [&](double b) {
 #pragma unroll
-            for (int k = 0; k < kNu; ++k) {                     // L y = b
+            for (int k = 0; k < NU; ++k) {                     // L y = b
                 const double yk = grp_bcast(b * rinv, gb, k);
                 if (r == k) b = yk;
                 else if (r > k) b = __builtin_fma(-a[k], yk, b);
             }
 #pragma unroll
-            for (int k = kNu - 1; k >= 0; --k) {                // L' x = y
+            for (int k = NU - 1; k >= 0; --k) {                // L' x = y
                 const double xk = grp_bcast(b * rinv, gb, k);
                 if (r == k) b = xk;
                 else if (r < k) b = __builtin_fma(-a[k], xk, b);
@@ -185,10 +191,10 @@ __device__ inline int box_qp_full12(const double (&h)[kNu], double f_r, int r, i
         const double dsua = -rpu - dua, dsla = -rpl + dua;
         const double dzua = -zu - wu * dsua, dzla = -zl - wl * dsla;
         double ratio = go2 ? fmax(fmax(-dsua * isu, -dsla * isl), fmax(-dzua * izu, -dzla * izl)) : 0.0;
-        ratio = grp_reduce(ratio, gb, [](double x, double y) { return fmax(x, y); });
+        ratio = grp_reduce<NU>(ratio, gb, [](double x, double y) { return fmax(x, y); });
         const double a_aff = (ratio > 1.0) ? fast_rcp(ratio) : 1.0;
         double mu_aff = go2 ? (su + a_aff * dsua) * (zu + a_aff * dzua) + (sl + a_aff * dsla) * (zl + a_aff * dzla) : 0.0;
-        mu_aff = grp_reduce(mu_aff, gb, [](double x, double y) { return x + y; }) / (double)rows;
+        mu_aff = grp_reduce<NU>(mu_aff, gb, [](double x, double y) { return x + y; }) / (double)rows;
         double sigma = (mu > 0.0) ? mu_aff * fast_rcp(mu) : 0.0;
         sigma = sigma * sigma * sigma;
         const double rcu = su * zu + dsua * dzua - sigma * mu, rcl = sl * zl + dsla * dzla - sigma * mu;
@@ -196,7 +202,7 @@ __device__ inline int box_qp_full12(const double (&h)[kNu], double f_r, int r, i
         const double dsu = -rpu - du, dsl = -rpl + du;
         const double dzu = -(rcu + zu * dsu) * isu, dzl = -(rcl + zl * dsl) * isl;
         ratio = go2 ? fmax(fmax(-dsu * isu, -dsl * isl), fmax(-dzu * izu, -dzl * izl)) : 0.0;
-        ratio = grp_reduce(ratio, gb, [](double x, double y) { return fmax(x, y); });
+        ratio = grp_reduce<NU>(ratio, gb, [](double x, double y) { return fmax(x, y); });
         const double tau = qp_step_fraction(mu);
         const double alpha = (ratio > tau) ? tau * fast_rcp(ratio) : 1.0;
         if (go2) {
@@ -258,52 +264,45 @@ struct LatResult {
     int idx, iters, status;        // match index, QP iterations / Riccati sweeps, status bits
 };
 
-// ref: Lateral_MPC_controller._control (:313-337) for the vehicle of MY 12-lane group (lane r of the group at lane gb), from its
-// state in registers: the body of mpc_lateral_kernel and of a tick of mpc_rollout_kernel.  `path` is the vehicle's row, np_ its
-// clamped count, idx the previous match.  h, *f_r_out, *u_out: row r of H, f_r and control r (lane-local); *o is group-uniform.
-__device__ __forceinline__ void mpc_lateral_core(const Params& prm, const double* __restrict__ path, int np_, double x, double y,
-                                                 double fi, double Vy, double fi_dot, double Vx, int idx, bool live, int r, int gb,
-                                                 double (&h)[kNu], double* f_r_out, double* u_out, LatResult* o) {
-    // ---- continuous error model (ref :115-148)
+// ---- what the three lateral laws (mpc_lateral_core, lqr::lqr_lateral_core, mpcff::mpc_ff_lateral_core) share.  Each core reads
+// top to bottom as: model, predict, match, error, discretise, problem or Riccati, solve, outputs.
+
+// continuous error model of cal_A_B_C_fun (ref :115-148, :424-455, :778-809).  V is the velocity that divides: the clamped Vx
+// for the MPC, Vx + 0.0001 for the other two.  The LQR has no Cc.
+__device__ __forceinline__ void error_model(const Params& prm, double V, M4* A_out, V4* Bc, V4* Cc) {
     M4 A;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) A.a[i][j] = 0.0;
     A.a[0][1] = 1.0;
-    A.a[1][1] = (prm.Cf + prm.Cr) / (prm.m * Vx);
+    A.a[1][1] = (prm.Cf + prm.Cr) / (prm.m * V);
     A.a[1][2] = -(prm.Cf + prm.Cr) / prm.m;
-    A.a[1][3] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.m * Vx);
+    A.a[1][3] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.m * V);
     A.a[2][3] = 1.0;
-    A.a[3][1] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.Iz * Vx);
+    A.a[3][1] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.Iz * V);
     A.a[3][2] = -(prm.a * prm.Cf - prm.b * prm.Cr) / prm.Iz;
-    A.a[3][3] = (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * Vx);
-    const V4 Bc{{0.0, -prm.Cf / prm.m, 0.0, -prm.a * prm.Cf / prm.Iz}};
-    const V4 Cc{{0.0, (prm.a * prm.Cf + prm.b * prm.Cr) / (prm.m * Vx) - Vx, 0.0,
-                 (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * Vx)}};
-    // ---- prediction and tracking error (ref :170-251, ts = 0.1)
-    {
-        const double c = cos(fi), s = sin(fi);
-        const double xn = x + Vx * kTs * c - Vy * kTs * s;
-        const double yn = y + Vy * kTs * c + Vx * kTs * s;
-        x = xn;
-        y = yn;
-        fi = fi + fi_dot * kTs;
-    }
-    bool bad_index = live && (np_ < 1 || idx < 0 || idx >= np_);   // the reference raises IndexError at :224
-    if (bad_index || !live) idx = 0;                               // (an idle group follows no index at all)
-    {
-        double min_d = 10000.0;                                     // squared metres (ref :201): farther than 100 m
-        const int first = idx, last = min(first + kWindow, np_);    // keeps the previous match
-        for (int i = first; i < last; ++i) {
-            const double dx = path[4 * i] - x, dy = path[4 * i + 1] - y;
-            const double d = dx * dx + dy * dy;
-            if (d < min_d) {
-                min_d = d;
-                idx = i;
-            }
-        }
-    }
+    A.a[3][3] = (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * V);
+    *A_out = A;
+    *Bc = V4{{0.0, -prm.Cf / prm.m, 0.0, -prm.a * prm.Cf / prm.Iz}};
+    *Cc = V4{{0.0, (prm.a * prm.Cf + prm.b * prm.Cr) / (prm.m * V) - V, 0.0,
+              (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * V)}};
+}
+
+// the pose kTs ahead (cal_error_k_fun(ts = 0.1), ref :170-180): always with the law's own Vx, never the guarded one
+__device__ __forceinline__ void predict_pose(double Vx, double Vy, double fi_dot, double* x, double* y, double* fi) {
+    const double c = cos(*fi), s = sin(*fi);
+    const double xn = *x + Vx * kTs * c - Vy * kTs * s;
+    const double yn = *y + Vy * kTs * c + Vx * kTs * s;
+    *x = xn;
+    *y = yn;
+    *fi = *fi + fi_dot * kTs;
+}
+
+// tracking error of the predicted pose (x, y, fi) at path point idx (ref :226-251): o's e_rr, pk, pre and idx.
+// raw_e_fi: e_fi is the angle fi - theta_r itself (the feed-forward law, ref :889), not its sine.
+__device__ __forceinline__ void tracking_error(const double* __restrict__ path, int idx, double x, double y, double fi, double Vx,
+                                               double Vy, double fi_dot, bool raw_e_fi, LatResult* o) {
     const double px = path[4 * idx], py = path[4 * idx + 1], pth = path[4 * idx + 2], pk = path[4 * idx + 3];
     const double ct = cos(pth), st = sin(pth);
     const double dvx = x - px, dvy = y - py;
@@ -312,11 +311,21 @@ __device__ __forceinline__ void mpc_lateral_core(const Params& prm, const double
     const double theta_r = pth + pk * e_s;
     const double cd = cos(fi - theta_r), sd = sin(fi - theta_r);
     const double e_d_dot = Vy * cd + Vx * sd;
-    const double e_fi = sd;
+    const double e_fi = raw_e_fi ? fi - theta_r : sd;
     const double S_dot = (Vx * cd - Vy * sd) / (1.0 - pk * e_d);
     const double e_fi_dot = fi_dot - pk * S_dot;
-    const V4 e_rr{{e_d, e_d_dot, e_fi, e_fi_dot}};
-    // ---- bilinear discretisation (ref :159-165)
+    o->e_rr = V4{{e_d, e_d_dot, e_fi, e_fi_dot}};
+    o->pk = pk;
+    o->pre[0] = x;
+    o->pre[1] = y;
+    o->pre[2] = px + e_s * ct;
+    o->pre[3] = py + e_s * st;
+    o->idx = idx;
+}
+
+// bilinear discretisation (ref :159-165): A_bar = inv (I + kTs A / 2), B_bar = inv Bc kTs with inv = (I - kTs A / 2)^-1.
+// Returns false where that inverse does not exist.
+__device__ __forceinline__ bool discretise(const M4& A, const V4& Bc, M4* inv_out, M4* Ab_out, V4* Bb_out) {
     M4 lhs, rhs, inv;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -333,23 +342,37 @@ __device__ __forceinline__ void mpc_lateral_core(const Params& prm, const double
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             Ab.a[i][j] = ((inv.a[i][0] * rhs.a[0][j] + inv.a[i][1] * rhs.a[1][j]) + inv.a[i][2] * rhs.a[2][j]) + inv.a[i][3] * rhs.a[3][j];
-    V4 Bb = matvec(inv, Bc), Cb = matvec(inv, Cc);
+    V4 Bb = matvec(inv, Bc);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        Bb.v[i] = Bb.v[i] * kTs;
-        Cb.v[i] = Cb.v[i] * kTs * pk * Vx;
-    }
-    // ---- condensed problem (ref :262-298): g_t = A_bar^t B_bar, free response w_i = A_bar^i e_rr + Cc_i
-    V4 g[kN];
+    for (int i = 0; i < 4; ++i) Bb.v[i] = Bb.v[i] * kTs;
+    *inv_out = inv;
+    *Ab_out = Ab;
+    *Bb_out = Bb;
+    return inv_ok;
+}
+// ... and the MPCs' C_bar = inv Cc kTs k_r Vx (ref :164, :821), with discretise's inv
+__device__ __forceinline__ V4 discretise_offset(const M4& inv, const V4& Cc, double pk, double Vx) {
+    V4 Cb = matvec(inv, Cc);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) Cb.v[i] = Cb.v[i] * kTs * pk * Vx;
+    return Cb;
+}
+
+// condensed problem of N steps x P controls per step (ref :262-298, :924-948) for the lane that owns control r: row r of H and
+// f_r, with g_t = A_bar^t B_bar and the free response w_i = A_bar^i e_rr + Cc_i.  R_bar regularises controls 0 .. n_reg - 1.
+template <int N, int P>
+__device__ __forceinline__ void condensed_row(const Params& prm, const M4& Ab, const V4& Bb, const V4& Cb, const V4& e_rr, int r,
+                                              int n_reg, double (&h)[N * P], double* f_r_out) {
+    V4 g[N];
     g[0] = Bb;
 #pragma unroll
-    for (int t = 1; t < kN; ++t) g[t] = matvec(Ab, g[t - 1]);
-    V4 w[kN + 1];
+    for (int t = 1; t < N; ++t) g[t] = matvec(Ab, g[t - 1]);
+    V4 w[N + 1];
     {
         V4 me = e_rr, cc{{0.0, 0.0, 0.0, 0.0}};
         w[0] = me;
 #pragma unroll
-        for (int i = 1; i <= kN; ++i) {
+        for (int i = 1; i <= N; ++i) {
             me = matvec(Ab, me);
             cc = matvec(Ab, cc);
 #pragma unroll
@@ -359,50 +382,75 @@ __device__ __forceinline__ void mpc_lateral_core(const Params& prm, const double
             }
         }
     }
-    const int jr = r / kP;
+    const int jr = r / P;
     double f_r = 0.0;
 #pragma unroll
-    for (int c = 0; c < kNu; ++c) {
-        const int jc = c / kP;
+    for (int c = 0; c < N * P; ++c) {
+        const int jc = c / P;
         double acc = 0.0;
 #pragma unroll
-        for (int i = 1; i <= kN; ++i) {
+        for (int i = 1; i <= N; ++i) {
             // block row i of C holds A_bar^(i-1-j) B_bar in the P columns of step j < i (ref :268-273)
             if (i - 1 - jr < 0 || i - 1 - jc < 0) continue;
-            const double* wt = (i == kN) ? prm.f : prm.q;
+            const double* wt = (i == N) ? prm.f : prm.q;
             const V4& ga = g[(i - 1 - jr) < 0 ? 0 : (i - 1 - jr)];
             const V4& gc = g[i - 1 - jc];
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc += ga.v[q] * wt[q] * gc.v[q];
         }
-        if (c == r) acc += prm.r;
+        if (c == r && c < n_reg) acc += prm.r;
         h[c] = 2.0 * acc;
     }
 #pragma unroll
-    for (int i = 1; i <= kN; ++i) {
+    for (int i = 1; i <= N; ++i) {
         if (i - 1 - jr < 0) continue;
-        const double* wt = (i == kN) ? prm.f : prm.q;
+        const double* wt = (i == N) ? prm.f : prm.q;
         const V4& ga = g[(i - 1 - jr) < 0 ? 0 : (i - 1 - jr)];
 #pragma unroll
         for (int q = 0; q < 4; ++q) f_r += ga.v[q] * wt[q] * w[i].v[q];
     }
-    f_r = 2.0 * f_r;
+    *f_r_out = 2.0 * f_r;
+}
+
+// ref: Lateral_MPC_controller._control (:313-337) for the vehicle of MY 12-lane group (lane r of the group at lane gb), from its
+// state in registers: the body of mpc_lateral_kernel and of a tick of mpc_rollout_kernel.  `path` is the vehicle's row, np_ its
+// clamped count, idx the previous match.  h, *f_r_out, *u_out: row r of H, f_r and control r (lane-local); *o is group-uniform.
+__device__ __forceinline__ void mpc_lateral_core(const Params& prm, const double* __restrict__ path, int np_, double x, double y,
+                                                 double fi, double Vy, double fi_dot, double Vx, int idx, bool live, int r, int gb,
+                                                 double (&h)[kNu], double* f_r_out, double* u_out, LatResult* o) {
+    M4 A, inv, Ab;
+    V4 Bc, Cc, Bb;
+    error_model(prm, Vx, &A, &Bc, &Cc);
+    predict_pose(Vx, Vy, fi_dot, &x, &y, &fi);
+    // ---- match (ref :201-224): a 50-point window from the previous index
+    bool bad_index = live && (np_ < 1 || idx < 0 || idx >= np_);   // the reference raises IndexError at :224
+    if (bad_index || !live) idx = 0;                               // (an idle group follows no index at all)
+    {
+        double min_d = 10000.0;                                     // squared metres (ref :201): farther than 100 m
+        const int first = idx, last = min(first + kWindow, np_);    // keeps the previous match
+        for (int i = first; i < last; ++i) {
+            const double dx = path[4 * i] - x, dy = path[4 * i + 1] - y;
+            const double d = dx * dx + dy * dy;
+            if (d < min_d) {
+                min_d = d;
+                idx = i;
+            }
+        }
+    }
+    tracking_error(path, idx, x, y, fi, Vx, Vy, fi_dot, false, o);
+    const bool inv_ok = discretise(A, Bc, &inv, &Ab, &Bb);
+    const V4 Cb = discretise_offset(inv, Cc, o->pk, Vx);
+    double f_r;
+    condensed_row<kN, kP>(prm, Ab, Bb, Cb, o->e_rr, r, kNu, h, &f_r);
     // ---- box QP (ref :300-311) and outputs
     const bool solvable = live && !bad_index && inv_ok;
     double u = 0.0;
     int it = 0;
-    const int rc = box_qp_full12(h, f_r, r, gb, solvable, &u, &it);
+    const int rc = box_qp_full<kNu>(h, f_r, r, gb, solvable, &u, &it);
     const bool ok = solvable && rc == 0;
     *f_r_out = f_r;
     *u_out = ok ? u : 0.0;
     o->steer = grp_bcast(ok ? u : 0.0, gb, 0);                    // ref :311: res['x'][0]
-    o->e_rr = e_rr;
-    o->pk = pk;
-    o->pre[0] = x;
-    o->pre[1] = y;
-    o->pre[2] = px + e_s * ct;
-    o->pre[3] = py + e_s * st;
-    o->idx = idx;
     o->iters = it;
     o->status = bad_index ? kStSOutOfRange : ((!inv_ok || rc != 0) ? kStQpFailed : 0);
 }
@@ -483,37 +531,11 @@ __device__ __forceinline__ M4 matmul(const M4& A, const M4& B) {
 __device__ __forceinline__ void lqr_lateral_core(const mpc::Params& prm, const double* __restrict__ path, int np_, double x, double y,
                                                  double fi, double Vy, double fi_dot, double Vx, int idx, V4* K_out,
                                                  mpc::LatResult* o) {
-    // ---- continuous model (ref :424-455): Vx + 0.0001 guards the divisions
-    const double Vg = Vx + 0.0001;
-    M4 A;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) A.a[i][j] = 0.0;
-    A.a[0][1] = 1.0;
-    A.a[1][1] = (prm.Cf + prm.Cr) / (prm.m * Vg);
-    A.a[1][2] = -(prm.Cf + prm.Cr) / prm.m;
-    A.a[1][3] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.m * Vg);
-    A.a[2][3] = 1.0;
-    A.a[3][1] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.Iz * Vg);
-    A.a[3][2] = -(prm.a * prm.Cf - prm.b * prm.Cr) / prm.Iz;
-    A.a[3][3] = (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * Vg);
-    const V4 Bc{{0.0, -prm.Cf / prm.m, 0.0, -prm.a * prm.Cf / prm.Iz}};
-    // ---- discretisation and Riccati iteration (ref :466-481)
-    M4 lhs, rhs, inv;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double e = (i == j) ? 1.0 : 0.0;
-            lhs.a[i][j] = e - (mpc::kTs * A.a[i][j]) / 2.0;
-            rhs.a[i][j] = e + (mpc::kTs * A.a[i][j]) / 2.0;
-        }
-    const bool inv_ok = mpc::inverse4(lhs, &inv);
-    const M4 Ad = matmul(inv, rhs);
-    V4 Bd = mpc::matvec(inv, Bc);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) Bd.v[i] = Bd.v[i] * mpc::kTs;
+    // ---- model (ref :424-455: Vx + 0.0001 guards the divisions), discretisation and Riccati iteration (ref :466-481)
+    M4 A, inv, Ad;
+    V4 Bc, Cc, Bd;
+    mpc::error_model(prm, Vx + 0.0001, &A, &Bc, &Cc);
+    const bool inv_ok = mpc::discretise(A, Bc, &inv, &Ad, &Bd);
     M4 AT;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -562,15 +584,8 @@ __device__ __forceinline__ void lqr_lateral_core(const mpc::Params& prm, const d
         for (int j = 0; j < 4; ++j)
             K.v[j] = g * (((BTP.v[0] * Ad.a[0][j] + BTP.v[1] * Ad.a[1][j]) + BTP.v[2] * Ad.a[2][j]) + BTP.v[3] * Ad.a[3][j]);
     }
-    // ---- prediction and tracking error (ref :488-567, ts = 0.1): nearest point over the whole path
-    {
-        const double c = cos(fi), s = sin(fi);
-        const double xn = x + Vx * mpc::kTs * c - Vy * mpc::kTs * s;
-        const double yn = y + Vy * mpc::kTs * c + Vx * mpc::kTs * s;
-        x = xn;
-        y = yn;
-        fi = fi + fi_dot * mpc::kTs;
-    }
+    mpc::predict_pose(Vx, Vy, fi_dot, &x, &y, &fi);
+    // ---- match (ref :519-535): the nearest point of the whole path
     {
         double min_d = 10000.0;
         for (int i = 0; i < np_; ++i) {
@@ -584,33 +599,17 @@ __device__ __forceinline__ void lqr_lateral_core(const mpc::Params& prm, const d
     }
     const bool bad_index = np_ < 1 || idx < 0 || idx >= np_;          // IndexError in the reference
     if (bad_index) idx = 0;
-    const double px = path[4 * idx], py = path[4 * idx + 1], pth = path[4 * idx + 2], pk = path[4 * idx + 3];
-    const double ct = cos(pth), st = sin(pth);
-    const double dvx = x - px, dvy = y - py;
-    const double e_d = -st * dvx + ct * dvy;
-    const double e_s = ct * dvx + st * dvy;
-    const double theta_r = pth + pk * e_s;
-    const double cd = cos(fi - theta_r), sd = sin(fi - theta_r);
-    const double e_d_dot = Vy * cd + Vx * sd;
-    const double e_fi = sd;
-    const double S_dot = (Vx * cd - Vy * sd) / (1.0 - pk * e_d);
-    const double e_fi_dot = fi_dot - pk * S_dot;
+    mpc::tracking_error(path, idx, x, y, fi, Vx, Vy, fi_dot, false, o);
     // ---- feed-forward (ref :569-583) and control (ref :606)
+    const V4& e = o->e_rr;
     const double K3 = K.v[2];
-    double delta_f = pk * (prm.a + prm.b - prm.b * K3 -
-                           (prm.b / prm.Cf + prm.a * K3 / prm.Cr - prm.a / prm.Cr) * (prm.m * Vx * Vx) / (prm.a + prm.b));
+    double delta_f = o->pk * (prm.a + prm.b - prm.b * K3 -
+                              (prm.b / prm.Cf + prm.a * K3 / prm.Cr - prm.a / prm.Cr) * (prm.m * Vx * Vx) / (prm.a + prm.b));
     delta_f = delta_f * 3.141592653589793 / 180.0;
-    const double u = -(((K.v[0] * e_d + K.v[1] * e_d_dot) + K.v[2] * e_fi) + K.v[3] * e_fi_dot) + delta_f;
+    const double u = -(((K.v[0] * e.v[0] + K.v[1] * e.v[1]) + K.v[2] * e.v[2]) + K.v[3] * e.v[3]) + delta_f;
     const bool ok = inv_ok && !bad_index;
     o->steer = ok ? u : 0.0;
     *K_out = K;
-    o->e_rr = V4{{e_d, e_d_dot, e_fi, e_fi_dot}};
-    o->pk = pk;
-    o->pre[0] = x;
-    o->pre[1] = y;
-    o->pre[2] = px + e_s * ct;
-    o->pre[3] = py + e_s * st;
-    o->idx = idx;
     o->iters = sweeps;
     o->status = bad_index ? kStSOutOfRange : (inv_ok ? 0 : kStQpFailed);
 }
@@ -669,176 +668,26 @@ namespace mpcff {
 using mpc::M4;
 using mpc::V4;
 using mpc::grp_bcast;
+using mpc::grp_bcast_int;
 
 constexpr int kN = 4, kP = 2, kNu = kN * kP;     // ref :737-739
 constexpr int kGroupsPerWave = 64 / kNu;
 constexpr int kRegularised = kP * kP;            // R_bar's blocks i < P (ref :939-940): controls 0..3
 
-__device__ __forceinline__ int grp_bcast_int(int v, int group_base, int k) {
-    return __builtin_amdgcn_ds_bpermute((group_base + k) << 2, v);
-}
-template <class Op>
-__device__ __forceinline__ double grp_reduce8(double v, int group_base, Op op) {
-    double acc = grp_bcast(v, group_base, 0);
-#pragma unroll
-    for (int k = 1; k < kNu; ++k) acc = op(acc, grp_bcast(v, group_base, k));
-    return acc;
-}
-
-// box_qp_full12 (the same Mehrotra interior point, G = I) on an 8-lane group.  H may be singular (see above): M = H +
-// diag(wu + wl) stays positive definite because the barrier weights are.  Returns 0 ok / 2 failed (group-uniform).
-__device__ inline int box_qp_full8(const double (&h)[kNu], double f_r, int r, int gb, bool live, double* u_out, int* iters_out) {
-    const double eps_p = 1e-10, eps_mu = 1e-13, eps_d_rel = 1e-10;
-    const double lo = -1.0, hi = 1.0;
-    double u = 0.0, su = 1.0, sl = 1.0, zu = 1.0, zl = 1.0;
-    const double qscale = fmax(1.0, grp_reduce8(fabs(f_r), gb, [](double a, double b) { return fmax(a, b); }));
-    int state = live ? 1 : 0, iters = 0;
-    bool acceptable = false;
-    const int rows = 2 * kNu;
-    while (__any(state == 1)) {
-        const bool run = state == 1;
-        const double rpu = u - hi + su, rpl = lo - u + sl;
-        const double isu = fast_rcp(su), isl = fast_rcp(sl), izu = fast_rcp(zu), izl = fast_rcp(zl);
-        const double wu = zu * isu, wl = zl * isl;
-        double hu = 0.0;
-#pragma unroll
-        for (int c = 0; c < kNu; ++c) hu = __builtin_fma(h[c], grp_bcast(u, gb, c), hu);
-        const double rd = (hu + f_r) + (zu - zl);
-        const double rd_max = grp_reduce8(fabs(rd), gb, [](double a, double b) { return fmax(a, b); });
-        const double rp_max = grp_reduce8(fmax(fabs(rpu), fabs(rpl)), gb, [](double a, double b) { return fmax(a, b); });
-        const double zmax = grp_reduce8(fmax(zu, zl), gb, [](double a, double b) { return fmax(a, b); });
-        const double mu = grp_reduce8(su * zu + sl * zl, gb, [](double a, double b) { return a + b; }) / (double)rows;
-        if (run) {
-            const double dscale = fmax(qscale, zmax);
-            if (rd_max <= eps_d_rel * dscale && rp_max <= eps_p && mu <= eps_mu) state = 0;
-            else if (!(mu == mu) || mu > 1e30 || (iters >= kQpStallIter && rp_max > kQpStallResidual)) state = 2;
-            else if (iters >= kQpMaxIter) state = acceptable ? 0 : 2;
-            if (rd_max <= 100.0 * eps_d_rel * dscale && rp_max <= 10.0 * eps_p && mu <= 1000.0 * eps_mu) acceptable = true;
-        }
-        const bool go = state == 1;
-        // dense Cholesky of M = H + diag(wu + wl), row r on lane r (box_qp_full12)
-        double a[kNu], rinv = 1.0;
-#pragma unroll
-        for (int c = 0; c < kNu; ++c) a[c] = go ? h[c] : ((c == r) ? 1.0 : 0.0);
-#pragma unroll
-        for (int c = 0; c < kNu; ++c)
-            if (c == r && go) a[c] += wu + wl;
-        bool bad = false;
-#pragma unroll
-        for (int k = 0; k < kNu; ++k) {
-            double rowk[kNu];
-#pragma unroll
-            for (int j = k; j < kNu; ++j) rowk[j] = grp_bcast(a[j], gb, k);
-            const double piv = rowk[k];
-            if (!(piv > 0.0)) bad = true;
-            const double rs = fast_rsqrt(piv > 0.0 ? piv : 1.0);
-            const double lik = a[k] * rs;
-#pragma unroll
-            for (int j = k + 1; j < kNu; ++j) {
-                const double ukj = rowk[j] * rs;
-                if (r > k) a[j] = __builtin_fma(-lik, ukj, a[j]);
-                else if (r == k) a[j] = ukj;
-            }
-            if (r >= k) a[k] = (r == k) ? piv * rs : lik;
-            if (r == k) rinv = rs;
-        }
-        if (go && bad) state = acceptable ? 0 : 2;
-        const bool go2 = state == 1;
-        auto solve = [&](double b) {
-#pragma unroll
-            for (int k = 0; k < kNu; ++k) {                     // L y = b
-                const double yk = grp_bcast(b * rinv, gb, k);
-                if (r == k) b = yk;
-                else if (r > k) b = __builtin_fma(-a[k], yk, b);
-            }
-#pragma unroll
-            for (int k = kNu - 1; k >= 0; --k) {                // L' x = y
-                const double xk = grp_bcast(b * rinv, gb, k);
-                if (r == k) b = xk;
-                else if (r < k) b = __builtin_fma(-a[k], xk, b);
-            }
-            return b;
-        };
-        const double dua = solve(go2 ? -rd - ((wu * rpu - zu) - (wl * rpl - zl)) : 0.0);
-        const double dsua = -rpu - dua, dsla = -rpl + dua;
-        const double dzua = -zu - wu * dsua, dzla = -zl - wl * dsla;
-        double ratio = go2 ? fmax(fmax(-dsua * isu, -dsla * isl), fmax(-dzua * izu, -dzla * izl)) : 0.0;
-        ratio = grp_reduce8(ratio, gb, [](double x, double y) { return fmax(x, y); });
-        const double a_aff = (ratio > 1.0) ? fast_rcp(ratio) : 1.0;
-        double mu_aff = go2 ? (su + a_aff * dsua) * (zu + a_aff * dzua) + (sl + a_aff * dsla) * (zl + a_aff * dzla) : 0.0;
-        mu_aff = grp_reduce8(mu_aff, gb, [](double x, double y) { return x + y; }) / (double)rows;
-        double sigma = (mu > 0.0) ? mu_aff * fast_rcp(mu) : 0.0;
-        sigma = sigma * sigma * sigma;
-        const double rcu = su * zu + dsua * dzua - sigma * mu, rcl = sl * zl + dsla * dzla - sigma * mu;
-        const double du = solve(go2 ? -rd - ((zu * rpu - rcu) * isu - (zl * rpl - rcl) * isl) : 0.0);
-        const double dsu = -rpu - du, dsl = -rpl + du;
-        const double dzu = -(rcu + zu * dsu) * isu, dzl = -(rcl + zl * dsl) * isl;
-        ratio = go2 ? fmax(fmax(-dsu * isu, -dsl * isl), fmax(-dzu * izu, -dzl * izl)) : 0.0;
-        ratio = grp_reduce8(ratio, gb, [](double x, double y) { return fmax(x, y); });
-        const double tau = qp_step_fraction(mu);
-        const double alpha = (ratio > tau) ? tau * fast_rcp(ratio) : 1.0;
-        if (go2) {
-            su += alpha * dsu;
-            sl += alpha * dsl;
-            zu += alpha * dzu;
-            zl += alpha * dzl;
-            u += alpha * du;
-            ++iters;
-        }
-    }
-    *u_out = u;
-    *iters_out = iters;
-    return state;
-}
-
-// ref: Lateral_MPC__with_feedforward_controller.MPC_control (:972-990) for B vehicles; grid = ceil(B / 8), block = 64.
-__global__ __launch_bounds__(64) void mpc_ff_lateral_kernel(int B, int max_path, mpc::Params prm, const double* __restrict__ target_path,
-                                                            const int* __restrict__ n_path, const double* __restrict__ state,
-                                                            const double* __restrict__ vx, const int* __restrict__ min_index_in,
-                                                            double* __restrict__ steer, double* __restrict__ u_out,
-                                                            double* __restrict__ e_rr_out, double* __restrict__ k_r_out,
-                                                            int* __restrict__ min_index_out, double* __restrict__ pre_pro,
-                                                            double* __restrict__ H_out, double* __restrict__ f_out,
-                                                            int* __restrict__ iters_out, int* __restrict__ status) {
-    const int lane = threadIdx.x & 63;
-    const int grp = lane / kNu, r = lane - grp * kNu;
-    const int gb = grp * kNu;
-    const int b = blockIdx.x * kGroupsPerWave + grp;
-    const bool live = b < B;
-    const int bb = live ? b : 0;
-    // ---- vehicle state (cal_vehicle_info, ref :758-776: no clamp on Vx)
-    double x = state[5 * bb], y = state[5 * bb + 1], fi = state[5 * bb + 2];
-    const double Vy = state[5 * bb + 3], fi_dot = state[5 * bb + 4], Vx = vx[bb];
-    // ---- continuous model (cal_A_B_C_fun, ref :778-809): Vx + 0.0001 everywhere, the C terms included
-    const double Vg = Vx + 0.0001;
-    M4 A;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) A.a[i][j] = 0.0;
-    A.a[0][1] = 1.0;
-    A.a[1][1] = (prm.Cf + prm.Cr) / (prm.m * Vg);
-    A.a[1][2] = -(prm.Cf + prm.Cr) / prm.m;
-    A.a[1][3] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.m * Vg);
-    A.a[2][3] = 1.0;
-    A.a[3][1] = (prm.a * prm.Cf - prm.b * prm.Cr) / (prm.Iz * Vg);
-    A.a[3][2] = -(prm.a * prm.Cf - prm.b * prm.Cr) / prm.Iz;
-    A.a[3][3] = (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * Vg);
-    const V4 Bc{{0.0, -prm.Cf / prm.m, 0.0, -prm.a * prm.Cf / prm.Iz}};
-    const V4 Cc{{0.0, (prm.a * prm.Cf + prm.b * prm.Cr) / (prm.m * Vg) - Vg, 0.0,
-                 (prm.a * prm.a * prm.Cf + prm.b * prm.b * prm.Cr) / (prm.Iz * Vg)}};
-    // ---- prediction and tracking error (cal_error_k_fun(ts = 0.1), ref :827-912) with the raw Vx
-    {
-        const double c = cos(fi), s = sin(fi);
-        const double xn = x + Vx * mpc::kTs * c - Vy * mpc::kTs * s;
-        const double yn = y + Vy * mpc::kTs * c + Vx * mpc::kTs * s;
-        x = xn;
-        y = yn;
-        fi = fi + fi_dot * mpc::kTs;
-    }
-    const double* path = target_path + (size_t)bb * max_path * 4;
-    const int np_ = min(max(n_path[bb], 0), max_path);
-    int idx = min_index_in[bb];
+// ref: Lateral_MPC__with_feedforward_controller.MPC_control (:972-990) for the vehicle of MY 8-lane group (lane r of the group at
+// lane gb), from its state in registers (cal_vehicle_info, ref :758-776: no clamp on Vx): the body of mpc_ff_lateral_kernel.
+// Arguments as mpc_lateral_core's, idx being only the fallback match.  h, *f_r_out, *u_out: row r of H, f_r and control r
+// (lane-local).  *o is group-uniform but for o->steer, which like *u_out is this lane's control: the command, control 0, on the
+// group's lane 0, the lane that stores it.  No caller reads it on another lane, so it is not broadcast as mpc_lateral_core's is.
+__device__ __forceinline__ void mpc_ff_lateral_core(const mpc::Params& prm, const double* __restrict__ path, int np_, double x,
+                                                    double y, double fi, double Vy, double fi_dot, double Vx, int idx, bool live,
+                                                    int r, int gb, double (&h)[kNu], double* f_r_out, double* u_out,
+                                                    mpc::LatResult* o) {
+    M4 A, inv, Ab;
+    V4 Bc, Cc, Bb;
+    mpc::error_model(prm, Vx + 0.0001, &A, &Bc, &Cc);             // ref :778-809: guarded everywhere, the C terms included
+    mpc::predict_pose(Vx, Vy, fi_dot, &x, &y, &fi);                // with the raw Vx
+    // ---- match (ref :850-866): the whole path, lane r scanning points r, r + 8, ...
     {
         double best = 10000.0;                                      // squared metres (ref :851)
         int best_i = -1;
@@ -865,115 +714,63 @@ __global__ __launch_bounds__(64) void mpc_ff_lateral_kernel(int B, int max_path,
     }
     const bool bad_index = live && (np_ < 1 || idx < 0 || idx >= np_);  // IndexError in the reference
     if (bad_index || !live) idx = 0;
-    const double px = path[4 * idx], py = path[4 * idx + 1], pth = path[4 * idx + 2], pk = path[4 * idx + 3];
-    const double ct = cos(pth), st = sin(pth);
-    const double dvx = x - px, dvy = y - py;
-    const double e_d = -st * dvx + ct * dvy;
-    const double e_s = ct * dvx + st * dvy;
-    const double theta_r = pth + pk * e_s;
-    const double cd = cos(fi - theta_r), sd = sin(fi - theta_r);
-    const double e_d_dot = Vy * cd + Vx * sd;
-    const double e_fi = fi - theta_r;
-    const double S_dot = (Vx * cd - Vy * sd) / (1.0 - pk * e_d);
-    const double e_fi_dot = fi_dot - pk * S_dot;
-    const V4 e_rr{{e_d, e_d_dot, e_fi, e_fi_dot}};
-    // ---- bilinear discretisation (cal_discretized_matrix, ref :811-822)
-    M4 lhs, rhs, inv;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double e = (i == j) ? 1.0 : 0.0;
-            lhs.a[i][j] = e - (mpc::kTs * A.a[i][j]) / 2.0;
-            rhs.a[i][j] = e + (mpc::kTs * A.a[i][j]) / 2.0;
-        }
-    const bool inv_ok = mpc::inverse4(lhs, &inv);
-    M4 Ab;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            Ab.a[i][j] = ((inv.a[i][0] * rhs.a[0][j] + inv.a[i][1] * rhs.a[1][j]) + inv.a[i][2] * rhs.a[2][j]) + inv.a[i][3] * rhs.a[3][j];
-    V4 Bb = mpc::matvec(inv, Bc), Cb = mpc::matvec(inv, Cc);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        Bb.v[i] = Bb.v[i] * mpc::kTs;
-        Cb.v[i] = Cb.v[i] * mpc::kTs * pk * Vx;
-    }
-    // ---- condensed problem (cal_control_para_fun, ref :924-948): g_t = A_bar^t B_bar, w_i = A_bar^i e_rr + Cc_i
-    V4 g[kN];
-    g[0] = Bb;
-#pragma unroll
-    for (int t = 1; t < kN; ++t) g[t] = mpc::matvec(Ab, g[t - 1]);
-    V4 w[kN + 1];
-    {
-        V4 me = e_rr, cc{{0.0, 0.0, 0.0, 0.0}};
-        w[0] = me;
-#pragma unroll
-        for (int i = 1; i <= kN; ++i) {
-            me = mpc::matvec(Ab, me);
-            cc = mpc::matvec(Ab, cc);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                cc.v[q] += Cb.v[q];
-                w[i].v[q] = cc.v[q] + me.v[q];
-            }
-        }
-    }
-    const int jr = r / kP;
-    double h[kNu], f_r = 0.0;
-#pragma unroll
-    for (int c = 0; c < kNu; ++c) {
-        const int jc = c / kP;
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 1; i <= kN; ++i) {
-            if (i - 1 - jr < 0 || i - 1 - jc < 0) continue;     // block row i of C: A_bar^(i-1-j) B_bar in step j < i
-            const double* wt = (i == kN) ? prm.f : prm.q;
-            const V4& ga = g[(i - 1 - jr) < 0 ? 0 : (i - 1 - jr)];
-            const V4& gc = g[i - 1 - jc];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc += ga.v[q] * wt[q] * gc.v[q];
-        }
-        if (c == r && r < kRegularised) acc += prm.r;
-        h[c] = 2.0 * acc;
-    }
-#pragma unroll
-    for (int i = 1; i <= kN; ++i) {
-        if (i - 1 - jr < 0) continue;
-        const double* wt = (i == kN) ? prm.f : prm.q;
-        const V4& ga = g[(i - 1 - jr) < 0 ? 0 : (i - 1 - jr)];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) f_r += ga.v[q] * wt[q] * w[i].v[q];
-    }
-    f_r = 2.0 * f_r;
+    mpc::tracking_error(path, idx, x, y, fi, Vx, Vy, fi_dot, true, o);
+    const bool inv_ok = mpc::discretise(A, Bc, &inv, &Ab, &Bb);
+    const V4 Cb = mpc::discretise_offset(inv, Cc, o->pk, Vx);      // ref :821: k_r x the RAW Vx
+    double f_r;
+    mpc::condensed_row<kN, kP>(prm, Ab, Bb, Cb, o->e_rr, r, kRegularised, h, &f_r);
     // ---- box QP (ref :950-970) and outputs
     const bool solvable = live && !bad_index && inv_ok;
     double u = 0.0;
     int it = 0;
-    const int rc = box_qp_full8(h, f_r, r, gb, solvable, &u, &it);
+    const int rc = mpc::box_qp_full<kNu>(h, f_r, r, gb, solvable, &u, &it);
+    const bool ok = solvable && rc == 0;
+    *f_r_out = f_r;
+    *u_out = ok ? u : 0.0;
+    o->steer = ok ? u : 0.0;                                      // ref :990: res['x'][0], on lane 0
+    o->iters = it;
+    o->status = bad_index ? kStSOutOfRange : ((!inv_ok || rc != 0) ? kStQpFailed : 0);
+}
+
+// ref: Lateral_MPC__with_feedforward_controller.MPC_control (:972-990) for B vehicles; grid = ceil(B / 8), block = 64.
+__global__ __launch_bounds__(64) void mpc_ff_lateral_kernel(int B, int max_path, mpc::Params prm, const double* __restrict__ target_path,
+                                                            const int* __restrict__ n_path, const double* __restrict__ state,
+                                                            const double* __restrict__ vx, const int* __restrict__ min_index_in,
+                                                            double* __restrict__ steer, double* __restrict__ u_out,
+                                                            double* __restrict__ e_rr_out, double* __restrict__ k_r_out,
+                                                            int* __restrict__ min_index_out, double* __restrict__ pre_pro,
+                                                            double* __restrict__ H_out, double* __restrict__ f_out,
+                                                            int* __restrict__ iters_out, int* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int grp = lane / kNu, r = lane - grp * kNu;
+    const int gb = grp * kNu;
+    const int b = blockIdx.x * kGroupsPerWave + grp;
+    const bool live = b < B;
+    const int bb = live ? b : 0;
+    double h[kNu], f_r, u;
+    mpc::LatResult o;
+    // a count beyond the path's row is clamped, never followed
+    mpc_ff_lateral_core(prm, target_path + (size_t)bb * max_path * 4, min(max(n_path[bb], 0), max_path), state[5 * bb],
+                        state[5 * bb + 1], state[5 * bb + 2], state[5 * bb + 3], state[5 * bb + 4], vx[bb], min_index_in[bb], live, r,
+                        gb, h, &f_r, &u, &o);
     if (live) {
-        const bool ok = solvable && rc == 0;
         if (H_out)
 #pragma unroll
             for (int c = 0; c < kNu; ++c) H_out[((size_t)b * kNu + r) * kNu + c] = h[c];
         if (f_out) f_out[(size_t)b * kNu + r] = f_r;
-        if (u_out) u_out[(size_t)b * kNu + r] = ok ? u : 0.0;
+        if (u_out) u_out[(size_t)b * kNu + r] = u;
         if (r == 0) {
-            steer[b] = ok ? u : 0.0;                              // ref :990: res['x'][0]
+            steer[b] = o.steer;
             if (e_rr_out)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) e_rr_out[4 * b + q] = e_rr.v[q];
-            if (k_r_out) k_r_out[b] = pk;
-            min_index_out[b] = idx;
-            if (pre_pro) {
-                pre_pro[4 * b] = x;
-                pre_pro[4 * b + 1] = y;
-                pre_pro[4 * b + 2] = px + e_s * ct;
-                pre_pro[4 * b + 3] = py + e_s * st;
-            }
-            if (iters_out) iters_out[b] = it;
-            status[b] = bad_index ? kStSOutOfRange : ((!inv_ok || rc != 0) ? kStQpFailed : 0);
+                for (int q = 0; q < 4; ++q) e_rr_out[4 * b + q] = o.e_rr.v[q];
+            if (k_r_out) k_r_out[b] = o.pk;
+            min_index_out[b] = o.idx;
+            if (pre_pro)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pre_pro[4 * b + q] = o.pre[q];
+            if (iters_out) iters_out[b] = o.iters;
+            status[b] = o.status;
         }
     }
 }
