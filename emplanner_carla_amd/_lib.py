@@ -105,6 +105,16 @@ class DriveParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class RolloutTimedIO(C.Structure):
+    """emp_rollout_timed_io: emp_rollout's arrays, the timed trajectory, the clock and the cursor."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "target_path", "n_path", "state", "min_index", "target_speed", "err_in", "n_err_in", "trajectory", "t0", "cursor_in",
+        "state_out", "min_index_out", "err_out", "n_err_out", "status", "fail_tick", "cursor_out", "tgt_status",
+        "log_state", "log_control", "log_err", "log_index", "log_target")] + [("reserved", C.c_int32)]
+
+
+TGT_BEFORE, TGT_PAST, TGT_NO_PROFILE, TGT_CAPPED = 1, 2, 4, 8     # EMP_TGT_*
+TIMED_POINTS = 401                 # EMP_TIMED_POINTS
 DRIVE_MAX_PERIODS = 4096           # EMP_DRIVE_MAX_PERIODS
 DRV_TRUNCATED = 1                  # EMP_DRV_TRUNCATED
 ROLLOUT_MAX_TICKS = 65536          # EMP_ROLLOUT_MAX_TICKS
@@ -234,6 +244,9 @@ PROTOTYPES = {
     "emp_vehicle_step": (C.c_int, [_vp, C.POINTER(VehicleParams), _i32] + [_vp] * 6 + [C.c_int]),
     "emp_rollout": (C.c_int, [_vp, _i32, C.POINTER(MpcParams), C.POINTER(PidParams), C.POINTER(VehicleParams), _i32, _i32]
                     + [_vp] * 7 + [_i32, _i32] + [_vp] * 10 + [C.c_int]),
+    "emp_speed_target": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _f64] + [_vp] * 5 + [C.c_int]),
+    "emp_rollout_timed": (C.c_int, [_vp, _i32, C.POINTER(MpcParams), C.POINTER(PidParams), C.POINTER(VehicleParams)] + [_i32] * 5
+                          + [C.POINTER(RolloutTimedIO), C.c_int]),
     "emp_drive_params_default": (None, [C.POINTER(DriveParams)]),
     "emp_drive_request": (C.c_int, [_vp, C.POINTER(DriveParams), _i32, _i32, _i32, _i32] + [_vp] * 18 + [C.c_int]),
     "emp_drive": (C.c_int, [_vp, C.POINTER(DpParams), C.POINTER(QpParams), C.POINTER(SmoothParams), C.POINTER(DriveParams), _i32,

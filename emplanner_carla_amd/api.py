@@ -117,6 +117,30 @@ class RolloutResult:
     log_index: object    # (n_log, B) int32 the tick's match index
 
 
+@dataclass
+class SpeedTargetResult:
+    target_kmh: object   # (B,) the PID's target of this tick
+    cursor: object       # (B,) int32 the bracket used: the next tick's cursor
+    tgt_status: object   # (B,) int32 EMP_TGT_* bits of this tick
+
+
+@dataclass
+class TimedRolloutResult:
+    state: object        # (B, 6) after T ticks
+    min_index: object    # (B,) int32 the last tick's match: the next rollout's min_index
+    err: object          # (B, 60) PID error buffer after the rollout
+    n_err: object        # (B,) int32
+    status: object       # (B,) int32 OR of the ticks' lateral statuses
+    fail_tick: object    # (B,) int32 first tick with a non-zero status, -1 if none
+    log_state: object    # (n_log, B, 6) the state the controller saw at ticks 0, log_every, ...; None without logs
+    log_control: object  # (n_log, B, 3) throttle, steer, brake
+    log_err: object      # (n_log, B, 4) e_rr
+    log_index: object    # (n_log, B) int32 the tick's match index
+    cursor: object       # (B,) int32 the last tick's bracket: the next rollout's cursor
+    tgt_status: object   # (B,) int32 OR of the ticks' EMP_TGT_* bits
+    log_target: object   # (n_log, B) the km/h target of each logged tick; None without logs
+
+
 def drive_params(dis_limitation=50.0, lateral_band=5.0, behind=-10.0, dynamic_speed=1.0, static_gate=30.0, pred_ts=0.2,
                  advance_s=0.0) -> DriveParams:
     """Thresholds of the driver's get_actor_from_world and predict_block (test_9.py:48-89, :116, :335, :377; its values).
@@ -1063,6 +1087,71 @@ class Planner:
         self._check(self._lib.emp_rollout(self._h, law, C.byref(lat), C.byref(pid), C.byref(vp), B, M, *ins, T, every, sop, mip, eop,
                                           nop, stp, ftp, *logp, a.where))
         return RolloutResult(so, mi, eo, no, st, ft, *logs)
+
+    # ---- the timed rollout: the PID follows the speed planner's profile (include/emplanner.h states the rule) -------
+    def speed_target(self, trajectory, t0, tick, dt, cap, cursor=None, in_place=False) -> SpeedTargetResult:
+        """One tick's PID target for B vehicles from a timed trajectory (B, 7, 401) (its speed and time rows): t0 (B,) the
+        clock at tick 0, cap (B,) km/h, cursor (B,) int32 the last tick's bracket (None: zeros).  in_place=True writes the new
+        cursor into ``cursor``."""
+        a = self._args(trajectory, t0, cap)
+        B, N = int(trajectory.shape[0]), L.TIMED_POINTS
+        tg, tgp = a.out((B,), np.float64)
+        cin = a.inp(cursor, np.int32, (B,))
+        if in_place and cursor is None:
+            raise ValueError("in_place needs a cursor array")
+        co, cop = a.out((B,), np.int32, into=_same_array(cursor, np.int32) if in_place else None)
+        ts, tsp = a.out((B,), np.int32)
+        self._check(self._lib.emp_speed_target(self._h, B, a.inp(trajectory, np.float64, (B, 7, N)), a.inp(t0, np.float64, (B,)),
+                                               int(tick), float(dt), a.inp(cap, np.float64, (B,)), cin, tgp, cop, tsp, a.where))
+        return SpeedTargetResult(tg, co, ts)
+
+    def rollout_timed(self, lat: MpcParams, pid: PidParams, vp: VehicleParams, target_path, n_path, state, min_index, target_speed,
+                      err, n_err, trajectory, t0, T, tick0=0, cursor=None, lateral="mpc", log_every=None,
+                      in_place=False) -> TimedRolloutResult:
+        """``rollout`` with the PID's target sampled every tick from a timed trajectory (speed_target's rule, clock
+        t0 + (tick0 + t) * vp.dt), in ONE kernel launch, bit-identical to the chain speed_target -> vehicle_control ->
+        vehicle_step.  trajectory (B, 7, 401) may be ``CycleResult.speed.trajectory`` as plan_cycle(speed=...) left it on the
+        device, t0 (B,) the plan_start_time that was passed in; target_speed (B,) km/h is the cap and the target without a
+        profile.  A rollout resumes bit for bit from ``tick0`` = the ticks done, fed with the previous result's state,
+        min_index, err, n_err and cursor.  in_place=True also updates ``cursor`` where it lives (it must then be given)."""
+        law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
+        if law is None:
+            raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+        T, tick0 = int(T), int(tick0)
+        every = 1 if log_every is None else int(log_every)
+        if in_place and cursor is None:
+            raise ValueError("in_place needs a cursor array")
+        a = self._args(target_path, state, err, trajectory)
+        B, M = int(target_path.shape[0]), int(target_path.shape[1])
+        nb, N = L.PID_BUFFER, L.TIMED_POINTS
+        io = L.RolloutTimedIO()
+        io.target_path, io.n_path = a.inp(target_path, np.float64, (B, M, 4)), a.inp(n_path, np.int32, (B,))
+        io.state, io.min_index = a.inp(state, np.float64, (B, 6)), a.inp(min_index, np.int32, (B,))
+        io.target_speed = a.inp(target_speed, np.float64, (B,))
+        io.err_in, io.n_err_in = a.inp(err, np.float64, (B, nb)), a.inp(n_err, np.int32, (B,))
+        io.trajectory, io.t0 = a.inp(trajectory, np.float64, (B, 7, N)), a.inp(t0, np.float64, (B,))
+        io.cursor_in = a.inp(cursor, np.int32, (B,))
+        same = (lambda x, dt: _same_array(x, dt)) if in_place else (lambda x, dt: None)
+        so, io.state_out = a.out((B, 6), np.float64, into=same(state, np.float64))
+        mi, io.min_index_out = a.out((B,), np.int32, into=same(min_index, np.int32))
+        eo, io.err_out = a.out((B, nb), np.float64, into=same(err, np.float64))
+        no, io.n_err_out = a.out((B,), np.int32, into=same(n_err, np.int32))
+        st, io.status = a.out((B,), np.int32)
+        ft, io.fail_tick = a.out((B,), np.int32)
+        cu, io.cursor_out = a.out((B,), np.int32, into=same(cursor, np.int32))
+        ts, io.tgt_status = a.out((B,), np.int32)
+        logs = [None] * 5
+        if log_every is not None and every >= 1 and T >= 1:
+            n_log = (T + every - 1) // every
+            logs[0], io.log_state = a.out((n_log, B, 6), np.float64)
+            logs[1], io.log_control = a.out((n_log, B, 3), np.float64)
+            logs[2], io.log_err = a.out((n_log, B, 4), np.float64)
+            logs[3], io.log_index = a.out((n_log, B), np.int32)
+            logs[4], io.log_target = a.out((n_log, B), np.float64)
+        io.reserved = 0
+        self._check(self._lib.emp_rollout_timed(self._h, law, C.byref(lat), C.byref(pid), C.byref(vp), B, M, T, tick0, every,
+                                                C.byref(io), a.where))
+        return TimedRolloutResult(so, mi, eo, no, st, ft, *logs[:4], cu, ts, logs[4])
 
     # ---- the fleet loop (the reference driver's main loop, test_9.py:336-436) ---------------------------------------
     def drive_request(self, dp: DriveParams, state, accel, actors, n_act, max_obs: int, max_dyn: int = 8,

@@ -2517,9 +2517,20 @@ ctl::VehicleParams vehicle_params(const emp_vehicle_params* p) {
 int launch_rollout(emp_ctx* ctx, int lateral, const emp_mpc_params* lat, int B, int max_path, const double* d_path, const int* d_np,
                    const rollout::IO& io) {
     if (lateral == EMP_LAT_MPC)
-        return launch(ctx, "rollout", rollout::mpc_rollout_kernel, grid_groups(B, mpc::kGroupsPerWave), dim3(64), 0, B, max_path,
-                      mpc_params(lat), d_path, d_np, io);
-    return launch(ctx, "rollout", rollout::lqr_rollout_kernel, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(lat), d_path, d_np, io);
+        return launch(ctx, "rollout", rollout::mpc_rollout_kernel<rollout::NoProfile>, grid_groups(B, mpc::kGroupsPerWave), dim3(64), 0, B,
+                      max_path, mpc_params(lat), d_path, d_np, io, rollout::NoProfile{});
+    return launch(ctx, "rollout", rollout::lqr_rollout_kernel<rollout::NoProfile>, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(lat),
+                  d_path, d_np, io, rollout::NoProfile{});
+}
+
+// the one launch of emp_rollout_timed: the same kernels with the target sampled from the profile every tick
+int launch_rollout_timed(emp_ctx* ctx, int lateral, const emp_mpc_params* lat, int B, int max_path, const double* d_path, const int* d_np,
+                         const rollout::IO& io, const rollout::Profile& tg) {
+    if (lateral == EMP_LAT_MPC)
+        return launch(ctx, "rollout_timed", rollout::mpc_rollout_kernel<rollout::Profile>, grid_groups(B, mpc::kGroupsPerWave), dim3(64), 0,
+                      B, max_path, mpc_params(lat), d_path, d_np, io, tg);
+    return launch(ctx, "rollout_timed", rollout::lqr_rollout_kernel<rollout::Profile>, grid1(B, 64), dim3(64), 0, B, max_path,
+                  mpc_params(lat), d_path, d_np, io, tg);
 }
 
 }  // namespace
@@ -2599,6 +2610,85 @@ int emp_rollout(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const 
     io.log_index = st.out(log_index, n_log * B, false);
     if (const int rc = st.ready()) return rc;
     if (const int rc = launch_rollout(ctx, lateral, lat, B, max_path, d_path, d_np, io)) return rc;
+    return st.finish();
+}
+
+int emp_speed_target(emp_ctx* ctx, int32_t B, const double* trajectory, const double* t0, int32_t tick, double dt, const double* cap,
+                     const int32_t* cursor_in, double* target_kmh, int32_t* cursor_out, int32_t* tgt_status, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_speed_target takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, B >= 0, "bad sizes");
+    EMP_REQUIRE(ctx, tick >= 0, "tick must be at least 0");
+    EMP_REQUIRE(ctx, trajectory && t0 && cap && target_kmh && cursor_out && tgt_status, "NULL argument");
+    EMP_STAGE(st, where);
+    const double* d_tr = st.in(trajectory, (size_t)B * rollout::kTrajRows * EMP_TIMED_POINTS);
+    const double* d_t0 = st.in(t0, (size_t)B);
+    const double* d_cap = st.in(cap, (size_t)B);
+    const int* d_ci = st.in(cursor_in, (size_t)B);
+    double* d_tg = st.out(target_kmh, (size_t)B, false);
+    int* d_co = st.out(cursor_out, (size_t)B, false);
+    int* d_ts = st.out(tgt_status, (size_t)B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "speed_target", rollout::speed_target_kernel, grid1(B, 256), dim3(256), 0, B, d_tr, d_t0, (int)tick, dt,
+                              d_cap, d_ci, d_tg, d_co, d_ts))
+        return rc;
+    return st.finish();
+}
+
+int emp_rollout_timed(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, const emp_vehicle_params* vp,
+                      int32_t B, int32_t max_path, int32_t T, int32_t tick0, int32_t log_every, const emp_rollout_timed_io* a,
+                      emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_rollout_timed takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, lateral == EMP_LAT_MPC || lateral == EMP_LAT_LQR, "lateral must be EMP_LAT_MPC or EMP_LAT_LQR");
+    EMP_REQUIRE(ctx, lat && pid && vp && a, "NULL parameter struct");
+    EMP_REQUIRE(ctx, B >= 0 && max_path >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    EMP_REQUIRE(ctx, a->reserved == 0, "emp_rollout_timed_io.reserved must be 0");
+    EMP_REQUIRE(ctx, T >= 1 && T <= EMP_ROLLOUT_MAX_TICKS, "T must be in [1, 65536]");
+    EMP_REQUIRE(ctx, tick0 >= 0, "tick0 must be at least 0");
+    EMP_REQUIRE(ctx, (int64_t)tick0 + (int64_t)T <= (int64_t)INT32_MAX, "tick0 + T must not exceed INT32_MAX");
+    EMP_REQUIRE(ctx, log_every >= 1, "log_every must be at least 1");
+    EMP_REQUIRE(ctx, a->target_path && a->n_path && a->state && a->min_index && a->target_speed && a->err_in && a->n_err_in &&
+                         a->trajectory && a->t0,
+                "NULL input array");
+    EMP_REQUIRE(ctx, a->state_out && a->min_index_out && a->err_out && a->n_err_out && a->status && a->fail_tick && a->cursor_out &&
+                         a->tgt_status,
+                "NULL output array");
+    const size_t n_log = ((size_t)T + (size_t)log_every - 1) / (size_t)log_every;
+    EMP_STAGE(st, where);
+    const double* d_path = st.in(a->target_path, (size_t)B * max_path * 4);
+    const int* d_np = st.in(a->n_path, (size_t)B);
+    rollout::IO io{};
+    io.pid = pid_params(pid);
+    io.vp = vehicle_params(vp);
+    io.T = T;
+    io.log_every = log_every;
+    io.state_in = st.in(a->state, (size_t)B * 6);
+    io.min_index_in = st.in(a->min_index, (size_t)B);
+    io.target_speed = st.in(a->target_speed, (size_t)B);
+    io.err_in = st.in(a->err_in, (size_t)B * ctl::kPidBuffer);
+    io.n_err_in = st.in(a->n_err_in, (size_t)B);
+    rollout::Profile tg{};
+    tg.trajectory = st.in(a->trajectory, (size_t)B * rollout::kTrajRows * EMP_TIMED_POINTS);
+    tg.t0 = st.in(a->t0, (size_t)B);
+    tg.cursor_in = st.in(a->cursor_in, (size_t)B);
+    tg.tick0 = tick0;
+    io.state_out = st.out(a->state_out, (size_t)B * 6, false);
+    io.min_index_out = st.out(a->min_index_out, (size_t)B, false);
+    io.err_out = st.out(a->err_out, (size_t)B * ctl::kPidBuffer, false);
+    io.n_err_out = st.out(a->n_err_out, (size_t)B, false);
+    io.status = st.out(a->status, (size_t)B, false);
+    io.fail_tick = st.out(a->fail_tick, (size_t)B, false);
+    io.log_state = st.out(a->log_state, n_log * B * 6, false);
+    io.log_control = st.out(a->log_control, n_log * B * 3, false);
+    io.log_err = st.out(a->log_err, n_log * B * 4, false);
+    io.log_index = st.out(a->log_index, n_log * B, false);
+    tg.cursor_out = st.out(a->cursor_out, (size_t)B, false);
+    tg.tgt_status = st.out(a->tgt_status, (size_t)B, false);
+    tg.log_target = st.out(a->log_target, n_log * B, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch_rollout_timed(ctx, lateral, lat, B, max_path, d_path, d_np, io, tg)) return rc;
     return st.finish();
 }
 

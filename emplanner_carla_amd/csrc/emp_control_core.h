@@ -1,6 +1,7 @@
 // emp_control_core.h - the longitudinal PID step and the actuation mapping of the reference's Vehicle_control, and the
-// project's vehicle model (vehicle_step, below), as plain functions that hipcc (device code of the fused control and rollout
-// kernels) and g++ (tests/host_check/control_check.cpp, tests/host_check/vehicle_check.cpp) both compile.
+// project's vehicle model (vehicle_step, below) and its rule for sampling a timed trajectory (speed_target), as plain functions
+// that hipcc (device code of the fused control and rollout kernels) and g++ (tests/host_check/control_check.cpp,
+// tests/host_check/vehicle_check.cpp, tests/host_check/speed_target_check.cpp) both compile.
 // ref: controller/controller.py class Longitudinal_PID_controller (:614-678) and Vehicle_control.run_step (:680-724).
 //
 // Arithmetic contract: bit-exact with the reference's Python floats.  Every expression is evaluated in the written order with
@@ -71,6 +72,63 @@ EMP_HD double pid_step(const PidParams& p, double speed_kmh, double target_speed
     for (int i = keep; i < kPidBuffer; ++i) out[i] = 0.0;
     *n_out = keep;
     return (p.kp * e + p.ki * integral) + p.kd * differential;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The PID's target from a timed trajectory (emp_speed_target / emp_rollout_timed).  THE RULE IS THE PROJECT'S: the reference plans
+// the 401-point profile (speed_planning_test.py:517, "control runs 10x as often as planning") and then drives with a constant
+// ref_speed (test_10.py:554).  include/emplanner.h states the rule in full; tests/speed_target_port.py is its port.  Only + - * /
+// and comparisons: g++ and the device give the same bits.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int kTimedPoints = 401;              // EMP_TIMED_POINTS: increase_points' samples (ref speed_planning_test.py:517)
+constexpr int kTgtBefore = 1, kTgtPast = 2, kTgtNoProfile = 4, kTgtCapped = 8;     // EMP_TGT_*
+
+// n_v: the number of leading samples in which neither the time nor the speed is NaN
+EMP_HD int profile_count(const double* speed, const double* time) {
+    int n = 0;
+    while (n < kTimedPoints && !(time[n] != time[n]) && !(speed[n] != speed[n])) ++n;
+    return n;
+}
+
+// the clock of tick `tick`: the product is rounded, then the sum
+EMP_HD double tick_clock(double t0, int tick, double dt) { return t0 + (double)tick * dt; }
+
+// One tick's target in km/h from rows speed[0..n_v) (m/s) and time[0..n_v) (s).  *cursor is the bracket the last tick used (any
+// int: it is clamped) and receives this tick's; *bits receives this tick's EMP_TGT_* bits.
+EMP_HD double speed_target(const double* speed, const double* time, int n_v, double clock, double cap, int* cursor, int* bits) {
+    if (n_v <= 0 || clock != clock) {
+        if (n_v <= 0) *cursor = 0;
+        *bits = kTgtNoProfile;
+        return cap;
+    }
+    int b = 0;
+    double v;
+    if (clock < time[0]) {
+        v = speed[0];
+        b = kTgtBefore;
+    } else if (clock >= time[n_v - 1]) {
+        v = speed[n_v - 1];
+        b = kTgtPast;
+    } else {                                   // time[0] <= clock < time[n_v - 1]: n_v >= 2
+        int j = *cursor;
+        j = j < 0 ? 0 : (j > n_v - 2 ? n_v - 2 : j);
+        while (j + 1 <= n_v - 2 && time[j + 1] <= clock) ++j;
+        const double tj = time[j], sj = speed[j];
+        const double d = time[j + 1] - tj;
+        v = sj;
+        if (d > 0.0) {
+            const double w = (clock - tj) / d;
+            v = sj + w * (speed[j + 1] - sj);
+        }
+        *cursor = j;
+    }
+    double target = 3.6 * v;
+    if (target > cap) {
+        target = cap;
+        b |= kTgtCapped;
+    }
+    *bits = b;
+    return target;
 }
 
 // Actuation of Vehicle_control.run_step (ref :705-718) with the reference's limits (max steer 1, min steer -1, max throttle 1,

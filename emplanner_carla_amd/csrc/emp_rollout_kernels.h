@@ -1,5 +1,6 @@
 // emp_rollout_kernels.h - the vehicle model on the device (emp_vehicle_step) and the closed loop in ONE launch (emp_rollout):
-// T ticks of [lateral law + PID + actuation] (emp_vehicle_control) followed by the vehicle model (emp_vehicle_step).
+// T ticks of [lateral law + PID + actuation] (emp_vehicle_control) followed by the vehicle model (emp_vehicle_step); and the same
+// loop with the PID's target sampled every tick from a timed trajectory (emp_speed_target, emp_rollout_timed).
 //
 // The model is the project's own (csrc/emp_control_core.h: ctl::vehicle_step) - the reference's plant is CARLA (its main loop,
 // test_9.py:336-436, calls Controller.run_step 100 times per planning cycle against the simulator).
@@ -43,6 +44,28 @@ struct IO {
     double* log_err;               // [n_log][B][4] or null
     int* log_index;                // [n_log][B] or null
 };
+
+// What emp_rollout_timed adds to IO: the timed trajectory whose speed / time rows give every tick's PID target (ctl::speed_target,
+// the rule of include/emplanner.h), with target_speed as the cap.  emp_rollout's instantiations take NoProfile and are the kernels
+// they were: every timed statement sits behind `if constexpr (Tgt::kTimed)`.
+struct NoProfile {
+    static constexpr bool kTimed = false;
+};
+struct Profile {
+    static constexpr bool kTimed = true;
+    const double* trajectory;      // [B][7][401]; rows 4 (speed, m/s) and 6 (time, s) are read
+    const double* t0;              // [B]
+    const int* cursor_in;          // [B] or null (zeros)
+    int tick0;
+    int* cursor_out;               // [B] (may be cursor_in)
+    int* tgt_status;               // [B] OR of the ticks' EMP_TGT_* bits
+    double* log_target;            // [n_log][B] or null
+};
+constexpr int kTrajRows = 7, kSpeedRow = 4, kTimeRow = 6;
+
+__device__ __forceinline__ const double* profile_row(const double* trajectory, int b, int row) {
+    return trajectory + ((size_t)b * kTrajRows + row) * ctl::kTimedPoints;
+}
 
 // control_epilogue (emp_mpc_kernels.h) on PID state that stays on chip: the deque `e` (60 doubles in LDS, updated in place as
 // ctl::pid_step allows) and its count in a register.  A failing vehicle: zero controls, PID state untouched.
@@ -96,8 +119,9 @@ __device__ __forceinline__ ctl::VehicleState load_state(const double* state, int
 
 // grid = ceil(B / 5), block = 64 (mpc_lateral_kernel's).  The 12 lanes of a group carry the vehicle's state redundantly and step
 // it with the same arithmetic; the group's lane 0 owns the PID deque and hands the three controls to the others.
+template <class Tgt>
 __global__ __launch_bounds__(64) void mpc_rollout_kernel(int B, int max_path, mpc::Params prm, const double* __restrict__ target_path,
-                                                         const int* __restrict__ n_path, IO io) {
+                                                         const int* __restrict__ n_path, IO io, Tgt tg) {
     __shared__ double pid_err[mpc::kGroupsPerWave][ctl::kPidBuffer];
     const int lane = threadIdx.x & 63;
     const int grp = lane / mpc::kNu, r = lane - grp * mpc::kNu;
@@ -110,17 +134,43 @@ __global__ __launch_bounds__(64) void mpc_rollout_kernel(int B, int max_path, mp
     const int np_ = min(max(n_path[bb], 0), max_path);             // a count beyond the row is clamped, never followed
     ctl::VehicleState s = load_state(io.state_in, bb);
     int idx = io.min_index_in[bb];
-    const double target = io.target_speed[bb];
+    double target = io.target_speed[bb];                           // timed: the cap, and every tick's target on the owner lane
     int n_err = io.n_err_in[bb];
     double* e = pid_err[owner ? grp : 0];
     if (owner)
         for (int i = 0; i < ctl::kPidBuffer; ++i) e[i] = io.err_in[(size_t)b * ctl::kPidBuffer + i];
+    // timed: the group's 12 lanes scan the two rows strided for the first NaN; the owner lane keeps the profile's state
+    const double *p_speed = nullptr, *p_time = nullptr;
+    double cap = 0.0, t0 = 0.0;
+    int n_v = 0, cursor = 0, tgt_bits = 0;
+    if constexpr (Tgt::kTimed) {
+        p_speed = profile_row(tg.trajectory, bb, kSpeedRow);
+        p_time = profile_row(tg.trajectory, bb, kTimeRow);
+        int first = ctl::kTimedPoints;
+        for (int i = r; i < ctl::kTimedPoints; i += mpc::kNu) {
+            const double tv = p_time[i], sv = p_speed[i];
+            if ((tv != tv || sv != sv) && first == ctl::kTimedPoints) first = i;
+        }
+        n_v = first;
+#pragma unroll
+        for (int k = 0; k < mpc::kNu; ++k) n_v = min(n_v, mpc::grp_bcast_int(first, gb, k));
+        cap = target;
+        t0 = tg.t0[bb];
+        cursor = tg.cursor_in ? tg.cursor_in[bb] : 0;
+    }
     int status = 0, fail_tick = -1;
     for (int t = 0; t < io.T; ++t) {
         double h[mpc::kNu], f_r, u;
         mpc::LatResult o;
         mpc::mpc_lateral_core(prm, path, np_, s.x, s.y, s.fi, s.Vy, s.fi_dot, ctl::clamp_vx(s.Vx), idx, live, r, gb, h, &f_r, &u, &o);
         double c3[3] = {0.0, 0.0, 0.0};
+        if constexpr (Tgt::kTimed)
+            if (owner) {
+                int bits = 0;
+                target = ctl::speed_target(p_speed, p_time, n_v, ctl::tick_clock(t0, tg.tick0 + t, io.vp.dt), cap, &cursor, &bits);
+                tgt_bits |= bits;
+                if (tg.log_target && t % io.log_every == 0) tg.log_target[(size_t)(t / io.log_every) * B + b] = target;
+            }
         if (owner) control_tick(io.pid, ctl::speed_kmh_of(s.Vx, s.Vy), target, e, &n_err, o.status, o.steer, c3);
 #pragma unroll
         for (int k = 0; k < 3; ++k) c3[k] = mpc::grp_bcast(c3[k], gb, 0);
@@ -131,14 +181,20 @@ __global__ __launch_bounds__(64) void mpc_rollout_kernel(int B, int max_path, mp
         s = ctl::vehicle_step(io.vp, s, c3[0], c3[1], c3[2]);
     }
     if (owner) write_final(io, b, s, idx, e, n_err, status, fail_tick);
+    if constexpr (Tgt::kTimed)
+        if (owner) {
+            tg.cursor_out[b] = cursor;
+            tg.tgt_status[b] = tgt_bits;
+        }
 }
 
 // grid = ceil(B / 64), block = 64 (lqr_lateral_kernel's): one vehicle per lane.  A deque row is 61 doubles apart from the next,
 // so that the 64 lanes' accesses to entry i fall on distinct LDS banks.
 constexpr int kPidStride = ctl::kPidBuffer + 1;
 
+template <class Tgt>
 __global__ __launch_bounds__(64) void lqr_rollout_kernel(int B, int max_path, mpc::Params prm, const double* __restrict__ target_path,
-                                                         const int* __restrict__ n_path, IO io) {
+                                                         const int* __restrict__ n_path, IO io, Tgt tg) {
     __shared__ double pid_err[64 * kPidStride];
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -146,15 +202,33 @@ __global__ __launch_bounds__(64) void lqr_rollout_kernel(int B, int max_path, mp
     const int np_ = min(max(n_path[b], 0), max_path);              // a count beyond the row is clamped, never followed
     ctl::VehicleState s = load_state(io.state_in, b);
     int idx = io.min_index_in[b];
-    const double target = io.target_speed[b];
+    double target = io.target_speed[b];                            // timed: the cap, and every tick's target
     int n_err = io.n_err_in[b];
     double* e = pid_err + threadIdx.x * kPidStride;
     for (int i = 0; i < ctl::kPidBuffer; ++i) e[i] = io.err_in[(size_t)b * ctl::kPidBuffer + i];
+    // timed: each lane scans its own two rows (uncoalesced, once per rollout against T Riccati iterations)
+    const double *p_speed = nullptr, *p_time = nullptr;
+    double cap = 0.0, t0 = 0.0;
+    int n_v = 0, cursor = 0, tgt_bits = 0;
+    if constexpr (Tgt::kTimed) {
+        p_speed = profile_row(tg.trajectory, b, kSpeedRow);
+        p_time = profile_row(tg.trajectory, b, kTimeRow);
+        n_v = ctl::profile_count(p_speed, p_time);
+        cap = target;
+        t0 = tg.t0[b];
+        cursor = tg.cursor_in ? tg.cursor_in[b] : 0;
+    }
     int status = 0, fail_tick = -1;
     for (int t = 0; t < io.T; ++t) {
         mpc::V4 K;
         mpc::LatResult o;
         lqr::lqr_lateral_core(prm, path, np_, s.x, s.y, s.fi, s.Vy, s.fi_dot, ctl::clamp_vx(s.Vx), idx, &K, &o);
+        if constexpr (Tgt::kTimed) {
+            int bits = 0;
+            target = ctl::speed_target(p_speed, p_time, n_v, ctl::tick_clock(t0, tg.tick0 + t, io.vp.dt), cap, &cursor, &bits);
+            tgt_bits |= bits;
+            if (tg.log_target && t % io.log_every == 0) tg.log_target[(size_t)(t / io.log_every) * B + b] = target;
+        }
         double c3[3];
         control_tick(io.pid, ctl::speed_kmh_of(s.Vx, s.Vy), target, e, &n_err, o.status, o.steer, c3);
         write_log(io, B, b, t, s, c3, o);
@@ -164,6 +238,26 @@ __global__ __launch_bounds__(64) void lqr_rollout_kernel(int B, int max_path, mp
         s = ctl::vehicle_step(io.vp, s, c3[0], c3[1], c3[2]);
     }
     write_final(io, b, s, idx, e, n_err, status, fail_tick);
+    if constexpr (Tgt::kTimed) {
+        tg.cursor_out[b] = cursor;
+        tg.tgt_status[b] = tgt_bits;
+    }
+}
+
+// emp_speed_target: one tick's sampling, one vehicle per lane.  cursor_out may be cursor_in (a lane reads its own before it writes).
+__global__ __launch_bounds__(256) void speed_target_kernel(int B, const double* __restrict__ trajectory, const double* __restrict__ t0,
+                                                           int tick, double dt, const double* __restrict__ cap, const int* cursor_in,
+                                                           double* __restrict__ target_kmh, int* cursor_out,
+                                                           int* __restrict__ tgt_status) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double* p_speed = profile_row(trajectory, b, kSpeedRow);
+    const double* p_time = profile_row(trajectory, b, kTimeRow);
+    int cursor = cursor_in ? cursor_in[b] : 0, bits = 0;
+    target_kmh[b] = ctl::speed_target(p_speed, p_time, ctl::profile_count(p_speed, p_time), ctl::tick_clock(t0[b], tick, dt), cap[b],
+                                      &cursor, &bits);
+    cursor_out[b] = cursor;
+    tgt_status[b] = bits;
 }
 
 // emp_vehicle_step: one vehicle per lane.  state_out may be state_in (a lane reads its six values before it writes them).

@@ -723,6 +723,85 @@ int emp_rollout(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const 
                 int32_t log_every, double* state_out, int32_t* min_index_out, double* err_out, int32_t* n_err_out, int32_t* status,
                 int32_t* fail_tick, double* log_state, double* log_control, double* log_err, int32_t* log_index, emp_mem where);
 
+/* ---- the timed rollout: the PID follows the speed planner's profile, tick by tick ------------------------------------------
+ * THE SAMPLING RULE IS THIS PROJECT'S DEFINITION, NOT THE REFERENCE'S.  The reference densifies its speed plan to 401 points
+ * "because control runs 10x as often as planning" (speed_planning_test.py:517) and then drives with a constant ref_speed
+ * (test_10.py:554): it never closes this loop.  New with ABI 13's library; adding functions does not change EMP_ABI_VERSION.
+ *
+ * trajectory [B][7][EMP_TIMED_POINTS] is emp_plan_trajectory's (x, y, heading, kappa, speed, accel, time); only two rows are read:
+ * speed = trajectory[b][4][.] in m/s and time = trajectory[b][6][.] in s, on the clock base the caller chose with
+ * plan_start_time.  t0 [B] is the vehicle's clock at tick 0, cap [B] (emp_rollout_timed: target_speed [B]) a speed in km/h: the
+ * road limit (the reference's ref_speed), and the target where there is no profile.  cursor [B] is the bracket the last tick used.
+ *
+ * The rule, per vehicle; every operation is rounded separately (no contraction), `/` is IEEE division:
+ *   n_v = the largest n in [0, 401] such that for all i < n neither time[i] nor speed[i] is NaN (x != x)
+ *   clock = t0 + (double)tick * dt              (the product is rounded, then the sum)
+ *   if n_v == 0 or clock is NaN:  target = cap, bits = EMP_TGT_NO_PROFILE; the cursor is unchanged (0 if n_v == 0); nothing else
+ *     applies (no cap test)
+ *   else if clock < time[0]:          v = speed[0],        bit EMP_TGT_BEFORE;  the cursor is unchanged
+ *   else if clock >= time[n_v - 1]:   v = speed[n_v - 1],  bit EMP_TGT_PAST;    the cursor is unchanged
+ *   else (n_v >= 2):  j = the incoming cursor clamped to [0, n_v - 2];  while (j + 1 <= n_v - 2 && time[j + 1] <= clock) ++j;
+ *     d = time[j + 1] - time[j];  if d > 0: w = (clock - time[j]) / d, v = speed[j] + w * (speed[j + 1] - speed[j]); else v = speed[j];
+ *     the outgoing cursor is j
+ *   target = 3.6 * v;  if target > cap: target = cap, bit EMP_TGT_CAPPED (a NaN cap compares false: no cap)
+ * "Unchanged" means the incoming value as it is, not clamped.  The rule is defined by this text for any row, ascending or not; on
+ * the planner's ascending rows (increase_points: (i - 1) * T / 400) the cursor makes the common tick three loads and at most one
+ * step: the clock moves dt = 0.01 s per tick against about 0.02 s per sample.
+ *
+ * emp_speed_target: one tick's sampling for B vehicles.  cursor_in may be NULL (zeros); cursor_out may alias cursor_in; tick >= 0.
+ * target_kmh [B], cursor_out [B], tgt_status [B] = this tick's bits.
+ *
+ * emp_rollout_timed: emp_rollout with the constant target replaced by the rule, in ONE kernel launch, for both laws: tick t uses
+ * clock = t0 + (double)(tick0 + t) * vp->dt and the cursor tick t - 1 left (tick 0: cursor_in).  The target and the cursor are
+ * computed on every tick whatever the tick's lateral status.  EVERY OUTPUT EQUALS, BIT FOR BIT, T iterations of
+ * emp_speed_target(tick0 + t, dt = vp->dt) -> emp_vehicle_control(target_speed = target_kmh) -> emp_vehicle_step on the same arrays,
+ * so a rollout cut in two (T1 ticks, then tick0 = T1 on the first one's outputs) resumes bit for bit.
+ * emp_rollout_timed_io holds emp_rollout's arrays under their names (target_speed [B] is the cap), and
+ *   inputs:  trajectory, t0 [B], cursor_in [B] (NULL = zeros)
+ *   outputs: cursor_out [B], tgt_status [B] = OR of the ticks' bits (both required); log_target [n_log][B] (optional): the km/h
+ *            target of each logged tick, rows as log_state
+ * Each output may alias the input of its name.  reserved must be 0.  The lateral path stays target_path / n_path (the cycle's traj /
+ * traj_len): the trajectory's x / y / heading / kappa rows are not read.
+ * Refused (EMP_ERR_INVALID): T outside [1, EMP_ROLLOUT_MAX_TICKS], tick0 < 0, tick0 + T > INT32_MAX, log_every < 1, reserved != 0,
+ * a NULL required pointer, EMP_HOST_PINNED.  B == 0: EMP_OK.  With a pipeline set both calls fence like every non-cycle entry
+ * point.  Cost: as emp_rollout, plus one scan of the two rows per vehicle and three loads per tick. */
+#define EMP_TGT_BEFORE 1
+#define EMP_TGT_PAST 2
+#define EMP_TGT_NO_PROFILE 4
+#define EMP_TGT_CAPPED 8
+#define EMP_TIMED_POINTS 401
+int emp_speed_target(emp_ctx* ctx, int32_t B, const double* trajectory, const double* t0, int32_t tick, double dt, const double* cap,
+                     const int32_t* cursor_in, double* target_kmh, int32_t* cursor_out, int32_t* tgt_status, emp_mem where);
+typedef struct emp_rollout_timed_io {
+    const double* target_path;             /* [B][max_path][4] */
+    const int32_t* n_path;                 /* [B] */
+    const double* state;                   /* [B][6] */
+    const int32_t* min_index;              /* [B] */
+    const double* target_speed;            /* [B] km/h: the cap */
+    const double* err_in;                  /* [B][EMP_PID_BUFFER] */
+    const int32_t* n_err_in;               /* [B] */
+    const double* trajectory;              /* [B][7][EMP_TIMED_POINTS] */
+    const double* t0;                      /* [B] */
+    const int32_t* cursor_in;              /* [B] or NULL */
+    double* state_out;
+    int32_t* min_index_out;
+    double* err_out;
+    int32_t* n_err_out;
+    int32_t* status;
+    int32_t* fail_tick;
+    int32_t* cursor_out;
+    int32_t* tgt_status;
+    double* log_state;                     /* optional logs */
+    double* log_control;
+    double* log_err;
+    int32_t* log_index;
+    double* log_target;
+    int32_t reserved;                      /* must be 0 */
+} emp_rollout_timed_io;
+int emp_rollout_timed(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, const emp_vehicle_params* vp,
+                      int32_t B, int32_t max_path, int32_t T, int32_t tick0, int32_t log_every, const emp_rollout_timed_io* io,
+                      emp_mem where);
+
 /* ---- S-T speed DP (BASELINE config 5; reference planner/speed_planning_test.py) ----------------
  * The S-T grid is hard-coded in the reference (40 non-uniform s samples :114, 16 t samples :116); tables are
  * [B][EMP_ST_ROWS][EMP_ST_COLS], row 0 = largest s (CalcSTCoordinate, :287-305).  Obstacle slots hold NaN when

@@ -5,7 +5,12 @@ outside the timed span), HIP events on the context's stream around blocks of `--
 block and each reports the median of `--blocks` blocks after a warm-up run.  Both forms' final states are compared bit for bit
 before anything is timed.  Prints one JSON line per (law, B).
 
-    python tools/rollout_bench.py [--sizes 1,4096,32768] [--ticks 100] [--reps 2] [--blocks 7] [--out rollout_bench.json]
+--timed measures emp_rollout_timed instead (the PID's target sampled every tick from a timed trajectory [B][7][401]): against
+emp_rollout on the same fleet, and against the timed chain it replaces (T x [emp_speed_target, emp_vehicle_control,
+emp_vehicle_step], 3 T launches); the three forms alternate block by block (default 5 blocks), the two timed forms are compared
+bit for bit first.
+
+    python tools/rollout_bench.py [--timed] [--sizes 1,4096,32768] [--ticks 100] [--reps 2] [--blocks 7] [--out rollout_bench.json]
 """
 from __future__ import annotations
 
@@ -47,15 +52,29 @@ def fleet(B, seed=7):
                 n_err=torch.zeros(B, dtype=torch.int32, device="cuda"))
 
 
+def profile(B, v, seed=11):
+    """An ascending profile per vehicle as increase_points leaves it (times (i - 1) * 8 / 400), its speed falling 2 m/s from the
+    vehicle's own over the 8 s, the clock starting up to 1 s into the row; the rows that are not read hold NaN."""
+    rng = np.random.default_rng(seed)
+    traj = torch.full((B, 7, L.TIMED_POINTS), float("nan"), dtype=torch.float64, device="cuda")
+    x = torch.arange(L.TIMED_POINTS, dtype=torch.float64, device="cuda")
+    traj[:, 6] = x * (8.0 / 400.0)
+    traj[:, 4] = v[:, None] - 2.0 * (x / 400.0)[None, :]
+    return dict(traj=traj, t0=torch.from_numpy(rng.uniform(0.0, 1.0, B)).cuda(), cap=3.6 * v + 30.0,
+                cursor=torch.zeros(B, dtype=torch.int32, device="cuda"))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--timed", action="store_true")
     ap.add_argument("--sizes", default="1,4096,32768")
     ap.add_argument("--ticks", type=int, default=100)
     ap.add_argument("--reps", type=int, default=2)
-    ap.add_argument("--blocks", type=int, default=7)
+    ap.add_argument("--blocks", type=int, default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     T = a.ticks
+    a.blocks = a.blocks or (5 if a.timed else 7)
     pl = Planner(0)
     lib, h = pl._lib, pl._h
     stream = pl.torch_stream()
@@ -68,6 +87,19 @@ def main():
         w = {k: torch.empty(s, dtype=dt, device="cuda") for k, s, dt in (
             ("state", (B, 6), f64), ("mi", (B,), i32), ("err", (B, L.PID_BUFFER), f64), ("n_err", (B,), i32), ("cs", (B, 5), f64),
             ("vx", (B,), f64), ("kmh", (B,), f64), ("control", (B, 3), f64), ("st", (B,), i32), ("ft", (B,), i32))}
+        if a.timed:
+            q = profile(B, f["state"][:, 5].clone())
+            w["cursor"] = torch.empty(B, dtype=i32, device="cuda")
+            w["tgt"], w["ts"] = torch.empty(B, dtype=f64, device="cuda"), torch.empty(B, dtype=i32, device="cuda")
+            tio = L.RolloutTimedIO()
+            tio.target_path, tio.n_path, tio.target_speed = P(f["path"]), P(f["n"]), P(q["cap"])
+            tio.trajectory, tio.t0 = P(q["traj"]), P(q["t0"])
+            tio.state = tio.state_out = P(w["state"])
+            tio.min_index = tio.min_index_out = P(w["mi"])
+            tio.err_in = tio.err_out = P(w["err"])
+            tio.n_err_in = tio.n_err_out = P(w["n_err"])
+            tio.cursor_in = tio.cursor_out = P(w["cursor"])
+            tio.status, tio.fail_tick, tio.tgt_status = P(w["st"]), P(w["ft"]), P(w["ts"])
         vx0 = torch.clamp(f["state"][:, 5], min=0.005)                       # the fleet moves forward: the clamp's >= 0 branch
         kmh0 = 3.6 * torch.sqrt(f["state"][:, 5] * f["state"][:, 5] + f["state"][:, 3] * f["state"][:, 3])
 
@@ -77,6 +109,8 @@ def main():
             w["cs"].copy_(f["state"][:, :5])
             w["vx"].copy_(vx0)
             w["kmh"].copy_(kmh0)
+            if a.timed:
+                w["cursor"].copy_(q["cursor"])
             torch.cuda.synchronize()
 
         def rollout(law, prm):
@@ -89,6 +123,25 @@ def main():
             for _ in range(T):
                 rc = lib.emp_vehicle_control(h, law, C.byref(prm), C.byref(pid), B, MAX_PATH, P(f["path"]), P(f["n"]), P(w["cs"]),
                                              P(w["vx"]), P(w["mi"]), P(w["kmh"]), P(f["target"]), P(w["err"]), P(w["n_err"]),
+                                             P(w["control"]), None, None, P(w["mi"]), None, None, None, P(w["err"]), P(w["n_err"]),
+                                             P(w["st"]), L.EMP_DEVICE)
+                assert rc == 0, rc
+                rc = lib.emp_vehicle_step(h, C.byref(vpar), B, P(w["state"]), P(w["control"]), P(w["state"]), P(w["cs"]), P(w["vx"]),
+                                          P(w["kmh"]), L.EMP_DEVICE)
+                assert rc == 0, rc
+
+        def rollout_timed(law, prm):
+            rc = lib.emp_rollout_timed(h, law, C.byref(prm), C.byref(pid), C.byref(vpar), B, MAX_PATH, T, 0, T + 1, C.byref(tio),
+                                       L.EMP_DEVICE)
+            assert rc == 0, rc
+
+        def chain_timed(law, prm):
+            for t in range(T):
+                rc = lib.emp_speed_target(h, B, P(q["traj"]), P(q["t0"]), t, vpar.dt, P(q["cap"]), P(w["cursor"]), P(w["tgt"]),
+                                          P(w["cursor"]), P(w["ts"]), L.EMP_DEVICE)
+                assert rc == 0, rc
+                rc = lib.emp_vehicle_control(h, law, C.byref(prm), C.byref(pid), B, MAX_PATH, P(f["path"]), P(f["n"]), P(w["cs"]),
+                                             P(w["vx"]), P(w["mi"]), P(w["kmh"]), P(w["tgt"]), P(w["err"]), P(w["n_err"]),
                                              P(w["control"]), None, None, P(w["mi"]), None, None, None, P(w["err"]), P(w["n_err"]),
                                              P(w["st"]), L.EMP_DEVICE)
                 assert rc == 0, rc
@@ -109,6 +162,28 @@ def main():
             return sum(per) / len(per)
 
         for name, law, prm in (("mpc", L.EMP_LAT_MPC, mpc_params()), ("lqr", L.EMP_LAT_LQR, lqr_params())):
+            if a.timed:
+                finals = []
+                for fn in (rollout_timed, chain_timed, rollout):               # warm-up, and the two timed forms agree
+                    restore()
+                    fn(law, prm)
+                    pl.synchronize()
+                    finals.append([w[k].clone() for k in ("state", "mi", "err", "n_err", "cursor")])
+                assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(*finals[:2])), "rollout_timed != chain"
+                forms = {"timed": (rollout_timed, []), "untimed": (rollout, []), "chain": (chain_timed, [])}
+                for _ in range(a.blocks):                                      # alternate: drift of the machine hits all alike
+                    for fn, ms in forms.values():
+                        ms.append(block(fn, law, prm))
+                med = {k: statistics.median(ms) for k, (_, ms) in forms.items()}
+                row = {"law": name, "B": B, "T": T, "rollout_timed_ms": round(med["timed"], 4), "rollout_ms": round(med["untimed"], 4),
+                       "timed_chain_ms": round(med["chain"], 4),
+                       **{f"{k}_spread_ms": [round(min(ms), 4), round(max(ms), 4)] for k, (_, ms) in forms.items()},
+                       "timed_over_rollout": round(med["timed"] / med["untimed"], 3),
+                       "chain_over_timed": round(med["chain"] / med["timed"], 3),
+                       "timed_us_per_tick": round(1000.0 * med["timed"] / T, 3), "reps": a.reps, "blocks": a.blocks}
+                results.append(row)
+                print(json.dumps(row), flush=True)
+                continue
             finals = []
             for fn in (rollout, chain):                                        # warm-up, and the two forms agree
                 restore()
