@@ -285,6 +285,18 @@ def _same_array(x, dtype):
     return x
 
 
+def _in_place(x, dtype, in_place):
+    """Where an output that may update the input ``x`` goes: ``x`` itself when the call works in place, else None - a new array."""
+    return _same_array(x, dtype) if in_place else None
+
+
+def _lateral_law(lateral):
+    law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
+    if law is None:
+        raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+    return law
+
+
 class _Args:
     """Collects array arguments of one call, checks they live in one memory space, makes outputs."""
 
@@ -989,12 +1001,8 @@ class Planner:
         nb = L.PID_BUFFER
         cmd, cp = a.out((B,), np.float64)
         ein, niin = a.inp(err, np.float64, (B, nb)), a.inp(n_err, np.int32, (B,))
-        if in_place:
-            eo, eop = a.out((B, nb), np.float64, into=_same_array(err, np.float64))
-            no, nop = a.out((B,), np.int32, into=_same_array(n_err, np.int32))
-        else:
-            eo, eop = a.out((B, nb), np.float64)
-            no, nop = a.out((B,), np.int32)
+        eo, eop = a.out((B, nb), np.float64, into=_in_place(err, np.float64, in_place))
+        no, nop = a.out((B,), np.int32, into=_in_place(n_err, np.int32, in_place))
         self._check(self._lib.emp_pid_longitudinal(
             self._h, C.byref(p), B, a.inp(speed_kmh, np.float64, (B,)), a.inp(target_speed, np.float64, (B,)), ein, niin, cp,
             eop, nop, a.where))
@@ -1005,9 +1013,7 @@ class Planner:
         """ref Vehicle_control.run_step for B vehicles in one kernel launch: the lateral law (``lateral`` = "mpc": as
         mpc_lateral, "lqr": as lqr_lateral, with ``lat`` as their params and the same inputs), the PID step (as
         pid_longitudinal) and the actuation.  in_place=True updates ``err`` / ``n_err`` as pid_longitudinal does."""
-        law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
-        if law is None:
-            raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+        law = _lateral_law(lateral)
         a = self._args(target_path, state, err)
         B, M = int(target_path.shape[0]), int(target_path.shape[1])
         nb = L.PID_BUFFER
@@ -1021,12 +1027,8 @@ class Planner:
         e, ep = a.out((B, 4), np.float64)
         k, kp = a.out((B,), np.float64)
         pp, ppp = a.out((B, 4), np.float64)
-        if in_place:
-            eo, eop = a.out((B, nb), np.float64, into=_same_array(err, np.float64))
-            no, nop = a.out((B,), np.int32, into=_same_array(n_err, np.int32))
-        else:
-            eo, eop = a.out((B, nb), np.float64)
-            no, nop = a.out((B,), np.int32)
+        eo, eop = a.out((B, nb), np.float64, into=_in_place(err, np.float64, in_place))
+        no, nop = a.out((B,), np.int32, into=_in_place(n_err, np.int32, in_place))
         st, stp = a.out((B,), np.int32)
         self._check(self._lib.emp_vehicle_control(
             self._h, law, C.byref(lat), C.byref(pid), B, M, *ins, ctp, lcp, ocp, mip, ep, kp, ppp, eop, nop, stp, a.where))
@@ -1039,7 +1041,7 @@ class Planner:
         next state into ``state``."""
         a = self._args(state, control)
         B = int(state.shape[0])
-        so, sop = a.out((B, 6), np.float64, into=_same_array(state, np.float64) if in_place else None)
+        so, sop = a.out((B, 6), np.float64, into=_in_place(state, np.float64, in_place))
         cs, csp = a.out((B, 5), np.float64)
         vx, vxp = a.out((B,), np.float64)
         kmh, kmhp = a.out((B,), np.float64)
@@ -1055,38 +1057,37 @@ class Planner:
         n_err (B,).  log_every=k records ticks 0, k, 2k, ... (None: no logs).  in_place=True updates ``state``, ``min_index``,
         ``err`` and ``n_err`` where they live.  With lateral="lqr" keep the fleet moving: a creeping vehicle costs up to 5000
         Riccati sweeps per tick."""
-        law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
-        if law is None:
-            raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+        law = _lateral_law(lateral)
         T = int(T)
         if not 1 <= T <= L.ROLLOUT_MAX_TICKS:
             raise ValueError(f"T must be in [1, {L.ROLLOUT_MAX_TICKS}]")
         if log_every is not None and int(log_every) < 1:
             raise ValueError("log_every must be at least 1")
+        every = 1 if log_every is None else int(log_every)
         a = self._args(target_path, state, err)
-        B, M = int(target_path.shape[0]), int(target_path.shape[1])
-        nb = L.PID_BUFFER
+        B, M, ins, outs, logs = self._rollout_arrays(a, target_path, n_path, state, min_index, target_speed, err, n_err,
+                                                     None if log_every is None else (T + every - 1) // every, in_place)
+        self._check(self._lib.emp_rollout(self._h, law, C.byref(lat), C.byref(pid), C.byref(vp), B, M, *ins, T, every,
+                                          *[o[1] for o in outs], *[o[1] for o in logs], a.where))
+        return RolloutResult(*[o[0] for o in outs], *[o[0] for o in logs])
+
+    @staticmethod
+    def _rollout_arrays(a, target_path, n_path, state, min_index, target_speed, err, n_err, n_log, in_place):
+        """What ``rollout`` and ``rollout_timed`` pass alike: B, M, the pointers of the 7 inputs, and (array, pointer) of the 6
+        outputs and of the 4 logs of n_log rows (None: no logs)."""
+        B, M, nb = int(target_path.shape[0]), int(target_path.shape[1]), L.PID_BUFFER
         ins = [a.inp(target_path, np.float64, (B, M, 4)), a.inp(n_path, np.int32, (B,)), a.inp(state, np.float64, (B, 6)),
                a.inp(min_index, np.int32, (B,)), a.inp(target_speed, np.float64, (B,)), a.inp(err, np.float64, (B, nb)),
                a.inp(n_err, np.int32, (B,))]
-        same = (lambda x, dt: _same_array(x, dt)) if in_place else (lambda x, dt: None)
-        so, sop = a.out((B, 6), np.float64, into=same(state, np.float64))
-        mi, mip = a.out((B,), np.int32, into=same(min_index, np.int32))
-        eo, eop = a.out((B, nb), np.float64, into=same(err, np.float64))
-        no, nop = a.out((B,), np.int32, into=same(n_err, np.int32))
-        st, stp = a.out((B,), np.int32)
-        ft, ftp = a.out((B,), np.int32)
-        if log_every is None:
-            every, logs, logp = 1, [None] * 4, [None] * 4
-        else:
-            every = int(log_every)
-            n_log = (T + every - 1) // every
-            pairs = [a.out((n_log, B, 6), np.float64), a.out((n_log, B, 3), np.float64), a.out((n_log, B, 4), np.float64),
-                     a.out((n_log, B), np.int32)]
-            logs, logp = [q[0] for q in pairs], [q[1] for q in pairs]
-        self._check(self._lib.emp_rollout(self._h, law, C.byref(lat), C.byref(pid), C.byref(vp), B, M, *ins, T, every, sop, mip, eop,
-                                          nop, stp, ftp, *logp, a.where))
-        return RolloutResult(so, mi, eo, no, st, ft, *logs)
+        outs = [a.out((B, 6), np.float64, into=_in_place(state, np.float64, in_place)),
+                a.out((B,), np.int32, into=_in_place(min_index, np.int32, in_place)),
+                a.out((B, nb), np.float64, into=_in_place(err, np.float64, in_place)),
+                a.out((B,), np.int32, into=_in_place(n_err, np.int32, in_place)), a.out((B,), np.int32), a.out((B,), np.int32)]
+        logs = [(None, None)] * 4
+        if n_log is not None:
+            logs = [a.out((n_log, B, 6), np.float64), a.out((n_log, B, 3), np.float64), a.out((n_log, B, 4), np.float64),
+                    a.out((n_log, B), np.int32)]
+        return B, M, ins, outs, logs
 
     # ---- the timed rollout: the PID follows the speed planner's profile (include/emplanner.h states the rule) -------
     def speed_target(self, trajectory, t0, tick, dt, cap, cursor=None, in_place=False) -> SpeedTargetResult:
@@ -1099,7 +1100,7 @@ class Planner:
         cin = a.inp(cursor, np.int32, (B,))
         if in_place and cursor is None:
             raise ValueError("in_place needs a cursor array")
-        co, cop = a.out((B,), np.int32, into=_same_array(cursor, np.int32) if in_place else None)
+        co, cop = a.out((B,), np.int32, into=_in_place(cursor, np.int32, in_place))
         ts, tsp = a.out((B,), np.int32)
         self._check(self._lib.emp_speed_target(self._h, B, a.inp(trajectory, np.float64, (B, 7, N)), a.inp(t0, np.float64, (B,)),
                                                int(tick), float(dt), a.inp(cap, np.float64, (B,)), cin, tgp, cop, tsp, a.where))
@@ -1114,44 +1115,30 @@ class Planner:
         device, t0 (B,) the plan_start_time that was passed in; target_speed (B,) km/h is the cap and the target without a
         profile.  A rollout resumes bit for bit from ``tick0`` = the ticks done, fed with the previous result's state,
         min_index, err, n_err and cursor.  in_place=True also updates ``cursor`` where it lives (it must then be given)."""
-        law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
-        if law is None:
-            raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+        law = _lateral_law(lateral)
         T, tick0 = int(T), int(tick0)
         every = 1 if log_every is None else int(log_every)
         if in_place and cursor is None:
             raise ValueError("in_place needs a cursor array")
+        n_log = (T + every - 1) // every if log_every is not None and every >= 1 and T >= 1 else None
         a = self._args(target_path, state, err, trajectory)
-        B, M = int(target_path.shape[0]), int(target_path.shape[1])
-        nb, N = L.PID_BUFFER, L.TIMED_POINTS
+        B, M, ins, outs, logs = self._rollout_arrays(a, target_path, n_path, state, min_index, target_speed, err, n_err, n_log, in_place)
+        N = L.TIMED_POINTS
         io = L.RolloutTimedIO()
-        io.target_path, io.n_path = a.inp(target_path, np.float64, (B, M, 4)), a.inp(n_path, np.int32, (B,))
-        io.state, io.min_index = a.inp(state, np.float64, (B, 6)), a.inp(min_index, np.int32, (B,))
-        io.target_speed = a.inp(target_speed, np.float64, (B,))
-        io.err_in, io.n_err_in = a.inp(err, np.float64, (B, nb)), a.inp(n_err, np.int32, (B,))
+        io.target_path, io.n_path, io.state, io.min_index, io.target_speed, io.err_in, io.n_err_in = ins
         io.trajectory, io.t0 = a.inp(trajectory, np.float64, (B, 7, N)), a.inp(t0, np.float64, (B,))
         io.cursor_in = a.inp(cursor, np.int32, (B,))
-        same = (lambda x, dt: _same_array(x, dt)) if in_place else (lambda x, dt: None)
-        so, io.state_out = a.out((B, 6), np.float64, into=same(state, np.float64))
-        mi, io.min_index_out = a.out((B,), np.int32, into=same(min_index, np.int32))
-        eo, io.err_out = a.out((B, nb), np.float64, into=same(err, np.float64))
-        no, io.n_err_out = a.out((B,), np.int32, into=same(n_err, np.int32))
-        st, io.status = a.out((B,), np.int32)
-        ft, io.fail_tick = a.out((B,), np.int32)
-        cu, io.cursor_out = a.out((B,), np.int32, into=same(cursor, np.int32))
+        io.state_out, io.min_index_out, io.err_out, io.n_err_out, io.status, io.fail_tick = [o[1] for o in outs]
+        cu, io.cursor_out = a.out((B,), np.int32, into=_in_place(cursor, np.int32, in_place))
         ts, io.tgt_status = a.out((B,), np.int32)
-        logs = [None] * 5
-        if log_every is not None and every >= 1 and T >= 1:
-            n_log = (T + every - 1) // every
-            logs[0], io.log_state = a.out((n_log, B, 6), np.float64)
-            logs[1], io.log_control = a.out((n_log, B, 3), np.float64)
-            logs[2], io.log_err = a.out((n_log, B, 4), np.float64)
-            logs[3], io.log_index = a.out((n_log, B), np.int32)
-            logs[4], io.log_target = a.out((n_log, B), np.float64)
+        io.log_state, io.log_control, io.log_err, io.log_index = [o[1] for o in logs]
+        lt = None
+        if n_log is not None:
+            lt, io.log_target = a.out((n_log, B), np.float64)
         io.reserved = 0
         self._check(self._lib.emp_rollout_timed(self._h, law, C.byref(lat), C.byref(pid), C.byref(vp), B, M, T, tick0, every,
                                                 C.byref(io), a.where))
-        return TimedRolloutResult(so, mi, eo, no, st, ft, *logs[:4], cu, ts, logs[4])
+        return TimedRolloutResult(*[o[0] for o in outs], *[o[0] for o in logs], cu, ts, lt)
 
     # ---- the fleet loop (the reference driver's main loop, test_9.py:336-436) ---------------------------------------
     def drive_request(self, dp: DriveParams, state, accel, actors, n_act, max_obs: int, max_dyn: int = 8,
@@ -1171,7 +1158,7 @@ class Planner:
             ((B, 2), np.float64), ((B, 2), np.float64), ((B,), np.int32))]
         nxt, nxtp = (None, None)
         if advance or in_place:
-            nxt, nxtp = a.out((B, A, 4), np.float64, into=_same_array(actors, np.float64) if in_place else None)
+            nxt, nxtp = a.out((B, A, 4), np.float64, into=_in_place(actors, np.float64, in_place))
         self._check(self._lib.emp_drive_request(self._h, C.byref(dp), B, A, mo, md, *ins, *[o[1] for o in outs], nxtp, a.where))
         return DriveRequest(*[o[0] for o in outs], nxt)
 
@@ -1185,9 +1172,7 @@ class Planner:
         (B,), track (B, max_pts + 1, 4), track_len (B,), held (B,), target_speed (B,).  A vehicle with track_len 0 and no valid
         plan coasts.  logs=False skips the per-period logs.  in_place=True updates state, actors, pre_match_index, track,
         track_len and held (and accel, when given) where they live.  Equals the chain of the separate calls bit for bit."""
-        law = {"mpc": L.EMP_LAT_MPC, "lqr": L.EMP_LAT_LQR}.get(lateral)
-        if law is None:
-            raise ValueError(f"lateral must be 'mpc' or 'lqr', not {lateral!r}")
+        law = _lateral_law(lateral)
         K, T = int(K), int(T)
         a = self._args(global_path, state, actors, track)
         B, G, A = int(global_path.shape[0]), int(global_path.shape[1]), int(actors.shape[1])
@@ -1204,14 +1189,13 @@ class Planner:
         io.track_len = a.inp(track_len, np.int32, (B,))
         io.held = a.inp(held, np.int32, (B,))
         tsp = a.inp(target_speed, np.float64, (B,))
-        same = (lambda x, dt: _same_array(x, dt) if x is not None else None) if in_place else (lambda x, dt: None)
         res = []
         for name, src, shape, dt in (("state_out", state, (B, 6), np.float64), ("accel_out", accel, (B, 2), np.float64),
                                      ("actors_out", actors, (B, A, 4), np.float64),
                                      ("pre_match_index_out", pre_match_index, (B,), np.int32),
                                      ("track_out", track, (B, M + 1, 4), np.float64), ("track_len_out", track_len, (B,), np.int32),
                                      ("held_out", held, (B,), np.int32)):
-            arr, ptr = a.out(shape, dt, into=same(src, dt))
+            arr, ptr = a.out(shape, dt, into=_in_place(src, dt, in_place and src is not None))
             res.append(arr)
             setattr(io, name, ptr)
         for name, shape, dt in (("log_state", (K, B, 6), np.float64), ("log_plan_status", (K, B), np.int32),

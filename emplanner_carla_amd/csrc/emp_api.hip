@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <tuple>
 
 #include "emp_context.h"
 #ifndef EMP_QP_LDS_PAD
@@ -1896,6 +1897,73 @@ static emp::StDev make_st_dev(const emp_speed_dp_params* p, int B, int max_obs) 
     return d;
 }
 
+// ---- device-level launchers of the speed stages (as dev_project: device pointers, nothing of the caller's checked, no sync) ----
+// The speed DP takes its heaviest scenes first (emp_st_kernels.h: st_count_kernel) beyond this many: pointless while every block
+// is resident at once.  The caller stages the ordering's temporaries before its Stage::ready().
+constexpr int kStOrderAbove = 512;
+struct StOrderTmp {
+    int* order = nullptr;
+    unsigned char* key = nullptr;
+    int* hist = nullptr;
+};
+static StOrderTmp st_order_tmp(Stage& st, int B) {
+    if (B <= kStOrderAbove) return {};
+    int* order = st.tmp<int>((size_t)B);
+    unsigned char* key = st.tmp<unsigned char>((size_t)B);
+    return {order, key, st.tmp<int>(2 * (size_t)kStKeys, true)};
+}
+
+static int dev_speed_dp(emp_ctx* ctx, const emp_speed_dp_params* p, int B, int max_obs, const double* s_in, const double* s_out,
+                        const double* t_in, const double* t_out, const double* v_start, double* cost, double* s_dot, int* node,
+                        int* end_node, double* speed_s, double* speed_t, const StOrderTmp& o) {
+    if (o.order) {           // two launches, one timing interval
+        if (const int rc = launch_gate(ctx)) return rc;
+        KernelTimer t(ctx, "speed_dp_order");
+        hipLaunchKernelGGL(st_count_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, max_obs, s_in, o.key, o.hist);
+        hipLaunchKernelGGL(st_scatter_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, o.key, o.hist, o.hist + kStKeys, o.order);
+        EMP_LAUNCH_CHECK(ctx);
+    }
+    return launch(ctx, "speed_dp", max_obs <= 32 ? speed_dp_kernel<uint32_t> : speed_dp_kernel<uint64_t>, dim3(B), dim3(kStBlock),
+                  speed_dp_lds_bytes(max_obs), make_st_dev(p, B, max_obs), s_in, s_out, t_in, t_out, v_start, cost, s_dot, node,
+                  end_node, speed_s, speed_t, (const int*)o.order);
+}
+
+constexpr double kDefaultMaxLateralAccel = 0.2 * 9.8;       // ref: generate_convex_space's default, speed_planning_test.py:309
+static int dev_speed_convex_space(emp_ctx* ctx, int B, int n_slots, int max_path, double max_lateral_accel, const double* dp_s,
+                                  const double* dp_t, const double* index2s, const double* kappa, const int* path_len,
+                                  const double* s_in, const double* s_out, const double* t_in, const double* t_out, double* s_lb,
+                                  double* s_ub, double* sd_lb, double* sd_ub, int* status) {
+    return launch(ctx, "speed_convex_space", stb::convex_space_kernel, grid1(B, 64), dim3(64), 0, B, n_slots, max_path,
+                  max_lateral_accel, dp_s, dp_t, index2s, kappa, path_len, s_in, s_out, t_in, t_out, s_lb, s_ub, sd_lb, sd_ub, status);
+}
+
+static int dev_speed_qp(emp_ctx* ctx, const emp_speed_qp_params* p, int B, const double* v0, const double* a0, const double* dp_s,
+                        const double* dp_t, const double* s_lb, const double* s_ub, const double* sd_lb, const double* sd_ub,
+                        double* qs, double* qv, double* qa, double* qt, int* iters, int* status) {
+    const stb::SpeedQpParams prm{p->w_cost_s_dot2, p->w_cost_v_ref, p->w_cost_jerk, p->reference_speed};
+    const size_t lds = 2 * (size_t)(stb::speed_qp_words(stb::kQp) + 1) * sizeof(double);
+    return launch(ctx, "speed_qp", stb::speed_qp_kernel<32>, dim3((B + 1) / 2) /* two scenes per wavefront */, dim3(64), lds, B, prm, v0, a0, dp_s, dp_t, s_lb, s_ub,
+                  sd_lb, sd_ub, qs, qv, qa, qt, iters, status);
+}
+
+static int dev_speed_increase_points(emp_ctx* ctx, int B, const double* qs, const double* qv, const double* qa, const double* qt,
+                                     double* s, double* v, double* a, double* t, int* status) {
+    return launch(ctx, "speed_increase_points", stb::densify_kernel, dim3(B), dim3(64), 0, B, qs, qv, qa, qt, s, v, a, t, status);
+}
+
+constexpr const char* kMergeTooLong = "path too long for the LDS-resident merge kernel";
+static size_t merge_lds_bytes(int max_path) { return (size_t)5 * max_path * sizeof(double); }
+
+static int dev_path_speed_merge(emp_ctx* ctx, int B, int max_path, const double* s, const double* v, const double* a, const double* t,
+                                const double* now, const double* path_s, const double* x, const double* y, const double* heading,
+                                const double* kappa, const int* n_init, double* trajectory, int* status) {
+    if (B == 0) return EMP_OK;
+    const size_t lds = merge_lds_bytes(max_path);
+    if (const int rc = set_lds(ctx, stb::merge_kernel, lds, kMergeTooLong)) return rc;
+    return launch(ctx, "path_speed_merge", stb::merge_kernel, dim3(B), dim3(64), lds, B, max_path, s, v, a, t, now, path_s, x, y,
+                  heading, kappa, n_init, trajectory, status);
+}
+
 int emp_st_graph(emp_ctx* ctx, int32_t B, int32_t max_obs, const double* obs_s, const double* obs_l,
                  const double* obs_s_dot, const double* obs_l_dot, double* s_in, double* s_out, double* t_in,
                  double* t_out, emp_mem where) {
@@ -1942,23 +2010,9 @@ int emp_speed_dp(emp_ctx* ctx, const emp_speed_dp_params* p, int32_t B, int32_t 
     int* d_e = st.out(end_node, (size_t)B * 2, false);
     double* d_ss = st.out(speed_s, (size_t)B * emp::st::kCols, false);
     double* d_tt = st.out(speed_t, (size_t)B * emp::st::kCols, false);
-    // heaviest scenes first (emp_st_kernels.h: st_count_kernel); pointless when every block is resident at once
-    const bool order = B > 512;
-    int* d_order = order ? st.tmp<int>((size_t)B) : nullptr;
-    unsigned char* d_key = order ? st.tmp<unsigned char>((size_t)B) : nullptr;
-    int* d_hist = order ? st.tmp<int>(2 * (size_t)kStKeys, true) : nullptr;
+    const StOrderTmp order = st_order_tmp(st, B);
     if (const int rc = st.ready()) return rc;
-    if (order) {           // two launches, one timing interval
-        if (const int rc = launch_gate(ctx)) return rc;
-        KernelTimer t(ctx, "speed_dp_order");
-        hipLaunchKernelGGL(st_count_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, max_obs, d_si, d_key, d_hist);
-        hipLaunchKernelGGL(st_scatter_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, d_key, d_hist, d_hist + kStKeys, d_order);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    if (const int rc = launch(ctx, "speed_dp", max_obs <= 32 ? speed_dp_kernel<uint32_t> : speed_dp_kernel<uint64_t>, dim3(B),
-                              dim3(kStBlock), speed_dp_lds_bytes(max_obs), make_st_dev(p, B, max_obs), d_si, d_so, d_ti, d_to, d_v,
-                              d_c, d_sd, d_n, d_e, d_ss, d_tt, d_order))
-        return rc;
+    if (const int rc = dev_speed_dp(ctx, p, B, max_obs, d_si, d_so, d_ti, d_to, d_v, d_c, d_sd, d_n, d_e, d_ss, d_tt, order)) return rc;
     return st.finish();
 }
 
@@ -2053,9 +2107,8 @@ int emp_speed_convex_space(emp_ctx* ctx, int32_t B, int32_t n_slots, int32_t max
     double* d_vub = st.out(s_dot_ub, (size_t)B * stb::kDp, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, "speed_convex_space", stb::convex_space_kernel, grid1(B, 64), dim3(64), 0, B, n_slots, max_path,
-                              max_lateral_accel, d_ds, d_dt, d_i2s, d_k, d_pl, d_si, d_so, d_ti, d_to, d_lb, d_ub, d_vlb, d_vub,
-                              d_st))
+    if (const int rc = dev_speed_convex_space(ctx, B, n_slots, max_path, max_lateral_accel, d_ds, d_dt, d_i2s, d_k, d_pl, d_si, d_so,
+                                              d_ti, d_to, d_lb, d_ub, d_vlb, d_vub, d_st))
         return rc;
     return st.finish();
 }
@@ -2085,10 +2138,7 @@ int emp_speed_qp(emp_ctx* ctx, const emp_speed_qp_params* p, int32_t B, const do
     int* d_it = st.out(iters, (size_t)B, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    const stb::SpeedQpParams prm{p->w_cost_s_dot2, p->w_cost_v_ref, p->w_cost_jerk, p->reference_speed};
-    const size_t lds = 2 * (size_t)(stb::speed_qp_words(stb::kQp) + 1) * sizeof(double);
-    if (const int rc = launch(ctx, "speed_qp", stb::speed_qp_kernel<32>, dim3((B + 1) / 2), dim3(64), lds, B, prm, d_v0, d_a0, d_ds,
-                              d_dt, d_lb, d_ub, d_vlb, d_vub, d_qs, d_qv, d_qa, d_qt, d_it, d_st))
+    if (const int rc = dev_speed_qp(ctx, p, B, d_v0, d_a0, d_ds, d_dt, d_lb, d_ub, d_vlb, d_vub, d_qs, d_qv, d_qa, d_qt, d_it, d_st))
         return rc;
     return st.finish();
 }
@@ -2110,9 +2160,7 @@ int emp_speed_increase_points(emp_ctx* ctx, int32_t B, const double* s_init, con
     double* d_t = st.out(relative_time, (size_t)B * stb::kDense, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, "speed_increase_points", stb::densify_kernel, dim3(B), dim3(64), 0, B, d_qs, d_qv, d_qa, d_qt,
-                              d_s, d_v, d_a, d_t, d_st))
-        return rc;
+    if (const int rc = dev_speed_increase_points(ctx, B, d_qs, d_qv, d_qa, d_qt, d_s, d_v, d_a, d_t, d_st)) return rc;
     return st.finish();
 }
 
@@ -2125,8 +2173,7 @@ int emp_path_speed_merge(emp_ctx* ctx, int32_t B, int32_t max_path, const double
     EMP_REQUIRE(ctx, B >= 0 && max_path >= 1, "bad sizes");
     EMP_REQUIRE(ctx, s && s_dot && s_dot2 && relative_time && current_time && path_s && x_init && y_init && heading_init &&
                          kappa_init && n_init && trajectory && status, "NULL argument");
-    const size_t lds = (size_t)5 * max_path * sizeof(double);
-    EMP_REQUIRE(ctx, lds <= 64 * 1024, "path too long for the LDS-resident merge kernel");
+    EMP_REQUIRE(ctx, merge_lds_bytes(max_path) <= 64 * 1024, kMergeTooLong);     // this entry's own limit, before anything is staged
     EMP_STAGE(st, where);
     const double* d_s = st.in(s, (size_t)B * stb::kDense);
     const double* d_v = st.in(s_dot, (size_t)B * stb::kDense);
@@ -2142,10 +2189,7 @@ int emp_path_speed_merge(emp_ctx* ctx, int32_t B, int32_t max_path, const double
     double* d_out = st.out(trajectory, (size_t)B * 7 * stb::kDense, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    if (B && lds > 48 * 1024)
-        EMP_HIP(ctx, hipFuncSetAttribute((const void*)stb::merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (const int rc = launch(ctx, "path_speed_merge", stb::merge_kernel, dim3(B), dim3(64), lds, B, max_path, d_s, d_v, d_a, d_t,
-                              d_now, d_ps, d_x, d_y, d_h, d_k, d_n, d_out, d_st))
+    if (const int rc = dev_path_speed_merge(ctx, B, max_path, d_s, d_v, d_a, d_t, d_now, d_ps, d_x, d_y, d_h, d_k, d_n, d_out, d_st))
         return rc;
     return st.finish();
 }
@@ -2190,57 +2234,29 @@ int SpeedHalf::run(emp_ctx* ctx, Stage& st, int B, int max_pts, const double* d_
     double* dense = st.tmp<double>(4 * nb * stb::kDense);
     int* st_dense = st.tmp<int>(nb);
     int* st_merge = st.tmp<int>(nb);
-    // emp_speed_dp's heaviest-first order beyond 512 scenes (emp_st_kernels.h: st_count_kernel)
-    const bool order = B > 512;
-    int* d_order = order ? st.tmp<int>(nb) : nullptr;
-    unsigned char* d_key = order ? st.tmp<unsigned char>(nb) : nullptr;
-    int* d_hist = order ? st.tmp<int>(2 * (size_t)kStKeys, true) : nullptr;
+    const StOrderTmp order = st_order_tmp(st, B);
     if (const int rc = st.ready()) return rc;          // (temporaries staged behind the cycle's launches: checked here)
-    const size_t sp = nb * max_dyn;
-    double *si = seg, *so = seg + sp, *ti = seg + 2 * sp, *to = seg + 3 * sp;
-    double *ds = dp_speed, *dt = dp_speed + nb * stb::kDp;
-    if (const int rc = launch(ctx, "speed_front", speed_front_wave_kernel, dim3(B), dim3(64), 2 * (size_t)W * sizeof(double), B,
-                              max_pts, W, max_dyn, d_traj, d_tlen, d_v, d_a, heading, dyn, n_dyn, pre, rows, i2s, v0, a0, seg,
-                              width, st_front))
-        return rc;
-    if (order) {
-        if (const int rc = launch_gate(ctx)) return rc;
-        KernelTimer t(ctx, "speed_dp_order");
-        hipLaunchKernelGGL(st_count_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, max_dyn, (const double*)si, d_key, d_hist);
-        hipLaunchKernelGGL(st_scatter_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, (const unsigned char*)d_key,
-                           (const int*)d_hist, d_hist + kStKeys, d_order);
-        EMP_LAUNCH_CHECK(ctx);
-    }
-    if (const int rc = launch(ctx, "speed_dp", max_dyn <= 32 ? speed_dp_kernel<uint32_t> : speed_dp_kernel<uint64_t>, dim3(B),
-                              dim3(kStBlock), speed_dp_lds_bytes(max_dyn), make_st_dev(dp, B, max_dyn), (const double*)si,
-                              (const double*)so, (const double*)ti, (const double*)to, (const double*)v0, (double*)nullptr,
-                              (double*)nullptr, (int*)nullptr, end_node, ds, dt, (const int*)d_order))
-        return rc;
-    // generate_convex_space on the W-wide rows (the reference's default max_lateral_accel = 0.2 * 9.8, speed_planning_test.py:309);
-    // path_len = merge width: W, or 0 for a scene that already raised
+    const size_t sp = nb * max_dyn, n16 = nb * stb::kDp, n17 = nb * stb::kQp, n401 = nb * stb::kDense;
+    const double *si = seg, *so = seg + sp, *ti = seg + 2 * sp, *to = seg + 3 * sp;
+    double *ds = dp_speed, *dt = dp_speed + n16;
     const double* kappa = rows + 3 * bw;
-    if (const int rc = launch(ctx, "speed_convex_space", stb::convex_space_kernel, grid1(B, 64), dim3(64), 0, B, max_dyn, W, 0.2 * 9.8,
-                              (const double*)ds, (const double*)dt, (const double*)i2s, kappa, (const int*)width, (const double*)si,
-                              (const double*)so, (const double*)ti, (const double*)to, cs, cs + nb * stb::kDp, cs + 2 * nb * stb::kDp,
-                              cs + 3 * nb * stb::kDp, st_cs))
+    int rc;
+    if ((rc = launch(ctx, "speed_front", speed_front_wave_kernel, dim3(B), dim3(64), 2 * (size_t)W * sizeof(double), B, max_pts, W,
+                     max_dyn, d_traj, d_tlen, d_v, d_a, heading, dyn, n_dyn, pre, rows, i2s, v0, a0, seg, width, st_front)))
         return rc;
-    const stb::SpeedQpParams prm{qp->w_cost_s_dot2, qp->w_cost_v_ref, qp->w_cost_jerk, qp->reference_speed};
-    const size_t qlds = 2 * (size_t)(stb::speed_qp_words(stb::kQp) + 1) * sizeof(double);
-    const size_t q17 = nb * stb::kQp, d401 = nb * stb::kDense;
-    if (const int rc = launch(ctx, "speed_qp", stb::speed_qp_kernel<32>, dim3((B + 1) / 2), dim3(64), qlds, B, prm, (const double*)v0,
-                              (const double*)a0, (const double*)ds, (const double*)dt, (const double*)cs,
-                              (const double*)(cs + nb * stb::kDp), (const double*)(cs + 2 * nb * stb::kDp),
-                              (const double*)(cs + 3 * nb * stb::kDp), qp4, qp4 + q17, qp4 + 2 * q17, qp4 + 3 * q17, (int*)nullptr,
-                              st_qp))
+    if ((rc = dev_speed_dp(ctx, dp, B, max_dyn, si, so, ti, to, v0, nullptr, nullptr, nullptr, end_node, ds, dt, order))) return rc;
+    // generate_convex_space on the W-wide rows; path_len = merge width: W, or 0 for a scene that already raised
+    if ((rc = dev_speed_convex_space(ctx, B, max_dyn, W, kDefaultMaxLateralAccel, ds, dt, i2s, kappa, width, si, so, ti, to, cs,
+                                     cs + n16, cs + 2 * n16, cs + 3 * n16, st_cs)))
         return rc;
-    if (const int rc = launch(ctx, "speed_increase_points", stb::densify_kernel, dim3(B), dim3(64), 0, B, (const double*)qp4,
-                              (const double*)(qp4 + q17), (const double*)(qp4 + 2 * q17), (const double*)(qp4 + 3 * q17), dense,
-                              dense + d401, dense + 2 * d401, dense + 3 * d401, st_dense))
+    if ((rc = dev_speed_qp(ctx, qp, B, v0, a0, ds, dt, cs, cs + n16, cs + 2 * n16, cs + 3 * n16, qp4, qp4 + n17, qp4 + 2 * n17,
+                           qp4 + 3 * n17, nullptr, st_qp)))
         return rc;
-    if (const int rc = launch(ctx, "path_speed_merge", stb::merge_kernel, dim3(B), dim3(64), 5 * (size_t)W * sizeof(double), B, W,
-                              (const double*)dense, (const double*)(dense + d401), (const double*)(dense + 2 * d401),
-                              (const double*)(dense + 3 * d401), t0, (const double*)i2s, (const double*)rows,
-                              (const double*)(rows + bw), (const double*)(rows + 2 * bw), kappa, (const int*)width, traj, st_merge))
+    if ((rc = dev_speed_increase_points(ctx, B, qp4, qp4 + n17, qp4 + 2 * n17, qp4 + 3 * n17, dense, dense + n401, dense + 2 * n401,
+                                        dense + 3 * n401, st_dense)))
+        return rc;
+    if ((rc = dev_path_speed_merge(ctx, B, W, dense, dense + n401, dense + 2 * n401, dense + 3 * n401, t0, i2s, rows, rows + bw,
+                                   rows + 2 * bw, kappa, width, traj, st_merge)))
         return rc;
     return launch(ctx, "speed_status", speed_status_kernel, grid1(B, 64), dim3(64), 0, B, (const int*)st_front, (const int*)st_cs,
                   (const int*)st_qp, (const int*)st_dense, (const int*)st_merge, status);
@@ -2301,14 +2317,29 @@ static mpc::Params mpc_params(const emp_mpc_params* p) {
 
 }  // extern "C"
 
-// Stage and launch a lateral law of the MPC shape (emp_mpc_lateral, emp_mpc_ff_lateral): one vehicle per group of nu lanes, 64 / nu
-// groups per wavefront, nu controls and an nu x nu Hessian out.  `tail` is what the kernel takes after status (the fused
-// epilogue's CtlIO, or nothing).
-template <typename K, typename... Tail>
-static int mpc_shaped_lateral(emp_ctx* ctx, const char* name, K kern, int nu, const emp_mpc_params* p, int B, int max_path,
-                              const double* target_path, const int32_t* n_path, const double* state, const double* vx,
-                              const int32_t* min_index, double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out,
-                              double* pre_pro, double* H, double* f, int32_t* iters, int32_t* status, emp_mem where, Tail... tail) {
+// The one launch of a lateral law chosen at run time (emp_vehicle_control, the rollouts, emp_drive), timed under `name`: the MPC
+// kernel with kGroupsPerWave vehicle groups per wavefront or the LQR kernel with one vehicle per lane, each with its argument list.
+template <typename KM, typename KL, typename... AM, typename... AL>
+static int launch_lateral(emp_ctx* ctx, const char* name, int lateral, int B, KM mpc_kern, KL lqr_kern, const std::tuple<AM...>& mpc_args,
+                          const std::tuple<AL...>& lqr_args) {
+    const auto go = [&](auto kern, dim3 grid, const auto& args) {
+        return std::apply([&](auto... a) { return launch(ctx, name, kern, grid, dim3(64), 0, a...); }, args);
+    };
+    return lateral == EMP_LAT_MPC ? go(mpc_kern, grid_groups(B, mpc::kGroupsPerWave), mpc_args) : go(lqr_kern, grid1(B, 64), lqr_args);
+}
+
+// Stage and launch a stand-alone lateral law (emp_mpc_lateral, emp_mpc_ff_lateral, emp_lqr_lateral): one vehicle per group of `lanes`
+// lanes, 64 / lanes groups per wavefront.  `gain` is the law's own [B][n_gain] output (the MPCs' controls u, the LQR's K) and `iters`
+// its count (QP iterations, Riccati sweeps); HF: the kernel also writes the condensed problem, H [n_gain x n_gain] and f [n_gain].
+// `tail`: what the kernel takes after status (the fused epilogue's CtlIO, or nothing).
+template <bool HF, typename K, typename... Tail>
+static int stage_lateral(emp_ctx* ctx, const char* name, K kern, int lanes, int n_gain, const emp_mpc_params* p, int B, int max_path,
+                         const double* target_path, const int32_t* n_path, const double* state, const double* vx,
+                         const int32_t* min_index, double* steer, double* gain, double* e_rr, double* k_r, int32_t* min_index_out,
+                         double* pre_pro, double* H, double* f, int32_t* iters, int32_t* status, emp_mem where, Tail... tail) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
     EMP_STAGE(st, where);
     const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
     const int* d_np = st.in(n_path, (size_t)B);
@@ -2316,20 +2347,24 @@ static int mpc_shaped_lateral(emp_ctx* ctx, const char* name, K kern, int nu, co
     const double* d_vx = st.in(vx, (size_t)B);
     const int* d_mi = st.in(min_index, (size_t)B);
     double* d_steer = st.out(steer, (size_t)B, false);
-    double* d_u = st.out(u, (size_t)B * nu, false);
+    double* d_g = st.out(gain, (size_t)B * n_gain, false);
     double* d_e = st.out(e_rr, (size_t)B * 4, false);
     double* d_k = st.out(k_r, (size_t)B, false);
     int* d_mo = st.out(min_index_out, (size_t)B, false);
     double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
-    double* d_H = st.out(H, (size_t)B * nu * nu, false);
-    double* d_f = st.out(f, (size_t)B * nu, false);
+    double* d_H = st.out(H, (size_t)B * n_gain * n_gain, false);
+    double* d_f = st.out(f, (size_t)B * n_gain, false);
     int* d_it = st.out(iters, (size_t)B, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, name, kern, grid_groups(B, 64 / nu), dim3(64), 0, B, max_path, mpc_params(p), d_path, d_np, d_state,
-                              d_vx, d_mi, d_steer, d_u, d_e, d_k, d_mo, d_pp, d_H, d_f, d_it, d_st, tail...))
-        return rc;
-    return st.finish();
+    const auto go = [&](auto... rest) {
+        return launch(ctx, name, kern, grid_groups(B, 64 / lanes), dim3(64), 0, B, max_path, mpc_params(p), d_path, d_np, d_state, d_vx,
+                      d_mi, d_steer, d_g, d_e, d_k, d_mo, d_pp, rest...);
+    };
+    int rc;
+    if constexpr (HF) rc = go(d_H, d_f, d_it, d_st, tail...);
+    else rc = go(d_it, d_st, tail...);
+    return rc ? rc : st.finish();
 }
 
 extern "C" {
@@ -2338,11 +2373,8 @@ int emp_mpc_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
                     const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
                     double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
                     double* H, double* f, int32_t* iters, int32_t* status, emp_mem where) {
-    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
-    EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
-    EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
-    return mpc_shaped_lateral(ctx, "mpc_lateral", mpc::mpc_lateral_kernel<false>, mpc::kNu, p, B, max_path, target_path, n_path, state, vx,
-                              min_index, steer, u, e_rr, k_r, min_index_out, pre_pro, H, f, iters, status, where, mpc::CtlIO{});
+    return stage_lateral<true>(ctx, "mpc_lateral", mpc::mpc_lateral_kernel<false>, mpc::kNu, mpc::kNu, p, B, max_path, target_path, n_path,
+                               state, vx, min_index, steer, u, e_rr, k_r, min_index_out, pre_pro, H, f, iters, status, where, mpc::CtlIO{});
 }
 
 void emp_lqr_params_default(emp_mpc_params* p) {
@@ -2355,28 +2387,9 @@ int emp_lqr_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
                     const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
                     double* steer, double* K, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
                     int32_t* sweeps, int32_t* status, emp_mem where) {
-    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
-    EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
-    EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
-    EMP_STAGE(st, where);
-    const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
-    const int* d_np = st.in(n_path, (size_t)B);
-    const double* d_state = st.in(state, (size_t)B * 5);
-    const double* d_vx = st.in(vx, (size_t)B);
-    const int* d_mi = st.in(min_index, (size_t)B);
-    double* d_steer = st.out(steer, (size_t)B, false);
-    double* d_K = st.out(K, (size_t)B * 4, false);
-    double* d_e = st.out(e_rr, (size_t)B * 4, false);
-    double* d_k = st.out(k_r, (size_t)B, false);
-    int* d_mo = st.out(min_index_out, (size_t)B, false);
-    double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
-    int* d_sw = st.out(sweeps, (size_t)B, false);
-    int* d_st = st.out(status, (size_t)B, false);
-    if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, "lqr_lateral", lqr::lqr_lateral_kernel<false>, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(p),
-                              d_path, d_np, d_state, d_vx, d_mi, d_steer, d_K, d_e, d_k, d_mo, d_pp, d_sw, d_st, mpc::CtlIO{}))
-        return rc;
-    return st.finish();
+    return stage_lateral<false>(ctx, "lqr_lateral", lqr::lqr_lateral_kernel<false>, 1, 4, p, B, max_path, target_path, n_path, state, vx,
+                                min_index, steer, K, e_rr, k_r, min_index_out, pre_pro, nullptr, nullptr, sweeps, status, where,
+                                mpc::CtlIO{});
 }
 
 }  // extern "C"
@@ -2448,11 +2461,8 @@ int emp_mpc_ff_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t
                        const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
                        double* steer, double* u, double* e_rr, double* k_r, int32_t* min_index_out, double* pre_pro,
                        double* H, double* f, int32_t* iters, int32_t* status, emp_mem where) {
-    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
-    EMP_REQUIRE(ctx, p && B >= 0 && max_path >= 1, "bad sizes");
-    EMP_REQUIRE(ctx, target_path && n_path && state && vx && min_index && steer && min_index_out && status, "NULL argument");
-    return mpc_shaped_lateral(ctx, "mpc_ff_lateral", mpcff::mpc_ff_lateral_kernel, mpcff::kNu, p, B, max_path, target_path, n_path, state,
-                              vx, min_index, steer, u, e_rr, k_r, min_index_out, pre_pro, H, f, iters, status, where);
+    return stage_lateral<true>(ctx, "mpc_ff_lateral", mpcff::mpc_ff_lateral_kernel, mpcff::kNu, mpcff::kNu, p, B, max_path, target_path,
+                               n_path, state, vx, min_index, steer, u, e_rr, k_r, min_index_out, pre_pro, H, f, iters, status, where);
 }
 
 int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, int32_t B,
@@ -2489,18 +2499,14 @@ int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat
     double* d_pp = st.out(pre_pro, (size_t)B * 4, false);
     int* d_st = st.out(status, (size_t)B, false);
     if (const int rc = st.ready()) return rc;
-    if (lateral == EMP_LAT_MPC) {
-        if (const int rc = launch(ctx, "vehicle_control", mpc::mpc_lateral_kernel<true>,
-                                  grid_groups(B, mpc::kGroupsPerWave), dim3(64), 0, B, max_path, mpc_params(lat), d_path, d_np, d_state,
-                                  d_vx, d_mi, d_lat, (double*)nullptr, d_e, d_k, d_mo, d_pp, (double*)nullptr, (double*)nullptr,
-                                  (int*)nullptr, d_st, io))
-            return rc;
-    } else {
-        if (const int rc = launch(ctx, "vehicle_control", lqr::lqr_lateral_kernel<true>, grid1(B, 64), dim3(64), 0, B, max_path,
-                                  mpc_params(lat), d_path, d_np, d_state, d_vx, d_mi, d_lat, (double*)nullptr, d_e, d_k, d_mo, d_pp,
-                                  (int*)nullptr, d_st, io))
-            return rc;
-    }
+    const mpc::Params prm = mpc_params(lat);
+    double* const no_d = nullptr;                 // the stand-alone laws' own outputs: none here
+    int* const no_i = nullptr;
+    if (const int rc = launch_lateral(
+            ctx, "vehicle_control", lateral, B, mpc::mpc_lateral_kernel<true>, lqr::lqr_lateral_kernel<true>,
+            std::make_tuple(B, max_path, prm, d_path, d_np, d_state, d_vx, d_mi, d_lat, no_d, d_e, d_k, d_mo, d_pp, no_d, no_d, no_i, d_st, io),
+            std::make_tuple(B, max_path, prm, d_path, d_np, d_state, d_vx, d_mi, d_lat, no_d, d_e, d_k, d_mo, d_pp, no_i, d_st, io)))
+        return rc;
     return st.finish();
 }
 
@@ -2513,24 +2519,70 @@ ctl::VehicleParams vehicle_params(const emp_vehicle_params* p) {
     return ctl::VehicleParams{p->a, p->b, p->Cf, p->Cr, p->m, p->Iz, p->dt, p->steer_gain, p->throttle_accel, p->brake_decel, p->drag};
 }
 
-// the one launch of emp_rollout (and of every period of emp_drive): the lateral kernels' mappings
-int launch_rollout(emp_ctx* ctx, int lateral, const emp_mpc_params* lat, int B, int max_path, const double* d_path, const int* d_np,
-                   const rollout::IO& io) {
-    if (lateral == EMP_LAT_MPC)
-        return launch(ctx, "rollout", rollout::mpc_rollout_kernel<rollout::NoProfile>, grid_groups(B, mpc::kGroupsPerWave), dim3(64), 0, B,
-                      max_path, mpc_params(lat), d_path, d_np, io, rollout::NoProfile{});
-    return launch(ctx, "rollout", rollout::lqr_rollout_kernel<rollout::NoProfile>, grid1(B, 64), dim3(64), 0, B, max_path, mpc_params(lat),
-                  d_path, d_np, io, rollout::NoProfile{});
+// the one launch of a rollout: `tg` is rollout::NoProfile (emp_rollout, every period of emp_drive) or the rollout::Profile whose
+// target emp_rollout_timed samples every tick
+template <typename TG>
+int launch_rollout(emp_ctx* ctx, const char* name, int lateral, const emp_mpc_params* lat, int B, int max_path, const double* d_path,
+                   const int* d_np, const rollout::IO& io, const TG& tg) {
+    const auto args = std::make_tuple(B, max_path, mpc_params(lat), d_path, d_np, io, tg);
+    return launch_lateral(ctx, name, lateral, B, rollout::mpc_rollout_kernel<TG>, rollout::lqr_rollout_kernel<TG>, args, args);
 }
 
-// the one launch of emp_rollout_timed: the same kernels with the target sampled from the profile every tick
-int launch_rollout_timed(emp_ctx* ctx, int lateral, const emp_mpc_params* lat, int B, int max_path, const double* d_path, const int* d_np,
-                         const rollout::IO& io, const rollout::Profile& tg) {
-    if (lateral == EMP_LAT_MPC)
-        return launch(ctx, "rollout_timed", rollout::mpc_rollout_kernel<rollout::Profile>, grid_groups(B, mpc::kGroupsPerWave), dim3(64), 0,
-                      B, max_path, mpc_params(lat), d_path, d_np, io, tg);
-    return launch(ctx, "rollout_timed", rollout::lqr_rollout_kernel<rollout::Profile>, grid1(B, 64), dim3(64), 0, B, max_path,
-                  mpc_params(lat), d_path, d_np, io, tg);
+// the checks every rollout shares, behind the caller's own for NULL structs (emp_drive derives its log_every)
+int rollout_args_ok(emp_ctx* ctx, int lateral, const emp_vehicle_params* vp, int T, int log_every) {
+    EMP_REQUIRE(ctx, lateral == EMP_LAT_MPC || lateral == EMP_LAT_LQR, "lateral must be EMP_LAT_MPC or EMP_LAT_LQR");
+    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    EMP_REQUIRE(ctx, T >= 1 && T <= EMP_ROLLOUT_MAX_TICKS, "T must be in [1, 65536]");
+    EMP_REQUIRE(ctx, log_every >= 1, "log_every must be at least 1");
+    return EMP_OK;
+}
+size_t rollout_log_rows(int T, int log_every) { return ((size_t)T + (size_t)log_every - 1) / (size_t)log_every; }
+
+// The caller's arrays of a rollout (emp_rollout's positional arguments, emp_rollout_timed_io's members): 7 inputs, 6 outputs, 4 logs.
+struct RolloutArrays {
+    const double *target_path, *state, *target_speed, *err_in;
+    const int32_t *n_path, *min_index, *n_err_in;
+    double *state_out, *err_out, *log_state, *log_control, *log_err;
+    int32_t *min_index_out, *n_err_out, *status, *fail_tick, *log_index;
+};
+
+// ... staged into the kernels' rollout::IO: inputs, outputs, logs; the timed rollout's own (`timed` into `tg`) behind the inputs and last
+struct RolloutDev {
+    const double* path;
+    const int* n_path;
+    rollout::IO io;
+};
+RolloutDev stage_rollout(Stage& st, const RolloutArrays& a, const emp_pid_params* pid, const emp_vehicle_params* vp, int B, int max_path,
+                         int T, int log_every, const emp_rollout_timed_io* timed = nullptr, rollout::Profile* tg = nullptr) {
+    const size_t nB = (size_t)B, n_log = rollout_log_rows(T, log_every);
+    RolloutDev d{st.in(a.target_path, nB * max_path * 4), st.in(a.n_path, nB), {pid_params(pid), vehicle_params(vp), T, log_every}};
+    rollout::IO& io = d.io;
+    io.state_in = st.in(a.state, nB * 6);
+    io.min_index_in = st.in(a.min_index, nB);
+    io.target_speed = st.in(a.target_speed, nB);
+    io.err_in = st.in(a.err_in, nB * ctl::kPidBuffer);
+    io.n_err_in = st.in(a.n_err_in, nB);
+    if (timed) {
+        tg->trajectory = st.in(timed->trajectory, nB * rollout::kTrajRows * EMP_TIMED_POINTS);
+        tg->t0 = st.in(timed->t0, nB);
+        tg->cursor_in = st.in(timed->cursor_in, nB);
+    }
+    io.state_out = st.out(a.state_out, nB * 6, false);
+    io.min_index_out = st.out(a.min_index_out, nB, false);
+    io.err_out = st.out(a.err_out, nB * ctl::kPidBuffer, false);
+    io.n_err_out = st.out(a.n_err_out, nB, false);
+    io.status = st.out(a.status, nB, false);
+    io.fail_tick = st.out(a.fail_tick, nB, false);
+    io.log_state = st.out(a.log_state, n_log * nB * 6, false);
+    io.log_control = st.out(a.log_control, n_log * nB * 3, false);
+    io.log_err = st.out(a.log_err, n_log * nB * 4, false);
+    io.log_index = st.out(a.log_index, n_log * nB, false);
+    if (timed) {
+        tg->cursor_out = st.out(timed->cursor_out, nB, false);
+        tg->tgt_status = st.out(timed->tgt_status, nB, false);
+        tg->log_target = st.out(timed->log_target, n_log * nB, false);
+    }
+    return d;
 }
 
 }  // namespace
@@ -2576,40 +2628,17 @@ int emp_rollout(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, const 
                 int32_t log_every, double* state_out, int32_t* min_index_out, double* err_out, int32_t* n_err_out, int32_t* status,
                 int32_t* fail_tick, double* log_state, double* log_control, double* log_err, int32_t* log_index, emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
-    EMP_REQUIRE(ctx, lateral == EMP_LAT_MPC || lateral == EMP_LAT_LQR, "lateral must be EMP_LAT_MPC or EMP_LAT_LQR");
     EMP_REQUIRE(ctx, lat && pid && vp && B >= 0 && max_path >= 1, "bad sizes");
-    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
-    EMP_REQUIRE(ctx, T >= 1 && T <= EMP_ROLLOUT_MAX_TICKS, "T must be in [1, 65536]");
-    EMP_REQUIRE(ctx, log_every >= 1, "log_every must be at least 1");
+    if (const int rc = rollout_args_ok(ctx, lateral, vp, T, log_every)) return rc;
     EMP_REQUIRE(ctx, target_path && n_path && state && min_index && target_speed && err_in && n_err_in && state_out &&
                          min_index_out && err_out && n_err_out && status && fail_tick,
                 "NULL argument");
-    const size_t n_log = ((size_t)T + (size_t)log_every - 1) / (size_t)log_every;
+    const RolloutArrays a{target_path, state, target_speed, err_in, n_path, min_index, n_err_in, state_out, err_out, log_state,
+                          log_control, log_err, min_index_out, n_err_out, status, fail_tick, log_index};
     EMP_STAGE(st, where);
-    const double* d_path = st.in(target_path, (size_t)B * max_path * 4);
-    const int* d_np = st.in(n_path, (size_t)B);
-    rollout::IO io{};
-    io.pid = pid_params(pid);
-    io.vp = vehicle_params(vp);
-    io.T = T;
-    io.log_every = log_every;
-    io.state_in = st.in(state, (size_t)B * 6);
-    io.min_index_in = st.in(min_index, (size_t)B);
-    io.target_speed = st.in(target_speed, (size_t)B);
-    io.err_in = st.in(err_in, (size_t)B * ctl::kPidBuffer);
-    io.n_err_in = st.in(n_err_in, (size_t)B);
-    io.state_out = st.out(state_out, (size_t)B * 6, false);
-    io.min_index_out = st.out(min_index_out, (size_t)B, false);
-    io.err_out = st.out(err_out, (size_t)B * ctl::kPidBuffer, false);
-    io.n_err_out = st.out(n_err_out, (size_t)B, false);
-    io.status = st.out(status, (size_t)B, false);
-    io.fail_tick = st.out(fail_tick, (size_t)B, false);
-    io.log_state = st.out(log_state, n_log * B * 6, false);
-    io.log_control = st.out(log_control, n_log * B * 3, false);
-    io.log_err = st.out(log_err, n_log * B * 4, false);
-    io.log_index = st.out(log_index, n_log * B, false);
+    const RolloutDev d = stage_rollout(st, a, pid, vp, B, max_path, T, log_every);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch_rollout(ctx, lateral, lat, B, max_path, d_path, d_np, io)) return rc;
+    if (const int rc = launch_rollout(ctx, "rollout", lateral, lat, B, max_path, d.path, d.n_path, d.io, rollout::NoProfile{})) return rc;
     return st.finish();
 }
 
@@ -2640,55 +2669,27 @@ int emp_rollout_timed(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat, 
                       emp_mem where) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_rollout_timed takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
-    EMP_REQUIRE(ctx, lateral == EMP_LAT_MPC || lateral == EMP_LAT_LQR, "lateral must be EMP_LAT_MPC or EMP_LAT_LQR");
     EMP_REQUIRE(ctx, lat && pid && vp && a, "NULL parameter struct");
     EMP_REQUIRE(ctx, B >= 0 && max_path >= 1, "bad sizes");
-    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    if (const int rc = rollout_args_ok(ctx, lateral, vp, T, log_every)) return rc;
     EMP_REQUIRE(ctx, a->reserved == 0, "emp_rollout_timed_io.reserved must be 0");
-    EMP_REQUIRE(ctx, T >= 1 && T <= EMP_ROLLOUT_MAX_TICKS, "T must be in [1, 65536]");
     EMP_REQUIRE(ctx, tick0 >= 0, "tick0 must be at least 0");
     EMP_REQUIRE(ctx, (int64_t)tick0 + (int64_t)T <= (int64_t)INT32_MAX, "tick0 + T must not exceed INT32_MAX");
-    EMP_REQUIRE(ctx, log_every >= 1, "log_every must be at least 1");
     EMP_REQUIRE(ctx, a->target_path && a->n_path && a->state && a->min_index && a->target_speed && a->err_in && a->n_err_in &&
                          a->trajectory && a->t0,
                 "NULL input array");
     EMP_REQUIRE(ctx, a->state_out && a->min_index_out && a->err_out && a->n_err_out && a->status && a->fail_tick && a->cursor_out &&
                          a->tgt_status,
                 "NULL output array");
-    const size_t n_log = ((size_t)T + (size_t)log_every - 1) / (size_t)log_every;
+    const RolloutArrays ra{a->target_path, a->state, a->target_speed, a->err_in, a->n_path, a->min_index, a->n_err_in, a->state_out,
+                           a->err_out, a->log_state, a->log_control, a->log_err, a->min_index_out, a->n_err_out, a->status, a->fail_tick,
+                           a->log_index};
     EMP_STAGE(st, where);
-    const double* d_path = st.in(a->target_path, (size_t)B * max_path * 4);
-    const int* d_np = st.in(a->n_path, (size_t)B);
-    rollout::IO io{};
-    io.pid = pid_params(pid);
-    io.vp = vehicle_params(vp);
-    io.T = T;
-    io.log_every = log_every;
-    io.state_in = st.in(a->state, (size_t)B * 6);
-    io.min_index_in = st.in(a->min_index, (size_t)B);
-    io.target_speed = st.in(a->target_speed, (size_t)B);
-    io.err_in = st.in(a->err_in, (size_t)B * ctl::kPidBuffer);
-    io.n_err_in = st.in(a->n_err_in, (size_t)B);
     rollout::Profile tg{};
-    tg.trajectory = st.in(a->trajectory, (size_t)B * rollout::kTrajRows * EMP_TIMED_POINTS);
-    tg.t0 = st.in(a->t0, (size_t)B);
-    tg.cursor_in = st.in(a->cursor_in, (size_t)B);
     tg.tick0 = tick0;
-    io.state_out = st.out(a->state_out, (size_t)B * 6, false);
-    io.min_index_out = st.out(a->min_index_out, (size_t)B, false);
-    io.err_out = st.out(a->err_out, (size_t)B * ctl::kPidBuffer, false);
-    io.n_err_out = st.out(a->n_err_out, (size_t)B, false);
-    io.status = st.out(a->status, (size_t)B, false);
-    io.fail_tick = st.out(a->fail_tick, (size_t)B, false);
-    io.log_state = st.out(a->log_state, n_log * B * 6, false);
-    io.log_control = st.out(a->log_control, n_log * B * 3, false);
-    io.log_err = st.out(a->log_err, n_log * B * 4, false);
-    io.log_index = st.out(a->log_index, n_log * B, false);
-    tg.cursor_out = st.out(a->cursor_out, (size_t)B, false);
-    tg.tgt_status = st.out(a->tgt_status, (size_t)B, false);
-    tg.log_target = st.out(a->log_target, n_log * B, false);
+    const RolloutDev d = stage_rollout(st, ra, pid, vp, B, max_path, T, log_every, a, &tg);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch_rollout_timed(ctx, lateral, lat, B, max_path, d_path, d_np, io, tg)) return rc;
+    if (const int rc = launch_rollout(ctx, "rollout_timed", lateral, lat, B, max_path, d.path, d.n_path, d.io, tg)) return rc;
     return st.finish();
 }
 
@@ -2787,13 +2788,11 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
     EMP_REQUIRE(ctx, dp && qp && smooth && drv && lat && pid && vp && io, "NULL parameter struct");
     EMP_REQUIRE(ctx, drv->reserved == 0, "emp_drive_params.reserved must be 0");
     EMP_REQUIRE(ctx, io->reserved == 0, "emp_drive_io.reserved must be 0");
-    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    if (const int rc = rollout_args_ok(ctx, lateral, vp, T, 1)) return rc;
     EMP_REQUIRE(ctx, qp_reserved_ok(qp), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
     EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_drive takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
-    EMP_REQUIRE(ctx, lateral == EMP_LAT_MPC || lateral == EMP_LAT_LQR, "lateral must be EMP_LAT_MPC or EMP_LAT_LQR");
     EMP_REQUIRE(ctx, B >= 0 && max_global >= 1, "bad sizes");
     EMP_REQUIRE(ctx, K >= 1 && K <= EMP_DRIVE_MAX_PERIODS, "K must be in [1, 4096]");
-    EMP_REQUIRE(ctx, T >= 1 && T <= EMP_ROLLOUT_MAX_TICKS, "T must be in [1, 65536]");
     EMP_REQUIRE(ctx, max_act >= 1 && max_act <= 64, "max_act must be in [1, 64]");
     EMP_REQUIRE(ctx, max_obs >= 1 && max_obs <= 253 && max_dyn >= 1 && max_dyn <= 64, "max_obs must be in [1, 253], max_dyn in [1, 64]");
     EMP_REQUIRE(ctx, max_pts >= 2 && max_pts <= 255, "2 <= max_pts <= 255 required");
@@ -2884,12 +2883,8 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
     ad.pre_match_out = o_prem;
     // the rollout: a new controller every period (min_index 0, an empty PID deque); its tick-(T - 1) log row feeds the acceleration
     const int log_every = std::max(T - 1, 1);
-    const size_t n_log = ((size_t)T + log_every - 1) / log_every;
-    rollout::IO ro{};
-    ro.pid = pid_params(pid);
-    ro.vp = vehicle_params(vp);
-    ro.T = T;
-    ro.log_every = log_every;
+    const size_t n_log = rollout_log_rows(T, log_every);
+    rollout::IO ro{pid_params(pid), vehicle_params(vp), T, log_every};
     ro.min_index_in = st.tmp<int>(nB, true);
     ro.target_speed = d_target;
     ro.err_in = st.tmp<double>(nB * ctl::kPidBuffer, true);
@@ -2930,7 +2925,7 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
         if (const int rc = launch(ctx, "drive_adopt", drive::drive_adopt_kernel, dim3(wp.grid), dim3(wp.block), 0, B, max_pts, ad)) return rc;
         ro.state_in = rq.state;
         ro.status = l_roll ? l_roll + kB : t_roll;
-        if (const int rc = launch_rollout(ctx, lateral, lat, B, max_pts + 1, o_track, o_tlen, ro)) return rc;
+        if (const int rc = launch_rollout(ctx, "rollout", lateral, lat, B, max_pts + 1, o_track, o_tlen, ro, rollout::NoProfile{})) return rc;
         if (const int rc = launch(ctx, "drive_accel", drive::drive_accel_kernel, grid1(B, 256), dim3(256), 0, B, vp->dt, (const double*)o_state,
                                   last_seen, o_accel))
             return rc;
