@@ -161,6 +161,22 @@ class DriveIO(C.Structure):
         "log_state", "log_plan_status", "log_roll_status", "log_held", "log_counts", "log_traj", "log_traj_len")] + [("reserved", C.c_int32)]
 
 
+class DriveTimedParams(C.Structure):
+    """emp_drive_timed_params: what emp_drive_timed adds to the parameter blocks of emp_drive and emp_plan_trajectory."""
+    _fields_ = [("plan_lead", C.c_double), ("reserved", C.c_int32)]
+
+
+class DriveTimedIO(C.Structure):
+    """emp_drive_timed_io: emp_drive_io's arrays under their names, the clock, the profile with its cursor and counter, their logs."""
+    _fields_ = [(n, _vp) for n in (
+        "global_path", "n_global", "state", "accel", "actors", "n_act", "pre_match_index", "track", "track_len", "held",
+        "t0", "profile", "cursor", "speed_held",
+        "state_out", "accel_out", "actors_out", "pre_match_index_out", "track_out", "track_len_out", "held_out",
+        "profile_out", "cursor_out", "speed_held_out",
+        "log_state", "log_plan_status", "log_roll_status", "log_held", "log_counts", "log_traj", "log_traj_len",
+        "log_speed_status", "log_speed_held", "log_tgt_status", "log_cursor", "log_profile")] + [("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); data pointers are void* so numpy arrays and raw device addresses both fit
 PROTOTYPES = {
     "emp_abi_version": (C.c_int, []),
@@ -252,6 +268,13 @@ PROTOTYPES = {
     "emp_drive": (C.c_int, [_vp, C.POINTER(DpParams), C.POINTER(QpParams), C.POINTER(SmoothParams), C.POINTER(DriveParams), _i32,
                             C.POINTER(MpcParams), C.POINTER(PidParams), C.POINTER(VehicleParams)] + [_i32] * 8
                   + [_vp, C.POINTER(DriveIO), C.c_int]),
+    "emp_drive_timed_params_default": (None, [C.POINTER(DriveTimedParams)]),
+    "emp_drive_request_timed": (C.c_int, [_vp, C.POINTER(DriveParams), _i32, _i32, _i32, _i32] + [_vp] * 5 + [_i32, _f64, _f64]
+                                + [_vp] * 17 + [C.c_int]),
+    "emp_drive_timed": (C.c_int, [_vp, C.POINTER(DpParams), C.POINTER(QpParams), C.POINTER(SmoothParams), C.POINTER(SpeedDpParams),
+                                  C.POINTER(SpeedQpParams), C.POINTER(DriveParams), C.POINTER(DriveTimedParams), _i32,
+                                  C.POINTER(MpcParams), C.POINTER(PidParams), C.POINTER(VehicleParams)] + [_i32] * 9
+                        + [_vp, C.POINTER(DriveTimedIO), C.c_int]),
     "emp_speed_dp_params_default": (None, [C.POINTER(SpeedDpParams)]),
     "emp_st_graph": (C.c_int, [_vp, _i32, _i32] + [_vp] * 8 + [C.c_int]),
     "emp_speed_dp": (C.c_int, [_vp, C.POINTER(SpeedDpParams), _i32, _i32] + [_vp] * 11 + [C.c_int]),

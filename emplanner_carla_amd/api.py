@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from ._lib import DpParams, QpParams, SmoothParams, SpeedDpParams, SpeedQpParams, MpcParams, PidParams, VehicleParams, DriveParams, EmpError
+from ._lib import DpParams, QpParams, SmoothParams, SpeedDpParams, SpeedQpParams, MpcParams, PidParams, VehicleParams, DriveParams, DriveTimedParams, EmpError
 
 
 def dp_params(row=12, col=6, sample_s=15, sample_l=1.5, sampling_res=2, w_collision_cost=1e12,
@@ -185,6 +185,33 @@ class DriveResult:
     log_counts: object       # (K, B, 2) int32 n_obs, n_dyn
     log_traj: object         # (K, B, max_pts + 1, 4) the period's plan, adopted or not
     log_traj_len: object     # (K, B) int32
+
+
+def drive_timed_params(plan_lead=0.1) -> DriveTimedParams:
+    """What ``drive_timed`` adds to the parameter blocks: plan_lead, the seconds between a period's first tick and its plan's
+    start time (test_10.py:325: cur_time + 0.1)."""
+    return DriveTimedParams(float(plan_lead), 0)
+
+
+@dataclass
+class TimedDriveRequest(DriveRequest):
+    """``Planner.drive_request_timed``: a ``DriveRequest`` (the same bits) and the inputs of ``plan_cycle(speed=...)``."""
+    dyn_obs: object          # (B, max_dyn, 4) x, y, vx, vy of the kept dynamic actors in ``dyn``'s order, before the advance
+    start_heading: object    # (B,) atan2 of start_v
+    plan_start_time: object  # (B,) (t0 + tick * dt) + plan_lead
+
+
+@dataclass
+class TimedDriveResult(DriveResult):
+    """Outputs of ``Planner.drive_timed``: a ``DriveResult``, the profile's in/out state and its per-period logs."""
+    profile: object           # (B, 7, 401) the timed trajectory being followed
+    cursor: object            # (B,) int32 the sampling rule's bracket: the next call's cursor
+    speed_held: object        # (B,) int32 periods since the profile was last replaced
+    log_speed_status: object  # (K, B) int32 STB_* bits of the period's speed plan; None without logs
+    log_speed_held: object    # (K, B) int32
+    log_tgt_status: object    # (K, B) int32 OR of the period's ticks' TGT_* bits
+    log_cursor: object        # (K, B) int32 the cursor the period's ticks start from
+    log_profile: object       # (K, B, 7, 401) the period's timed trajectory, adopted or not; only with log_profile=True
 
 
 @dataclass
@@ -1211,6 +1238,81 @@ class Planner:
         self._check(self._lib.emp_drive(self._h, C.byref(p), C.byref(q), C.byref(sp), C.byref(dp), law, C.byref(lat), C.byref(pid),
                                         C.byref(vp), B, G, int(max_obs), M, A, int(max_dyn), K, T, tsp, C.byref(io), a.where))
         return DriveResult(*res)
+
+    def drive_request_timed(self, dp: DriveParams, state, accel, actors, n_act, t0, tick, dt, max_obs: int, max_dyn: int = 8,
+                            plan_lead=0.1, advance=False, in_place=False) -> TimedDriveRequest:
+        """``drive_request`` (the same bits) with the speed planner's inputs beside the cycle's: dyn_obs (B, max_dyn, 4) =
+        x, y, vx, vy of the kept dynamic actors, start_heading (B,) and plan_start_time (B,) = (t0 + tick * dt) + plan_lead -
+        what ``TrajectoryInputs`` takes.  t0 (B,) is each vehicle's clock at tick 0; tick >= 0."""
+        a = self._args(state, actors)
+        B, A = int(actors.shape[0]), int(actors.shape[1])
+        mo, md = int(max_obs), int(max_dyn)
+        ins = [a.inp(state, np.float64, (B, 6)), a.inp(accel, np.float64, (B, 2)), a.inp(actors, np.float64, (B, A, 4)),
+               a.inp(n_act, np.int32, (B,)), a.inp(t0, np.float64, (B,))]
+        outs = [a.out(shape, dt_) for shape, dt_ in (
+            ((B, mo, 2), np.float64), ((B,), np.int32), ((B, mo), np.float64), ((B, md, 4), np.float64), ((B,), np.int32),
+            ((B, 2), np.float64), ((B,), np.int32), ((B, 2), np.float64), ((B, 2), np.float64), ((B,), np.float64),
+            ((B, 2), np.float64), ((B, 2), np.float64), ((B,), np.int32))]
+        nxt, nxtp = (None, None)
+        if advance or in_place:
+            nxt, nxtp = a.out((B, A, 4), np.float64, into=_in_place(actors, np.float64, in_place))
+        extra = [a.out((B, md, 4), np.float64), a.out((B,), np.float64), a.out((B,), np.float64)]
+        self._check(self._lib.emp_drive_request_timed(self._h, C.byref(dp), B, A, mo, md, *ins, int(tick), float(dt), float(plan_lead),
+                                                      *[o[1] for o in outs], nxtp, *[o[1] for o in extra], a.where))
+        return TimedDriveRequest(*[o[0] for o in outs], nxt, *[o[0] for o in extra])
+
+    def drive_timed(self, p: DpParams, q: QpParams, sp: SmoothParams, sdp: SpeedDpParams, sqp: SpeedQpParams, dp: DriveParams,
+                    lat: MpcParams, pid: PidParams, vp: VehicleParams, global_path, n_global, state, accel, actors, n_act,
+                    pre_match_index, track, track_len, held, t0, profile, cursor, speed_held, target_speed, K, T, max_obs: int,
+                    max_dyn: int = 8, tick0=0, tp: DriveTimedParams = None, max_pts=None, lateral="mpc", logs=True, log_profile=False,
+                    in_place=False) -> TimedDriveResult:
+        """``drive`` with the speed planner in the loop: per period ``drive_request_timed`` at tick0 + k * T, ``plan_cycle(
+        global_path=..., speed=...)``, adopt the track by ``drive``'s rule and the timed trajectory as the profile when the path
+        is valid and speed_status is 0 (else hold the profile and its cursor and count in ``speed_held``), ``rollout_timed`` of T
+        ticks on the adopted track and profile, the acceleration.  ``drive``'s arrays, and t0 (B,) each vehicle's clock at tick
+        0, profile (B, 7, 401) (all NaN: none yet - the vehicle tracks the cap with TGT_NO_PROFILE until a plan is adopted),
+        cursor (B,), speed_held (B,); target_speed (B,) km/h is the cap.  A call resumes bit for bit with tick0 advanced by the
+        K * T ticks done on the previous result's arrays.  log_profile=True also returns every period's timed trajectory (22 KB
+        per vehicle per period).  in_place=True updates ``drive``'s arrays and profile, cursor and speed_held where they live.
+        Equals the chain of the separate calls bit for bit."""
+        law = _lateral_law(lateral)
+        K, T = int(K), int(T)
+        tp = tp if tp is not None else drive_timed_params()
+        a = self._args(global_path, state, actors, track, profile)
+        B, G, A = int(global_path.shape[0]), int(global_path.shape[1]), int(actors.shape[1])
+        M, N = (int(max_pts) if max_pts else max_path_points(p)), L.TIMED_POINTS
+        io = L.DriveTimedIO()
+        for name, src, shape, dt in (("global_path", global_path, (B, G, 4), np.float64), ("n_global", n_global, (B,), np.int32),
+                                     ("state", state, (B, 6), np.float64), ("accel", accel, (B, 2), np.float64),
+                                     ("actors", actors, (B, A, 4), np.float64), ("n_act", n_act, (B,), np.int32),
+                                     ("pre_match_index", pre_match_index, (B,), np.int32), ("track", track, (B, M + 1, 4), np.float64),
+                                     ("track_len", track_len, (B,), np.int32), ("held", held, (B,), np.int32),
+                                     ("t0", t0, (B,), np.float64), ("profile", profile, (B, 7, N), np.float64),
+                                     ("cursor", cursor, (B,), np.int32), ("speed_held", speed_held, (B,), np.int32)):
+            setattr(io, name, a.inp(src, dt, shape))
+        tsp = a.inp(target_speed, np.float64, (B,))
+        res = {}
+        for name, src, shape, dt in (("state", state, (B, 6), np.float64), ("accel", accel, (B, 2), np.float64),
+                                     ("actors", actors, (B, A, 4), np.float64), ("pre_match_index", pre_match_index, (B,), np.int32),
+                                     ("track", track, (B, M + 1, 4), np.float64), ("track_len", track_len, (B,), np.int32),
+                                     ("held", held, (B,), np.int32), ("profile", profile, (B, 7, N), np.float64),
+                                     ("cursor", cursor, (B,), np.int32), ("speed_held", speed_held, (B,), np.int32)):
+            res[name], ptr = a.out(shape, dt, into=_in_place(src, dt, in_place and src is not None))
+            setattr(io, name + "_out", ptr)
+        for name, shape, dt in (("log_state", (K, B, 6), np.float64), ("log_plan_status", (K, B), np.int32),
+                                ("log_roll_status", (K, B), np.int32), ("log_held", (K, B), np.int32),
+                                ("log_counts", (K, B, 2), np.int32), ("log_traj", (K, B, M + 1, 4), np.float64),
+                                ("log_traj_len", (K, B), np.int32), ("log_speed_status", (K, B), np.int32),
+                                ("log_speed_held", (K, B), np.int32), ("log_tgt_status", (K, B), np.int32),
+                                ("log_cursor", (K, B), np.int32), ("log_profile", (K, B, 7, N), np.float64)):
+            res[name] = None
+            if logs and K >= 1 and (name != "log_profile" or log_profile):
+                res[name], ptr = a.out(shape, dt)
+                setattr(io, name, ptr)
+        self._check(self._lib.emp_drive_timed(self._h, C.byref(p), C.byref(q), C.byref(sp), C.byref(sdp), C.byref(sqp), C.byref(dp),
+                                              C.byref(tp), law, C.byref(lat), C.byref(pid), C.byref(vp), B, G, int(max_obs), M, A,
+                                              int(max_dyn), K, T, int(tick0), tsp, C.byref(io), a.where))
+        return TimedDriveResult(**res)
 
     # ---- S-T speed DP (reference planner/speed_planning_test.py) ------------------------------
     def st_graph(self, obs_s, obs_l, obs_s_dot, obs_l_dot):

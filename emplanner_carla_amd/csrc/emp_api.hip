@@ -1485,7 +1485,7 @@ struct SpeedHalf {
 }  // namespace emp
 
 // emp_plan_cycle's body; with `speed` (emp_plan_trajectory) the speed half runs behind the Cartesian tail, before the lane is done;
-// `plain` (emp_drive): EMP_OPT_CYCLE_GRAPH is neither used nor touched
+// `plain` (emp_drive, emp_drive_timed): EMP_OPT_CYCLE_GRAPH is neither used nor touched
 static int plan_cycle_impl(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q, const emp_smooth_params* sp, int32_t B,
                            int32_t max_ref, int32_t max_obs, int32_t max_pts, emp_dp_mode mode, const emp_cycle_io* io,
                            emp_mem where, SpeedHalf* speed, bool plain = false) {
@@ -2264,6 +2264,13 @@ int SpeedHalf::run(emp_ctx* ctx, Stage& st, int B, int max_pts, const double* d_
 
 }  // namespace emp
 
+// the speed planner's parameter checks, behind the caller's own for NULL structs (emp_plan_trajectory, emp_drive_timed)
+static int speed_params_ok(emp_ctx* ctx, const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp) {
+    EMP_REQUIRE(ctx, !(sdp->w_cost_obs < 0.0), "w_cost_obs must not be negative");
+    EMP_REQUIRE(ctx, sqp->w_cost_s_dot2 > 0 && sqp->w_cost_v_ref > 0 && sqp->w_cost_jerk >= 0, "speed QP weights must be positive");
+    return EMP_OK;
+}
+
 extern "C" int emp_plan_trajectory(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_params* q, const emp_smooth_params* sp,
                                    const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp, int32_t B, int32_t max_ref,
                                    int32_t max_obs, int32_t max_pts, int32_t max_dyn, emp_dp_mode mode, const emp_cycle_io* io,
@@ -2277,8 +2284,7 @@ extern "C" int emp_plan_trajectory(emp_ctx* ctx, const emp_dp_params* p, const e
     EMP_REQUIRE(ctx, sio->dyn_obs && sio->n_dyn && sio->start_heading && sio->plan_start_time,
                 "dyn_obs, n_dyn, start_heading and plan_start_time are required inputs");
     EMP_REQUIRE(ctx, sio->trajectory && sio->speed_status, "trajectory and speed_status are required outputs");
-    EMP_REQUIRE(ctx, !(sdp->w_cost_obs < 0.0), "w_cost_obs must not be negative");
-    EMP_REQUIRE(ctx, sqp->w_cost_s_dot2 > 0 && sqp->w_cost_v_ref > 0 && sqp->w_cost_jerk >= 0, "speed QP weights must be positive");
+    if (const int rc = speed_params_ok(ctx, sdp, sqp)) return rc;
     SpeedHalf speed{sdp, sqp, sio, (int)max_dyn};
     return plan_cycle_impl(ctx, p, q, sp, B, max_ref, max_obs, max_pts, mode, io, where, &speed);
 }
@@ -2520,7 +2526,7 @@ ctl::VehicleParams vehicle_params(const emp_vehicle_params* p) {
 }
 
 // the one launch of a rollout: `tg` is rollout::NoProfile (emp_rollout, every period of emp_drive) or the rollout::Profile whose
-// target emp_rollout_timed samples every tick
+// target emp_rollout_timed and every period of emp_drive_timed sample every tick
 template <typename TG>
 int launch_rollout(emp_ctx* ctx, const char* name, int lateral, const emp_mpc_params* lat, int B, int max_path, const double* d_path,
                    const int* d_np, const rollout::IO& io, const TG& tg) {
@@ -2702,10 +2708,24 @@ drive::Params drive_params(const emp_drive_params* p, double advance_s) {
     return drive::Params{p->dis_limitation, p->lateral_band, p->behind, p->dynamic_speed, p->static_gate, p->pred_ts, advance_s};
 }
 
-int launch_drive_request(emp_ctx* ctx, int B, int max_act, int max_obs, int max_dyn, const drive::Params& prm, const drive::RequestIO& io) {
+// the one launch of a request: `tm` is drive::NoClock (emp_drive_request, every period of emp_drive) or the drive::Clock whose
+// extras the speed planner takes (emp_drive_request_timed, every period of emp_drive_timed)
+template <typename TM>
+int launch_drive_request(emp_ctx* ctx, int B, int max_act, int max_obs, int max_dyn, const drive::Params& prm, const drive::RequestIO& io,
+                         const TM& tm) {
     const DriveRequestPlan p = plan_drive_request(B);
     if (const int rc = plan_refused(ctx, p.error)) return rc;
-    return launch(ctx, "drive_request", drive::drive_request_kernel, dim3(p.grid), dim3(p.block), 0, B, max_act, max_obs, max_dyn, prm, io);
+    return launch(ctx, TM::kTimed ? "drive_request_timed" : "drive_request", drive::drive_request_kernel<TM>, dim3(p.grid), dim3(p.block), 0,
+                  B, max_act, max_obs, max_dyn, prm, io, tm);
+}
+
+// ... and of an adoption: drive::NoSpeed (emp_drive) or the drive::Speed that carries the profile (emp_drive_timed)
+template <typename TS>
+int launch_drive_adopt(emp_ctx* ctx, int B, int max_pts, const drive::AdoptIO& io, const TS& ts) {
+    const DriveRequestPlan p = plan_drive_request(B);
+    if (const int rc = plan_refused(ctx, p.error)) return rc;
+    return launch(ctx, TS::kTimed ? "drive_adopt_timed" : "drive_adopt", drive::drive_adopt_kernel<TS>, dim3(p.grid), dim3(p.block), 0, B,
+                  max_pts, io, ts);
 }
 
 // While emp_drive stages its arrays the context's pool is the drive pool; while its periods run, the pipeline setting is off.
@@ -2725,72 +2745,85 @@ struct DriveScope {
     }
 };
 
-}  // namespace
+// The caller's arrays of a request: emp_drive_request's positional arguments.
+struct RequestArrays {
+    const double *state, *accel, *actors;
+    const int32_t* n_act;
+    double *static_xy, *static_dis, *dyn, *dyn_dis_speed, *origin_xy, *start_xy, *pred_fi, *start_v, *start_a, *actors_next;
+    int32_t *n_static, *n_dyn, *n_obs, *req_status;
+};
 
-extern "C" {
-
-void emp_drive_params_default(emp_drive_params* p) {
-    if (!p) return;
-    p->dis_limitation = 50.0;       // ref test_9.py:377
-    p->lateral_band = 5.0;          // :77
-    p->behind = -10.0;              // :78
-    p->dynamic_speed = 1.0;         // :81
-    p->static_gate = 30.0;          // :116
-    p->pred_ts = 0.2;               // :335
-    p->advance_s = 0.0;
-    p->reserved = 0;
-}
-
-int emp_drive_request(emp_ctx* ctx, const emp_drive_params* p, int32_t B, int32_t max_act, int32_t max_obs, int32_t max_dyn,
-                      const double* state, const double* accel, const double* actors, const int32_t* n_act, double* static_xy,
-                      int32_t* n_static, double* static_dis, double* dyn, int32_t* n_dyn, double* dyn_dis_speed, int32_t* n_obs,
-                      double* origin_xy, double* start_xy, double* pred_fi, double* start_v, double* start_a,
-                      int32_t* req_status, double* actors_next, emp_mem where) {
+// emp_drive_request's body; `ck` (emp_drive_request_timed) holds the CALLER's pointers of the timed extras and is staged with the rest
+int drive_request_impl(emp_ctx* ctx, const emp_drive_params* p, int B, int max_act, int max_obs, int max_dyn, const RequestArrays& a,
+                       emp_mem where, const drive::Clock* ck) {
     EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
     EMP_REQUIRE(ctx, p && B >= 0, "bad sizes");
     EMP_REQUIRE(ctx, p->reserved == 0, "emp_drive_params.reserved must be 0");
     EMP_REQUIRE(ctx, max_act >= 1 && max_act <= 64, "max_act must be in [1, 64]");
     EMP_REQUIRE(ctx, max_obs >= 1 && max_obs <= 256 && max_dyn >= 1 && max_dyn <= 64, "max_obs must be in [1, 256], max_dyn in [1, 64]");
     EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "EMP_HOST_PINNED is emp_plan_cycle's");
-    EMP_REQUIRE(ctx, state && actors && n_act && static_xy && n_static && static_dis && dyn && n_dyn && dyn_dis_speed && n_obs &&
-                         origin_xy && start_xy && pred_fi && start_v && start_a && req_status,
+    EMP_REQUIRE(ctx, a.state && a.actors && a.n_act && a.static_xy && a.n_static && a.static_dis && a.dyn && a.n_dyn && a.dyn_dis_speed &&
+                         a.n_obs && a.origin_xy && a.start_xy && a.pred_fi && a.start_v && a.start_a && a.req_status,
                 "NULL argument");
+    if (ck) {
+        EMP_REQUIRE(ctx, ck->tick >= 0, "tick must be at least 0");
+        EMP_REQUIRE(ctx, std::isfinite(ck->dt) && ck->dt > 0.0, "dt must be finite and positive");
+        EMP_REQUIRE(ctx, std::isfinite(ck->plan_lead), "plan_lead must be finite");
+        EMP_REQUIRE(ctx, ck->t0 && ck->dyn_obs && ck->start_heading && ck->plan_start_time, "NULL argument");
+    }
     EMP_STAGE(st, where);
     drive::RequestIO io{};
-    io.state = st.in(state, (size_t)B * 6);
-    io.accel = st.in(accel, (size_t)B * 2);
-    io.actors = st.in(actors, (size_t)B * max_act * 4);
-    io.n_act = st.in(n_act, (size_t)B);
-    io.static_xy = st.out(static_xy, (size_t)B * max_obs * 2, false);
-    io.n_static = st.out(n_static, (size_t)B, false);
-    io.static_dis = st.out(static_dis, (size_t)B * max_obs, false);
-    io.dyn = st.out(dyn, (size_t)B * max_dyn * 4, false);
-    io.n_dyn = st.out(n_dyn, (size_t)B, false);
-    io.dyn_dis_speed = st.out(dyn_dis_speed, (size_t)B * 2, false);
-    io.n_obs = st.out(n_obs, (size_t)B, false);
-    io.origin_xy = st.out(origin_xy, (size_t)B * 2, false);
-    io.start_xy = st.out(start_xy, (size_t)B * 2, false);
-    io.pred_fi = st.out(pred_fi, (size_t)B, false);
-    io.start_v = st.out(start_v, (size_t)B * 2, false);
-    io.start_a = st.out(start_a, (size_t)B * 2, false);
-    io.req_status = st.out(req_status, (size_t)B, false);
-    io.actors_next = st.out(actors_next, (size_t)B * max_act * 4, false);
+    io.state = st.in(a.state, (size_t)B * 6);
+    io.accel = st.in(a.accel, (size_t)B * 2);
+    io.actors = st.in(a.actors, (size_t)B * max_act * 4);
+    io.n_act = st.in(a.n_act, (size_t)B);
+    drive::Clock dck{};
+    if (ck) {
+        dck = *ck;
+        dck.t0 = st.in(ck->t0, (size_t)B);
+    }
+    io.static_xy = st.out(a.static_xy, (size_t)B * max_obs * 2, false);
+    io.n_static = st.out(a.n_static, (size_t)B, false);
+    io.static_dis = st.out(a.static_dis, (size_t)B * max_obs, false);
+    io.dyn = st.out(a.dyn, (size_t)B * max_dyn * 4, false);
+    io.n_dyn = st.out(a.n_dyn, (size_t)B, false);
+    io.dyn_dis_speed = st.out(a.dyn_dis_speed, (size_t)B * 2, false);
+    io.n_obs = st.out(a.n_obs, (size_t)B, false);
+    io.origin_xy = st.out(a.origin_xy, (size_t)B * 2, false);
+    io.start_xy = st.out(a.start_xy, (size_t)B * 2, false);
+    io.pred_fi = st.out(a.pred_fi, (size_t)B, false);
+    io.start_v = st.out(a.start_v, (size_t)B * 2, false);
+    io.start_a = st.out(a.start_a, (size_t)B * 2, false);
+    io.req_status = st.out(a.req_status, (size_t)B, false);
+    io.actors_next = st.out(a.actors_next, (size_t)B * max_act * 4, false);
+    if (ck) {
+        dck.dyn_obs = st.out(ck->dyn_obs, (size_t)B * max_dyn * 4, false);
+        dck.start_heading = st.out(ck->start_heading, (size_t)B, false);
+        dck.plan_start_time = st.out(ck->plan_start_time, (size_t)B, false);
+    }
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch_drive_request(ctx, B, max_act, max_obs, max_dyn, drive_params(p, p->advance_s), io)) return rc;
+    const drive::Params prm = drive_params(p, p->advance_s);
+    if (const int rc = ck ? launch_drive_request(ctx, B, max_act, max_obs, max_dyn, prm, io, dck)
+                          : launch_drive_request(ctx, B, max_act, max_obs, max_dyn, prm, io, drive::NoClock{}))
+        return rc;
     return st.finish();
 }
 
-int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
-              const emp_drive_params* drv, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
-              const emp_vehicle_params* vp, int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act,
-              int32_t max_dyn, int32_t K, int32_t T, const double* target_speed, const emp_drive_io* io, emp_mem where) {
-    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
-    EMP_REQUIRE(ctx, dp && qp && smooth && drv && lat && pid && vp && io, "NULL parameter struct");
-    EMP_REQUIRE(ctx, drv->reserved == 0, "emp_drive_params.reserved must be 0");
-    EMP_REQUIRE(ctx, io->reserved == 0, "emp_drive_io.reserved must be 0");
-    if (const int rc = rollout_args_ok(ctx, lateral, vp, T, 1)) return rc;
-    EMP_REQUIRE(ctx, qp_reserved_ok(qp), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
-    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_drive takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+// What emp_drive_timed adds to emp_drive: the speed planner's parameters, the clock, and the arrays emp_drive_io does not have.
+struct DriveTimed {
+    const emp_speed_dp_params* sdp;
+    const emp_speed_qp_params* sqp;
+    double plan_lead;
+    DriveClockPlan clock;
+    const emp_drive_timed_io* io;
+};
+
+// emp_drive's body behind its own checks of ctx, NULL structs and `where`; with `tm` emp_drive_timed's: the same periods with the
+// timed request, the speed half behind the cycle, the profile adopted beside the track, the timed rollout
+int drive_impl(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth, const emp_drive_params* drv,
+               int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, const emp_vehicle_params* vp, int32_t B,
+               int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act, int32_t max_dyn, int32_t K, int32_t T,
+               const double* target_speed, const emp_drive_io* io, emp_mem where, const DriveTimed* tm) {
     EMP_REQUIRE(ctx, B >= 0 && max_global >= 1, "bad sizes");
     EMP_REQUIRE(ctx, K >= 1 && K <= EMP_DRIVE_MAX_PERIODS, "K must be in [1, 4096]");
     EMP_REQUIRE(ctx, max_act >= 1 && max_act <= 64, "max_act must be in [1, 64]");
@@ -2803,6 +2836,12 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
     EMP_REQUIRE(ctx, io->state_out && io->accel_out && io->actors_out && io->pre_match_index_out && io->track_out && io->track_len_out &&
                          io->held_out,
                 "NULL output array");
+    if (tm) {
+        if (const int rc = plan_refused(ctx, tm->clock.error)) return rc;
+        if (const int rc = speed_params_ok(ctx, tm->sdp, tm->sqp)) return rc;
+        EMP_REQUIRE(ctx, tm->io->t0 && tm->io->profile && tm->io->cursor && tm->io->speed_held, "NULL input array");
+        EMP_REQUIRE(ctx, tm->io->profile_out && tm->io->cursor_out && tm->io->speed_held_out, "NULL output array");
+    }
     {   // the lattice parameters are checked here, before anything is staged or launched, by the cycle's own rule; the DpDev
         // is not kept (plan_cycle_impl makes its own every period).  max_obs + 3: the cycle adds up to three virtual obstacles
         // for the dynamic one and holds 256 in all, hence this call's limit of 253 against emp_drive_request's 256
@@ -2812,7 +2851,7 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
     EMP_HIP(ctx, hipSetDevice(ctx->device));
     DriveScope scope(ctx);
     Stage st(ctx, where);                       // (with a pipeline set: the main stream waits for the cycles in flight)
-    const size_t nB = (size_t)B, row = (size_t)(max_pts + 1) * 4, nK = (size_t)K;
+    const size_t nB = (size_t)B, row = (size_t)(max_pts + 1) * 4, nK = (size_t)K, prof = (size_t)drive::kProfile;
     const double* d_glob = st.in(io->global_path, nB * max_global * 4);
     const int* d_nglob = st.in(io->n_global, nB);
     const double* d_state = st.in(io->state, nB * 6);
@@ -2824,6 +2863,10 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
     const int* d_tlen = st.in(io->track_len, nB);
     const int* d_held = st.in(io->held, nB);
     const double* d_target = st.in(target_speed, nB);
+    const double* d_t0 = tm ? st.in(tm->io->t0, nB) : nullptr;
+    const double* d_prof = tm ? st.in(tm->io->profile, nB * prof) : nullptr;
+    const int* d_cur = tm ? st.in(tm->io->cursor, nB) : nullptr;
+    const int* d_sheld = tm ? st.in(tm->io->speed_held, nB) : nullptr;
     double* o_state = st.out(io->state_out, nB * 6, false);
     double* o_accel = st.out(io->accel_out, nB * 2, false);
     double* o_actors = st.out(io->actors_out, nB * max_act * 4, false);
@@ -2838,6 +2881,18 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
     int* l_counts = st.out(io->log_counts, nK * nB * 2, false);
     double* l_traj = st.out(io->log_traj, nK * nB * row, false);
     int* l_tlen = st.out(io->log_traj_len, nK * nB, false);
+    double *o_prof = nullptr, *l_prof = nullptr;
+    int *o_cur = nullptr, *o_sheld = nullptr, *l_sst = nullptr, *l_sheld = nullptr, *l_tgt = nullptr, *l_cur = nullptr;
+    if (tm) {
+        o_prof = st.out(tm->io->profile_out, nB * prof, false);
+        o_cur = st.out(tm->io->cursor_out, nB, false);
+        o_sheld = st.out(tm->io->speed_held_out, nB, false);
+        l_sst = st.out(tm->io->log_speed_status, nK * nB, false);
+        l_sheld = st.out(tm->io->log_speed_held, nK * nB, false);
+        l_tgt = st.out(tm->io->log_tgt_status, nK * nB, false);
+        l_cur = st.out(tm->io->log_cursor, nK * nB, false);
+        l_prof = st.out(tm->io->log_profile, nK * nB * prof, false);
+    }
     // the request's outputs, the cycle's, the rollout's: temporaries of the drive pool, the same for every period
     drive::RequestIO rq{};
     rq.n_act = d_nact;
@@ -2881,6 +2936,31 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
     ad.track_len_out = o_tlen;
     ad.held_out = o_held;
     ad.pre_match_out = o_prem;
+    // the timed loop's own: the request's extras are the speed half's inputs, its trajectory the adoption's
+    drive::Clock ck{};
+    emp_speed_io sio{};
+    drive::Speed sp{};
+    int* t_tgt = nullptr;
+    if (tm) {
+        ck.t0 = d_t0;
+        ck.dt = vp->dt;
+        ck.plan_lead = tm->plan_lead;
+        ck.dyn_obs = st.tmp<double>(nB * max_dyn * 4);
+        ck.start_heading = st.tmp<double>(nB);
+        ck.plan_start_time = st.tmp<double>(nB);
+        sio.dyn_obs = ck.dyn_obs;
+        sio.n_dyn = rq.n_dyn;
+        sio.start_heading = ck.start_heading;
+        sio.plan_start_time = ck.plan_start_time;
+        sio.trajectory = st.tmp<double>(nB * prof);
+        sio.speed_status = st.tmp<int>(nB);
+        sp.trajectory = sio.trajectory;
+        sp.speed_status = sio.speed_status;
+        sp.profile_out = o_prof;
+        sp.cursor_out = o_cur;
+        sp.speed_held_out = o_sheld;
+        t_tgt = st.tmp<int>(nB);
+    }
     // the rollout: a new controller every period (min_index 0, an empty PID deque); its tick-(T - 1) log row feeds the acceleration
     const int log_every = std::max(T - 1, 1);
     const size_t n_log = rollout_log_rows(T, log_every);
@@ -2902,7 +2982,6 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
     scope.swap_pool();                          // the cycles recycle the context's pool as ever
     ctx->pipe_mode = 0;                         // ... and run one batch at a time on the main stream
     const drive::Params prm = drive_params(drv, (double)T * vp->dt);
-    const DriveRequestPlan wp = plan_drive_request(B);
     for (int k = 0; k < K; ++k) {
         const size_t kB = (size_t)k * nB;
         rq.state = k ? o_state : d_state;
@@ -2910,10 +2989,18 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
         rq.actors = k ? o_actors : d_actors;
         rq.log_state = l_state ? l_state + kB * 6 : nullptr;
         rq.log_counts = l_counts ? l_counts + kB * 2 : nullptr;
-        if (const int rc = launch_drive_request(ctx, B, max_act, max_obs, max_dyn, prm, rq)) return rc;
+        ck.tick = tm ? tm->clock.tick(k) : 0;
+        if (const int rc = tm ? launch_drive_request(ctx, B, max_act, max_obs, max_dyn, prm, rq, ck)
+                              : launch_drive_request(ctx, B, max_act, max_obs, max_dyn, prm, rq, drive::NoClock{}))
+            return rc;
         cio.pre_match_index = k ? o_prem : d_prem;
-        if (const int rc = plan_cycle_impl(ctx, dp, qp, smooth, B, kRefLinePoints, max_obs, max_pts, EMP_DP_TWO_KERNEL, &cio, EMP_DEVICE,
-                                           nullptr, true))
+        if (tm) {
+            SpeedHalf speed{tm->sdp, tm->sqp, &sio, (int)max_dyn};
+            if (const int rc = plan_cycle_impl(ctx, dp, qp, smooth, B, kRefLinePoints, max_obs, max_pts, EMP_DP_TWO_KERNEL, &cio, EMP_DEVICE,
+                                               &speed, true))
+                return rc;
+        } else if (const int rc = plan_cycle_impl(ctx, dp, qp, smooth, B, kRefLinePoints, max_obs, max_pts, EMP_DP_TWO_KERNEL, &cio,
+                                                  EMP_DEVICE, nullptr, true))
             return rc;
         ad.track_in = k ? o_track : d_track;
         ad.track_len_in = k ? o_tlen : d_tlen;
@@ -2922,16 +3009,136 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
         ad.log_held = l_held ? l_held + kB : nullptr;
         ad.log_traj = l_traj ? l_traj + kB * row : nullptr;
         ad.log_traj_len = l_tlen ? l_tlen + kB : nullptr;
-        if (const int rc = launch(ctx, "drive_adopt", drive::drive_adopt_kernel, dim3(wp.grid), dim3(wp.block), 0, B, max_pts, ad)) return rc;
         ro.state_in = rq.state;
         ro.status = l_roll ? l_roll + kB : t_roll;
-        if (const int rc = launch_rollout(ctx, "rollout", lateral, lat, B, max_pts + 1, o_track, o_tlen, ro, rollout::NoProfile{})) return rc;
+        if (tm) {
+            sp.profile_in = k ? o_prof : d_prof;
+            sp.cursor_in = k ? o_cur : d_cur;
+            sp.speed_held_in = k ? o_sheld : d_sheld;
+            sp.log_speed_status = l_sst ? l_sst + kB : nullptr;
+            sp.log_speed_held = l_sheld ? l_sheld + kB : nullptr;
+            sp.log_cursor = l_cur ? l_cur + kB : nullptr;
+            sp.log_profile = l_prof ? l_prof + kB * prof : nullptr;
+            if (const int rc = launch_drive_adopt(ctx, B, max_pts, ad, sp)) return rc;
+            // on the adopted track and profile, from the carried cursor, on the clock of this period's first tick
+            const rollout::Profile tg{o_prof, d_t0, o_cur, ck.tick, o_cur, l_tgt ? l_tgt + kB : t_tgt, nullptr};
+            if (const int rc = launch_rollout(ctx, "rollout_timed", lateral, lat, B, max_pts + 1, o_track, o_tlen, ro, tg)) return rc;
+        } else {
+            if (const int rc = launch_drive_adopt(ctx, B, max_pts, ad, drive::NoSpeed{})) return rc;
+            if (const int rc = launch_rollout(ctx, "rollout", lateral, lat, B, max_pts + 1, o_track, o_tlen, ro, rollout::NoProfile{})) return rc;
+        }
         if (const int rc = launch(ctx, "drive_accel", drive::drive_accel_kernel, grid1(B, 256), dim3(256), 0, B, vp->dt, (const double*)o_state,
                                   last_seen, o_accel))
             return rc;
     }
     ctx->pipe_mode = scope.pipe_mode;
     return st.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+void emp_drive_params_default(emp_drive_params* p) {
+    if (!p) return;
+    p->dis_limitation = 50.0;       // ref test_9.py:377
+    p->lateral_band = 5.0;          // :77
+    p->behind = -10.0;              // :78
+    p->dynamic_speed = 1.0;         // :81
+    p->static_gate = 30.0;          // :116
+    p->pred_ts = 0.2;               // :335
+    p->advance_s = 0.0;
+    p->reserved = 0;
+}
+
+void emp_drive_timed_params_default(emp_drive_timed_params* p) {
+    if (!p) return;
+    p->plan_lead = 0.1;             // ref test_10.py:325 (cur_time + 0.1)
+    p->reserved = 0;
+}
+
+int emp_drive_request(emp_ctx* ctx, const emp_drive_params* p, int32_t B, int32_t max_act, int32_t max_obs, int32_t max_dyn,
+                      const double* state, const double* accel, const double* actors, const int32_t* n_act, double* static_xy,
+                      int32_t* n_static, double* static_dis, double* dyn, int32_t* n_dyn, double* dyn_dis_speed, int32_t* n_obs,
+                      double* origin_xy, double* start_xy, double* pred_fi, double* start_v, double* start_a,
+                      int32_t* req_status, double* actors_next, emp_mem where) {
+    const RequestArrays a{state, accel, actors, n_act, static_xy, static_dis, dyn, dyn_dis_speed, origin_xy, start_xy, pred_fi, start_v,
+                          start_a, actors_next, n_static, n_dyn, n_obs, req_status};
+    return drive_request_impl(ctx, p, B, max_act, max_obs, max_dyn, a, where, nullptr);
+}
+
+int emp_drive_request_timed(emp_ctx* ctx, const emp_drive_params* p, int32_t B, int32_t max_act, int32_t max_obs, int32_t max_dyn,
+                            const double* state, const double* accel, const double* actors, const int32_t* n_act, const double* t0,
+                            int32_t tick, double dt, double plan_lead, double* static_xy, int32_t* n_static, double* static_dis,
+                            double* dyn, int32_t* n_dyn, double* dyn_dis_speed, int32_t* n_obs, double* origin_xy, double* start_xy,
+                            double* pred_fi, double* start_v, double* start_a, int32_t* req_status, double* actors_next,
+                            double* dyn_obs, double* start_heading, double* plan_start_time, emp_mem where) {
+    const RequestArrays a{state, accel, actors, n_act, static_xy, static_dis, dyn, dyn_dis_speed, origin_xy, start_xy, pred_fi, start_v,
+                          start_a, actors_next, n_static, n_dyn, n_obs, req_status};
+    const drive::Clock ck{t0, tick, dt, plan_lead, dyn_obs, start_heading, plan_start_time};
+    return drive_request_impl(ctx, p, B, max_act, max_obs, max_dyn, a, where, &ck);
+}
+
+int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
+              const emp_drive_params* drv, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
+              const emp_vehicle_params* vp, int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act,
+              int32_t max_dyn, int32_t K, int32_t T, const double* target_speed, const emp_drive_io* io, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, dp && qp && smooth && drv && lat && pid && vp && io, "NULL parameter struct");
+    EMP_REQUIRE(ctx, drv->reserved == 0, "emp_drive_params.reserved must be 0");
+    EMP_REQUIRE(ctx, io->reserved == 0, "emp_drive_io.reserved must be 0");
+    if (const int rc = rollout_args_ok(ctx, lateral, vp, T, 1)) return rc;
+    EMP_REQUIRE(ctx, qp_reserved_ok(qp), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_drive takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    return drive_impl(ctx, dp, qp, smooth, drv, lateral, lat, pid, vp, B, max_global, max_obs, max_pts, max_act, max_dyn, K, T, target_speed,
+                      io, where, nullptr);
+}
+
+int emp_drive_timed(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
+                    const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp, const emp_drive_params* drv,
+                    const emp_drive_timed_params* tp, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
+                    const emp_vehicle_params* vp, int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act,
+                    int32_t max_dyn, int32_t K, int32_t T, int32_t tick0, const double* target_speed, const emp_drive_timed_io* io,
+                    emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, dp && qp && smooth && sdp && sqp && drv && tp && lat && pid && vp && io, "NULL parameter struct");
+    EMP_REQUIRE(ctx, drv->reserved == 0, "emp_drive_params.reserved must be 0");
+    EMP_REQUIRE(ctx, tp->reserved == 0, "emp_drive_timed_params.reserved must be 0");
+    EMP_REQUIRE(ctx, std::isfinite(tp->plan_lead), "emp_drive_timed_params.plan_lead must be finite");
+    EMP_REQUIRE(ctx, io->reserved == 0, "emp_drive_timed_io.reserved must be 0");
+    if (const int rc = rollout_args_ok(ctx, lateral, vp, T, 1)) return rc;
+    EMP_REQUIRE(ctx, qp_reserved_ok(qp), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE,
+                "emp_drive_timed takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    // emp_drive's arrays under their names
+    emp_drive_io base{};
+    base.global_path = io->global_path;
+    base.n_global = io->n_global;
+    base.state = io->state;
+    base.accel = io->accel;
+    base.actors = io->actors;
+    base.n_act = io->n_act;
+    base.pre_match_index = io->pre_match_index;
+    base.track = io->track;
+    base.track_len = io->track_len;
+    base.held = io->held;
+    base.state_out = io->state_out;
+    base.accel_out = io->accel_out;
+    base.actors_out = io->actors_out;
+    base.pre_match_index_out = io->pre_match_index_out;
+    base.track_out = io->track_out;
+    base.track_len_out = io->track_len_out;
+    base.held_out = io->held_out;
+    base.log_state = io->log_state;
+    base.log_plan_status = io->log_plan_status;
+    base.log_roll_status = io->log_roll_status;
+    base.log_held = io->log_held;
+    base.log_counts = io->log_counts;
+    base.log_traj = io->log_traj;
+    base.log_traj_len = io->log_traj_len;
+    const DriveTimed tm{sdp, sqp, tp->plan_lead, plan_drive_clock(tick0, K, T), io};
+    return drive_impl(ctx, dp, qp, smooth, drv, lateral, lat, pid, vp, B, max_global, max_obs, max_pts, max_act, max_dyn, K, T, target_speed,
+                      &base, where, &tm);
 }
 
 }  // extern "C"

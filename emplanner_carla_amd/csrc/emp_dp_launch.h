@@ -317,4 +317,30 @@ static inline DriveRequestPlan plan_drive_request(int B) {
     return p;
 }
 
+// The clock of emp_drive_timed (include/emplanner.h): period k starts at tick tick0 + k * T, a function of the tick number like
+// emp_rollout_timed's own clock, so a run cut in two resumes bit for bit.  Refused: a negative tick0 and a last tick beyond int32.
+struct DriveClockPlan {
+    long long end = 0;          // tick0 + K * T: the first tick behind the call, the tick0 of a call that resumes it
+    const char* error = nullptr;
+    int tick0 = 0, T = 0;
+    int tick(int k) const { return (int)((long long)tick0 + (long long)k * T); }
+};
+
+static inline DriveClockPlan plan_drive_clock(int tick0, int K, int T) {
+    DriveClockPlan p;
+    p.tick0 = tick0;
+    p.T = T;
+    if (K < 1 || T < 1) {
+        p.error = "K and T must be at least 1";
+        return p;
+    }
+    if (tick0 < 0) {
+        p.error = "tick0 must be at least 0";
+        return p;
+    }
+    p.end = (long long)tick0 + (long long)K * (long long)T;
+    if (p.end > 2147483647ll) p.error = "tick0 + K * T must not exceed INT32_MAX";
+    return p;
+}
+
 }  // namespace emp

@@ -5,6 +5,9 @@
 //   drive_adopt_kernel    adopt a valid plan as the track the controller follows, or hold the previous one and count
 //   drive_accel_kernel    the world-frame acceleration over the period's last tick, the next request's start_a
 // emp_drive (emp_api.hip) strings them together with the cycle and the rollout kernel, K periods without a host round trip.
+// emp_drive_timed is the same loop with the speed planner in it: the request and the adopt kernel take a policy, as
+// mpc_rollout_kernel<TG> does - NoClock / NoSpeed are emp_drive's kernels, statement for statement; Clock adds the speed planner's
+// inputs to the request, Speed the profile (the period's timed trajectory), its cursor and its counter to the adoption.
 //
 // Arithmetic contract as in emp_control_core.h: written order, separately rounded binary64 operations (-ffp-contract=off), IEEE
 // `/` and sqrt; libm enters through sin, cos and atan2 only.  include/emplanner.h states the formulas in order; tests/drive_port.py
@@ -49,11 +52,27 @@ struct RequestIO {
     int* log_counts;            // [B][2] or null: n_obs, n_dyn
 };
 
+// What emp_drive_request_timed and emp_drive_timed add to the request: the speed planner's inputs (emp_speed_io), which only this
+// kernel can give - it holds each dynamic actor's (x, y, vx, vy) and its rank in registers, and the actors advance in place.
+struct NoClock {
+    static constexpr bool kTimed = false;
+};
+struct Clock {
+    static constexpr bool kTimed = true;
+    const double* t0;           // [B] the vehicle's clock at tick 0
+    int tick;                   // the period's first tick
+    double dt, plan_lead;
+    double* dyn_obs;            // [B][max_dyn][4] x, y, vx, vy of the kept dynamics in dyn's order, before the advance; idle slots 0
+    double* start_heading;      // [B] atan2(wy, wx): the value beta is made of
+    double* plan_start_time;    // [B] (t0 + (double)tick * dt) + plan_lead
+};
+
 // One wavefront per vehicle, one actor per lane (max_act <= 64); grid and block from plan_drive_request (emp_dp_launch.h).
 // Each class (static, dynamic) is ordered by (dis, actor index): a lane's rank is the number of same-class lanes that come
 // before it, counted in a wave-uniform loop over the set bits of the class masks - no atomics, no per-lane branches.  A lane
 // reads its actor before it writes it, so actors_next may be actors.
-__global__ __launch_bounds__(256) void drive_request_kernel(int B, int max_act, int max_obs, int max_dyn, Params prm, RequestIO io) {
+template <typename TM>
+__global__ __launch_bounds__(256) void drive_request_kernel(int B, int max_act, int max_obs, int max_dyn, Params prm, RequestIO io, TM tm) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
     if (b >= B) return;                                            // (the whole wavefront)
@@ -98,6 +117,10 @@ __global__ __launch_bounds__(256) void drive_request_kernel(int B, int max_act, 
     if (is_dyn && rank < max_dyn) {
         double* o = io.dyn + 4 * ((size_t)b * max_dyn + rank);
         o[0] = ax; o[1] = ay; o[2] = dis; o[3] = speed;
+        if constexpr (TM::kTimed) {
+            double* v = tm.dyn_obs + 4 * ((size_t)b * max_dyn + rank);
+            v[0] = ax; v[1] = ay; v[2] = avx; v[3] = avy;
+        }
     }
     for (int q = ns + lane; q < max_obs; q += 64) {                // unused slots are 0: every output is determined
         const size_t o = (size_t)b * max_obs + q;
@@ -108,6 +131,10 @@ __global__ __launch_bounds__(256) void drive_request_kernel(int B, int max_act, 
     for (int q = nd + lane; q < max_dyn; q += 64) {
         double* o = io.dyn + 4 * ((size_t)b * max_dyn + q);
         o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; o[3] = 0.0;
+        if constexpr (TM::kTimed) {
+            double* v = tm.dyn_obs + 4 * ((size_t)b * max_dyn + q);
+            v[0] = 0.0; v[1] = 0.0; v[2] = 0.0; v[3] = 0.0;
+        }
     }
     if (io.actors_next) {
         double* o = io.actors_next + 4 * slot;
@@ -129,7 +156,8 @@ __global__ __launch_bounds__(256) void drive_request_kernel(int B, int max_act, 
     if (lane != 0) return;
     // ref planning_utils.py:599-612 (products left to right)
     const double V = sqrt((w.wx * w.wx + w.wy * w.wy) + 0.0);
-    const double beta = atan2(w.wy, w.wx) - fi;
+    const double heading = atan2(w.wy, w.wx);
+    const double beta = heading - fi;
     const double V_y = V * sin(beta), V_x = V * cos(beta);
     const double ts = prm.pred_ts;
     io.n_static[b] = ns;
@@ -153,6 +181,10 @@ __global__ __launch_bounds__(256) void drive_request_kernel(int B, int max_act, 
         io.log_counts[2 * (size_t)b] = n_obs;
         io.log_counts[2 * (size_t)b + 1] = nd;
     }
+    if constexpr (TM::kTimed) {
+        tm.start_heading[b] = heading;                                           // ref test_10.py:247
+        tm.plan_start_time[b] = (tm.t0[b] + (double)tm.tick * tm.dt) + tm.plan_lead;      // :325; nothing accumulates over periods
+    }
 }
 
 struct AdoptIO {
@@ -174,10 +206,34 @@ struct AdoptIO {
     int* log_traj_len;          // [B] or null
 };
 
+// What emp_drive_timed adds to the adoption: the period's timed trajectory becomes the profile the PID follows when the path is
+// valid AND speed_status == 0 (cursor 0, speed_held 0); otherwise the profile and its cursor stay - still on the absolute clock, so
+// the sampling rule goes on reading it - and speed_held counts.  The track is adopted or held by its own rule, independently.
+constexpr int kProfile = 7 * ctl::kTimedPoints;      // doubles of one vehicle's profile: 22 456 B
+struct NoSpeed {
+    static constexpr bool kTimed = false;
+};
+struct Speed {
+    static constexpr bool kTimed = true;
+    const double* trajectory;   // [B][7][401] the period's
+    const int* speed_status;    // [B]
+    const double* profile_in;   // [B][7][401]
+    const int* cursor_in;       // [B]
+    const int* speed_held_in;   // [B]
+    double* profile_out;        // each output may be its input: an element is read by the lane that writes it
+    int* cursor_out;
+    int* speed_held_out;
+    int* log_speed_status;      // [B] or null
+    int* log_speed_held;        // [B] or null
+    int* log_cursor;            // [B] or null: the cursor the period's ticks start from
+    double* log_profile;        // [B][7][401] or null: the period's trajectory, adopted or not
+};
+
 // One wavefront per vehicle, rows copied by lanes (consecutive lanes, consecutive doubles).  A plan is valid when ref_status == 0
 // and status has no bit but EMP_ST_DP_INFEASIBLE (service.py's rule): its first traj_len rows become the track and held is 0;
 // otherwise the track stays and held counts the periods it has been held.
-__global__ __launch_bounds__(256) void drive_adopt_kernel(int B, int max_pts, AdoptIO io) {
+template <typename TS>
+__global__ __launch_bounds__(256) void drive_adopt_kernel(int B, int max_pts, AdoptIO io, TS ts) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
     if (b >= B) return;
@@ -193,6 +249,27 @@ __global__ __launch_bounds__(256) void drive_adopt_kernel(int B, int max_pts, Ad
         const bool take = valid && i < 4 * tl;
         if (take) io.track_out[base + i] = t;
         else if (moved) io.track_out[base + i] = io.track_in[base + i];
+    }
+    if constexpr (TS::kTimed) {
+        const bool adopt = valid && ts.speed_status[b] == 0;
+        const bool read = adopt || ts.log_profile != nullptr, kept = !adopt && ts.profile_out != ts.profile_in;
+        const size_t pb = (size_t)b * kProfile;
+        if (read || kept) {                                        // (a profile held in place without a log: nothing moves)
+            for (int i = lane; i < kProfile; i += 64) {
+                const double t = read ? ts.trajectory[pb + i] : 0.0;
+                if (ts.log_profile) ts.log_profile[pb + i] = t;
+                if (adopt) ts.profile_out[pb + i] = t;
+                else if (kept) ts.profile_out[pb + i] = ts.profile_in[pb + i];
+            }
+        }
+        if (lane == 0) {
+            const int sheld = adopt ? 0 : ts.speed_held_in[b] + 1, cur = adopt ? 0 : ts.cursor_in[b];
+            ts.cursor_out[b] = cur;
+            ts.speed_held_out[b] = sheld;
+            if (ts.log_speed_status) ts.log_speed_status[b] = ts.speed_status[b];
+            if (ts.log_speed_held) ts.log_speed_held[b] = sheld;
+            if (ts.log_cursor) ts.log_cursor[b] = cur;
+        }
     }
     if (lane != 0) return;
     const int held = valid ? 0 : io.held_in[b] + 1;

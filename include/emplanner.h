@@ -1026,7 +1026,8 @@ int emp_drive_request(emp_ctx* ctx, const emp_drive_params* p, int32_t B, int32_
  *   - the reference tracks the reply to the PREVIOUS request (a blocking recv sits right behind the send, test_9.py:390-395); here
  *     the plan of period k drives period k.  The one-period lag is the reference's way of hiding a 0.3 s planner: not reproduced
  *   - the reference's plant is CARLA; ours is emp_vehicle_step, and its caveat stands: gentle paths only
- *   - the speed planner (emp_plan_trajectory) is not part of the loop: target_speed is the caller's constant, as test_9.py:420
+ *   - the speed planner (emp_plan_trajectory) is not part of THIS loop: target_speed is the caller's constant, as test_9.py:420.
+ *     emp_drive_timed below is the loop with the speed planner in it and the PID on its profile
  * Limits: 1 <= K <= EMP_DRIVE_MAX_PERIODS, T as emp_rollout, max_obs <= 253, the emp_plan_cycle and emp_drive_request limits.
  * B == 0: EMP_OK.  EMP_HOST_PINNED is refused.  With a pipeline set the call fences like every non-cycle entry point, runs its
  * periods one at a time and leaves the setting as it found it; EMP_OPT_CYCLE_GRAPH is ignored (plain launches).  With
@@ -1066,6 +1067,123 @@ int emp_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, co
               const emp_drive_params* drive_params, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
               const emp_vehicle_params* vp, int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act,
               int32_t max_dyn, int32_t K, int32_t T, const double* target_speed, const emp_drive_io* io, emp_mem where);
+
+/* ---- the timed fleet loop: the speed planner and profile tracking inside the drive (additions: the ABI stays 13) -------------
+ * ref: the reference's most complete loop, test_10.py - emp_drive with emp_plan_trajectory in place of emp_plan_cycle and
+ * emp_rollout_timed in place of emp_rollout, so a fleet driven on the device slows down for a vehicle ahead.
+ *
+ * THE CLOCK (the one new rule).  emp_drive_timed takes t0 [B] (seconds, per vehicle) and a scalar tick0 >= 0: emp_rollout_timed's
+ * convention, continued over periods.  With dt = vp->dt:
+ *   tick_k = tick0 + k * T                                           period k's first tick (integer arithmetic)
+ *   the rollout of period k is emp_rollout_timed's kernel with t0 and tick0 = tick_k: tick t of it samples the profile at
+ *     clock = t0 + (double)(tick_k + t) * dt                         a function of the tick NUMBER, as in emp_rollout_timed
+ *   plan_start_time of period k = (t0 + (double)tick_k * dt) + plan_lead        the product rounded, then each sum
+ * plan_lead is emp_drive_timed_params' field, 0.1 by default (test_10.py:325: cur_time + 0.1).  NOTHING ACCUMULATES: a run of K
+ * periods equals a run of K1 periods followed by a run of K - K1 periods with tick0 + K1 * T on the first run's outputs, BIT FOR
+ * BIT.  Refused (EMP_ERR_INVALID): tick0 < 0, and tick0 + K * T > INT32_MAX.
+ *
+ * emp_drive_request_timed: emp_drive_request with the speed planner's inputs (emp_speed_io) beside the cycle's, from the same
+ * kernel text - the request holds each dynamic actor's (x, y, vx, vy) and its rank in registers, and no later kernel can recover
+ * them once the actors have advanced in place.  Every output it shares with emp_drive_request equals that call's bit for bit, and
+ *   dyn_obs [B][max_dyn][4]  = x, y, vx, vy of the kept dynamic actors in dyn's order (dis ascending, ties in actor-index
+ *                              order), positions BEFORE the advance; slots at or beyond n_dyn are 0
+ *   start_heading [B]        = atan2(wy, wx): the value beta is made of, not a second evaluation (test_10.py:247)
+ *   plan_start_time [B]      = (t0 + (double)tick * dt) + plan_lead
+ * t0 [B], dyn_obs, start_heading and plan_start_time are required; tick >= 0, dt finite and > 0, plan_lead finite (also in
+ * emp_drive_timed_params), else EMP_ERR_INVALID. */
+int emp_drive_request_timed(emp_ctx* ctx, const emp_drive_params* p, int32_t B, int32_t max_act, int32_t max_obs, int32_t max_dyn,
+                            const double* state, const double* accel, const double* actors, const int32_t* n_act, const double* t0,
+                            int32_t tick, double dt, double plan_lead, double* static_xy, int32_t* n_static, double* static_dis,
+                            double* dyn, int32_t* n_dyn, double* dyn_dis_speed, int32_t* n_obs, double* origin_xy, double* start_xy,
+                            double* pred_fi, double* start_v, double* start_a, int32_t* req_status, double* actors_next,
+                            double* dyn_obs, double* start_heading, double* plan_start_time, emp_mem where);
+
+/* emp_drive_timed: K periods of [timed request, path and speed plan, adopt, T timed ticks, acceleration] on emp_stream(), stream-
+ * ordered, without a host synchronisation or a copy between them.  Period k:
+ *   1. emp_drive_request_timed at tick_k on state / accel / actors, advance_s = T * vp->dt (actors move in place)
+ *   2. emp_plan_trajectory exactly as it runs with io->global_path set (EMP_DP_TWO_KERNEL, one batch at a time): the path half as
+ *      in emp_drive; the speed half on the request's dyn_obs, n_dyn, start_heading and plan_start_time, dyn_pre_match = NULL
+ *   3. adopt.  The TRACK by emp_drive's rule: valid when ref_status == 0 and (status & ~EMP_ST_DP_INFEASIBLE) == 0.  The PROFILE
+ *      when the path is valid AND speed_status == 0: the 7 x 401 doubles of the period's trajectory become profile_out,
+ *      cursor = 0, speed_held = 0.  Otherwise the profile and the cursor stay as they are and speed_held += 1; the track is adopted
+ *      or held by its own rule, independently.  A held profile is still on the absolute clock, so the sampling rule goes on
+ *      reading it; when the clock passes its end the rule holds its last speed and reports EMP_TGT_PAST.  A VEHICLE THAT NEVER HAD
+ *      A PROFILE carries the caller's initial one - all NaN is the natural start: the rule then gives it the cap (target_speed) and
+ *      sets EMP_TGT_NO_PROFILE
+ *   4. emp_rollout_timed's kernel: T ticks on the adopted track and profile with t0, the carried cursor and tick0 = tick_k; a new
+ *      controller every period (min_index 0, an empty PID deque), as in emp_drive.  target_speed [B] is the cap, in km/h
+ *   5. accel as in emp_drive (the same kernel)
+ * EVERY OUTPUT AND LOG EQUALS, BIT FOR BIT, K iterations of emp_drive_request_timed -> emp_plan_trajectory (io->global_path set)
+ * -> the adopt rule of 3 -> emp_rollout_timed(tick0 = tick_k) -> the acceleration formula, on the same arrays.
+ * emp_drive_timed_io holds emp_drive_io's fields under their names, and
+ *   inputs:  t0 [B]; profile [B][7][EMP_TIMED_POINTS]; cursor [B]; speed_held [B]                                  (all required)
+ *   outputs: profile_out, cursor_out, speed_held_out (required; each may alias the input of its name: an element is read by the
+ *            lane that writes it)
+ *   logs, one row per period, NULL to skip: log_speed_status [K][B] the period's speed_status; log_speed_held [K][B];
+ *            log_tgt_status [K][B] the OR of the period's ticks' EMP_TGT_* bits; log_cursor [K][B] the cursor the period's ticks
+ *            START from (0 for a profile adopted in that period); log_profile [K][B][7][401] the period's timed trajectory, adopted
+ *            or not - 22 456 B per vehicle per period: 736 MB for one period of 32768 vehicles
+ * Limits: emp_drive's, emp_plan_trajectory's (1 <= max_dyn <= 64) and emp_rollout_timed's, and the clock's above.  EMP_HOST_PINNED
+ * is refused; EMP_OPT_CYCLE_GRAPH is ignored (plain launches); with a pipeline set the call fences like every non-cycle entry point,
+ * runs its periods one at a time and leaves the setting as it found it.  B == 0: EMP_OK.  reserved must be 0 in both structs.
+ * Memory: the call keeps one timed trajectory per vehicle (22 456 B) beside emp_drive's temporaries. */
+typedef struct emp_drive_timed_params {
+    double plan_lead;               /* 0.1 (test_10.py:325): plan_start_time = clock at the period's first tick + plan_lead */
+    int32_t reserved;               /* must be 0 */
+} emp_drive_timed_params;
+void emp_drive_timed_params_default(emp_drive_timed_params* p);
+
+typedef struct emp_drive_timed_io {
+    /* inputs: emp_drive_io's */
+    const double* global_path;      /* [B][max_global][4] */
+    const int32_t* n_global;        /* [B] */
+    const double* state;            /* [B][6] */
+    const double* accel;            /* [B][2] world-frame acceleration, NULL = zeros */
+    const double* actors;           /* [B][max_act][4] */
+    const int32_t* n_act;           /* [B] */
+    const int32_t* pre_match_index; /* [B] */
+    const double* track;            /* [B][max_pts + 1][4] */
+    const int32_t* track_len;       /* [B] */
+    const int32_t* held;            /* [B] */
+    /* ... and the timed loop's */
+    const double* t0;               /* [B] the vehicle's clock at tick 0, seconds */
+    const double* profile;          /* [B][7][EMP_TIMED_POINTS] the timed trajectory being followed; all NaN = none yet */
+    const int32_t* cursor;          /* [B] the sampling rule's bracket */
+    const int32_t* speed_held;      /* [B] */
+    /* outputs (required; each may alias the input of its name) */
+    double* state_out;
+    double* accel_out;
+    double* actors_out;
+    int32_t* pre_match_index_out;
+    double* track_out;
+    int32_t* track_len_out;
+    int32_t* held_out;
+    double* profile_out;
+    int32_t* cursor_out;
+    int32_t* speed_held_out;
+    /* per-period logs, NULL to skip: emp_drive_io's */
+    double* log_state;              /* [K][B][6] state at the start of the period */
+    int32_t* log_plan_status;       /* [K][B] status | ref_status */
+    int32_t* log_roll_status;       /* [K][B] */
+    int32_t* log_held;              /* [K][B] */
+    int32_t* log_counts;            /* [K][B][2] n_obs, n_dyn */
+    double* log_traj;               /* [K][B][max_pts + 1][4] the period's plan, adopted or not */
+    int32_t* log_traj_len;          /* [K][B] */
+    /* ... and the timed loop's */
+    int32_t* log_speed_status;      /* [K][B] EMP_STB_* bits of the period's speed plan */
+    int32_t* log_speed_held;        /* [K][B] */
+    int32_t* log_tgt_status;        /* [K][B] OR of the period's ticks' EMP_TGT_* bits */
+    int32_t* log_cursor;            /* [K][B] the cursor the period's ticks start from */
+    double* log_profile;            /* [K][B][7][EMP_TIMED_POINTS] the period's timed trajectory, adopted or not */
+    int32_t reserved;               /* must be 0 */
+} emp_drive_timed_io;
+
+int emp_drive_timed(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
+                    const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp, const emp_drive_params* drive_params,
+                    const emp_drive_timed_params* timed_params, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
+                    const emp_vehicle_params* vp, int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act,
+                    int32_t max_dyn, int32_t K, int32_t T, int32_t tick0, const double* target_speed, const emp_drive_timed_io* io,
+                    emp_mem where);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,14 @@ speed-up bar (launch counts alone buy nothing when the host runs ahe
 period.  Prints one JSON line per (law, B).
 
     python tools/drive_bench.py [--sizes 1,4096,32768] [--periods 10] [--ticks 100] [--reps 1] [--blocks 5] [--out drive_bench.json]
+
+--timed times the timed fleet loop instead: Planner.drive_timed (one call) against the same loop written with the separate calls
+(drive_request_timed, plan_cycle(global_path=..., speed=...), the adoption with torch.where, rollout_timed: all on device tensors, so
+this form pays launches and Python, no round trip) and against Planner.drive on the same fleet (what the speed half and the profile
+copy cost).  Same method: HIP events, the three forms alternated block by block, median of the blocks with [min, max].  The two
+timed forms run the same kernels on the same bits: their final states must be identical.
+
+    python tools/drive_bench.py --timed [--out profiles/drive/drive_timed_bench.json]
 """
 from __future__ import annotations
 
@@ -84,6 +92,112 @@ def host_request(state, actors, n_act, ts=0.2):
     return static_xy, n_obs, dds, state[:, :2].copy(), start, np.column_stack([wx, wy])
 
 
+def main_timed(a):
+    K, T = a.periods, a.ticks
+    pl = api.Planner(0)
+    stream = pl.torch_stream()
+    p, q, sp, pid, vpar, dprm = api.dp_params(), api.qp_params(), api.smooth_params(), api.pid_params(), api.vehicle_params(), api.drive_params()
+    sdp, sqp, adv = api.speed_dp_params(), api.speed_qp_params(), api.drive_params(advance_s=T * vpar.dt)
+    M, N = api.max_path_points(p), 401
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    results = []
+    for B in (int(s) for s in a.sizes.split(",")):
+        f = fleet(B)
+        f.update(track=np.zeros((B, M + 1, 4)), track_len=np.zeros(B, np.int32), profile=np.full((B, 7, N), np.nan),
+                 cursor=np.zeros(B, np.int32), speed_held=np.zeros(B, np.int32))
+        const = {k: up(f[k]) for k in ("global_path", "n_global", "n_act", "target_speed")}
+        const["t0"] = torch.zeros(B, dtype=torch.float64, device="cuda")
+        zeros = dict(mi=torch.zeros(B, dtype=torch.int32, device="cuda"), err=torch.zeros((B, 60), dtype=torch.float64, device="cuda"),
+                     n_err=torch.zeros(B, dtype=torch.int32, device="cuda"))
+        every = max(T - 1, 1)
+
+        def fresh():
+            g = {k: up(f[k]) for k in ("state", "accel", "actors", "pre_match_index", "track", "track_len", "held", "profile", "cursor",
+                                       "speed_held")}
+            torch.cuda.synchronize()
+            return g
+
+        def drive_timed(law, lat, g):
+            return pl.drive_timed(p, q, sp, sdp, sqp, dprm, lat, pid, vpar, const["global_path"], const["n_global"], g["state"], g["accel"],
+                                  g["actors"], const["n_act"], g["pre_match_index"], g["track"], g["track_len"], g["held"], const["t0"],
+                                  g["profile"], g["cursor"], g["speed_held"], const["target_speed"], K, T, MAX_OBS, MAX_DYN, lateral=law,
+                                  logs=False, in_place=True).state
+
+        def drive(law, lat, g):
+            return pl.drive(p, q, sp, dprm, lat, pid, vpar, const["global_path"], const["n_global"], g["state"], g["accel"], g["actors"],
+                            const["n_act"], g["pre_match_index"], g["track"], g["track_len"], g["held"], const["target_speed"], K, T,
+                            MAX_OBS, MAX_DYN, lateral=law, logs=False, in_place=True).state
+
+        def separate(law, lat, g):
+            state, accel, actors, prem, track, tlen, held, prof, cur, sheld = (g[k] for k in (
+                "state", "accel", "actors", "pre_match_index", "track", "track_len", "held", "profile", "cursor", "speed_held"))
+            w_of = lambda st_: pl.drive_request(dprm, st_, None, actors, const["n_act"], MAX_OBS, MAX_DYN).start_v
+            for k in range(K):
+                rq = pl.drive_request_timed(adv, state, accel, actors, const["n_act"], const["t0"], k * T, vpar.dt, MAX_OBS, MAX_DYN,
+                                            in_place=True)
+                cy = pl.plan_cycle(p, q, sp, None, None, rq.origin_xy, rq.start_xy, rq.start_v, rq.start_a, rq.static_xy, rq.n_obs,
+                                   max_pts=M, dyn_dis_speed=rq.dyn_dis_speed, global_path=const["global_path"],
+                                   n_global=const["n_global"], pre_match_index=prem,
+                                   speed=api.TrajectoryInputs(sdp, sqp, rq.dyn_obs, rq.n_dyn, rq.plan_start_time,
+                                                              start_heading=rq.start_heading, intermediates=False))
+                valid = (cy.ref_status == 0) & ((cy.status & ~1) == 0)
+                take = valid[:, None] & (torch.arange(M + 1, device="cuda")[None, :] < cy.traj_len[:, None])
+                track = torch.where(take[:, :, None], cy.traj, track)
+                tlen = torch.where(valid, cy.traj_len, tlen)
+                held = torch.where(valid, torch.zeros_like(held), held + 1)
+                both = valid & (cy.speed.speed_status == 0)
+                prof = torch.where(both[:, None, None], cy.speed.trajectory, prof)
+                cur = torch.where(both, torch.zeros_like(cur), cur)
+                sheld = torch.where(both, torch.zeros_like(sheld), sheld + 1)
+                ro = pl.rollout_timed(lat, pid, vpar, track, tlen, state, zeros["mi"], const["target_speed"], zeros["err"], zeros["n_err"],
+                                      prof, const["t0"], T, tick0=k * T, cursor=cur, lateral=law, log_every=every)
+                accel = (w_of(ro.state) - w_of(ro.log_state[0 if T == 1 else 1])) / vpar.dt
+                state, prem, cur = ro.state, cy.match_index, ro.cursor
+            return state
+
+        def block(fn, law, lat):
+            per = []
+            for _ in range(a.reps):
+                g = fresh()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                fn(law, lat, g)
+                e1.record(stream)
+                pl.synchronize()
+                torch.cuda.synchronize()
+                per.append(e0.elapsed_time(e1))
+            return sum(per) / len(per)
+
+        forms = (("drive_timed", drive_timed), ("separate_timed", separate), ("drive", drive))
+        for law, lat in (("mpc", api.mpc_params()), ("lqr", api.lqr_params())):
+            finals = {}
+            for name, fn in forms:                                             # warm-up, and the two timed forms are one computation
+                st = fn(law, lat, fresh())
+                pl.synchronize()
+                torch.cuda.synchronize()
+                finals[name] = st.cpu().numpy()
+            assert finals["drive_timed"].tobytes() == finals["separate_timed"].tobytes(), "drive_timed and the separate calls differ"
+            ms = {name: [] for name, _ in forms}
+            for _ in range(a.blocks):                                          # alternate: drift of the machine hits all alike
+                for name, fn in forms:
+                    ms[name].append(block(fn, law, lat))
+            med = {name: statistics.median(v) for name, v in ms.items()}
+            row = {"law": law, "B": B, "K": K, "T": T, "reps": a.reps, "blocks": a.blocks,
+                   "separate_over_drive_timed": round(med["separate_timed"] / med["drive_timed"], 3),
+                   "drive_timed_over_drive": round(med["drive_timed"] / med["drive"], 3),
+                   "mean_vx_timed": float(finals["drive_timed"][:, 5].mean()), "mean_vx_drive": float(finals["drive"][:, 5].mean())}
+            for name, v in ms.items():
+                row[name + "_ms"] = round(med[name], 3)
+                row[name + "_spread_ms"] = [round(min(v), 3), round(max(v), 3)]
+            results.append(row)
+            print(json.dumps(row), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(results, fh, indent=1)
+    pl.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1,4096,32768")
@@ -92,7 +206,10 @@ def main():
     ap.add_argument("--reps", type=int, default=1)
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--timed", action="store_true", help="time Planner.drive_timed against the separate timed calls and Planner.drive")
     a = ap.parse_args()
+    if a.timed:
+        return main_timed(a)
     K, T = a.periods, a.ticks
     pl = api.Planner(0)
     stream = pl.torch_stream()
