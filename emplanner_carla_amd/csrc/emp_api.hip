@@ -978,9 +978,9 @@ static int dev_cycle_qp(emp_ctx* ctx, int B, int max_pts, int max_obs, const QpD
     const bool pair_form = ctx->opt[EMP_OPT_PATH_QP_FORM] == 1;
     if (cap <= 66 && !pair_form) {                                    // 8 (4) scenes per wavefront on groups of 8 (16) lanes
         const int gp = cap <= 34 ? 8 : 16;
-        const size_t words = cap <= 26 ? cycle_qp_group_words<8, 3>(cap, max_obs) : cap <= 34 ? cycle_qp_group_words<8, 4>(cap, max_obs)
-                                                                                                : cycle_qp_group_words<16, 4>(cap, max_obs);
-        const size_t per_wave = (size_t)(64 / gp) * words * sizeof(double) + EMP_QP_LDS_PAD;
+        // the kernel's own carve-up (PathQpRowsLayout, emp_qp_core.h: cycle_qp_group_words doubles between two groups)
+        const size_t per_wave = (cap <= 26 ? PathQpRowsLayout<8, 3>::wave_bytes(max_obs) : cap <= 34 ? PathQpRowsLayout<8, 4>::wave_bytes(max_obs)
+                                                                                          : PathQpRowsLayout<16, 4>::wave_bytes(max_obs)) + EMP_QP_LDS_PAD;
         auto kern = cap <= 26 ? cycle_qp_rows_kernel<8, 3> : cap <= 34 ? cycle_qp_rows_kernel<8, 4> : cycle_qp_rows_kernel<16, 4>;
         if ((rc = set_lds(ctx, kern, per_wave, kQpTooLarge))) return rc;
         const int spw = 64 / gp;

@@ -625,6 +625,67 @@ EMP_HD void path_qp_finish(const double* cc, int n, double ds, double* out_l, do
 EMP_HD constexpr int path_qp_words_pair() { return 36 + PathRangeQp::words_fast(32, 32); }
 EMP_HD constexpr int path_qp_words(int n) { return PathRangeQp::words(n - 4 > 0 ? n - 4 : 0, n - 2 > 0 ? n - 2 : 0) + n + 2; }
 
+// ---------------------------------------------------------------------------------------------
+// Storage of one problem of the rows solver (emp_qp_rows.h: GP lanes, R stations and R unknowns per lane, capacity
+// C = GP R of each), in doubles from the start of the group's region.  The solver reads its arrays in WINDOWS with plain
+// lane offsets: up to three unknowns below index 0 and three past C - 1, two stations past C - 1, three Hessian rows above
+// row 0.  Every array therefore carries guard entries on the sides its windows reach over, INSIDE the group's region, and
+// guards and the entries between a problem's N / ns and C hold what lies outside a problem: +0.0 (c, lo, hi: 0, -1e300,
+// +1e300).  path_qp_group_rows writes them once (pad_ranges below).  Every store of the loop goes to one of the problem's own
+// N / ns entries - u only while the group iterates, the scratch arrays tmp, wgt, dua and rhs from stopped groups too - so the
+// padding holds for the whole solve.
+//   cc [C + 4] | 12 | P [4 C] | q [C] | 3 | u [C] | 3 | dua [C] | 2 | rhs [C] | c lo hi [2 C each] | tmp [2 C] | 4 | wgt [2 C] | 4
+// The kernel around the solver (emp_tail_kernels.h, cycle_qp_body) keeps arrays that are dead while the solver runs inside
+// these: the obstacle table in P, the decimated path and its bounds (4 cap doubles) from tmp on, the result in dua .. rhs.
+// ---------------------------------------------------------------------------------------------
+template <int GP, int R>
+struct PathQpRowsLayout {
+    static constexpr int C = GP * R;
+    static constexpr int kBelowU = 3, kAboveU = 3, kBelowStep = 2, kAboveStation = 2, kRowsAboveP = 3;   // window reaches
+    static constexpr int cc = 0;                                  // coefficient slots (n + 2 <= C + 4 used)
+    static constexpr int P = cc + C + 4 + kRowsAboveP * 4;
+    static constexpr int q = P + C * 4;
+    static constexpr int u = q + C + kBelowU;
+    static constexpr int dua = u + C + kAboveU;                   // (u's upper guard is dua's lower one)
+    static constexpr int rhs = dua + C + kBelowStep;
+    static constexpr int c = rhs + C;
+    static constexpr int lo = c + C * 2;
+    static constexpr int hi = lo + C * 2;
+    static constexpr int tmp = hi + C * 2;
+    static constexpr int wgt = tmp + C * 2 + kAboveStation * 2;
+    static constexpr int words = wgt + C * 2 + kAboveStation * 2;
+    // most stations of a scene, and the arrays of the kernel around the solver
+    static constexpr int max_stations = C + 2;
+    static constexpr int result = dua;                            // max_stations doubles, written behind the last iteration
+    static constexpr int path = tmp;                              // 4 max_stations doubles, dead once the problem is set up
+    static constexpr int obstacles = P;                           // 4 max_obs doubles when they fit into P, else behind `words`
+    static_assert(kAboveU >= kBelowStep, "dua's windows start inside u's upper guard");
+    static_assert(rhs + C - result >= max_stations, "the result fits into dua .. rhs");
+    static_assert(words - path >= 4 * max_stations, "the decimated path and its bounds fit into tmp .. wgt");
+    // doubles between the regions of two groups of a wavefront: an ODD number (emp_tail_kernels.h, cycle_qp_group_words)
+    static constexpr int stride(int max_obs) { return (words + (max_obs <= C ? 0 : 4 * max_obs)) | 1; }
+    // bytes of dynamic LDS of one wavefront (64 / GP groups)
+    static constexpr size_t wave_bytes(int max_obs) { return (size_t)(64 / GP) * stride(max_obs) * sizeof(double); }
+    // The padding of a problem with N unknowns and ns stations (a group without a problem: 0, 0): fill(first, last, value) is
+    // called for every range [first, last) of doubles of the group's region that must hold `value`.  The ONE list of them:
+    // path_qp_pad_rows (emp_qp_rows.h) stores through it, the host check replays it.
+    template <class Fill>
+    static EMP_HD void pad_ranges(int N, int ns, Fill fill) {
+        fill(P - kRowsAboveP * 4, P, 0.0);
+        fill(P + N * 4, P + C * 4, 0.0);
+        fill(q + N, q + C, 0.0);
+        fill(u - kBelowU, u, 0.0);
+        fill(u + N, dua, 0.0);                                    // .. with u's upper guard
+        fill(dua + N, rhs, 0.0);                                  // .. with rhs's lower guard
+        fill(rhs + N, rhs + C, 0.0);
+        fill(c + ns * 2, c + C * 2, 0.0);
+        fill(lo + ns * 2, lo + C * 2, -1e300);
+        fill(hi + ns * 2, hi + C * 2, 1e300);
+        fill(tmp + ns * 2, wgt, 0.0);                             // .. with the two stations past C - 1
+        fill(wgt + ns * 2, words, 0.0);
+    }
+};
+
 // complete scalar path QP on caller storage `mem` (path_qp_words(n) doubles)
 // gi_work != NULL: the dual active-set solver (gi_words(n - 4) doubles) instead of the interior point
 EMP_HD int path_qp_solve_scalar(double* mem, const double* l_min, const double* l_max, int n, double l0, double dl0,

@@ -16,6 +16,11 @@
 // certified against the reference-built KKT system).  Measured: 15.7 M vector instructions per 4096
 // scenes (HISTORY.md section 3.3).
 //
+// Storage (round 8): a group's arrays carry guard entries and zero padding (PathQpRowsLayout, emp_qp_core.h), so the windows
+// the station / unknown phases read past a problem's ends need no select behind the load: 363 -> 111 v_cndmask and
+// 1802 -> 1638 vector instructions in the loop of <8, 3> as written, 303 -> 301 registers; measured 6.6 -> 6.2 us an
+// iteration, 132 -> 123 us per 4096 benchmark scenes, 12.8 -> 11.7 M vector instructions a launch (profiles/r08_qp/README.md).
+//
 // The problems of a wavefront iterate in lock step until the slowest has converged (finished groups idle through the
 // barriers): mean 10 iterations per wavefront of eight where a pair took 8.7.  Small batches (under 1024 scenes), which
 // cannot fill the chip and are served by latency, keep the two-per-wavefront kernel.
@@ -207,9 +212,11 @@ __device__ __forceinline__ void band_solve_rows(const double (&a)[R][4], const d
 
 // ---------------------------------------------------------------------------------------------
 // Interior point for the path QP (RangeQp<3, 2, 3>, window offset -2), R stations and R unknowns per lane.
-// Q must be bound with bind_fast(mem, GP R, GP R, N, ns) behind at least 12 readable doubles (the coefficient slots of
-// path_qp_group_rows): windows are read with plain lane offsets, up to three rows outside their arrays, and what lies
-// outside a problem is replaced by zero after the load.  Q.g must be the same for every lane of the wavefront.
+// Q must be bound to a group's PathQpRowsLayout<GP, R> (emp_qp_core.h) and padded by path_qp_pad_rows: windows are read with
+// plain lane offsets, up to three rows outside their arrays, and what lies outside a problem is the padding's zero - no
+// select behind the load.  Storage rules of the loop: u and `keep` are written for a group that still iterates only, and
+// for its own unknowns; tmp, wgt, dua and rhs are scratch within an iteration and are written by stopped groups too - for
+// the problem's own entries, or with the +0.0 that is there already.  Q.g must be the same for every lane of the wavefront.
 // returns (per group) 0 converged, 2 failed / infeasible.
 // ---------------------------------------------------------------------------------------------
 template <int GP, int R>
@@ -236,33 +243,22 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
         for (int p = 0; p < W - 1; ++p) gg1[p][f] = wave_uniform(g[f][p] * g[f][p + 1]);
         gg2[0][f] = wave_uniform(g[f][0] * g[f][2]);
     }
-    // existence masks (bit i of a window = that entry belongs to the problem)
-    unsigned tmask = 0, mmask = 0, uwm = 0, swm = 0, uxm = 0;
+    // What exists of the lane's R stations and R unknowns, evaluated once (the loop tests these, not `run`, wherever the
+    // guarded work of a group that has stopped is harmless: see the storage rules above).  Windows need no predicate: what
+    // they read outside the problem is the zero padding of PathQpRowsLayout.
+    bool tm[R], mm[R], in1[R], in2[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        if (live && base + r < ns) tmask |= 1u << r;
-        if (live && base + r < N) mmask |= 1u << r;
+        tm[r] = live && base + r < ns;
+        mm[r] = live && base + r < N;
+        in1[r] = live && base + r + 1 < N;                     // columns m + 1, m + 2 of the unknown's row of the normal matrix
+        in2[r] = live && base + r + 2 < N;
     }
-#pragma unroll
-    for (int i = 0; i < R + 2; ++i) {
-        const int k = base - 2 + i;                            // unknown window of the lane's stations
-        if (live && k >= 0 && k < N) uwm |= 1u << i;
-        if (live && base + i < ns) swm |= 1u << i;             // station window of the lane's unknowns: stations base..base+R+1
-    }
-#pragma unroll
-    for (int i = 0; i < R + 6; ++i) {
-        const int k = base - 3 + i;                            // unknowns base-3 .. base+R+2 (Hessian rows)
-        if (live && k >= 0 && k < N) uxm |= 1u << i;
-    }
-    auto ld = [](const double* a, int i, bool ok) {           // unconditional load, then select
-        const double raw = a[i];
-        return ok ? raw : 0.0;
-    };
     // sum_p g[f][p] vec[t - 2 + p] for the lane's R stations
     auto win = [&](const double* vec, double (&out)[R][F]) {
         double vals[R + 2];
 #pragma unroll
-        for (int i = 0; i < R + 2; ++i) vals[i] = ld(vec, base - 2 + i, (uwm >> i) & 1u);
+        for (int i = 0; i < R + 2; ++i) vals[i] = vec[base - 2 + i];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
 #pragma unroll
@@ -275,7 +271,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
 #pragma unroll
         for (int i = 0; i < R + 2; ++i) {
 #pragma unroll
-            for (int f = 0; f < F; ++f) cw[i][f] = ld(coef, (base + i) * F + f, (swm >> i) & 1u);
+            for (int f = 0; f < F; ++f) cw[i][f] = coef[(base + i) * F + f];
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -291,13 +287,11 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
     auto bounds = [&](double (&c_it)[R][F], double (&lo_it)[R][F], double (&hi_it)[R][F]) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const bool ok = (tmask >> r) & 1u;
 #pragma unroll
-            for (int f = 0; f < F; ++f) {
-                const double c = Q.c[(base + r) * F + f], lo = Q.lo[(base + r) * F + f], hi = Q.hi[(base + r) * F + f];
-                c_it[r][f] = ok ? c : 0.0;
-                lo_it[r][f] = ok ? lo : -1e300;
-                hi_it[r][f] = ok ? hi : 1e300;
+            for (int f = 0; f < F; ++f) {                          // (past ns: 0, -1e300, +1e300 from the padding)
+                c_it[r][f] = Q.c[(base + r) * F + f];
+                lo_it[r][f] = Q.lo[(base + r) * F + f];
+                hi_it[r][f] = Q.hi[(base + r) * F + f];
             }
         }
     };
@@ -306,9 +300,8 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
     double pdiag = 0.0, qabs = 0.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const bool ok = (mmask >> r) & 1u;
-        pdiag = fmax(pdiag, ld(Q.P, (base + r) * 4, ok));
-        qabs = fmax(qabs, fabs(ld(Q.q, base + r, ok)));
+        pdiag = fmax(pdiag, Q.P[(base + r) * 4]);
+        qabs = fmax(qabs, fabs(Q.q[base + r]));
     }
     const double pscale = oct_max<GP>(pdiag);                     // largest Hessian diagonal
     const double qscale = fmax(oct_max<GP>(qabs), 1.0);
@@ -322,10 +315,12 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
         for (int r = 0; r < R; ++r) {
 #pragma unroll
             for (int f = 0; f < F; ++f) {
-                zu[r][f] = zl[r][f] = z0;
+                // A station that does not exist carries multipliers 0 and - from the padding - slacks 1e300 and residuals 0 for
+                // the whole solve (the update leaves it alone): neutral in every maximum and sum over the stations below.
+                zu[r][f] = zl[r][f] = tm[r] ? z0 : 0.0;
                 su[r][f] = hi_it[r][f] - (c_it[r][f] + v[r][f]);
                 sl[r][f] = (c_it[r][f] + v[r][f]) - lo_it[r][f];
-                if ((tmask >> r) & 1u) smin = fmin(smin, fmin(su[r][f], sl[r][f]));
+                smin = fmin(smin, fmin(su[r][f], sl[r][f]));
             }
         }
         smin = oct_min<GP>(smin);
@@ -353,7 +348,6 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
             win(Q.u, v);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const bool ok = run && ((tmask >> r) & 1u);
 #pragma unroll
                 for (int f = 0; f < F; ++f) {
                     rpu[r][f] = (c_it[r][f] + v[r][f]) - hi_it[r][f] + su[r][f];
@@ -362,7 +356,10 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
                     isl[r][f] = fast_rcp(sl[r][f]);
                     izu[r][f] = fast_rcp(zu[r][f]);
                     izl[r][f] = fast_rcp(zl[r][f]);
-                    if (ok) {
+                    // (a group that has stopped rewrites scratch it no longer reads and reduces values nobody uses: no `run` here.
+                    // Running this block for every station - one that does not exist stores and adds +0.0 - was built and took
+                    // 24 registers more: profiles/r08_qp/README.md)
+                    if (tm[r]) {
                         Q.tmp[(base + r) * F + f] = zu[r][f] - zl[r][f];
                         Q.wgt[(base + r) * F + f] = zu[r][f] * isu[r][f] + zl[r][f] * isl[r][f];
                         rp_max = vmax(rp_max, vmax_abs(rpu[r][f], rpl[r][f]));
@@ -378,26 +375,26 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
         {
             double ux[R + 6], gz[R];
 #pragma unroll
-            for (int i = 0; i < R + 6; ++i) ux[i] = ld(Q.u, base - 3 + i, (uxm >> i) & 1u);
+            for (int i = 0; i < R + 6; ++i) ux[i] = Q.u[base - 3 + i];
             gather(Q.tmp, gz);
             double ww[R + 2][F];
 #pragma unroll
             for (int i = 0; i < R + 2; ++i) {
 #pragma unroll
-                for (int f = 0; f < F; ++f) ww[i][f] = ld(Q.wgt, (base + i) * F + f, (swm >> i) & 1u);
+                for (int f = 0; f < F; ++f) ww[i][f] = Q.wgt[(base + i) * F + f];
             }
             double rd_max = 0.0;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const bool ok = run && ((mmask >> r) & 1u);
                 const int m = base + r;
-                // P u: the row's own band and the three rows above it (all stored bands have zeros past column N-1)
+                // P u: the row's own band and the three rows above it (all stored bands have zeros past column N-1, the three
+                // rows above row 0 are padding)
                 double acc = Q.q[m];
 #pragma unroll
                 for (int d = 0; d < 4; ++d) acc += Q.P[m * 4 + d] * ux[r + 3 + d];
 #pragma unroll
-                for (int d = 1; d < 4; ++d) acc += ld(Q.P, (m - d) * 4 + d, m - d >= 0) * ux[r + 3 - d];
-                rd_m[r] = ok ? acc + gz[r] : 0.0;
+                for (int d = 1; d < 4; ++d) acc += Q.P[(m - d) * 4 + d] * ux[r + 3 - d];
+                rd_m[r] = mm[r] ? acc + gz[r] : 0.0;              // (unknowns N and N + 1 gather from stations that exist)
                 rd_max = vmax_abs(rd_max, rd_m[r]);
                 double e0 = Q.P[m * 4 + 0], e1 = Q.P[m * 4 + 1], e2 = Q.P[m * 4 + 2];
                 const double e3 = Q.P[m * 4 + 3];
@@ -408,10 +405,13 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
                     e1 += ww[r + 2][f] * gg1[0][f] + ww[r + 1][f] * gg1[1][f];
                     e2 += ww[r + 2][f] * gg2[0][f];
                 }
-                fa[r][0] = ok ? e0 : 0.0;
-                fa[r][1] = (ok && m + 1 < N) ? e1 : 0.0;
-                fa[r][2] = (ok && m + 2 < N) ? e2 : 0.0;
-                fa[r][3] = (ok && m + 3 < N) ? e3 : 0.0;
+                // band_chol_rows replaces the rows of unknowns that do not exist, and of groups that have stopped, by identity rows
+                // itself; columns N and N + 1 collect weights of the last two stations and are cut here, column m + 3 is P's alone
+                // and zero as stored
+                fa[r][0] = e0;
+                fa[r][1] = in1[r] ? e1 : 0.0;
+                fa[r][2] = in2[r] ? e2 : 0.0;
+                fa[r][3] = e3;
             }
             rd_max = oct_max<GP>(rd_max);
             rp_max = oct_max<GP>(rp_max);
@@ -436,7 +436,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
         if (run && acc_now) {                                 // remember the iterate the fallback exits return (the problem's own
 #pragma unroll                                                // unknowns only: `keep` shares the coefficient slots, whose entries past N stay 0)
             for (int r = 0; r < R; ++r)
-                if ((mmask >> r) & 1u) keep[base + r] = Q.u[base + r];
+                if (mm[r]) keep[base + r] = Q.u[base + r];
         }
         // Nobody left to iterate (the pass in which the last group of the wavefront converges or gives up): leave here.  The rest of
         // the body - factorisation, two solves, the step - would run fully masked: 4.5 us of a 6.6-us pass, once per wavefront
@@ -449,7 +449,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
         bool okf = true;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            frinv[r] = 1.0 / (fa[r][0] + 1.0);
+            frinv[r] = (go && mm[r]) ? 1.0 / (fa[r][0] + 1.0) : 1.0;      // (fa is no longer zeroed outside the problem: cut here)
 #pragma unroll
             for (int d = 0; d < 4; ++d) flow[r][d] = 0.0;
         }
@@ -465,7 +465,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
         // ---- 4: predictor
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            if (go2 && ((tmask >> r) & 1u)) {
+            if (tm[r]) {                                          // (tmp, dua, rhs: scratch nobody reads once a group has stopped)
 #pragma unroll
                 for (int f = 0; f < F; ++f)
                     Q.tmp[(base + r) * F + f] = -(((zu[r][f] * isu[r][f]) * rpu[r][f] - zu[r][f]) - ((zl[r][f] * isl[r][f]) * rpl[r][f] - zl[r][f]));
@@ -475,13 +475,13 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
         double dua[R];
         gather(Q.tmp, dua);
 #pragma unroll
-        for (int r = 0; r < R; ++r) dua[r] = (go2 && ((mmask >> r) & 1u)) ? (-rd_m[r] + dua[r]) : 0.0;
+        for (int r = 0; r < R; ++r) dua[r] = (go2 && mm[r]) ? (-rd_m[r] + dua[r]) : 0.0;
 #ifndef EMP_QP_PROBE_SKIP_SOLVE
         band_solve_rows<R>(fa, frinv, flow, dua, steps);
 #endif
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            if (go2 && ((mmask >> r) & 1u)) Q.dua[base + r] = dua[r];
+            if (mm[r]) Q.dua[base + r] = dua[r];
         __syncthreads();
         // ---- 5: affine step length, centring parameter, corrector coefficients
         double rcu[R][F], rcl[R][F];
@@ -491,7 +491,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
             double ratio = 0.0;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const bool ok = go2 && ((tmask >> r) & 1u);
+                const bool ok = tm[r];                            // (the step lengths of a stopped group are not used)
 #pragma unroll
                 for (int f = 0; f < F; ++f) {
                     dsua[r][f] = -rpu[r][f] - gda[r][f];
@@ -507,20 +507,18 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
             const double a_aff = (ratio > 1.0) ? fast_rcp(ratio) : 1.0;
             double mu_aff = 0.0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (go2 && ((tmask >> r) & 1u)) {
+            for (int r = 0; r < R; ++r) {                         // (a station that does not exist: z = 0, dz = -0, adds +0.0)
 #pragma unroll
-                    for (int f = 0; f < F; ++f)
-                        mu_aff += (su[r][f] + a_aff * dsua[r][f]) * (zu[r][f] + a_aff * dzua[r][f]) +
-                                  (sl[r][f] + a_aff * dsla[r][f]) * (zl[r][f] + a_aff * dzla[r][f]);
-                }
+                for (int f = 0; f < F; ++f)
+                    mu_aff += (su[r][f] + a_aff * dsua[r][f]) * (zu[r][f] + a_aff * dzua[r][f]) +
+                              (sl[r][f] + a_aff * dsla[r][f]) * (zl[r][f] + a_aff * dzla[r][f]);
             }
             mu_aff = oct_sum<GP>(mu_aff) / (double)rows;
             double sigma = (mu > 0.0) ? mu_aff * fast_rcp(mu) : 0.0;
             sigma = sigma * sigma * sigma;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const bool ok = go2 && ((tmask >> r) & 1u);
+                const bool ok = tm[r];
 #pragma unroll
                 for (int f = 0; f < F; ++f) {
                     rcu[r][f] = su[r][f] * zu[r][f] + dsua[r][f] * dzua[r][f] - sigma * mu;
@@ -537,13 +535,13 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
         double du[R];
         gather(Q.tmp, du);
 #pragma unroll
-        for (int r = 0; r < R; ++r) du[r] = (go2 && ((mmask >> r) & 1u)) ? (-rd_m[r] + du[r]) : 0.0;
+        for (int r = 0; r < R; ++r) du[r] = (go2 && mm[r]) ? (-rd_m[r] + du[r]) : 0.0;
 #ifndef EMP_QP_PROBE_SKIP_SOLVE
         band_solve_rows<R>(fa, frinv, flow, du, steps);
 #endif
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            if (go2 && ((mmask >> r) & 1u)) Q.rhs[base + r] = du[r];
+            if (mm[r]) Q.rhs[base + r] = du[r];
         __syncthreads();
         // ---- 6: step length and update
         {
@@ -552,7 +550,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
             double ratio = 0.0;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const bool ok = go2 && ((tmask >> r) & 1u);
+                const bool ok = tm[r];
 #pragma unroll
                 for (int f = 0; f < F; ++f) {
                     dsu[r][f] = -rpu[r][f] - gd[r][f];
@@ -571,7 +569,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
             if (go2) {
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    if ((tmask >> r) & 1u) {
+                    if (tm[r]) {
 #pragma unroll
                         for (int f = 0; f < F; ++f) {
                             su[r][f] += alpha * dsu[r][f];
@@ -580,7 +578,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
                             zl[r][f] += alpha * dzl[r][f];
                         }
                     }
-                    if ((mmask >> r) & 1u) Q.u[base + r] = Q.u[base + r] + alpha * du[r];      // (u is re-read, not kept: registers)
+                    if (mm[r]) Q.u[base + r] = Q.u[base + r] + alpha * du[r];      // (u is re-read, not kept: registers)
                 }
                 ++iters;
             }
@@ -590,7 +588,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
     if (restore) {
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            if ((mmask >> r) & 1u) Q.u[base + r] = keep[base + r];
+            if (mm[r]) Q.u[base + r] = keep[base + r];
     }
     __syncthreads();
     Q.iters = iters;
@@ -598,11 +596,21 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
 }
 
 // doubles of LDS one problem of path_qp_group_rows<GP, R> needs: GP R + 4 coefficient slots (n + 2 of them are used) and the
-// solver's arrays at capacity GP R
+// solver's arrays at capacity GP R with their guards (PathQpRowsLayout, emp_qp_core.h)
 // (round 5: the last acceptable iterate lives in the coefficient slots 3 .. GP R + 2, which hold nothing between the set-up - it
 // reads the three fixed start coefficients only - and the read-out that fills them from the final iterate: GP R doubles less)
 template <int GP, int R>
-__host__ __device__ constexpr int path_qp_words_rows() { return (GP * R + 4) + PathRangeQp::words_fast(GP * R, GP * R); }
+__host__ __device__ constexpr int path_qp_words_rows() { return PathQpRowsLayout<GP, R>::words; }
+
+// The padding of a group's arrays (PathQpRowsLayout): the guards, and every entry from the problem's N unknowns / ns stations up
+// to the capacity, hold what the solver's windows must read outside the problem.  A group without a problem to solve (N = ns = 0
+// here) gets all of it: whatever its lanes then compute stays finite and inside the group.
+template <int GP, int R>
+__device__ __forceinline__ void path_qp_pad_rows(double* lds, int N, int ns, int gl) {
+    PathQpRowsLayout<GP, R>::pad_ranges(N, ns, [&](int first, int last, double v) {
+        for (int i = first + gl; i < last; i += GP) lds[i] = v;
+    });
+}
 
 // ---------------------------------------------------------------------------------------------
 // Path QP on one group of GP lanes (64 / GP scenes per wavefront); n <= GP R + 2 stations (GP = 8: R = 3: 26, R = 4: 34;
@@ -613,13 +621,24 @@ template <int GP, int R>
 __device__ inline int path_qp_group_rows(double* lds, const double* l_min, const double* l_max, int n, double l0, double dl0,
                                          double ddl0, const PathQpParams& prm, double* out_l, int* iters_out, bool live,
                                          int debug_stage = 0) {
-    constexpr int kCc = GP * R + 4;
+    using L = PathQpRowsLayout<GP, R>;
     const int gl = (threadIdx.x & 63) & (GP - 1);
     *iters_out = 0;
     PathRangeQp Q;
-    double* cc = lds;
+    double* cc = lds + L::cc;
     const int nn = live ? n : 4;
-    Q.bind_fast(lds + kCc, GP * R, GP * R, nn - 4 > 0 ? nn - 4 : 0, nn - 2 > 0 ? nn - 2 : 0);
+    Q.N = nn - 4 > 0 ? nn - 4 : 0;
+    Q.ns = nn - 2 > 0 ? nn - 2 : 0;
+    Q.P = lds + L::P;
+    Q.q = lds + L::q;
+    Q.u = lds + L::u;
+    Q.dua = lds + L::dua;
+    Q.rhs = lds + L::rhs;
+    Q.c = lds + L::c;
+    Q.lo = lds + L::lo;
+    Q.hi = lds + L::hi;
+    Q.tmp = lds + L::tmp;
+    Q.wgt = lds + L::wgt;
     int rc = path_qp_setup_group<GP>(Q, cc, l_min, l_max, n, l0, dl0, ddl0, prm, gl, live);
     if (!live) rc = 2;
     if (EMP_DEV_HOOKS && debug_stage == 2) rc = 2;          // development timing: stop behind the set-up (tools/qp_phase_probe.py)
@@ -650,8 +669,10 @@ __device__ inline int path_qp_group_rows(double* lds, const double* l_min, const
         if (ok && !okc) rc = 2;
     }
     if (EMP_DEV_HOOKS && debug_stage == 3) rc = 2;          // ... behind the start point
-    __syncthreads();
     ok = rc == 0;
+    // the arrays that lived in the solver's storage until the set-up had read them are dead now: write the padding
+    path_qp_pad_rows<GP, R>(lds, ok ? Q.N : 0, ok ? Q.ns : 0, gl);        // (N = 0: the constant forms are checked below)
+    __syncthreads();
     const int cap_it = debug_stage >= 10 ? debug_stage - 10 : 1000;
     const int rs = path_qp_solve_rows<GP, R>(Q, gl, ok && Q.N > 0, cap_it, cc + 3);
     if (ok && Q.N > 0) {

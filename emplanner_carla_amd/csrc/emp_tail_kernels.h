@@ -626,7 +626,7 @@ __host__ __device__ constexpr int cycle_qp_group_words(int cap, int max_obs) {
     // every LDS instruction; with a stride that is a multiple of 32 doubles they would all sit on the same banks (468 doubles at
     // R = 3: the station and Hessian arrays at 2-4 times their conflict-free cost, 14.5 % of the kernel's wavefront cycles in
     // SQ_LDS_BANK_CONFLICT, profiles/r06a_sq.csv) - an odd stride walks the groups across the banks.
-    if (R > 0) return (path_qp_words_rows<(R > 0 ? G : 8), (R > 0 ? R : 3)>() + (4 * max_obs <= 4 * G * R ? 0 : 4 * max_obs)) | 1;
+    if (R > 0) return PathQpRowsLayout<(R > 0 ? G : 8), (R > 0 ? R : 3)>::stride(max_obs);
     return 5 * cap + 4 * max_obs + (G == 32 ? path_qp_words_pair() : path_qp_words(cap));
 }
 template <int G, int R = 0>
@@ -656,20 +656,20 @@ __device__ __forceinline__ void cycle_qp_body(int B, int max_pts, int max_obs, i
         // Rows form (round 5): a path-QP wavefront's LDS - eight scenes - is what bounds how many edge-cost blocks of the NEXT
         // batch fit on its CU (measured: +1.2 us per staged step for every KB a QP wavefront holds, profiles/r05_edge/README.md 8).
         // The arrays that are dead once the QP is set up live inside solver arrays that are not written before its first
-        // iteration: sd, ld, lmin, lmax in tmp | wgt (2 capS F + 4 F >= 4 cap: the station abscissae are re-read from device memory
-        // for the midpoints at the end), the QP's result ql - written after the last iteration - in rhs | dua (2 capN >= cap), the
-        // obstacle table in P.  Same values, same arithmetic; 5 cap + 4 max_obs doubles per scene less.
-        constexpr int capN = G * R, capS = G * R, kCc = G * R + 4;
+        // iteration (PathQpRowsLayout, emp_qp_core.h): sd, ld, lmin, lmax from tmp on (the station abscissae are re-read from
+        // device memory for the midpoints at the end), the QP's result ql - written after the last iteration - in dua .. rhs, the
+        // obstacle table in P.  Same values, same arithmetic; 5 cap + 4 max_obs doubles per scene less.  The solver's zero
+        // padding is written behind the set-up, when these are dead (path_qp_group_rows).
+        using L = PathQpRowsLayout<G, R>;
         qmem = lds;
-        double* qbase = qmem + kCc;                       // PathRangeQp::bind_fast(qbase, capN, capS, ...): P q u rhs dua c lo hi tmp wgt
-        ql = qbase + capN * 4 + capN * 2;                 // rhs | dua
-        sd = qbase + capN * 4 + capN * 4 + capS * 2 * 3;  // tmp | wgt | slack: sd, ld, lmin, lmax (4 cap <= 2 capS F + 4 F)
+        ql = qmem + L::result;
+        sd = qmem + L::path;
         ld = sd + cap;
         lmin = ld + cap;
         lmax = lmin + cap;
-        // the obstacle table is dead before the QP is set up: it lives where the Hessian band P will be written (4 capN doubles),
+        // the obstacle table is dead before the QP is set up: it lives where the Hessian band P will be written (4 C doubles),
         // or behind the group's other arrays when the obstacle rows are wider than that
-        otab = 4 * max_obs <= 4 * capN ? qbase : qmem + path_qp_words_rows<G, R>();
+        otab = qmem + (max_obs <= L::C ? L::obstacles : L::words);
     } else {
         ld = sd + cap;                // decimated DP l        [cap]
         lmin = ld + cap;              // [cap]

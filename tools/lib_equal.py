@@ -1,5 +1,5 @@
 """Bit-identity of two builds of the library on whole planning cycles (development aid for changes that must not change a bit:
-storage layouts, launch geometry): python tools/lib_equal.py A.so B.so [cfg2|cfg5] [scenes].  Each library plans the same scenes in
+storage layouts, launch geometry): python tools/lib_equal.py A.so B.so [cfg2|cfg5|stationsNN] [scenes].  Each library plans the same scenes in
 a child process of its own; every output array must be equal bit for bit (padding beyond each scene's length excluded)."""
 import os
 import subprocess
@@ -17,7 +17,14 @@ def child(lib, cfg_name, scenes, out):
     _lib.LIB_PATH = os.path.abspath(lib)
     from emplanner_carla_amd import scenes as S
     from emplanner_carla_amd.api import Planner, dp_params_from_cfg, qp_params, smooth_params
-    cfg = {"cfg2": S.CFG2, "cfg5": S.CFG5, "default": S.CFG_DEFAULT}[cfg_name]
+    extra = {}
+    if cfg_name.startswith("stations"):     # stationsNN: a small lattice whose scenes have NN - 1 or NN path-QP stations, planned with
+        st = int(cfg_name[8:])               # outputs of 2 NN points - the path QP's kernel is chosen by that capacity (27-34: <8, 4>)
+        cfg = S.LatticeConfig(f"stations_{st}x5", row=5, col=st - 1, sample_s=2.0, sample_l=1.0, sampling_res=1, n_obs=6,
+                              n_ref=max(61, st + 10))
+        extra = {"max_pts": 2 * st}
+    else:
+        cfg = {"cfg2": S.CFG2, "cfg5": S.CFG5, "default": S.CFG_DEFAULT}[cfg_name]
     res = {}
     pl = Planner(0)
     for tag, kw in (("bench", dict(start_ahead=S.BENCH_START_AHEAD)), ("tight", dict(per_seed=S.survey_geometry_kwargs))):
@@ -25,7 +32,7 @@ def child(lib, cfg_name, scenes, out):
         B, P = b.ref.shape[:2]
         r = pl.plan_cycle(dp_params_from_cfg(cfg), qp_params(obs_length=cfg.obs_length, obs_width=cfg.obs_width), smooth_params(),
                           ref_line=b.ref, n_ref=np.full(B, P, np.int32), origin_xy=b.origin_xy, start_xy=b.start_xy, start_v=b.start_v,
-                          start_a=b.start_a, obs_xy=b.obs_xy, n_obs=b.n_obs)
+                          start_a=b.start_a, obs_xy=b.obs_xy, n_obs=b.n_obs, **extra)
         for k in OUT:
             a = np.array(getattr(r, k))
             for arr, ln in (("dp_s", "dp_len"), ("dp_l", "dp_len"), ("path_s", "path_len"), ("path_l", "path_len"), ("traj", "traj_len")):
