@@ -769,7 +769,7 @@ __global__ __launch_bounds__(64 * WPB) void dp_sweep_kernel(DpDev P, const doubl
     // Without any backtrack the launch takes 19.0.)
     if constexpr (!BT) {
         if (live && i == 0) {
-            const bool bypass = (n_obs != nullptr) && (n_obs[b] == 0);
+            const bool bypass = (n_obs != nullptr) && (n_obs[b] <= 0);
             term_out[b] = arg;
             if (min_cost_out) min_cost_out[b] = bypass ? INF : best;
             status_out[b] = (!bypass && best > P.w_coll) ? 1 : 0;    // ref :351 (EMP_ST_DP_INFEASIBLE)
@@ -782,7 +782,7 @@ __global__ __launch_bounds__(64 * WPB) void dp_sweep_kernel(DpDev P, const doubl
         return;
     }
     if (live && i == 0) {
-        const bool bypass = (n_obs != nullptr) && (n_obs[b] == 0);
+        const bool bypass = (n_obs != nullptr) && (n_obs[b] <= 0);
         double* out = rows_out + (size_t)b * P.col;
         if (bypass) {                                     // ref :362-363 no obstacles: centre row, DP skipped
             const double centre = (double)(row + 1) / 2.0 - 1.0;
@@ -883,7 +883,7 @@ __global__ __launch_bounds__(256) void dp_sweep_wide_kernel(DpDev P, const doubl
         nxt = t;
     }
     if (threadIdx.x == 0) {
-        const bool bypass = (n_obs != nullptr) && (n_obs[b] == 0);
+        const bool bypass = (n_obs != nullptr) && (n_obs[b] <= 0);
         double* out = rows_out + (size_t)b * P.col;
         if (bypass) {                                     // ref :362-363 no obstacles: centre row, DP skipped
             const double centre = (double)(row + 1) / 2.0 - 1.0;
@@ -1079,7 +1079,7 @@ __global__ __launch_bounds__(256, 4) void dp_fused_kernel(DpDev P, const double*
     }
     __builtin_amdgcn_wave_barrier();
     if (live && i == 0) {
-        const bool bypass = n_obs[b] == 0;
+        const bool bypass = n_obs[b] <= 0;                   // (a negative count is clamped to 0)
         double* out = rows_out + (size_t)b * P.col;
         if (bypass) {                                     // ref :362-363 no obstacles: centre row, DP skipped
             const double centre = (double)(row + 1) / 2.0 - 1.0;
@@ -1138,7 +1138,7 @@ __global__ __launch_bounds__(64) void dp_enrich_wave_kernel(DpDev P, const doubl
             for (int r = 0; r < P.row; ++r) bt[j * P.row + r] = tp[j * 64 + r];
         __syncthreads();
         if (lane == 0) {
-            if (n_obs != nullptr && n_obs[b] == 0) {                                   // ref :362-363
+            if (n_obs != nullptr && n_obs[b] <= 0) {                                   // ref :362-363
                 const double centre = (double)(P.row + 1) / 2.0 - 1.0;
                 for (int j = 0; j < P.col; ++j) lrows[j] = centre;
             } else {

@@ -173,6 +173,13 @@ __global__ __launch_bounds__(64) void frenet_project_wave_kernel(
         lcos[i] = cos(th);
         lsin[i] = sin(th);
     }
+    // An empty line (the reference raises IndexError; the Cartesian tail refuses the scene): every scan below answers node 0,
+    // which nothing has loaded.  It reads as a node at the origin with heading 0, so that the scene's Frenet outputs - and the
+    // DP the cycle runs on them - are the same bits in any batch, not what an earlier kernel left in LDS.
+    if (P == 0 && lane == 0) {
+        lx[0] = ly[0] = lth[0] = lk[0] = sm[0] = lsin[0] = 0.0;
+        lcos[0] = 1.0;
+    }
     __syncthreads();
     // cumulative chord length (ref planning_utils.py:461-466).  The chords are computed one per lane, but the
     // running sum is formed strictly left to right like the reference's loop: the planning-start s inherits its
@@ -888,13 +895,13 @@ __device__ __forceinline__ void cycle_cartesian_body(
     const int st = status[b];
     double* out_rows = traj + (size_t)b * (max_pts + 1) * 4;
     auto body = [&]() -> int {          // returns the number of trajectory points (0 = none); wave-uniform control flow
-    if (st & (kStQpFailed | kStBoundIndex | kStTruncated)) return 0;
     const double* line = ref_line + (size_t)b * max_ref * 4;
     const int P = min(max(n_ref[b], 0), max_ref);       // clamped to the row's capacity
     const int n = path_len[b];
     for (int i = lane; i < P; i += 64) sm[i] = s_map[(size_t)b * max_ref + i];
     __syncthreads();
-    // planning start (ref :31-34)
+    // planning start (ref :31-34).  Checked for a scene the path QP has refused as well: the reference ignores its solver's
+    // status (path_planning.py:211-218) and raises IndexError here all the same
     bool off = false;
     const double bs = begin_sl[2 * b], bl = begin_sl[2 * b + 1];
     const int idx0 = walk_from_zero(sm, P, bs, &off);
@@ -902,6 +909,7 @@ __device__ __forceinline__ void cycle_cartesian_body(
         if (lane == 0) status[b] = st | kStSOutOfRange;
         return 0;
     }
+    if (st & (kStQpFailed | kStBoundIndex | kStTruncated)) return 0;
     if (lane == 0) {
         const Node m0 = node_at(line, idx0);
         const double ds = bs - sm[idx0];
@@ -1013,15 +1021,16 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
     int add = 0;                                 // status bits this kernel adds (scene-uniform)
     bool alive = present && !(st & (kStQpFailed | kStBoundIndex | kStTruncated));
     const double* line = ref_line + bb * max_ref * 4;
-    const int P = alive ? min(max(n_ref[bb], 0), max_ref) : 0;       // clamped to the row's capacity
+    const int P = present ? min(max(n_ref[bb], 0), max_ref) : 0;     // clamped to the row's capacity
     const int n = alive ? path_len[bb] : 0;
     for (int i = sl; i < P; i += SL) sm[i] = s_map[bb * max_ref + i];
     __syncthreads();
-    // planning start (ref :31-34)
+    // planning start (ref :31-34).  Checked for a scene the path QP has refused as well: the reference ignores its solver's
+    // status (path_planning.py:211-218) and raises IndexError here all the same
     bool off = false;
-    const double bs = alive ? begin_sl[2 * bb] : 0.0, bl = alive ? begin_sl[2 * bb + 1] : 0.0;
+    const double bs = present ? begin_sl[2 * bb] : 0.0, bl = alive ? begin_sl[2 * bb + 1] : 0.0;
     const int idx0 = walk_from_zero(sm, P, bs, &off);
-    if (alive && (off || P < 2)) {
+    if (present && (off || P < 2)) {
         add = kStSOutOfRange;
         alive = false;
     }

@@ -135,7 +135,20 @@ def _worst_obstacles(rng, n, horizon):
     return obs_s, side * rng.uniform(5.2, 5.8, n)
 
 
-def make_scene(seed: int, cfg: LatticeConfig = CFG2, origin_index: int = 5, start_ahead: float = 2.0,
+#: node of the reference line the ego sits near, unless a caller says otherwise
+ORIGIN_INDEX = 5
+
+
+def scene_frenet_to_xy(seed: int, cfg: LatticeConfig, s: float, l: float, origin_index: int = ORIGIN_INDEX,
+                       radius_range=GENTLE_ARCS) -> np.ndarray:
+    """x, y of the point ``s`` metres ahead of scene ``seed``'s ego along its reference arc and ``l`` metres to its left:
+    the mapping ``make_scene`` applies to its own obstacles (``sl_obs_s``, ``sl_obs_l`` -> ``obs_xy``, bit for bit;
+    tests/test_cycle_ragged_host.py holds the two together).  The arc is the first draw of the scene's generator."""
+    _, arc = _arc(np.random.default_rng(seed), cfg.n_ref, cfg.ref_ds, radius_range)
+    return _arc_point(arc, origin_index * cfg.ref_ds + s, l)[0]
+
+
+def make_scene(seed: int, cfg: LatticeConfig = CFG2, origin_index: int = ORIGIN_INDEX, start_ahead: float = 2.0,
                blocked_fraction: float = 0.1, dist: str = "corridor", radius_range=GENTLE_ARCS) -> Scene:
     """Scene ``seed``.  ``radius_range``: the arc radius is drawn from U(radius_range) (first draw of the scene's
     generator, so the default leaves every existing scene bit-identical); ``SURVEY_ARCS`` is SURVEY.md 8(d)'s range.

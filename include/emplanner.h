@@ -497,7 +497,18 @@ int emp_frenet_path_to_xy(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_
  *   dp_rows [B][col]; dp_s, dp_l [B][max_pts], dp_len [B]      (DP_algorithm's return)
  *   path_s, path_l [B][max_pts], path_len [B]                   (what test_9.py:220 sends back)
  *   traj [B][max_pts+1][4] x,y,theta,kappa, traj_len [B]        (the controller's input)
- *   status [B] bit mask                                                                       */
+ *   status [B] bit mask
+ * The counts are per scene: slots at or beyond n_ref[b], n_obs[b] and n_global[b] are never read, whatever they hold (NaN
+ * included), and a scene's outputs are the same bits in any batch, beside any neighbours and alone.  A count outside
+ * [0, capacity] is clamped (Conventions): n_obs[b] < 0 takes the no-obstacle bypass like 0.  A line of fewer than two nodes, or
+ * one that ends before the planning start, is refused with EMP_ST_S_OUT_OF_RANGE (the reference raises IndexError) - also
+ * when the path QP has refused the scene already; the DP of an empty line runs on a start state of zeros.
+ * A refused scene ((status & ~EMP_ST_DP_INFEASIBLE) != 0) has traj_len 0 and an all-zero traj row; dp_rows, dp_s, dp_l and dp_len
+ * are the DP's as for any scene; path_len is 0 (path_s, path_l all zero) when the bounds, the path QP or a capacity refused it
+ * (EMP_ST_BOUND_INDEX, EMP_ST_QP_FAILED, EMP_ST_TRUNCATED) and the path QP's result otherwise.  path_s, path_l and traj read
+ * as 0 beyond their lengths.  A trajectory of two points is the planning start twice (the line ends before the path's
+ * second station): its x, y are specified, its heading and curvature are not (the reference takes them from the rounding
+ * error between the two points).                                                                */
 typedef struct emp_cycle_io {
     /* inputs */
     const double* ref_line; const int32_t* n_ref;
