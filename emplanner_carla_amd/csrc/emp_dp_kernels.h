@@ -435,6 +435,9 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
     double* f_tab = f_all + (size_t)wave * cpw * P.S;
     const float inv_waves = 1.0f / (float)waves;
     int head[2] = {0, 0}, cnt[2] = {0, 0};                   // wave-uniform ring state
+    // masks of at most 16 bits (cfg2, cfg5): a lane's two reach masks travel as one word (the per-k block below)
+    const bool packed = kMaskBits == 32 && mask_bytes <= 2;
+    constexpr bool kAhead = TILED && kMaskBits == 32;         // the exchange of source row k + 1 is in flight during k
 
     auto store_edge = [&](int j, int k, int owner, double cost) {
         if (TILED) {
@@ -533,36 +536,52 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
         }
         const double F = jerk_unit_sum(t_smp, s0);                      // the column's jerk factor
         if (live && i == 0) f_tab[((j - j_begin - wave) / waves) * P.S + s] = F;
+        // The per-k block (round 9).  Lane first_lane + k's masks come through ds_bpermute: ONE word a k where the call's masks
+        // fit 16 bits (`packed`, wave-uniform: A in the low half, B in the high half, packed once per column), and that word's
+        // exchange for k + 1 is issued before the work on k, so its LDS round trip is never waited for.  (kAhead: the tiled
+        // kernels with 32-bit masks; wider masks fetch their other words in place as before, and the 64-bit and the
+        // canonical-layout kernels fetch every word in place - the word in flight is a register they do not have:
+        // profiles/r09_edge/README.md.)  The pair table's three values of the nothing-in-reach cost are read up front as well, in front of the
+        // mask arithmetic; only the store stays under the mask.
+        const unsigned x_own = kMaskBits == 32 && packed ? (unsigned)a_own | ((unsigned)b_own << 16) : (unsigned)a_own;
+        const unsigned code_j = (unsigned)j << 17;                       // scalar: the entry's column field
+        unsigned x_k = 0;
+        if constexpr (kAhead) x_k = (unsigned)__builtin_amdgcn_ds_bpermute(my_first_lane << 2, (int)x_own);    // every lane is active here
         for (int k = 0; k < row; ++k) {
             const int p = k * row + i;
-            const int src = (my_first_lane + k) << 2;                    // every lane of the wavefront is active here
-            MASK a_k, b_k;
+            const double t_base = tab[kF_BASE * rr + p], t_jerk = tab[kF_JERK * rr + p], t_ref = tab[kF_REF * rr + p];
+            const int src = (my_first_lane + k) << 2;
+            if constexpr (!kAhead) x_k = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)x_own);
+            const unsigned u = x_k | x_own;
+            if constexpr (kAhead) x_k = (unsigned)__builtin_amdgcn_ds_bpermute((my_first_lane + min(k + 1, row - 1)) << 2, (int)x_own);   // (the last k: unused)
+            MASK pass;                                                   // 0 on a dead lane (near_s = 0)
             if constexpr (kMaskBits == 32) {
-                a_k = (MASK)__builtin_amdgcn_ds_bpermute(src, (int)a_own);
-                b_k = (MASK)__builtin_amdgcn_ds_bpermute(src, (int)b_own);
+                unsigned v = u >> 16;                                    // packed: near_s has no bit above 15
+                if (!packed) v = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)b_own) | (unsigned)b_own;
+                pass = u & v & near_s;
             } else {
-                a_k = ((MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)(a_own >> 32)) << 32) |
-                      (MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)a_own);
-                b_k = ((MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)(b_own >> 32)) << 32) |
-                      (MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)b_own);
+                const MASK a_k = ((MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)(a_own >> 32)) << 32) | u;
+                const MASK b_k = ((MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)(b_own >> 32)) << 32) |
+                                 (MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)b_own);
+                pass = (a_k | a_own) & (b_k | b_own) & near_s;
             }
-            const MASK pass = (a_k | a_own) & (b_k | b_own) & near_s;    // 0 on a dead lane (near_s = 0)
-            if (live && pass == 0) {
-                const double smooth = tab[kF_BASE * rr + p] + tab[kF_JERK * rr + p] * F;
-                store_edge(j, k, lane, (smooth + 0.0) + tab[kF_REF * rr + p]);
-            }
-            const bool one = pass != 0 && (pass & (pass - 1)) == 0;
-            const bool many = pass != 0 && !one;
-            const unsigned long long b1 = __ballot(one), b2 = __ballot(many);
-            if (b1 | b2) {
-                const unsigned long long mine = one ? b1 : b2;
-                const int c = one ? 0 : 1;
-                const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(mine >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mine, 0));
+            if (live && pass == 0) store_edge(j, k, lane, ((t_base + t_jerk * F) + 0.0) + t_ref);
+            // one obstacle in reach: pass & (pass - 1) == 0.  The lanes with several are a ballot of their own, the lanes with
+            // one are the rest of the lanes with any - scalar.
+            const MASK more = pass & (pass - 1);
+            const unsigned long long b_any = __ballot(pass != 0), b2 = __ballot(more != 0), b1 = b_any & ~b2;
+            if (b_any) {
+                const int before1 = __builtin_amdgcn_mbcnt_hi((unsigned)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b1, 0));
+                const int before2 = __builtin_amdgcn_mbcnt_hi((unsigned)(b2 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b2, 0));
+                const unsigned code_jk = code_j | ((unsigned)k << 12);   // scalar
                 if (pass != 0) {
-                    const int slot = ((one ? head[0] + cnt[0] : head[1] + cnt[1]) + before) & (kRingSlots - 1);
+                    const bool many = more != 0;
+                    const int slot = (many ? head[1] + cnt[1] + before2 : head[0] + cnt[0] + before1) & (kRingSlots - 1);
                     const int m1 = (kMaskBits == 32 ? __ffs((int)pass) : __ffsll((long long)pass)) - 1;
-                    r_code[c * kRingSlots + slot] = ((unsigned)j << 17) | ((unsigned)k << 12) | ((unsigned)(one ? m1 : 0) << 6) | (unsigned)lane;
-                    if (!one) put_mask(slot, pass);
+                    // ring 1's code words follow ring 0's: bit 7 of the index is the ring.  (A several-obstacle entry carries its
+                    // first obstacle in the m field too: round(1) reads the mask, not the field.)
+                    r_code[slot | (many ? kRingSlots : 0)] = code_jk | ((unsigned)m1 << 6) | (unsigned)lane;
+                    if (many) put_mask(slot, pass);
                 }
                 cnt[0] += __popcll(b1);
                 cnt[1] += __popcll(b2);
