@@ -42,9 +42,23 @@ EMP_HD int match_scan(const double* line, int n_ref, double x, double y, int fir
 // 0.45 mm off, to one - whose tie is decided by the last bit of cos / sin instead.
 EMP_HD double dot2(double a0, double a1, double b0, double b1) { return __builtin_fma(a1, b1, a0 * b0); }
 
+// sin and cos of one angle.  The device compiler does not share the argument reduction between a sin(x) and a cos(x) of the
+// same x (two reductions, 302 vector instructions); sincos(x) does (one, 155), and returns the same bits as the two calls
+// (tools/sincos_bits_test.hip: 2^30 operands over every exponent, 0 differing).  Host builds keep the separate calls: the host
+// checks under tests/host_check compare against values computed that way.
+EMP_HD void sincos_pair(double x, double* s, double* c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    sincos(x, s, c);
+#else
+    *s = sin(x);
+    *c = cos(x);
+#endif
+}
+
 // ref: planning_utils.py:414-424 - projection on the tangent line of a matched node
 EMP_HD Node project_on(const Node& m, double x, double y) {
-    const double c = cos(m.theta), s = sin(m.theta);
+    double c, s;
+    sincos_pair(m.theta, &s, &c);
     const double ds = dot2(x - m.x, y - m.y, c, s);
     return Node{m.x + ds * c, m.y + ds * s, m.theta + m.kappa * ds, m.kappa};
 }
@@ -60,12 +74,20 @@ EMP_HD double projection_s_cs(const Node& m, double c, double s, double s_at_m, 
 
 // ref: cal_projection_s_fun, planning_utils.py:439-443
 EMP_HD double projection_s(const Node& m, double s_at_m, double x, double y) {
-    return s_at_m + dot2(x - m.x, y - m.y, cos(m.theta), sin(m.theta));
+    double c, sn;
+    sincos_pair(m.theta, &sn, &c);
+    return s_at_m + dot2(x - m.x, y - m.y, c, sn);
 }
 
 // ref: cal_s_l_fun tail, planning_utils.py:499-507
 EMP_HD double lateral_offset(const Node& proj, double x, double y) {
-    return dot2(x - proj.x, y - proj.y, -sin(proj.theta), cos(proj.theta));
+    double c, s;
+    sincos_pair(proj.theta, &s, &c);
+    return dot2(x - proj.x, y - proj.y, -s, c);
+}
+// the same with cos / sin of the projection's heading supplied (the planning start forms them once for this and frenet_state_cs)
+EMP_HD double lateral_offset_cs(const Node& proj, double c, double s, double x, double y) {
+    return dot2(x - proj.x, y - proj.y, -s, c);
 }
 
 // ref: cal_s_map_fun, planning_utils.py:448-472.  s_map has n_ref entries.
@@ -87,9 +109,10 @@ EMP_HD void s_map_build(const double* line, int n_ref, double ox, double oy, dou
 struct FrenetState {
     double l, l_dot, s_dot, l_ddot, dl_ds, s_ddot, ddl_ds;
 };
-EMP_HD FrenetState frenet_state(const Node& proj, double px, double py, double vx, double vy, double ax, double ay) {
+// (c, s) = cos / sin of proj.theta
+EMP_HD FrenetState frenet_state_cs(const Node& proj, double c, double s, double px, double py, double vx, double vy, double ax,
+                                   double ay) {
     FrenetState o;
-    const double c = cos(proj.theta), s = sin(proj.theta);
     const double k = proj.kappa;
     o.l = dot2(px - proj.x, py - proj.y, -s, c);
     o.l_dot = dot2(vx, vy, -s, c);
@@ -99,6 +122,11 @@ EMP_HD FrenetState frenet_state(const Node& proj, double px, double py, double v
     o.s_ddot = (dot2(ax, ay, c, s) + 2.0 * (o.s_dot * o.s_dot * k * o.dl_ds) + o.s_dot * o.s_dot * 0.0 * o.l) / (1.0 - k * o.l);
     o.ddl_ds = (fabs(o.s_dot) < 1e-6) ? 0.0 : (o.l_ddot - o.dl_ds * o.s_ddot) / (o.s_dot * o.s_dot);
     return o;
+}
+EMP_HD FrenetState frenet_state(const Node& proj, double px, double py, double vx, double vy, double ax, double ay) {
+    double c, s;
+    sincos_pair(proj.theta, &s, &c);
+    return frenet_state_cs(proj, c, s, px, py, vx, vy, ax, ay);
 }
 
 // ref: cal_proj_point, path_planning.py:52-75 - monotone walk; returns false where the reference would
@@ -112,7 +140,9 @@ EMP_HD bool proj_point(const double* line, const double* s_map, int n_ref, doubl
     }
     const Node m = node_at(line, i);
     const double ds = s - s_map[i];
-    *out = Node{m.x + ds * cos(m.theta), m.y + ds * sin(m.theta), m.theta + m.kappa * ds, m.kappa};
+    double c, sn;
+    sincos_pair(m.theta, &sn, &c);
+    *out = Node{m.x + ds * c, m.y + ds * sn, m.theta + m.kappa * ds, m.kappa};
     *idx = i;
     return true;
 }

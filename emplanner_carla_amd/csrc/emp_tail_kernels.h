@@ -170,8 +170,10 @@ __global__ __launch_bounds__(64) void frenet_project_wave_kernel(
         const double th = line[4 * i + 2];
         lth[i] = th;
         lk[i] = line[4 * i + 3];
-        lcos[i] = cos(th);
-        lsin[i] = sin(th);
+        double sn, cs;
+        sincos_pair(th, &sn, &cs);
+        lcos[i] = cs;
+        lsin[i] = sn;
     }
     // An empty line (the reference raises IndexError; the Cartesian tail refuses the scene): every scan below answers node 0,
     // which nothing has loaded.  It reads as a node at the origin with heading 0, so that the scene's Frenet outputs - and the
@@ -215,36 +217,19 @@ __global__ __launch_bounds__(64) void frenet_project_wave_kernel(
         s_map[(size_t)b * max_ref + i] = v;
     }
     __syncthreads();
-    // obstacles (ref test_9.py:122): matches one after the other (each scan is wave-parallel), then one
-    // obstacle per lane for the projection arithmetic; l uses the FIRST obstacle's match (quirk :413)
-    int my_match = 0, first_match = 0;
-    for (int j = 0; j < k; ++j) {
-        if (j >= 64 && (j & 63) == 0 && (j & ~63) + lane < k) {       // the next 64 obstacles (rows of more than 64 slots)
-            obx = obs_xy[((size_t)b * max_obs + (j & ~63) + lane) * 2];
-            oby = obs_xy[((size_t)b * max_obs + (j & ~63) + lane) * 2 + 1];
-        }
-        const double x = __shfl(obx, j & 63, 64), y = __shfl(oby, j & 63, 64);
-        const int mj = match_scan_wave(lx, ly, P, x, y, 50);
-        if (j == 0) first_match = mj;
-        if ((j & 63) == lane) my_match = mj;
-        if ((j & 63) == 63 || j == k - 1) {                 // flush a full set of lanes
-            const int jj = (j & ~63) + lane;
-            if (jj <= j) {
-                obs_s[(size_t)b * obs_cap + jj] = projection_s_cs(node(my_match), lcos[my_match], lsin[my_match], sm[my_match], obx, oby);
-                obs_l[(size_t)b * obs_cap + jj] = lateral_offset(project_on_cs(node(first_match), lcos[first_match], lsin[first_match], obx, oby), obx, oby);
-            }
-        }
-    }
-    // planning start (ref test_9.py:134 and :172-177)
-    const int ms = match_scan_wave(lx, ly, P, px, py, 50);
-    if (lane == 0) {
-        const Node proj = project_on_cs(node(ms), lcos[ms], lsin[ms], px, py);
-        const double bs = projection_s_cs(node(ms), lcos[ms], lsin[ms], sm[ms], px, py);
+    // obstacles (ref test_9.py:122) and the planning start (ref test_9.py:134 and :172-177): matches one after the other (each
+    // scan is wave-parallel, and none depends on another), then one point per lane for the projection arithmetic.  The start is
+    // point k behind the k obstacles: it takes the free lane k & 63 of the last group, so that its trigonometry is the pass the
+    // obstacles run anyway (as lane 0 of a pass of its own it cost the wavefront a second one).  Where k is a multiple of 64 no lane
+    // is free and the start is a group by itself (k == 0: the only one).  An obstacle's l uses the FIRST obstacle's match
+    // (quirk :413); the start uses its own match for s and l.
+    // the start's outputs (one lane): ref test_9.py:134 and :172-177
+    auto planning_start = [&](double bs, double l, const Node& proj, double pc, double psn) {
         if (begin_sl) {
             begin_sl[2 * b] = bs;
-            begin_sl[2 * b + 1] = lateral_offset(proj, px, py);
+            begin_sl[2 * b + 1] = l;
         }
-        const FrenetState fs = frenet_state(proj, px, py, start_v[2 * b], start_v[2 * b + 1], start_a[2 * b], start_a[2 * b + 1]);
+        const FrenetState fs = frenet_state_cs(proj, pc, psn, px, py, start_v[2 * b], start_v[2 * b + 1], start_a[2 * b], start_a[2 * b + 1]);
         start[4 * b + 0] = bs;
         start[4 * b + 1] = fs.l;
         start[4 * b + 2] = fs.dl_ds;
@@ -276,6 +261,38 @@ __global__ __launch_bounds__(64) void frenet_project_wave_kernel(
             }
         }
         if (n_obs_out) n_obs_out[b] = total;
+    };
+    const int ms = match_scan_wave(lx, ly, P, px, py, 50);
+    int my_match = 0, first_match = 0;
+    for (int j = 0; j <= k; ++j) {
+        if (j < k) {
+            if (j >= 64 && (j & 63) == 0 && (j & ~63) + lane < k) {   // the next 64 obstacles (rows of more than 64 slots)
+                obx = obs_xy[((size_t)b * max_obs + (j & ~63) + lane) * 2];
+                oby = obs_xy[((size_t)b * max_obs + (j & ~63) + lane) * 2 + 1];
+            }
+            const double x = __shfl(obx, j & 63, 64), y = __shfl(oby, j & 63, 64);
+            const int mj = match_scan_wave(lx, ly, P, x, y, 50);
+            if (j == 0) first_match = mj;
+            if ((j & 63) == lane) my_match = mj;
+        }
+        if ((j & 63) != 63 && j != k) continue;             // (uniform) flush a full set of lanes, or the last set with the start
+        const int jj = (j & ~63) + lane;
+        const bool is_start = jj == k;
+        if (jj <= j) {
+            const int m_s = is_start ? ms : my_match, m_l = is_start ? ms : first_match;
+            const double x = is_start ? px : obx, y = is_start ? py : oby;
+            const double bs = projection_s_cs(node(m_s), lcos[m_s], lsin[m_s], sm[m_s], x, y);
+            const Node proj = project_on_cs(node(m_l), lcos[m_l], lsin[m_l], x, y);
+            double pc, psn;
+            sincos_pair(proj.theta, &psn, &pc);
+            const double l = lateral_offset_cs(proj, pc, psn, x, y);
+            if (!is_start) {
+                obs_s[(size_t)b * obs_cap + jj] = bs;
+                obs_l[(size_t)b * obs_cap + jj] = l;
+            } else {
+                planning_start(bs, l, proj, pc, psn);
+            }
+        }
     }
 }
 
@@ -581,8 +598,10 @@ __device__ inline int frenet_path_to_xy(const double* line, const double* s_map,
         *s_error = true;
         return 0;
     }
-    target_xy[0] = pr.x + begin_l * (-sin(pr.theta));                             // ref :32-34
-    target_xy[1] = pr.y + begin_l * cos(pr.theta);
+    double pc, psn;
+    sincos_pair(pr.theta, &psn, &pc);
+    target_xy[0] = pr.x + begin_l * (-psn);                                       // ref :32-34
+    target_xy[1] = pr.y + begin_l * pc;
     m = 1;
     for (int i = 0; i < n; ++i) {
         const double s = path_s[i];
@@ -595,8 +614,9 @@ __device__ inline int frenet_path_to_xy(const double* line, const double* s_map,
             *trunc = true;
             break;
         }
-        target_xy[2 * m] = pr.x + path_l[i] * (-sin(pr.theta));                    // ref :44-46
-        target_xy[2 * m + 1] = pr.y + path_l[i] * cos(pr.theta);
+        sincos_pair(pr.theta, &psn, &pc);
+        target_xy[2 * m] = pr.x + path_l[i] * (-psn);                              // ref :44-46
+        target_xy[2 * m + 1] = pr.y + path_l[i] * pc;
         ++m;
     }
     return m;
@@ -914,8 +934,11 @@ __device__ __forceinline__ void cycle_cartesian_body(
         const Node m0 = node_at(line, idx0);
         const double ds = bs - sm[idx0];
         const double th0 = m0.theta + m0.kappa * ds;
-        txy[0] = (m0.x + ds * cos(m0.theta)) + bl * (-sin(th0));
-        txy[1] = (m0.y + ds * sin(m0.theta)) + bl * cos(th0);
+        double mc, msn, pc, psn;
+        sincos_pair(m0.theta, &msn, &mc);
+        sincos_pair(th0, &psn, &pc);
+        txy[0] = (m0.x + ds * mc) + bl * (-psn);
+        txy[1] = (m0.y + ds * msn) + bl * pc;
     }
     // path points: count = leading points with s <= s_map[-1] (ref :40-41), index = running max of walks
     const double s_last = sm[P - 1];
@@ -939,8 +962,11 @@ __device__ __forceinline__ void cycle_cartesian_body(
             const double ds = s - sm[k];
             const double thp = mm.theta + mm.kappa * ds;
             const double l = path_l[(size_t)b * max_pts + i];
-            txy[2 * (i + 1)] = (mm.x + ds * cos(mm.theta)) + l * (-sin(thp));       // ref :44-46
-            txy[2 * (i + 1) + 1] = (mm.y + ds * sin(mm.theta)) + l * cos(thp);
+            double mc, msn, pc, psn;
+            sincos_pair(mm.theta, &msn, &mc);
+            sincos_pair(thp, &psn, &pc);
+            txy[2 * (i + 1)] = (mm.x + ds * mc) + l * (-psn);                        // ref :44-46
+            txy[2 * (i + 1) + 1] = (mm.y + ds * msn) + l * pc;
         }
         if (first_bad) break;
     }
@@ -1034,28 +1060,25 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
         add = kStSOutOfRange;
         alive = false;
     }
-    if (alive && sl == 0) {
-        const Node m0 = node_at(line, idx0);
-        const double ds = bs - sm[idx0];
-        const double th0 = m0.theta + m0.kappa * ds;
-        txy[0] = (m0.x + ds * cos(m0.theta)) + bl * (-sin(th0));
-        txy[1] = (m0.y + ds * sin(m0.theta)) + bl * cos(th0);
-    }
-    // path points: count = leading points with s <= s_map[-1] (ref :40-41), index = running max of walks (:42-43)
+    // trajectory points, one per lane in passes of SL: point q = 0 is the planning start (s = bs, l = bl, node idx0), point
+    // q >= 1 is path point i = q - 1 (the start rides in the first pass: it used to cost a trigonometry pass of its own in front
+    // of this loop).  count = leading path points with s <= s_map[-1] (ref :40-41), index = running max of walks (:42-43) from
+    // idx0 on - the start's lane enters the maximum with 0, i.e. not at all.
     const double s_last = alive ? sm[P - 1] : 0.0;
     int carry = idx0, count = alive ? n : 0;
     bool stop = !alive;
-    int nmax = 0;
+    int qmax = 0;
 #pragma unroll
-    for (int g = 0; g < SPW; ++g) nmax = max(nmax, __builtin_amdgcn_readlane(alive ? n : 0, SL * g));
+    for (int g = 0; g < SPW; ++g) qmax = max(qmax, __builtin_amdgcn_readlane(alive ? n + 1 : 0, SL * g));
     constexpr unsigned long long kSceneMask = (SL == 32) ? 0xffffffffull : 0xffffull;
-    for (int base = 0; base < nmax; base += SL) {
-        const int i = base + sl;
-        const bool in = !stop && i < n;
+    for (int base = 0; base < qmax; base += SL) {
+        const int q = base + sl, i = q - 1;
+        const bool is0 = alive && q == 0;
+        const bool in = !stop && i >= 0 && i < n;
         const double s = in ? path_s[bb * max_pts + i] : 0.0;
         const unsigned bad16 = (unsigned)((__ballot(in && s > s_last) >> (SL * sc)) & kSceneMask);
         const int first_bad = __builtin_ffs((int)bad16);                               // 1-based lane of the scene, 0 if none
-        if (!stop && first_bad) count = min(count, base + first_bad - 1);
+        if (!stop && first_bad) count = min(count, base + first_bad - 2);              // (lane first_bad - 1 holds path point base + first_bad - 2)
         bool o2 = false;
         int k = in ? walk_from_zero(sm, P, fmin(s, s_last), &o2) : 0;
         for (int d = 1; d < SL; d <<= 1) {                 // inclusive running maximum across the scene's lanes
@@ -1064,13 +1087,16 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
         }
         k = max(k, carry);
         carry = __shfl(k, SL - 1, SL);
-        if (in && i < count && i + 1 < cap) {
+        if (is0 || (in && i < count && i + 1 < cap)) {
             const Node mm = node_at(line, k);
-            const double ds = s - sm[k];
+            const double ds = (is0 ? bs : s) - sm[k];
             const double thp = mm.theta + mm.kappa * ds;
-            const double l = path_l[bb * max_pts + i];
-            txy[2 * (i + 1)] = (mm.x + ds * cos(mm.theta)) + l * (-sin(thp));       // ref :44-46
-            txy[2 * (i + 1) + 1] = (mm.y + ds * sin(mm.theta)) + l * cos(thp);
+            const double l = is0 ? bl : path_l[bb * max_pts + i];
+            double mc, msn, pc, psn;
+            sincos_pair(mm.theta, &msn, &mc);
+            sincos_pair(thp, &psn, &pc);
+            txy[2 * q] = (mm.x + ds * mc) + l * (-psn);                              // ref :32-34 and :44-46
+            txy[2 * q + 1] = (mm.y + ds * msn) + l * pc;
         }
         if (first_bad) stop = true;
     }
@@ -1309,15 +1335,19 @@ __global__ void frenet2cartesian_kernel(int B, int max_ref, int max_pts, const d
         }
         const Node m = node_at(line, idx);
         const double ds = v[0] - sm[idx];
-        const double px = m.x + ds * cos(m.theta), py = m.y + ds * sin(m.theta);
+        double mc, msn;
+        sincos_pair(m.theta, &msn, &mc);
+        const double px = m.x + ds * mc, py = m.y + ds * msn;
         const double ph = m.theta + ds * m.kappa, pk = m.kappa;
         if (proj_only) {
             o[0] = px; o[1] = py; o[2] = ph; o[3] = pk;
             continue;
         }
         const double l = v[1], dl = v[2], ddl = v[3];
-        o[0] = px + l * (-sin(ph));
-        o[1] = py + l * cos(ph);
+        double pc, psn;
+        sincos_pair(ph, &psn, &pc);
+        o[0] = px + l * (-psn);
+        o[1] = py + l * pc;
         const double hd = ph + atan(dl / (1.0 - pk * l));                                   // ref :727
         const double dth = hd - ph;
         o[2] = hd;
