@@ -833,6 +833,13 @@ int emp_st_graph(emp_ctx* ctx, int32_t B, int32_t max_obs, const double* obs_s, 
  * here the predecessor is an integer and speed_s / speed_t [B][16] are separate (NaN after the terminal column).
  * cost, s_dot [B][40][16] doubles and node [B][40][16] int32 are the reference's dp_st_cost / dp_st_s_dot /
  * dp_st_node; each may be NULL.  end_node [B][2] = (row, col) of the terminal node, (-1, -1) if every cost is NaN.
+ * A NaN plan_start_s_dot does not get there: column 0 of cost is NaN, and since the sweep keeps a candidate only if it is
+ * < the +inf it starts from (:138-152), every later column stays +inf with s_dot 0 and node 0; the terminal search's <=
+ * then ends on (0, 15) and the profile runs along row 0.  A +-inf start leaves the whole table +inf in the same way.
+ * A slot is absent iff its s_in is NaN, and then its s_out, t_in and t_out are never looked at.  A live slot may hold
+ * anything: its cost is the reference's arithmetic on those values, where a NaN distance (a NaN member, a point segment
+ * with s_in == s_out and t_in == t_out, inf - inf) costs nothing and an infinite s_out / t_out leaves the distance to the
+ * finite end.
  * A negative w_cost_obs is refused (EMP_ERR_ARG): w ** (1.5 - d) (:281) is complex there and the reference fails on its
  * next comparison.  Scenes are independent; the order in which the library runs them (heaviest first) shows in nothing. */
 int emp_speed_dp(emp_ctx* ctx, const emp_speed_dp_params* p, int32_t B, int32_t max_obs, const double* s_in,

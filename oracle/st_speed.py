@@ -206,24 +206,57 @@ def backtrack(node, end_row, end_col):
 # --------------------------------------------------------------------------------------
 # exact (the kernel's arithmetic), vectorised
 # --------------------------------------------------------------------------------------
-def exact_collision_cost(w_cost_obs, d):
+def _two_product_tail(a, b, p):
+    """fma(a, b, -p) for p = fl(a * b): the rounding error of a binary64 product is itself a binary64 number, and Dekker's
+    split product yields it exactly (no overflow / underflow at the magnitudes of an exponent times a logarithm)."""
+    split = 134217729.0                                   # 2 ** 27 + 1 (Veltkamp)
+    ca, cb = split * a, split * b
+    a_hi, b_hi = ca - (ca - a), cb - (cb - b)
+    a_lo, b_lo = a - a_hi, b - b_hi
+    return ((a_hi * b_hi - p) + a_hi * b_lo + a_lo * b_hi) + a_lo * b_lo
+
+
+def kernel_pow(w_cost_obs, y):
+    """w ** y by the kernels' route (csrc/emp_st_core.h make_pow_base / pow_base): log2 w once as a double-double from a
+    ``longdouble`` log2, then exp2(y * lg_hi) with the first-order correction for the product's tail.  A base that is not
+    a positive finite number takes ``np.power`` as the kernels take pow().  Not bit-pinned to the device (exp2 and the
+    final fused multiply-add may round differently in the last place): it exists so that a test can show that none of its
+    comparisons hangs on the last bits of a power (tests/test_speed_front_cases_host.py)."""
+    w = np.float64(w_cost_obs)
+    y = np.asarray(y, dtype=np.float64)
+    if not (w > 0.0 and w < np.inf):
+        with np.errstate(divide="ignore"):
+            return np.power(w, y)
+    L = np.log2(np.longdouble(w))
+    lg_hi = np.float64(L)
+    lg_lo = np.float64(L - np.longdouble(lg_hi))
+    p = y * lg_hi
+    tail = _two_product_tail(y, lg_hi, p) + y * lg_lo
+    r = np.exp2(p)
+    return np.asarray(np.longdouble(r) * np.longdouble(0.6931471805599453 * tail) + np.longdouble(r), dtype=np.float64)
+
+
+def exact_collision_cost(w_cost_obs, d, pow_route=None):
+    """``pow_route``: None = ``np.power`` (the default, what every pinned result uses), "kernel" = ``kernel_pow``."""
+    assert pow_route in (None, "kernel")
     d = np.asarray(d, dtype=np.float64)
     a = np.abs(d)
-    with np.errstate(over="ignore", invalid="ignore"):
-        mid = np.power(np.float64(w_cost_obs), (0.5 - d) + 1.0)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        y = (0.5 - d) + 1.0
+        mid = np.power(np.float64(w_cost_obs), y) if pow_route is None else kernel_pow(w_cost_obs, y)
     return np.where(a < 0.5, np.float64(w_cost_obs), np.where((0.5 < a) & (a < 1.5), mid, 0.0))
 
 
-def exact_obs_cost(s0, t0, s1, t1, s_in, s_out, t_in, t_out, w_cost_obs):
-    """Obstacle cost of edges.  s0..t1 broadcast to a common shape ``E``; the obstacle arrays have shape
-    ``E + (n_obs,)`` or broadcast to it."""
+def exact_pair_costs(s0, t0, s1, t1, s_in, s_out, t_in, t_out, w_cost_obs, pow_route=None):
+    """Cost of every (sample, obstacle) pair of edges: shape ``(5,) + E + (n_obs,)``, 0 for absent slots.  s0..t1 broadcast
+    to a common shape ``E``; the obstacle arrays have shape ``E + (n_obs,)`` or broadcast to it."""
     s0, t0, s1, t1 = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (s0, t0, s1, t1)))
     s_in, s_out, t_in, t_out = (np.asarray(v, dtype=np.float64) for v in (s_in, s_out, t_in, t_out))
     with np.errstate(divide="ignore", invalid="ignore"):
         dt = (t1 - t0) / 4.0
         k = (s1 - s0) / (t1 - t0)
-        total = np.zeros(s0.shape)
         valid = ~np.isnan(s_in)
+        pairs = []
         for m in range(5):
             f = float(m - 1)
             t = (t0 + f * dt)[..., None]
@@ -238,15 +271,23 @@ def exact_obs_cost(s0, t0, s1, t1, s_in, s_out, t_in, t_out, w_cost_obs):
             ends = np.sqrt(np.where(d22 < d11, d22, d11))
             perp = np.abs(v1x * v3y - v1y * v3x) / np.sqrt(v3x * v3x + v3y * v3y)
             outside = ((p > 0) & (q > 0)) | ((p < 0) & (q < 0))
-            c = exact_collision_cost(w_cost_obs, np.where(outside, ends, perp))
-            c = np.where(valid, c, 0.0)
-            for j in range(c.shape[-1]):       # ordered accumulation (m outer, j inner)
-                total = total + c[..., j]
+            c = exact_collision_cost(w_cost_obs, np.where(outside, ends, perp), pow_route)
+            pairs.append(np.where(valid, c, 0.0))
+    return np.stack(pairs)
+
+
+def exact_obs_cost(s0, t0, s1, t1, s_in, s_out, t_in, t_out, w_cost_obs, pow_route=None):
+    """Obstacle cost of edges (shapes as ``exact_pair_costs``)."""
+    pairs = exact_pair_costs(s0, t0, s1, t1, s_in, s_out, t_in, t_out, w_cost_obs, pow_route)
+    total = np.zeros(pairs.shape[1:-1])
+    for c in pairs:
+        for j in range(c.shape[-1]):           # ordered accumulation (m outer, j inner)
+            total = total + c[..., j]
     return total
 
 
 def exact_edge_cost(s0, t0, v0, s1, t1, s_in, s_out, t_in, t_out, reference_speed=50, w_cost_ref_speed=4000,
-                    w_cost_accel=100, w_cost_obs=10000000, with_parts=False):
+                    w_cost_accel=100, w_cost_obs=10000000, with_parts=False, pow_route=None):
     s0, t0, v0, s1, t1 = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (s0, t0, v0, s1, t1)))
     with np.errstate(divide="ignore", invalid="ignore"):
         v = (s1 - s0) / (t1 - t0)
@@ -255,7 +296,7 @@ def exact_edge_cost(s0, t0, v0, s1, t1, s_in, s_out, t_in, t_out, reference_spee
         ref = np.float64(w_cost_ref_speed) * (e * e)
         a2 = a * a
         acc = np.where((4 > a) & (a > -6), np.float64(w_cost_accel) * a2, (100000.0 * np.float64(w_cost_accel)) * a2)
-    obs = exact_obs_cost(s0, t0, s1, t1, s_in, s_out, t_in, t_out, w_cost_obs)
+    obs = exact_obs_cost(s0, t0, s1, t1, s_in, s_out, t_in, t_out, w_cost_obs, pow_route)
     total = (obs + acc) + ref
     return (total, obs) if with_parts else total
 
@@ -282,15 +323,16 @@ def exact_generate_st_graph(obs_s, obs_l, obs_s_dot, obs_l_dot):
 
 
 def exact_speed_dp(s_in, s_out, t_in, t_out, plan_start_s_dot, reference_speed=50, w_cost_ref_speed=4000,
-                   w_cost_accel=100, w_cost_obs=10000000):
+                   w_cost_accel=100, w_cost_obs=10000000, pow_route=None):
     """Batched forward sweep + terminal node + int-cast backtrack.  Obstacle arrays [B, n_obs], start [B].
+    ``pow_route``: see ``exact_collision_cost`` (the default leaves every result as it was).
     Returns dict(cost [B,40,16], s_dot, node (int32), end [B,2], speed_s [B,16], speed_t [B,16])."""
     s_list, t_list = grid()
     s_in, s_out, t_in, t_out = (np.atleast_2d(np.asarray(v, dtype=np.float64)) for v in (s_in, s_out, t_in, t_out))
     v_start = np.atleast_1d(np.asarray(plan_start_s_dot, dtype=np.float64))
     B = s_in.shape[0]
     kw = dict(reference_speed=reference_speed, w_cost_ref_speed=w_cost_ref_speed, w_cost_accel=w_cost_accel,
-              w_cost_obs=w_cost_obs)
+              w_cost_obs=w_cost_obs, pow_route=pow_route)
     s_node = s_list[::-1].copy()                       # s of row r
     cost = np.full((B, N_ROWS, N_COLS), np.inf)
     s_dot = np.zeros((B, N_ROWS, N_COLS))

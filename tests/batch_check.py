@@ -1,5 +1,5 @@
 """Shared machinery of the ragged-batch GPU tests (test_gpu_frenet_batch.py, test_gpu_control_batch.py,
-test_gpu_speed_backend_batch.py, test_gpu_cycle_batch.py): bit comparison, the batch-invariance runs and raw guarded
+test_gpu_speed_backend_batch.py, test_gpu_cycle_batch.py, test_gpu_speed_front_batch.py): bit comparison, the batch-invariance runs and raw guarded
 C-ABI calls.  A plain helper module (no fixtures, no hooks)."""
 import numpy as np
 

@@ -108,14 +108,13 @@ def test_speed_dp_batch_vs_exact_oracle(pl):
     res = pl.speed_dp(_params(), *sets, o[4])
     ex = st_speed.exact_speed_dp(*ex_sets, o[4])
     assert_rel(res.cost, ex["cost"], 1e-12, scale=1.0)
-    same = res.node == ex["node"]
-    # a predecessor may differ only where two candidates tie to within pow()'s last-bit noise
-    assert same.mean() > 0.9999, f"node mismatch fraction {1 - same.mean():.2e}"
-    if same.all():
-        np.testing.assert_array_equal(res.s_dot, ex["s_dot"])
-        np.testing.assert_array_equal(res.end_node, ex["end"])
-        np.testing.assert_array_equal(res.speed_s, ex["speed_s"])
-        np.testing.assert_array_equal(res.speed_t, ex["speed_t"])
+    # no two candidates of these scenes tie to within pow()'s last-bit noise (tests/test_speed_front_cases_host.py):
+    # every predecessor is the oracle's
+    np.testing.assert_array_equal(res.node, ex["node"])
+    np.testing.assert_array_equal(res.s_dot, ex["s_dot"])
+    np.testing.assert_array_equal(res.end_node, ex["end"])
+    np.testing.assert_array_equal(res.speed_s, ex["speed_s"])
+    np.testing.assert_array_equal(res.speed_t, ex["speed_t"])
     # structure: one node per column up to the terminal column, t samples in order
     for b in range(len(o[4])):
         c = int(res.end_node[b, 1])
@@ -195,7 +194,7 @@ def test_speed_dp_edge_cases(pl):
     res = pl.speed_dp(_params(), s_in, s_out, t_in, t_out, v0)
     ex = st_speed.exact_speed_dp(s_in, s_out, t_in, t_out, v0)
     assert_rel(res.cost, ex["cost"], 1e-12, scale=1.0)
-    assert (res.node == ex["node"]).mean() > 0.999
+    np.testing.assert_array_equal(res.node, ex["node"])      # (no near-tie here either, same host test)
     with pytest.raises(Exception):
         pl.speed_dp(_params(), np.zeros((1, 65)), np.zeros((1, 65)), np.zeros((1, 65)), np.zeros((1, 65)), np.zeros(1))
 

@@ -244,6 +244,28 @@ def test_trajectory_edge_cases(pl):
     check_against_chain(pl, r, sl, M, cyc)
 
 
+def test_trajectory_ignores_what_lies_beyond_n_dyn(pl):
+    """dynamic_obstacles pads dyn_obs beyond n_dyn with plausible obstacles; NaN, +inf and -inf there change no bit of any
+    output of the speed half or of the cycle.  24 scenes, ragged counts with 0 and the capacity among them."""
+    cfg = S.CFG2
+    p, q, sp = A.dp_params_from_cfg(cfg), A.qp_params(), A.smooth_params()
+    b = S.make_batch(range(4200, 4224), cfg)
+    cyc = cycle_inputs(b)
+    dyn, n = dynamic_obstacles(b, 9)
+    assert len(n) == 24 and (n == 0).any() and (n == K).any() and ((n > 0) & (n < K)).any()
+    want = pl.plan_cycle(p, q, sp, speed=speed_inputs(cyc, dyn, n, 9), **cyc)
+    assert (want.speed.speed_status == 0).any() and not np.isnan(want.speed.st_segments).all()
+    beyond = np.arange(K)[None, :] >= n[:, None]
+    for fill in (NAN, np.inf, -np.inf):
+        poisoned = dyn.copy()
+        poisoned[beyond] = fill
+        r = pl.plan_cycle(p, q, sp, speed=speed_inputs(cyc, poisoned, n, 9), **cyc)
+        for f in path_fields(r):
+            assert same_bits(getattr(r, f), getattr(want, f)), (fill, f)
+        for f in ("trajectory", "speed_status", "path_index2s", "st_segments", "dp_speed", "speed_profile"):
+            assert same_bits(getattr(r.speed, f), getattr(want.speed, f)), (fill, f)
+
+
 def test_trajectory_refusals(pl):
     cfg = S.CFG2
     p, q, sp = A.dp_params_from_cfg(cfg), A.qp_params(), A.smooth_params()
