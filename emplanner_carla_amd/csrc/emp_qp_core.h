@@ -727,8 +727,12 @@ struct SmoothQpParams {
 EMP_HD void box_qp_forms(BoxRangeQp& Q) {
     Q.off0 = 0;
     Q.g[0][0] = 1.0;
-    Q.eps_p = 1e-10;                                     // box of 0.2 m: same rule as the path QP, tighter scale
-    Q.eps_mu = 1e-13;
+    // Box of 0.2 m: the path QP's rule on a tighter scale.  mu goes down to 1e-16: at 1e-13 a point beside a weakly active bound
+    // stopped 1e-8 m from the minimiser (slack and multiplier both ~ sqrt(mu)), which x, y and the heading do not notice and the
+    // curvature - a second difference over 2 m steps, compared at 1e-9 - does (tests/test_gpu_cycle_long.py: 67 to 130 points).
+    // An iterate that met the "acceptable" band (mu <= 1e-13, the old rule) is still what a late factorization failure returns.
+    Q.eps_p = 1e-11;
+    Q.eps_mu = 1e-16;
     Q.eps_d_rel = 1e-10;
 }
 

@@ -472,10 +472,10 @@ __global__ __launch_bounds__(64) void path_qp_wave_kernel(int B, int max_pts, in
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = blockIdx.x;
     const size_t o = (size_t)b * max_pts;
-    const int n = n_pts[b];
+    const int n = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
     int it = 0;
     int rc = 2;
-    const bool fits = n <= cap && n <= max_pts;
+    const bool fits = n <= cap;                         // (fewer than 4 stations: path_qp_setup_group refuses, EMP_ST_QP_FAILED)
     rc = path_qp_group<64>(lds, l_min + o, l_max + o, n, start_l3[3 * b], start_l3[3 * b + 1], start_l3[3 * b + 2], Q.qp,
                            qp_l + o, qp_dl + o, qp_ddl + o, &it, fits);
     if ((threadIdx.x & 63) == 0) {
@@ -496,10 +496,10 @@ __global__ __launch_bounds__(64) void smooth_wave_kernel(int B, int max_pts, int
                                                          int* __restrict__ iters, int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = blockIdx.x;
-    const int m = n_pts[b];
+    const int m = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
     int it = 0, rc = 2;
     double *px = nullptr, *py = nullptr;
-    if (m <= cap && m <= max_pts) rc = smooth_pair_wave<WIDE>(lds, xy + (size_t)b * max_pts * 2, 2, m, sx, sy, &px, &py, &it);
+    if (m <= cap) rc = smooth_pair_wave<WIDE>(lds, xy + (size_t)b * max_pts * 2, 2, m, sx, sy, &px, &py, &it);
     if (rc == 0) heading_kappa_wave(px, py, m, lds + 2 * BoxRangeQp::words(m, m), out + (size_t)b * max_pts * 4, 4);
     if ((threadIdx.x & 63) == 0) {
         if (iters) iters[b] = it;

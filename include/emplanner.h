@@ -471,13 +471,17 @@ int emp_lmin_lmax(emp_ctx* ctx, int32_t B, int32_t max_pts, int32_t max_obs,
                   emp_mem where);
 
 /* ref: Quadratic_planning (path_planning.py:78-219).  l_min, l_max [B][max_pts], n_pts [B],
- * start_l3 [B][3] = plan_start l, dl, ddl -> qp_l, qp_dl, qp_ddl [B][max_pts]; status EMP_ST_QP_FAILED */
+ * start_l3 [B][3] = plan_start l, dl, ddl -> qp_l, qp_dl, qp_ddl [B][max_pts]; status EMP_ST_QP_FAILED.
+ * n_pts[b] is clamped to [0, max_pts] like every per-scene count; a scene with fewer than 4 stations after the clamp (the pinned
+ * start and end overlap: the reference has no answer) reports EMP_ST_QP_FAILED and nothing is computed for it. */
 int emp_path_qp(emp_ctx* ctx, const emp_qp_params* q, int32_t B, int32_t max_pts,
                 const double* l_min, const double* l_max, const int32_t* n_pts, const double* start_l3,
                 double* qp_l, double* qp_dl, double* qp_ddl, int32_t* iters, int32_t* status, emp_mem where);
 
 /* ref: smooth_reference_line (planning_utils.py:262-361): box-QP smoothing + heading/kappa.
- * xy [B][max_pts][2] -> out [B][max_pts][4] = x, y, theta, kappa */
+ * xy [B][max_pts][2] -> out [B][max_pts][4] = x, y, theta, kappa; status EMP_ST_SMOOTH_FAILED.
+ * n_pts[b] is clamped to [0, max_pts] like every per-scene count; a polyline of fewer than 2 points after the clamp (the
+ * reference raises on it) reports EMP_ST_SMOOTH_FAILED and nothing is computed for it. */
 int emp_smooth_line(emp_ctx* ctx, const emp_smooth_params* sp, int32_t B, int32_t max_pts,
                     const double* xy, const int32_t* n_pts, double* out, int32_t* iters, int32_t* status,
                     emp_mem where);
