@@ -337,6 +337,22 @@ __global__ __launch_bounds__(1024, EMP_EDGE_WAVES) void dp_edge_kernel(DpDev P, 
 // stored by the lane that scanned them, 8 bytes each - the entries of a round are neighbours in (j, k, lane) order, so the
 // stores of a round still fall into two or three 512-byte rows of the tiled tensor.
 // (kRingSlots, the ring's bytes per wavefront and kRingMaxCol: emp_dp_launch.h)
+//
+// Source hits (round 11).  Sample 0 of a neighbour edge k -> i is its source node: t_0 = 0 and the quintic's a0 = l_k for every
+// i.  Whether obstacle m is a hard hit there (d2[0] <= 16) depends on (scene, column, m, k) only, such an obstacle is in reach
+// of every edge that leaves row k, and its scan returns exactly 0.0 + w_coll whatever the other nine samples are.  So each
+// lane forms the hit mask H of its own row as a SOURCE row once per column - d2[0] with the scan's operands and operations,
+// over the obstacles within 4 m along s of a station only - and H_k travels with the reach masks of lane first_lane + k.
+// An edge is then classified by `scan = pass & ~H_k`, what is left to scan:
+//   scan == 0               stored from the dense pass like the nothing-in-reach edges; coll is 0.0 followed by one addition of
+//                           w_hit = 0.0 + w_coll per obstacle in reach, in sequence (not a product: the reference adds);
+//   one bit, and at most    the one-obstacle ring; the hits are two flags in the spare bits of the code's obstacle field, and the
+//   one hit on either side  popping lane adds w_hit below and above its one scan - the reference's order of additions;
+//   everything else         the several-obstacle ring with the whole `pass` mask, scanned as before (a hit's scan stops at
+//                           sample 0 for its lane; the round is as long as its longest entry).
+// Priced on the CPU (tools/edge_source_hit_sim.py), measured in profiles/r11_edge/README.md: 24 % of the benchmark's
+// (edge, obstacle) pairs are source hits, 18 % of the ring entries need no scan at all.  Only the tiled kernels with a
+// compile-time row count and masks of at most 16 bits do this (kSrcHit); the others have no register for the hit mask.
 #ifndef EMP_EDGE_RING_BOUNDS
 #define EMP_EDGE_RING_BOUNDS __launch_bounds__(1024, EMP_EDGE_WAVES)
 #endif
@@ -438,6 +454,16 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
     // masks of at most 16 bits (cfg2, cfg5): a lane's two reach masks travel as one word (the per-k block below)
     const bool packed = kMaskBits == 32 && mask_bytes <= 2;
     constexpr bool kAhead = TILED && kMaskBits == 32;         // the exchange of source row k + 1 is in flight during k
+    // Source hits (round 11, the header above): the dense pass classifies by them where the source row's hit mask has a
+    // place in the exchange - the tiled kernels with a compile-time row count on packed masks (cfg2, cfg5); in its own byte
+    // of the packed word while the masks fit 8 bits (`hit_in_word`), else as a second word fetched ahead.  Everywhere else
+    // (wider masks, 64-bit masks, the canonical layout, ROW = 0) H_k is 0 and every obstacle in reach is scanned as before:
+    // those kernels have no register left for it (profiles/r11_edge/README.md).
+    constexpr bool kSrcHit = kAhead && ROW > 0;
+    const bool hit_in_word = packed && mask_bytes == 1, hit_word = packed && mask_bytes == 2;
+    // what obstacle_scan_dense returns for a hit at sample 0; the sum is a vector instruction, so it goes back to scalar registers
+    const double w_hit_v = 0.0 + P.w_coll;
+    const double w_hit = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(w_hit_v)), __builtin_amdgcn_readfirstlane(__double2loint(w_hit_v)));
 
     auto store_edge = [&](int j, int k, int owner, double cost) {
         if (TILED) {
@@ -464,8 +490,14 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
             double coll = 0.0;
             if (kEdgeNoScan) {
             } else if (c == 0) {                                              // exactly one obstacle in reach
-                const int m = (int)((code >> 6) & 63u);
+                const unsigned mf = (code >> 6) & 63u;
+                // kSrcHit on packed masks: an obstacle index has four bits, bit 4 / bit 5 of the field say that ONE source hit
+                // lies below / above the obstacle in slot order - its w_hit is added there, the reference's order of additions
+                const bool flags = kSrcHit && packed;
+                const int m = (int)(flags ? mf & 15u : mf);
+                if (flags && (mf & 16u)) coll = coll + w_hit;
                 coll = coll + obstacle_scan_dense(s0, t_smp, &tab[p], rr, o_s[m], o_l[m], P.w_coll);
+                if (flags && (mf & 32u)) coll = coll + w_hit;
             } else {
                 for (MASK rest = get_mask(slot); rest; rest &= rest - 1) {                              // ascending m, as the reference
                     const int m = (kMaskBits == 32 ? __ffs((int)rest) : __ffsll((long long)rest)) - 1;
@@ -494,17 +526,22 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
         // lane used to walk all the scene's obstacles itself (round 6: nob LDS reads and 4 nob instructions a column and lane;
         // its 6.5 m margin let through a few obstacles more, whose bands were empty all the same).
         MASK near_s = 0, near_w = 0;                                    // near_w: the union over the wavefront's scenes
+        MASK hit_w = 0;                                                 // kSrcHit: obstacles within 4 m along s of a scene's station, likewise
         const int my_first_lane = sl * row;
         const unsigned long long row_bits = (1ull << row) - 1;
         for (int m0 = 0; m0 < P.max_obs && m0 < kMaskBits; m0 += row) {      // wave-uniform trip count
             const int m = m0 + i;
-            bool in_reach = false;
+            bool in_reach = false, cand = false;
             if (live && m < nob) {
                 const double os = my_obs_s[m], ol = my_obs_l[m];
                 const double dx = fmax(fmax(s0 - os, os - s9), 0.0);
                 const double thr = 36.5 - dx * dx;
                 const double r = sqrt(fmax(thr, 0.0));
                 in_reach = thr > 0.0;
+                if constexpr (kSrcHit) if (packed) {                    // d2[0] <= 16 needs d_lon^2 <= 16: rounding is monotone
+                    const double d_lon = os - (s0 + t_smp[0]);
+                    cand = in_reach && d_lon * d_lon <= kDanger2;
+                }
                 my_band[2 * m] = in_reach ? ol - r : __builtin_inf();
                 my_band[2 * m + 1] = in_reach ? ol + r : -__builtin_inf();
             }
@@ -514,6 +551,12 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
             unsigned long long any = 0;
             for (int f = 0; f < lanes_used; f += row) any |= votes >> f;              // scalar: every scene's verdicts folded
             near_w |= (MASK)((MASK)(any & row_bits) << m0);
+            if constexpr (kSrcHit) if (packed) {                        // (wider masks: H stays 0, no ballot)
+                const unsigned long long hv = __ballot(cand);
+                unsigned long long hany = 0;
+                if (hv) for (int f = 0; f < lanes_used; f += row) hany |= hv >> f;
+                hit_w |= (MASK)((MASK)(hany & row_bits) << m0);
+            }
         }
         if (!live) near_s = 0;
         __builtin_amdgcn_wave_barrier();
@@ -524,17 +567,46 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
         // Every lane builds its own A and B once per column (one pass over the bands, wave-uniform: the obstacles in reach of
         // ANY scene of the wavefront, the others masked by near_s); lane first_lane_of_scene + k holds A_k and B_k.  The same
         // bits as testing every (edge, obstacle) pair - where the source row k walked near_s per lane, nine times a column.
-        MASK a_own = 0, b_own = 0;
+        // Behind it (kSrcHit), over the candidates hit_w alone, the source hits of row i as a SOURCE row: H_i = {m : d2[0] <= 16}
+        // with d2[0] formed as obstacle_scan_dense forms it for an edge that leaves row i (sample 0 of such an edge is the node itself, for every
+        // destination) - the same operands and the same operations in the same order, so the two never disagree.
+        MASK a_own = 0, b_own = 0, h_own = 0;
         {
             const double l_own = tab[kF_LHI * rr + i * row + i];      // fmax(l_i, l_i): the pair table's own value of row i
+            const double l_src = tab[i * row + i];                    // sample 0 of a pair whose source row is i
+            const double s_src = s0 + t_smp[0];
             for (MASK rest = near_w; rest; rest &= rest - 1) {
                 const int m = (kMaskBits == 32 ? __ffs((int)rest) : __ffsll((long long)rest)) - 1;
                 const double b_lo = my_band[2 * m], b_hi = my_band[2 * m + 1];
                 a_own |= (l_own > b_lo) ? (MASK)1 << m : (MASK)0;
                 b_own |= (l_own < b_hi) ? (MASK)1 << m : (MASK)0;
             }
+            if constexpr (kSrcHit) {
+                for (MASK rest = hit_w; rest; rest &= rest - 1) {
+                    const int m = (kMaskBits == 32 ? __ffs((int)rest) : __ffsll((long long)rest)) - 1;
+                    const double d_lon = my_obs_s[m] - s_src, d_lat = my_obs_l[m] - l_src;
+                    h_own |= (d_lon * d_lon + d_lat * d_lat <= kDanger2) ? (MASK)1 << m : (MASK)0;
+                }
+                h_own &= near_s;
+            }
         }
-        const double F = jerk_unit_sum(t_smp, s0);                      // the column's jerk factor
+        // the column's jerk factor.  (kSrcHit: jerk_unit_sum on a local copy of the table's tail whose unit-quintic
+        // coefficients pass through an empty asm, so that their multiples by constants are formed here, once a column, and
+        // not hoisted into eight vector registers that live across the whole kernel; the same operations on the same
+        // values.  The kSrcHit kernels' margin - 95 of the 96 registers of five wavefronts a SIMD, no scratch - DEPENDS on
+        // this: without it they spill 12 bytes.  A compiler that schedules differently may need it elsewhere or not at all:
+        // read the listing's register and scratch figures after a toolchain change, profiles/r11_edge/registers.txt.)
+        double F;
+        if constexpr (kSrcHit) {
+            double tail[kTableTail];
+#pragma unroll
+            for (int n = 0; n < kTableTail; ++n) tail[n] = t_smp[n];
+            asm volatile("" : "+s"(tail[kSamples + kSampleMoments + 0]), "+s"(tail[kSamples + kSampleMoments + 1]),
+                              "+s"(tail[kSamples + kSampleMoments + 2]));
+            F = jerk_unit_sum(tail, s0);
+        } else {
+            F = jerk_unit_sum(t_smp, s0);
+        }
         if (live && i == 0) f_tab[((j - j_begin - wave) / waves) * P.S + s] = F;
         // The per-k block (round 9).  Lane first_lane + k's masks come through ds_bpermute: ONE word a k where the call's masks
         // fit 16 bits (`packed`, wave-uniform: A in the low half, B in the high half, packed once per column), and that word's
@@ -543,17 +615,22 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
         // canonical-layout kernels fetch every word in place - the word in flight is a register they do not have:
         // profiles/r09_edge/README.md.)  The pair table's three values of the nothing-in-reach cost are read up front as well, in front of the
         // mask arithmetic; only the store stays under the mask.
-        const unsigned x_own = kMaskBits == 32 && packed ? (unsigned)a_own | ((unsigned)b_own << 16) : (unsigned)a_own;
+        // (hit_in_word: H in bits 8..15 of the word - near_s has no bit above 7 there, which keeps them out of the edge's mask)
+        const unsigned x_own = kMaskBits == 32 && packed ? (unsigned)a_own | ((unsigned)b_own << 16) | (hit_in_word ? (unsigned)h_own << 8 : 0u)
+                                                         : (unsigned)a_own;
         const unsigned code_j = (unsigned)j << 17;                       // scalar: the entry's column field
-        unsigned x_k = 0;
+        unsigned x_k = 0, hx_k = 0;                                      // hx_k: H_k as a word of its own (hit_word), else 0
         if constexpr (kAhead) x_k = (unsigned)__builtin_amdgcn_ds_bpermute(my_first_lane << 2, (int)x_own);    // every lane is active here
+        if constexpr (kSrcHit) if (hit_word) hx_k = (unsigned)__builtin_amdgcn_ds_bpermute(my_first_lane << 2, (int)(unsigned)h_own);
         for (int k = 0; k < row; ++k) {
             const int p = k * row + i;
             const double t_base = tab[kF_BASE * rr + p], t_jerk = tab[kF_JERK * rr + p], t_ref = tab[kF_REF * rr + p];
             const int src = (my_first_lane + k) << 2;
             if constexpr (!kAhead) x_k = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)x_own);
             const unsigned u = x_k | x_own;
+            const unsigned h_k = hit_in_word ? (x_k >> 8) & 0xffu : hx_k;     // from the fetched word alone, never the lane's own
             if constexpr (kAhead) x_k = (unsigned)__builtin_amdgcn_ds_bpermute((my_first_lane + min(k + 1, row - 1)) << 2, (int)x_own);   // (the last k: unused)
+            if constexpr (kSrcHit) if (hit_word) hx_k = (unsigned)__builtin_amdgcn_ds_bpermute((my_first_lane + min(k + 1, row - 1)) << 2, (int)(unsigned)h_own);
             MASK pass;                                                   // 0 on a dead lane (near_s = 0)
             if constexpr (kMaskBits == 32) {
                 unsigned v = u >> 16;                                    // packed: near_s has no bit above 15
@@ -565,19 +642,40 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
                                  (MASK)(unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)b_own);
                 pass = (a_k | a_own) & (b_k | b_own) & near_s;
             }
-            if (live && pass == 0) store_edge(j, k, lane, ((t_base + t_jerk * F) + 0.0) + t_ref);
+            // What is left to scan.  An edge whose obstacles in reach all hit its source node is stored from here like the
+            // nothing-in-reach edges: each contributes exactly w_hit, added one after the other as the scans would.
+            MASK scan = pass;
+            if constexpr (kSrcHit) {
+                scan = pass & ~(MASK)h_k;
+                if (live && scan == 0) {
+                    double coll = 0.0;
+                    for (int n = __popc((unsigned)pass); n > 0; --n) coll = coll + w_hit;
+                    store_edge(j, k, lane, ((t_base + t_jerk * F) + coll) + t_ref);
+                }
+            } else {
+                if (live && pass == 0) store_edge(j, k, lane, ((t_base + t_jerk * F) + 0.0) + t_ref);
+            }
             // one obstacle in reach: pass & (pass - 1) == 0.  The lanes with several are a ballot of their own, the lanes with
             // one are the rest of the lanes with any - scalar.
-            const MASK more = pass & (pass - 1);
-            const unsigned long long b_any = __ballot(pass != 0), b2 = __ballot(more != 0), b1 = b_any & ~b2;
+            MASK more = scan != 0 ? pass & (pass - 1) : (MASK)0;
+            unsigned m_flags = 0;
+            if constexpr (kSrcHit) {
+                // one obstacle to scan and at most one hit on either side of it: still the one-obstacle ring, the hits as two
+                // flags in the spare bits of the code's obstacle field (packed masks: an obstacle index has four bits)
+                const unsigned hb = pass & ~scan, below = hb & (scan - 1), above = hb ^ below;
+                const bool one = ((scan & (scan - 1)) | (below & (below - 1)) | (above & (above - 1))) == 0;
+                more = (scan != 0 && !one) ? 1u : 0u;
+                m_flags = (below ? 16u : 0u) | (above ? 32u : 0u);
+            }
+            const unsigned long long b_any = __ballot(scan != 0), b2 = __ballot(more != 0), b1 = b_any & ~b2;
             if (b_any) {
                 const int before1 = __builtin_amdgcn_mbcnt_hi((unsigned)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b1, 0));
                 const int before2 = __builtin_amdgcn_mbcnt_hi((unsigned)(b2 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b2, 0));
                 const unsigned code_jk = code_j | ((unsigned)k << 12);   // scalar
-                if (pass != 0) {
+                if (scan != 0) {
                     const bool many = more != 0;
                     const int slot = (many ? head[1] + cnt[1] + before2 : head[0] + cnt[0] + before1) & (kRingSlots - 1);
-                    const int m1 = (kMaskBits == 32 ? __ffs((int)pass) : __ffsll((long long)pass)) - 1;
+                    const int m1 = (int)m_flags | ((kMaskBits == 32 ? __ffs((int)scan) : __ffsll((long long)scan)) - 1);
                     // ring 1's code words follow ring 0's: bit 7 of the index is the ring.  (A several-obstacle entry carries its
                     // first obstacle in the m field too: round(1) reads the mask, not the field.)
                     r_code[slot | (many ? kRingSlots : 0)] = code_jk | ((unsigned)m1 << 6) | (unsigned)lane;
