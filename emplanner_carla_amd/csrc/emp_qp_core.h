@@ -736,21 +736,41 @@ EMP_HD void box_qp_forms(BoxRangeQp& Q) {
     Q.eps_d_rel = 1e-10;
 }
 
+// Entry H[j][j + d] (0 <= j, 0 <= d <= 2) of the smoothing Hessian H = 2 (ws D2'D2 + wl D1'D1 + wr I) of an m-point polyline
+// (ref planning_utils.py:313-344), as a gather: the second-difference rows rr (1, -2, 1 on columns rr .. rr + 2) and the
+// first-difference rows rr (1, -1 on columns rr, rr + 1) that hold both columns, then the reference weight on the diagonal.
+// Zero past column m - 1.  Every set-up of the smoothing QP, on the host and in the kernels, takes its entries from here.
+// Every product is an exact scaling by +-1, +-2 or 4, so a fused multiply-add rounds what the separate multiply and add
+// round: the result is the same bit for bit whichever side of an `fp contract` pragma it is compiled on.  The kernels'
+// set-ups are written under contract(fast) (emp_qp_wave.h), so the device build may fuse here too - one instruction
+// instead of two; the host build does not, and gets the same bits.
+EMP_HD double smooth_hess_entry(int j, int d, int m, const SmoothQpParams& prm) {
+#ifdef __clang__
+#pragma clang fp contract(fast)
+#endif
+    double e = 0.0;
+    if (j + d < m) {
+        for (int rr = (j + d - 2 > 0) ? j + d - 2 : 0; rr <= ((m - 3 < j) ? m - 3 : j); ++rr) {
+            const double a = (j - rr == 1) ? -2.0 : 1.0, b = (j + d - rr == 1) ? -2.0 : 1.0;
+            e += 2.0 * prm.w_smooth * a * b;
+        }
+        for (int rr = (j + d - 1 > 0) ? j + d - 1 : 0; rr <= ((m - 2 < j) ? m - 2 : j); ++rr) {
+            const double a = (j - rr == 0) ? 1.0 : -1.0, b = (j + d - rr == 0) ? 1.0 : -1.0;
+            e += 2.0 * prm.w_length * a * b;
+        }
+        if (d == 0) e += 2.0 * prm.w_ref;
+    }
+    return e;
+}
+
 // Q bound to N = ns = m.  ref[i*stride] = reference coordinate.  u starts at the reference (strictly interior).
+// (The Hessian is summed in the gather order of smooth_hess_entry, as in the kernels.  This set-up used to scatter w_ref first,
+// then the D2 and the D1 rows: for weights that are not exactly representable its entries can differ from that in the last place.)
 EMP_HD int box_qp_setup(BoxRangeQp& Q, const double* ref, int stride, int m, const SmoothQpParams& prm) {
     if (m < 2 || !(prm.thr > 0.0)) return 2;
     box_qp_forms(Q);
-    for (int i = 0; i < m * 3; ++i) Q.P[i] = 0.0;
-    for (int i = 0; i < m; ++i) Q.P[i * 3] += 2.0 * prm.w_ref;                     // H = 2 (ws D2'D2 + wl D1'D1 + wr I)
-    const double d2[3] = {1.0, -2.0, 1.0};
-    for (int r = 0; r + 2 < m; ++r)
-        for (int p = 0; p < 3; ++p)
-            for (int cidx = p; cidx < 3; ++cidx) Q.P[(r + p) * 3 + (cidx - p)] += 2.0 * prm.w_smooth * d2[p] * d2[cidx];
-    const double d1[2] = {1.0, -1.0};
-    for (int r = 0; r + 1 < m; ++r)
-        for (int p = 0; p < 2; ++p)
-            for (int cidx = p; cidx < 2; ++cidx) Q.P[(r + p) * 3 + (cidx - p)] += 2.0 * prm.w_length * d1[p] * d1[cidx];
     for (int i = 0; i < m; ++i) {
+        for (int d = 0; d < 3; ++d) Q.P[i * 3 + d] = smooth_hess_entry(i, d, m, prm);
         const double r = ref[i * stride];
         Q.q[i] = -2.0 * prm.w_ref * r;                                             // ref :346
         Q.c[i] = 0.0;

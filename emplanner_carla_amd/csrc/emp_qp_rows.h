@@ -68,17 +68,169 @@ __device__ __forceinline__ int oct_wave_max(int v) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Banded Cholesky (half bandwidth 3) with R consecutive rows per lane, row j = gl * R + r.
-// a[r][0..3] = A[j][j..j+3] on entry, the factor row U[j][..] on return; rinv[r] = 1 / U[j][j]; low[r][e] = U[j-e][e].
-// A lane-step fetches the left neighbour's last three rows (the entries a row below them can need: six values) and then
-// runs the lane's R rows in order - row r from rows r-1..r-3, its own where they exist, the neighbour's otherwise.  After
-// lane-step k the rows of lanes 0..k are final; `steps` = ceil(N / R) of the largest problem in the wavefront.
+// Banded Cholesky (half bandwidth KD: 2 for the smoothing QP, emp_smooth_rows.h; the path QP's 3 runs unrolled by hand,
+// band_chol_rows3 below) with R >= KD consecutive rows per lane, row j = gl * R + r.
+// a[r][0..KD] = A[j][j..j+KD] on entry, the factor row U[j][..] on return; rinv[r] = 1 / U[j][j]; low[r][e] = U[j-e][e].
+// A lane-step fetches the left neighbour's last KD rows (the entries a row below them can need: entries e..KD of its
+// e-th last row) and then runs the lane's R rows in order - row r from rows r-1..r-KD, its own where they exist, the
+// neighbour's otherwise.  After lane-step k the rows of lanes 0..k are final; `steps` = ceil(N / R) of the largest
+// problem in the wavefront.
 // Entries past column N-1 are written as exact zeros at every step, rows past N-1 are identity rows: what a shift
 // carries over a group's end (into idle lanes, or into the first lane of the next group) is zero, and a failed group
-// is left with the identity factor, as in band_chol_group.
+// is left with the identity factor: the failure rule of band_chol_group (emp_qp_wave.h), of which this is the form
+// with R rows per lane.
+// ---------------------------------------------------------------------------------------------
+// The last KD rows of the left neighbour, as a lane-step needs them: nb[e][d] = v[R-e][d] of lane - 1 (1 <= e <= d <= KD).
+template <int R, int KD>
+__device__ __forceinline__ void rows_fetch_left(const double (&v)[R][KD + 1], double (&nb)[KD + 1][KD + 1]) {
+#pragma unroll
+    for (int e = 1; e <= KD; ++e) {
+#pragma unroll
+        for (int d = e; d <= KD; ++d) nb[e][d] = lane_up1(v[R - e][d]);
+    }
+}
+// Column entries of a band stored by rows, R rows per lane: low[r][e] = v[j-e][e], from the lane's own rows or the left
+// neighbour's last ones; zero where the group has no such row (`first`: the group's lane 0).  What the forward
+// substitution needs of a factor, and what a product with the full symmetric matrix needs of its lower half.
+template <int R, int KD>
+__device__ __forceinline__ void rows_column_entries(const double (&v)[R][KD + 1], double (&low)[R][KD + 1], bool first) {
+    double nb[KD + 1][KD + 1];
+    rows_fetch_left<R, KD>(v, nb);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        low[r][0] = 0.0;
+#pragma unroll
+        for (int e = 1; e <= KD; ++e) low[r][e] = (r >= e) ? v[r - e][e] : (first ? 0.0 : nb[e - r][e]);
+    }
+}
+
+template <int GP, int R, int KD>
+__device__ __forceinline__ bool band_chol_rows(double (&a)[R][KD + 1], double (&rinv)[R], double (&low)[R][KD + 1], int N,
+                                               int gl, bool active, int steps) {
+    static_assert(R >= KD && KD >= 1, "a lane must hold at least KD rows");
+    double A[R][KD + 1];
+    bool rowv[R], inband[R][KD + 1];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int j = gl * R + r;
+        rowv[r] = active && j < N;
+#pragma unroll
+        for (int d = 0; d <= KD; ++d) {
+            A[r][d] = rowv[r] ? a[r][d] : (d == 0 ? 1.0 : 0.0);
+            a[r][d] = A[r][d];
+            inband[r][d] = rowv[r] && j + d < N;
+        }
+        rinv[r] = 1.0;
+    }
+    double diag[R];                                         // the pivots of the last lane-step: read behind `steps > 0` only
+    for (int k = 0; k < steps; ++k) {
+        double nb[KD + 1][KD + 1];
+        rows_fetch_left<R, KD>(a, nb);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            double acc[KD + 1];
+#pragma unroll
+            for (int d = 0; d <= KD; ++d) acc[d] = A[r][d];
+#pragma unroll
+            for (int e = 1; e <= KD; ++e) {
+                // u[d] = U[j-e][d] (d = e..KD): row r - e of this lane, or the neighbour's (e - r)-th last
+                double u[KD + 1];
+#pragma unroll
+                for (int d = e; d <= KD; ++d) u[d] = (r >= e) ? a[r - e][d] : nb[e - r][d];
+#pragma unroll
+                for (int d = 0; d <= KD - e; ++d) acc[d] = __builtin_fma(-u[e], u[e + d], acc[d]);
+            }
+            diag[r] = acc[0];
+            const double rs = fast_rsqrt(acc[0] > 0.0 ? acc[0] : 1.0);
+            // The selects below are what keeps the eight problems of a wavefront apart (round 6 tried without: A holds exact
+            // zeros past column N-1 and every product that meets them is zero by induction - in exact arithmetic.  But a lane
+            // that is not final yet iterates on garbage that squares itself every lane-step and overflows after seven of them,
+            // 0 x NaN is NaN, and the first lane of the NEXT group reads these entries at every step: tools/qp_rows_test.hip).
+            a[r][0] = acc[0] * rs;
+#pragma unroll
+            for (int d = 1; d <= KD; ++d) a[r][d] = inband[r][d] ? acc[d] * rs : 0.0;
+            rinv[r] = rs;
+        }
+    }
+    bool failed = false;
+    if (steps > 0) {                                        // (no lane-step: no row anywhere, the identity rows above stand)
+        bool bad = false;                                   // lane masks, combined without a branch
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            double offd = fabs(a[r][1]);
+#pragma unroll
+            for (int d = 2; d <= KD; ++d) offd += fabs(a[r][d]);
+            bad |= rowv[r] & !((diag[r] > 0.0) & (diag[r] < 1e300) & (offd < 1e300));
+        }
+        failed = oct_any<GP>(bad);
+        if (failed) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                a[r][0] = 1.0;
+#pragma unroll
+                for (int d = 1; d <= KD; ++d) a[r][d] = 0.0;
+                rinv[r] = 1.0;
+            }
+        }
+    }
+    rows_column_entries<R, KD>(a, low, gl == 0);            // for the forward substitution (no row above row 0)
+    return !failed;
+}
+
+// solve U'U x = b with the factor of band_chol_rows; b[r] is overwritten with x.  Rows past N-1 must carry b = 0.
+template <int R, int KD>
+__device__ __forceinline__ void band_solve_rows(const double (&a)[R][KD + 1], const double (&rinv)[R],
+                                                const double (&low)[R][KD + 1], double (&b)[R], int steps) {
+    static_assert(R >= KD && KD >= 1, "a lane must hold at least KD rows");
+    double rhs[R], y[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        rhs[r] = (fabs(b[r]) < 1e300) ? b[r] : 0.0;              // a NaN must not travel into the neighbouring group
+        y[r] = rhs[r] * rinv[r];
+    }
+    for (int k = 0; k < steps; ++k) {                               // U' y = b, lanes 0..k final after lane-step k
+        double p[KD + 1];                                           // the left neighbour's last KD entries
+#pragma unroll
+        for (int e = 1; e <= KD; ++e) p[e] = lane_up1(y[R - e]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            double acc = rhs[r];
+#pragma unroll
+            for (int e = 1; e <= KD; ++e) acc = __builtin_fma(-low[r][e], (r >= e) ? y[r - e] : p[e - r], acc);
+            y[r] = acc * rinv[r];
+        }
+    }
+    double x[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) x[r] = y[r] * rinv[r];
+    for (int k = 0; k < steps; ++k) {                               // U x = y, from the last lane with rows down to lane 0
+        double q[KD + 1];                                           // the right neighbour's first KD entries
+#pragma unroll
+        for (int e = 1; e <= KD; ++e) q[e] = lane_dn1(x[e - 1]);
+#pragma unroll
+        for (int r = R - 1; r >= 0; --r) {
+            double acc = y[r];
+#pragma unroll
+            for (int e = 1; e <= KD; ++e) acc = __builtin_fma(-a[r][e], (r + e < R) ? x[r + e] : q[r + e - R + 1], acc);
+            x[r] = acc * rinv[r];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) b[r] = x[r];
+}
+
+// ---------------------------------------------------------------------------------------------
+// The path QP's own pair: band_chol_rows<GP, R, 3> / band_solve_rows<R, 3> with the e / d loops written out by hand, the same
+// operations in the same order (tools/qp_rows_test.hip runs both against the scalar solver).  It stays because of the
+// compiler's instruction schedule, not for anything in the source: the path-QP kernels hold 300-377 registers, one wavefront
+// a SIMD, and are bound by the latency of the row-after-row chain of the factorisation's lane-step.  The generic form
+// compiles to the same instructions in that loop - equal counts of every opcode, equal registers, three vector instructions
+// fewer in the interior-point loop - in another order, and that order measured 3.6 % slower on <16, 4> (61 stations) and
+// 0.7 % on <8, 3>, outside the run-to-run spread of the parent (profiles/band_solvers/README.md).  The smoothing QP's
+// kernels showed no such difference and use the generic form.
 // ---------------------------------------------------------------------------------------------
 template <int GP, int R>
-__device__ __forceinline__ bool band_chol_rows(double (&a)[R][4], double (&rinv)[R], double (&low)[R][4], int N, int gl,
+__device__ __forceinline__ bool band_chol_rows3(double (&a)[R][4], double (&rinv)[R], double (&low)[R][4], int N, int gl,
                                                bool active, int steps) {
     static_assert(R >= 3, "a lane must hold at least KD = 3 rows");
     double A[R][4];
@@ -95,7 +247,8 @@ __device__ __forceinline__ bool band_chol_rows(double (&a)[R][4], double (&rinv)
         }
         rinv[r] = 1.0;
     }
-    double diag[R];
+    double diag[R];                                         // (not written when steps == 0: no row is valid then, and the &&
+                                                            // of the failure test stops at rowv before it reads a pivot)
     for (int k = 0; k < steps; ++k) {
         // neighbour's rows: n1 = row j0-1 (entries 1..3), n2 = row j0-2 (entries 2..3), n3 = row j0-3 (entry 3)
         const double n1_1 = lane_up1(a[R - 1][1]), n1_2 = lane_up1(a[R - 1][2]), n1_3 = lane_up1(a[R - 1][3]);
@@ -167,9 +320,8 @@ __device__ __forceinline__ bool band_chol_rows(double (&a)[R][4], double (&rinv)
     return !failed;
 }
 
-// solve U'U x = b with the factor of band_chol_rows; b[r] is overwritten with x.  Rows past N-1 must carry b = 0.
 template <int R>
-__device__ __forceinline__ void band_solve_rows(const double (&a)[R][4], const double (&rinv)[R], const double (&low)[R][4],
+__device__ __forceinline__ void band_solve_rows3(const double (&a)[R][4], const double (&rinv)[R], const double (&low)[R][4],
                                                 double (&b)[R], int steps) {
     double rhs[R], y[R];
 #pragma unroll
@@ -454,7 +606,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
             for (int d = 0; d < 4; ++d) flow[r][d] = 0.0;
         }
 #else
-        const bool okf = band_chol_rows<GP, R>(fa, frinv, flow, N, gl, go, steps);
+        const bool okf = band_chol_rows3<GP, R>(fa, frinv, flow, N, gl, go, steps);
 #endif
         EMP_QP_DEBUG_ROWS("R    chol ok %d\n", (int)okf);
         if (go && !okf) {
@@ -477,7 +629,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
 #pragma unroll
         for (int r = 0; r < R; ++r) dua[r] = (go2 && mm[r]) ? (-rd_m[r] + dua[r]) : 0.0;
 #ifndef EMP_QP_PROBE_SKIP_SOLVE
-        band_solve_rows<R>(fa, frinv, flow, dua, steps);
+        band_solve_rows3<R>(fa, frinv, flow, dua, steps);
 #endif
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -537,7 +689,7 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
 #pragma unroll
         for (int r = 0; r < R; ++r) du[r] = (go2 && mm[r]) ? (-rd_m[r] + du[r]) : 0.0;
 #ifndef EMP_QP_PROBE_SKIP_SOLVE
-        band_solve_rows<R>(fa, frinv, flow, du, steps);
+        band_solve_rows3<R>(fa, frinv, flow, du, steps);
 #endif
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -661,8 +813,8 @@ __device__ inline int path_qp_group_rows(double* lds, const double* l_min, const
             const double qr = Q.q[base + r];
             b0[r] = has ? -qr : 0.0;
         }
-        const bool okc = band_chol_rows<GP, R>(fa, frinv, flow, Q.N, gl, act, steps);
-        band_solve_rows<R>(fa, frinv, flow, b0, steps);
+        const bool okc = band_chol_rows3<GP, R>(fa, frinv, flow, Q.N, gl, act, steps);
+        band_solve_rows3<R>(fa, frinv, flow, b0, steps);
 #pragma unroll
         for (int r = 0; r < R; ++r)
             if (act && base + r < Q.N) Q.u[base + r] = b0[r];

@@ -9,7 +9,9 @@
 //   * box_qp_lanes / smooth_pair_lanes - the smoothing QP (G = I): registers only.
 //   * range_qp_solve_wave - any size: arrays in LDS, serial factorisation by lane 0 of the group.
 // The banded Cholesky and the substitutions of the first two tiers are lane-shift sweeps (band_chol_group /
-// band_solve_group); norms and ratio tests are group reductions without LDS traffic (group_reduce).
+// band_solve_group, and band_chol_group_n / band_solve_group_n for two problems in the same lanes: one set of
+// lane-steps, band_chol_lane_step / band_fwd_lane_step / band_bwd_lane_step, written for any half bandwidth);
+// norms and ratio tests are group reductions without LDS traffic (group_reduce).
 // Blocks must consist of exactly one wavefront so that __syncthreads() is a cheap wave-level LDS fence.
 //
 // Different summation order than the scalar solver, so results agree to round-off, not bitwise (QP outputs are
@@ -193,68 +195,110 @@ __device__ __forceinline__ double lane_dn1(double v) {               // lane i <
     return r.d;
 }
 
+// ---- the lane-steps every one-row-per-lane sweep below is made of (KD = half bandwidth, 1..3) ----
+// One lane-step of the left-looking Cholesky sweep: A = this lane's row of the matrix, a = its current factor row.  Row
+// gl - e reaches the lane by e shifts (s[c] = U[gl-e][e+c] after the e-th round); the row is then recomputed from A,
+//     U[j][j+d] = (A[j][j+d] - sum_{e=1..KD-d} U[j-e][e] U[j-e][e+d]) / U[j][j],
+// e ascending for every entry.  diag = the pivot before its root, rinv = 1 / U[j][j].  Entries that are not `inband`
+// (past column N-1) are written as exact zeros: see band_chol_group.
+template <int KD>
+__device__ __forceinline__ void band_chol_lane_step(const double (&A)[KD + 1], const bool (&inband)[KD + 1], double (&a)[KD + 1],
+                                                    double& diag, double& rinv) {
+    static_assert(KD >= 1 && KD <= 3, "the lane sweeps handle half bandwidths 1..3");
+    double s[KD + 1], acc[KD + 1];
+#pragma unroll
+    for (int d = 0; d <= KD; ++d) {
+        s[d] = a[d];
+        acc[d] = A[d];
+    }
+#pragma unroll
+    for (int e = 1; e <= KD; ++e) {
+#pragma unroll
+        for (int c = 0; c <= KD - e; ++c) s[c] = lane_up1(s[c + 1]);
+#pragma unroll
+        for (int c = 0; c <= KD - e; ++c) acc[c] = __builtin_fma(-s[0], s[c], acc[c]);
+    }
+    diag = acc[0];
+    const double r = fast_rsqrt(diag > 0.0 ? diag : 1.0);
+    a[0] = diag * r;
+#pragma unroll
+    for (int d = 1; d <= KD; ++d) a[d] = inband[d] ? acc[d] * r : 0.0;
+    rinv = r;
+}
+// One lane-step of U' y = b: y_j = (b_j - sum_e U[j-e][e] y_{j-e}) / U[j][j] from the neighbours' current values.
+template <int KD>
+__device__ __forceinline__ double band_fwd_lane_step(const double (&low)[KD + 1], double rinv, double rhs, double y) {
+    double acc = rhs;
+#pragma unroll
+    for (int e = 1; e <= KD; ++e) {
+        y = lane_up1(y);
+        acc = __builtin_fma(-low[e], y, acc);
+    }
+    return acc * rinv;
+}
+// One lane-step of U x = y: x_j = (y_j - sum_d U[j][d] x_{j+d}) / U[j][j].
+template <int KD>
+__device__ __forceinline__ double band_bwd_lane_step(const double (&a)[KD + 1], double rinv, double y, double x) {
+    double acc = y;
+#pragma unroll
+    for (int d = 1; d <= KD; ++d) {
+        x = lane_dn1(x);
+        acc = __builtin_fma(-a[d], x, acc);
+    }
+    return acc * rinv;
+}
+// Column entries of a band stored by rows, one row per lane: low[e] = v[gl-e][e] - entry e of the row e lanes up -
+// and zero where the group has no such row (gl < e).  What the forward substitution needs of a factor, and what a
+// product with the full symmetric matrix needs of its lower half.
+template <int KD>
+__device__ __forceinline__ void lane_column_entries(const double (&v)[KD + 1], double (&low)[KD + 1], int gl) {
+    low[0] = 0.0;
+#pragma unroll
+    for (int e = 1; e <= KD; ++e) {
+        double t = v[e];
+#pragma unroll
+        for (int i = 0; i < e; ++i) t = lane_up1(t);
+        low[e] = (gl >= e) ? t : 0.0;
+    }
+}
+
 // Band row in registers: a[0..KD] = A[gl][gl..gl+KD] (entries past column N-1 are 0; lanes gl >= N and groups
 // that are not `active` carry zeros).  On return a[] holds the factor row U[gl][..], rinv = 1/U[gl][gl] and
 // low[e] = U[gl-e][e] (the column entries the forward substitution needs).  ok == false if a pivot of this
 // group was <= 0.
 //
-// Left-looking Cholesky as a lane-parallel sweep: row j of U only needs rows j-1..j-KD,
-//     U[j][j+d] = (A[j][j+d] - sum_{e=1..KD-d} U[j-e][e] U[j-e][e+d]) / U[j][j],
-// so EVERY lane recomputes its row from A and its neighbours' current rows (fetched with lane shifts) at every
-// step; after step k rows 0..k are final.  No broadcasts, no selects on the pivot index, no LDS.  Rows that
-// are not final yet hold garbage (possibly NaN) that is overwritten, never accumulated.  Entries past column
-// N-1 are written as exact zeros at every step: those are the entries a shift carries across the end of a row
-// block (into idle lanes, or with G = 32 into the first rows of the next group), so nothing else needs a mask.
+// Left-looking Cholesky as a lane-parallel sweep: row j of U only needs rows j-1..j-KD, so EVERY lane recomputes
+// its row from A and its neighbours' current rows (band_chol_lane_step) at every step; after step k rows 0..k are
+// final.  No broadcasts, no selects on the pivot index, no LDS.  Rows that are not final yet hold garbage
+// (possibly NaN) that is overwritten, never accumulated.  Entries past column N-1 are written as exact zeros at
+// every step: those are the entries a shift carries across the end of a row block (into idle lanes, or with
+// G = 32 into the first rows of the next group), so nothing else needs a mask.
+//
+// Two families share the lane-steps and differ in what they do with a failed factorisation - on purpose:
+//   band_chol_group / band_solve_group      several problems side by side in one wavefront (G = 32).  A pivot <= 0 or
+//       anything that is not finite (diag or the off-diagonals >= 1e300) fails the GROUP, and the group is left with
+//       the identity factor, rinv = 1: the substitutions' shifts must not carry its garbage into the neighbouring
+//       group, where 0 * NaN would poison a healthy problem.  The solve also zeroes a non-finite right-hand side.
+//   band_chol_group_n / band_solve_group_n  NP problems in the SAME lanes of one wavefront: nothing to leak into.  Only
+//       `diag > 0` is checked, the factor stays as computed, and the lanes of a failed pivot mark rinv = -1 for the
+//       caller (which tests rinv per problem and stops that problem); the solve runs on with
+//       ri = rinv > 0 ? rinv : 1 and takes the right-hand side as it is.
 template <int G, int KD>
 __device__ __forceinline__ bool band_chol_group(double (&a)[KD + 1], double& rinv, double (&low)[KD + 1], int N, int gl,
                                                 bool active) {
-    static_assert(KD >= 1 && KD <= 3, "band_chol_group handles half bandwidths 1..3");
     const bool row = active && gl < N;
     double A[KD + 1];
-#pragma unroll
-    for (int d = 0; d <= KD; ++d) A[d] = row ? a[d] : (d == 0 ? 1.0 : 0.0);     // idle lanes: identity rows
-#pragma unroll
-    for (int d = 0; d <= KD; ++d) a[d] = A[d];
     bool inband[KD + 1];
 #pragma unroll
-    for (int d = 0; d <= KD; ++d) inband[d] = row && gl + d < N;
+    for (int d = 0; d <= KD; ++d) {
+        A[d] = row ? a[d] : (d == 0 ? 1.0 : 0.0);                  // idle lanes: identity rows
+        a[d] = A[d];
+        inband[d] = row && gl + d < N;
+    }
     double diag = A[0];
     rinv = 1.0;
     const int nmax = group_nmax<G>(N);                             // groups of one wavefront may differ in size
-    for (int k = 0; k < nmax; ++k) {
-        // s[e][c] = U[gl-e][e+c] (c = 0..KD-e): row gl-e shifted up by e lanes
-        double s1[KD], s2[KD > 1 ? KD - 1 : 1], s3[1];
-#pragma unroll
-        for (int c = 0; c < KD; ++c) s1[c] = lane_up1(a[1 + c]);
-        if constexpr (KD >= 2) {
-#pragma unroll
-            for (int c = 0; c < KD - 1; ++c) s2[c] = lane_up1(s1[1 + c]);
-        }
-        if constexpr (KD >= 3) s3[0] = lane_up1(s2[1]);
-        const double h1 = s1[0];
-        double acc[KD + 1];
-#pragma unroll
-        for (int d = 0; d <= KD; ++d) acc[d] = A[d];
-#pragma unroll
-        for (int c = 0; c < KD; ++c) acc[c] = __builtin_fma(-h1, s1[c], acc[c]);
-        if constexpr (KD >= 2) {
-            const double h2 = s2[0];
-#pragma unroll
-            for (int c = 0; c < KD - 1; ++c) acc[c] = __builtin_fma(-h2, s2[c], acc[c]);
-        }
-        if constexpr (KD >= 3) {
-            acc[0] = __builtin_fma(-s3[0], s3[0], acc[0]);
-        }
-        diag = acc[0];
-        const double r = fast_rsqrt(diag > 0.0 ? diag : 1.0);
-        a[0] = diag * r;
-#pragma unroll
-        for (int d = 1; d <= KD; ++d) a[d] = inband[d] ? acc[d] * r : 0.0;
-        rinv = r;
-    }
-    // A failed factorisation (pivot <= 0, or anything non-finite) must not leave its garbage in the registers:
-    // with G = 32 the substitutions' shifts would carry a NaN into the neighbouring group, where 0 * NaN poisons a
-    // healthy problem.  The failed group gets the identity factor (the caller stops it anyway).
+    for (int k = 0; k < nmax; ++k) band_chol_lane_step<KD>(A, inband, a, diag, rinv);
     double offd = 0.0;
 #pragma unroll
     for (int d = 1; d <= KD; ++d) offd += fabs(a[d]);
@@ -266,55 +310,24 @@ __device__ __forceinline__ bool band_chol_group(double (&a)[KD + 1], double& rin
         for (int d = 1; d <= KD; ++d) a[d] = 0.0;
         rinv = 1.0;
     }
-    // column entries for the forward substitution: low[e] = U[gl-e][e]
-    low[0] = 0.0;
-    {
-        double t = lane_up1(a[1]);
-        low[1] = (gl >= 1) ? t : 0.0;
-        if constexpr (KD >= 2) {
-            t = lane_up1(lane_up1(a[2]));
-            low[2] = (gl >= 2) ? t : 0.0;
-        }
-        if constexpr (KD >= 3) {
-            t = lane_up1(lane_up1(lane_up1(a[3])));
-            low[3] = (gl >= 3) ? t : 0.0;
-        }
-    }
+    lane_column_entries<KD>(a, low, gl);
     return !failed;
 }
 
 // solve U'U x = b with the factor from band_chol_group; b (one entry per lane) is overwritten with x.
-// Same sweep idea: y_j = (b_j - sum_e U[j-e][e] y_{j-e}) / U[j][j] is recomputed by every lane at every step from
-// its neighbours' current values; after step k entries 0..k are final (backward: N-1..N-1-k).  All operands are
-// finite (band_chol_group replaces a failed factor by the identity, a non-finite right-hand side is zeroed), and
-// shifted-in values from outside the group meet a zero coefficient.
+// Same sweep idea: every lane recomputes its entry at every step from its neighbours' current values; after step k
+// entries 0..k are final (backward: N-1..N-1-k).  All operands are finite (band_chol_group replaces a failed factor
+// by the identity, a non-finite right-hand side is zeroed), and shifted-in values from outside the group meet a
+// zero coefficient.
 template <int G, int KD>
 __device__ __forceinline__ void band_solve_group(const double (&a)[KD + 1], double rinv, const double (&low)[KD + 1],
                                                  double& b, int N, int gl) {
     const int nmax = group_nmax<G>(N);
     const double rhs = (fabs(b) < 1e300) ? b : 0.0;               // a NaN must not travel into the neighbouring group
     double y = rhs * rinv;
-    for (int k = 1; k < nmax; ++k) {                               // U' y = b
-        const double y1 = lane_up1(y);
-        double acc = __builtin_fma(-low[1], y1, rhs);
-        if constexpr (KD >= 2) {
-            const double y2 = lane_up1(y1);
-            acc = __builtin_fma(-low[2], y2, acc);
-            if constexpr (KD >= 3) acc = __builtin_fma(-low[3], lane_up1(y2), acc);
-        }
-        y = acc * rinv;
-    }
+    for (int k = 1; k < nmax; ++k) y = band_fwd_lane_step<KD>(low, rinv, rhs, y);      // U' y = b
     double x = y * rinv;
-    for (int k = 1; k < nmax; ++k) {                               // U x = y
-        const double x1 = lane_dn1(x);
-        double acc = __builtin_fma(-a[1], x1, y);
-        if constexpr (KD >= 2) {
-            const double x2 = lane_dn1(x1);
-            acc = __builtin_fma(-a[2], x2, acc);
-            if constexpr (KD >= 3) acc = __builtin_fma(-a[3], lane_dn1(x2), acc);
-        }
-        x = acc * rinv;
-    }
+    for (int k = 1; k < nmax; ++k) x = band_bwd_lane_step<KD>(a, rinv, y, x);          // U x = y
     b = x;
 }
 
@@ -322,7 +335,6 @@ __device__ __forceinline__ void band_solve_group(const double (&a)[KD + 1], doub
 template <int G, int KD, int NP>
 __device__ __forceinline__ bool band_chol_group_n(double (&a)[NP][KD + 1], double (&rinv)[NP], double (&low)[NP][KD + 1],
                                                   int N, int gl, const bool (&active)[NP]) {
-    static_assert(KD >= 1 && KD <= 3, "band_chol_group_n handles half bandwidths 1..3");
     double A[NP][KD + 1], diag[NP];
     bool row[NP], inband[NP][KD + 1];
 #pragma unroll
@@ -340,32 +352,7 @@ __device__ __forceinline__ bool band_chol_group_n(double (&a)[NP][KD + 1], doubl
     const int nmax = group_nmax<G>(N);
     for (int k = 0; k < nmax; ++k) {
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            double s1[KD], s2[KD > 1 ? KD - 1 : 1], s3[1];
-#pragma unroll
-            for (int c = 0; c < KD; ++c) s1[c] = lane_up1(a[p][1 + c]);
-            if constexpr (KD >= 2) {
-#pragma unroll
-                for (int c = 0; c < KD - 1; ++c) s2[c] = lane_up1(s1[1 + c]);
-            }
-            if constexpr (KD >= 3) s3[0] = lane_up1(s2[1]);
-            double acc[KD + 1];
-#pragma unroll
-            for (int d = 0; d <= KD; ++d) acc[d] = A[p][d];
-#pragma unroll
-            for (int c = 0; c < KD; ++c) acc[c] = __builtin_fma(-s1[0], s1[c], acc[c]);
-            if constexpr (KD >= 2) {
-#pragma unroll
-                for (int c = 0; c < KD - 1; ++c) acc[c] = __builtin_fma(-s2[0], s2[c], acc[c]);
-            }
-            if constexpr (KD >= 3) acc[0] = __builtin_fma(-s3[0], s3[0], acc[0]);
-            diag[p] = acc[0];
-            const double r = fast_rsqrt(diag[p] > 0.0 ? diag[p] : 1.0);
-            a[p][0] = diag[p] * r;
-#pragma unroll
-            for (int d = 1; d <= KD; ++d) a[p][d] = inband[p][d] ? acc[d] * r : 0.0;
-            rinv[p] = r;
-        }
+        for (int p = 0; p < NP; ++p) band_chol_lane_step<KD>(A[p], inband[p], a[p], diag[p], rinv[p]);
     }
     bool bad = false;
 #pragma unroll
@@ -374,17 +361,7 @@ __device__ __forceinline__ bool band_chol_group_n(double (&a)[NP][KD + 1], doubl
             bad = true;
             rinv[p] = -1.0;                              // marks this problem's failed pivot for the caller
         }
-        low[p][0] = 0.0;
-        double t = lane_up1(a[p][1]);
-        low[p][1] = (gl >= 1) ? t : 0.0;
-        if constexpr (KD >= 2) {
-            t = lane_up1(lane_up1(a[p][2]));
-            low[p][2] = (gl >= 2) ? t : 0.0;
-        }
-        if constexpr (KD >= 3) {
-            t = lane_up1(lane_up1(lane_up1(a[p][3])));
-            low[p][3] = (gl >= 3) ? t : 0.0;
-        }
+        lane_column_entries<KD>(a[p], low[p], gl);
     }
     return !group_any<G>(bad);
 }
@@ -402,31 +379,13 @@ __device__ __forceinline__ void band_solve_group_n(const double (&a)[NP][KD + 1]
     }
     for (int k = 1; k < nmax; ++k) {                               // U' y = b
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const double y1 = lane_up1(y[p]);
-            double acc = __builtin_fma(-low[p][1], y1, rhs[p]);
-            if constexpr (KD >= 2) {
-                const double y2 = lane_up1(y1);
-                acc = __builtin_fma(-low[p][2], y2, acc);
-                if constexpr (KD >= 3) acc = __builtin_fma(-low[p][3], lane_up1(y2), acc);
-            }
-            y[p] = acc * ri[p];
-        }
+        for (int p = 0; p < NP; ++p) y[p] = band_fwd_lane_step<KD>(low[p], ri[p], rhs[p], y[p]);
     }
 #pragma unroll
     for (int p = 0; p < NP; ++p) x[p] = y[p] * ri[p];
     for (int k = 1; k < nmax; ++k) {                               // U x = y
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const double x1 = lane_dn1(x[p]);
-            double acc = __builtin_fma(-a[p][1], x1, y[p]);
-            if constexpr (KD >= 2) {
-                const double x2 = lane_dn1(x1);
-                acc = __builtin_fma(-a[p][2], x2, acc);
-                if constexpr (KD >= 3) acc = __builtin_fma(-a[p][3], lane_dn1(x2), acc);
-            }
-            x[p] = acc * ri[p];
-        }
+        for (int p = 0; p < NP; ++p) x[p] = band_bwd_lane_step<KD>(a[p], ri[p], y[p], x[p]);
     }
 #pragma unroll
     for (int p = 0; p < NP; ++p) b[p] = x[p];
@@ -1153,21 +1112,7 @@ __device__ inline int box_qp_setup_group(BoxRangeQp& Q, const double* ref, int s
     if (m < 2 || !(prm.thr > 0.0)) return 2;
     for (int i = gl; i < m; i += 32) {
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            double e = 0.0;
-            if (i + d < m) {
-                for (int r = max(0, i + d - 2); r <= min(m - 3, i); ++r) {       // second-difference rows (ws)
-                    const double a = (i - r == 1) ? -2.0 : 1.0, b = (i + d - r == 1) ? -2.0 : 1.0;
-                    e += 2.0 * prm.w_smooth * a * b;
-                }
-                for (int r = max(0, i + d - 1); r <= min(m - 2, i); ++r) {       // first-difference rows (wl)
-                    const double a = (i - r == 0) ? 1.0 : -1.0, b = (i + d - r == 0) ? 1.0 : -1.0;
-                    e += 2.0 * prm.w_length * a * b;
-                }
-                if (d == 0) e += 2.0 * prm.w_ref;
-            }
-            Q.P[i * 3 + d] = e;
-        }
+        for (int d = 0; d < 3; ++d) Q.P[i * 3 + d] = smooth_hess_entry(i, d, m, prm);
         const double r = ref[i * stride];
         Q.q[i] = -2.0 * prm.w_ref * r;                                             // ref :346
         Q.c[i] = 0.0;
@@ -1205,27 +1150,8 @@ __device__ inline int box_qp_active_set_lanes(double r, int m, const SmoothQpPar
     if (m < 2 || !(prm.thr > 0.0)) return 2;
     double Prow[KD + 1], Plow[KD + 1];
 #pragma unroll
-    for (int d = 0; d <= KD; ++d) {                      // ref planning_utils.py:262-361 cost matrices, as box_qp_lanes
-        double e = 0.0;
-        if (has && gl + d < m) {
-            for (int rr = max(0, gl + d - 2); rr <= min(m - 3, gl); ++rr) {
-                const double a = (gl - rr == 1) ? -2.0 : 1.0, b = (gl + d - rr == 1) ? -2.0 : 1.0;
-                e += 2.0 * prm.w_smooth * a * b;
-            }
-            for (int rr = max(0, gl + d - 1); rr <= min(m - 2, gl); ++rr) {
-                const double a = (gl - rr == 0) ? 1.0 : -1.0, b = (gl + d - rr == 0) ? 1.0 : -1.0;
-                e += 2.0 * prm.w_length * a * b;
-            }
-            if (d == 0) e += 2.0 * prm.w_ref;
-        }
-        Prow[d] = e;
-    }
-    {
-        const double t1 = lane_up1(Prow[1]), t2 = lane_up1(lane_up1(Prow[2]));
-        Plow[0] = 0.0;
-        Plow[1] = (gl >= 1) ? t1 : 0.0;                  // P[gl-1][gl]
-        Plow[2] = (gl >= 2) ? t2 : 0.0;                  // P[gl-2][gl]
-    }
+    for (int d = 0; d <= KD; ++d) Prow[d] = has ? smooth_hess_entry(gl, d, m, prm) : 0.0;      // ref planning_utils.py:313-344
+    lane_column_entries<KD>(Prow, Plow, gl);             // P[gl-1][gl], P[gl-2][gl]
     const double q = has ? -2.0 * prm.w_ref * r : 0.0;   // ref :346
     const double lo = r - prm.thr, hi = r + prm.thr;     // ref :308-311
     const double c = 2.0 * (6.0 * prm.w_smooth + 2.0 * prm.w_length + prm.w_ref);   // the Hessian's interior diagonal
@@ -1285,27 +1211,8 @@ __device__ inline int box_qp_lanes(double r, int m, const SmoothQpParams& prm, d
     const double eps_p = 1e-10, eps_mu = 1e-13, eps_d_rel = 1e-10;   // box_qp_forms
     double Prow[KD + 1], Plow[KD + 1];
 #pragma unroll
-    for (int d = 0; d <= KD; ++d) {                      // ref planning_utils.py:262-361 cost matrices, as box_qp_setup_group
-        double e = 0.0;
-        if (has && gl + d < m) {
-            for (int rr = max(0, gl + d - 2); rr <= min(m - 3, gl); ++rr) {
-                const double a = (gl - rr == 1) ? -2.0 : 1.0, b = (gl + d - rr == 1) ? -2.0 : 1.0;
-                e += 2.0 * prm.w_smooth * a * b;
-            }
-            for (int rr = max(0, gl + d - 1); rr <= min(m - 2, gl); ++rr) {
-                const double a = (gl - rr == 0) ? 1.0 : -1.0, b = (gl + d - rr == 0) ? 1.0 : -1.0;
-                e += 2.0 * prm.w_length * a * b;
-            }
-            if (d == 0) e += 2.0 * prm.w_ref;
-        }
-        Prow[d] = e;
-    }
-    {
-        const double t1 = lane_up1(Prow[1]), t2 = lane_up1(lane_up1(Prow[2]));
-        Plow[0] = 0.0;
-        Plow[1] = (gl >= 1) ? t1 : 0.0;                  // P[gl-1][gl]
-        Plow[2] = (gl >= 2) ? t2 : 0.0;                  // P[gl-2][gl]
-    }
+    for (int d = 0; d <= KD; ++d) Prow[d] = has ? smooth_hess_entry(gl, d, m, prm) : 0.0;      // ref planning_utils.py:313-344
+    lane_column_entries<KD>(Prow, Plow, gl);             // P[gl-1][gl], P[gl-2][gl]
     const double q = has ? -2.0 * prm.w_ref * r : 0.0;   // ref :346
     const double lo = has ? r - prm.thr : -1e300;        // ref :308-311
     const double hi = has ? r + prm.thr : 1e300;
@@ -1408,24 +1315,8 @@ __device__ inline int smooth_pair_lanes(double rx, double ry, int m, const Smoot
     for (int p = 0; p < NP; ++p) {
         const double r = p == 0 ? rx : ry;
 #pragma unroll
-        for (int d = 0; d <= KD; ++d) {                  // ref planning_utils.py:262-361 cost matrices, as box_qp_setup_group
-            double e = 0.0;
-            if (has && gl + d < m) {
-                for (int rr = max(0, gl + d - 2); rr <= min(m - 3, gl); ++rr) {
-                    const double a = (gl - rr == 1) ? -2.0 : 1.0, b = (gl + d - rr == 1) ? -2.0 : 1.0;
-                    e += 2.0 * prm[p].w_smooth * a * b;
-                }
-                for (int rr = max(0, gl + d - 1); rr <= min(m - 2, gl); ++rr) {
-                    const double a = (gl - rr == 0) ? 1.0 : -1.0, b = (gl + d - rr == 0) ? 1.0 : -1.0;
-                    e += 2.0 * prm[p].w_length * a * b;
-                }
-                if (d == 0) e += 2.0 * prm[p].w_ref;
-            }
-            Prow[p][d] = e;
-        }
-        Plow[p][0] = 0.0;
-        Plow[p][1] = lane_up1(Prow[p][1]);               // P[gl-1][gl]; 0 for gl = 0 (lane 0 has no source)
-        Plow[p][2] = lane_up1(lane_up1(Prow[p][2]));
+        for (int d = 0; d <= KD; ++d) Prow[p][d] = has ? smooth_hess_entry(gl, d, m, prm[p]) : 0.0;     // ref planning_utils.py:313-344
+        lane_column_entries<KD>(Prow[p], Plow[p], gl);   // P[gl-1][gl], P[gl-2][gl]
         q[p] = has ? -2.0 * prm[p].w_ref * r : 0.0;      // ref :346
         lo[p] = has ? r - prm[p].thr : -1e300;           // ref :308-311
         hi[p] = has ? r + prm[p].thr : 1e300;
