@@ -110,8 +110,8 @@ __device__ __forceinline__ double grp_reduce(double v, int group_base, Op op) {
 }
 
 // Dense box QP  min 1/2 u'Hu + f'u, -1 <= u <= 1  on one group of NU lanes: lane r holds row r of H (h[]) and f_r.
-// Same interior point as smooth_pair_lanes (emp_qp_wave.h): G = I, so a row IS its unknown.  H may be singular (the
-// feed-forward law's is): M = H + diag(wu + wl) stays positive definite because the barrier weights are.
+// Same interior point as smooth_pair_lanes (emp_qp_wave.h; stopping rule: qp_stop_rule, emp_qp_core.h): G = I, so a row IS its
+// unknown.  H may be singular (the feed-forward law's is): M = H + diag(wu + wl) stays positive definite as the weights are.
 // Returns 0 ok / 2 failed (group-uniform); u_out = this lane's control.
 template <int NU>
 __device__ inline int box_qp_full(const double (&h)[NU], double f_r, int r, int gb, bool live, double* u_out, int* iters_out) {
@@ -135,13 +135,9 @@ __device__ inline int box_qp_full(const double (&h)[NU], double f_r, int r, int 
         const double rp_max = grp_reduce<NU>(fmax(fabs(rpu), fabs(rpl)), gb, [](double a, double b) { return fmax(a, b); });
         const double zmax = grp_reduce<NU>(fmax(zu, zl), gb, [](double a, double b) { return fmax(a, b); });
         const double mu = grp_reduce<NU>(su * zu + sl * zl, gb, [](double a, double b) { return a + b; }) / (double)rows;
-        if (run) {
-            const double dscale = fmax(qscale, zmax);
-            if (rd_max <= eps_d_rel * dscale && rp_max <= eps_p && mu <= eps_mu) state = 0;
-            else if (!(mu == mu) || mu > 1e30 || (iters >= kQpStallIter && rp_max > kQpStallResidual)) state = 2;
-            else if (iters >= kQpMaxIter) state = acceptable ? 0 : 2;
-            if (rd_max <= 100.0 * eps_d_rel * dscale && rp_max <= 10.0 * eps_p && mu <= 1000.0 * eps_mu) acceptable = true;
-        }
+        if (run)
+            state = qp_stop_rule<false, false>(rd_max, rp_max, mu, zmax, qscale, 0.0, iters, kQpMaxIter, eps_d_rel, eps_p, eps_mu,
+                                               acceptable).state;
         const bool go = state == 1;
         // ---- dense Cholesky of M = H + diag(wu + wl): lane r keeps row r; after step k its entry k is L[r][k]
         // (r > k) and lane k's entries j > k are U[k][j] = L[j][k]

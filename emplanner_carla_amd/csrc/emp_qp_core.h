@@ -52,6 +52,41 @@ EMP_HD double qp_step_fraction(double mu) { return EMP_QP_TAU(mu); }
 // iterations is reported as failure instead of iterating until the multipliers overflow.
 constexpr int kQpStallIter = 16;
 constexpr double kQpStallResidual = 1e-3;
+constexpr double kQpInfeasibleZ = 1e5;    // multipliers beyond this many Hessian diagonals with a stalled primal residual: infeasible
+
+// THE stopping rule of the interior-point solvers, applied once an iteration to the residual norms.  state: 1 go on, 0 converged,
+// 2 failed.  `acceptable` is the solver's flag "some iterate met the loose thresholds" (100 eps_d_rel, 10 eps_p, 1000 eps_mu): it
+// decides what the caps - and, in the caller, a factorisation that lost positive definiteness to z / s ~ 1e15 - return.  acc_now:
+// this iterate met them.  Clauses in the order tried: converged (0); mu NaN or beyond 1e30, or the residual rule of kQpStallIter
+// (2); INFEASIBLE_Z: a stalled primal residual with multipliers beyond kQpInfeasibleZ Hessian diagonals (pscale) - an infeasible
+// problem's grow x3..100 an iteration, the feasible benchmark problems' stay below 250, and most of a batch's slowest problems
+// were infeasible ones waiting for iteration 16 (2); kQpMaxIter or iter_cap reached (acceptable ? 0 : 2); ACCEPT_EXIT:
+// complementarity converged with the dual residual inside the acceptable band - at this mu the normal matrix carries weights of
+// 1e15, another iteration adds rounding noise instead of removing it (scene 446: rd 5.6e-6, then 2e-2, 2e+4) (0).
+// Which solver applies what is INHERITED from seven copies of this block that had drifted apart, not chosen; making them equal
+// changes iteration counts and is a change of its own:               INFEASIBLE_Z  ACCEPT_EXIT  iter_cap
+//   1 RangeQp::solve_scalar                                               -             x       (its loop bound)
+//   2 range_qp_solve_wave                  (emp_qp_wave.h)                -             x          x
+//   3 range_qp_solve_wave_fast             (emp_qp_wave.h)                x             x          x
+//   4 path_qp_solve_rows                   (emp_qp_rows.h)                x             x          x     (this text written out there)
+//   5, 6 box_qp_lanes, smooth_pair_lanes   (emp_qp_wave.h)                -             -       kQpMaxIter
+//   7 mpc::box_qp_full                     (emp_mpc_kernels.h)            -             -       kQpMaxIter
+// Products and comparisons only: the result does not depend on the side of an `fp contract` pragma it is compiled on.
+struct QpStop { int state; bool acc_now; };      // acc_now: for a caller that keeps the last acceptable iterate (emp_qp_rows.h)
+template <bool INFEASIBLE_Z, bool ACCEPT_EXIT>
+EMP_HD QpStop qp_stop_rule(double rd_max, double rp_max, double mu, double zmax, double qscale, double pscale, int iters,
+                           int iter_cap, double eps_d_rel, double eps_p, double eps_mu, bool& acceptable) {
+    const double dscale = fmax(qscale, zmax);
+    int state = 1;
+    if (rd_max <= eps_d_rel * dscale && rp_max <= eps_p && mu <= eps_mu) state = 0;
+    else if (!(mu == mu) || mu > 1e30 || (iters >= kQpStallIter && rp_max > kQpStallResidual)) state = 2;
+    else if (INFEASIBLE_Z && rp_max > kQpStallResidual && zmax > kQpInfeasibleZ * pscale) state = 2;
+    else if (iters >= kQpMaxIter || iters >= iter_cap) state = acceptable ? 0 : 2;
+    const bool acc_now = rd_max <= 100.0 * eps_d_rel * dscale && rp_max <= 10.0 * eps_p && mu <= 1000.0 * eps_mu;
+    if (acc_now) acceptable = true;
+    if (ACCEPT_EXIT && state == 1 && acc_now && rp_max <= eps_p && mu <= eps_mu) state = 0;
+    return {state, acc_now};
+}
 
 // ---------------------------------------------------------------------------------------------
 // banded SPD Cholesky: A = U'U, upper band storage a[i*(KD+1)+d] = A[i][i+d]
@@ -236,17 +271,12 @@ struct RangeQp {
                 }
             mu /= (double)rows;
             for (int m = 0; m < N; ++m) rd_max = fmax(rd_max, fabs(rhs[m]));
-            const double dscale = fmax(qscale, zmax);
             EMP_QP_TRACE("it %d rd %.3e rp %.3e mu %.3e\n", iters, rd_max, rp_max, mu);
-            if (rd_max <= eps_d_rel * dscale && rp_max <= eps_p && mu <= eps_mu) return 0;
-            if (rd_max <= 100.0 * eps_d_rel * dscale && rp_max <= 10.0 * eps_p && mu <= 1000.0 * eps_mu) {
-                acceptable = true;
-                // complementarity converged, dual residual inside the acceptable band: further iterations at this mu
-                // only add rounding noise to it (z / s weights of 1e15 and more in the normal matrix)
-                if (rp_max <= eps_p && mu <= eps_mu) return 0;
-            }
-            if (!(mu == mu) || mu > 1e30) return 2;
-            if (iters >= kQpStallIter && rp_max > kQpStallResidual) return 2;
+            // (ACCEPT_EXIT used to be tried before the failure clauses here: they exclude each other - rp_max <= eps_p and mu <= eps_mu
+            // against rp_max > kQpStallResidual or a NaN / huge mu.  The caps never fire inside this loop; its end returns the same.)
+            const int state = qp_stop_rule<false, true>(rd_max, rp_max, mu, zmax, qscale, pscale, iters, kQpMaxIter, eps_d_rel,
+                                                        eps_p, eps_mu, acceptable).state;
+            if (state != 1) return state;
             // ---- M = P + G'WG
             for (int m = 0; m < N * B; ++m) M[m] = P[m];
             for (int t = 0; t < ns; ++t)

@@ -10,8 +10,8 @@
 // stations) and every lane owns R CONSECUTIVE stations and R consecutive unknowns (GP = 8: R = 3 up to 26 stations, R = 4 up
 // to 34; GP = 16, R = 4: up to 66).  The station / unknown phases are the same arithmetic, R times per lane; the sweeps become
 // ceil(N / R) lane-steps in each of which a lane runs its R rows one after the other from its left neighbour's last KD rows
-// (KD <= R), so a sweep costs about what it cost before - for eight problems instead of two.  Same algorithm, stopping rule
-// and failure handling as range_qp_solve_wave_fast (Mehrotra predictor-corrector on the reduced normal equations); sums are
+// (KD <= R), so a sweep costs about what it cost before - for eight problems instead of two.  Same algorithm and failure
+// handling as range_qp_solve_wave_fast, same stopping rule (qp_stop_rule<true, true>, emp_qp_core.h); sums are
 // associated differently, so results agree to round-off (2e-9 on the benchmark batch; QP outputs are compared at 1e-6 and
 // certified against the reference-built KKT system).  Measured: 15.7 M vector instructions per 4096
 // scenes (HISTORY.md section 3.3).
@@ -570,16 +570,15 @@ __device__ int path_qp_solve_rows(PathRangeQp& Q, int gl, bool live, int iter_ca
             zmax = oct_max<GP>(zmax);
             mu = oct_sum<GP>(mu) / (double)rows;
             if (run) {
+                // qp_stop_rule<true, true> (emp_qp_core.h) written out - keep equal: with the call, in any of six shapes of the function,
+                // these kernels take 1-2 more of their 301-377 registers and their loop another schedule (profiles/ipm_step/README.md)
                 const double dscale = fmax(qscale, zmax);
                 if (rd_max <= Q.eps_d_rel * dscale && rp_max <= Q.eps_p && mu <= Q.eps_mu) state = 0;
                 else if (!(mu == mu) || mu > 1e30 || (iters >= kQpStallIter && rp_max > kQpStallResidual)) state = 2;
-                else if (rp_max > kQpStallResidual && zmax > kQpInfeasibleZ * pscale) state = 2;    // see range_qp_solve_wave_fast
+                else if (rp_max > kQpStallResidual && zmax > kQpInfeasibleZ * pscale) state = 2;
                 else if (iters >= kQpMaxIter || iters >= iter_cap) state = acceptable ? 0 : 2;
                 acc_now = rd_max <= 100.0 * Q.eps_d_rel * dscale && rp_max <= 10.0 * Q.eps_p && mu <= 1000.0 * Q.eps_mu;
                 if (acc_now) acceptable = true;
-                // Converged complementarity with the dual residual inside the acceptable band: at this mu the normal
-                // matrix carries weights z / s of 1e15 and more, another iteration adds rounding noise to the residual
-                // instead of removing it (and a few more destroy the iterate) - stop here.
                 if (state == 1 && acc_now && rp_max <= Q.eps_p && mu <= Q.eps_mu) state = 0;
                 if (state == 0 && acceptable && !acc_now) restore = true;      // left through the fallback: last good iterate
                 EMP_QP_DEBUG_ROWS("R it %d rd %.3e rp %.3e mu %.3e zmax %.3e -> state %d acc %d\n", iters, rd_max, rp_max, mu, zmax, state, (int)acceptable);

@@ -2,11 +2,13 @@
 //
 // One problem per GROUP of G lanes (G = 64: one problem per wavefront; G = 32: two problems side by side - two
 // scenes of the path QP, or the x and y smoothing problems of one polyline).  Three tiers, same algorithm
-// (Mehrotra predictor-corrector on the reduced normal equations) and stopping rule as RangeQp::solve_scalar:
+// (Mehrotra predictor-corrector on the reduced normal equations) as RangeQp::solve_scalar; the stopping rule is ONE function,
+// qp_stop_rule (emp_qp_core.h), and the table beside it says which tier applies which of its clauses:
 //   * range_qp_solve_wave_fast - one station and one unknown per lane (N, ns <= G): per-station and per-unknown
 //     state, the normal matrix and its factor in registers; vectors that lanes of different roles exchange go
 //     through LDS.  The path QP of the cycle runs here (two scenes per wavefront: LIN / UNI variants, 163 VGPRs).
-//   * box_qp_lanes / smooth_pair_lanes - the smoothing QP (G = I): registers only.
+//   * box_qp_lanes / smooth_pair_lanes - the smoothing QP (G = I) behind its active-set solver: registers only.  The same solver
+//     for one problem a half-wave and for x and y in the same lanes, kept as two texts (profiles/ipm_step/README.md).
 //   * range_qp_solve_wave - any size: arrays in LDS, serial factorisation by lane 0 of the group.
 // The banded Cholesky and the substitutions of the first two tiers are lane-shift sweeps (band_chol_group /
 // band_solve_group, and band_chol_group_n / band_solve_group_n for two problems in the same lanes: one set of
@@ -77,8 +79,6 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
     r = __builtin_fma(0.5 * r, e, r);
     return r;
 }
-
-constexpr double kQpInfeasibleZ = 1e5;    // multipliers beyond this many Hessian diagonals with a stalled primal residual: infeasible
 
 // All-lanes reductions over a group of G = 32 or 64 lanes without LDS traffic: four DPP butterfly levels inside
 // each row of 16 lanes (quad_perm x2, row_half_mirror, row_mirror: after level k every aligned block of 2^k
@@ -494,13 +494,8 @@ __device__ int range_qp_solve_wave(RangeQp<KD, F, W>& Q, int gl, bool live, int 
             rp_max = group_max<G>(rp_max);
             zmax = group_max<G>(zmax);
             mu = group_sum<G>(mu) / (double)rows;
-            const double dscale = fmax(qscale, zmax);
-            if (rd_max <= Q.eps_d_rel * dscale && rp_max <= Q.eps_p && mu <= Q.eps_mu) state = 0;
-            else if (!(mu == mu) || mu > 1e30 || (iters >= kQpStallIter && rp_max > kQpStallResidual)) state = 2;
-            else if (iters >= kQpMaxIter || iters >= iter_cap) state = acceptable ? 0 : 2;
-            const bool acc_now = rd_max <= 100.0 * Q.eps_d_rel * dscale && rp_max <= 10.0 * Q.eps_p && mu <= 1000.0 * Q.eps_mu;
-            if (acc_now) acceptable = true;
-            if (state == 1 && acc_now && rp_max <= Q.eps_p && mu <= Q.eps_mu) state = 0;     // see range_qp_solve_wave_fast
+            state = qp_stop_rule<false, true>(rd_max, rp_max, mu, zmax, qscale, 0.0, iters, iter_cap, Q.eps_d_rel, Q.eps_p, Q.eps_mu,
+                                              acceptable).state;
         }
         __syncthreads();
         if (!__any(state == 1)) break;          // nobody left to iterate: the rest of the pass would run fully masked (emp_qp_rows.h; one wavefront per block)
@@ -838,22 +833,9 @@ __device__ int range_qp_solve_wave_fast(RangeQp<KD, F, W>& Q, int gl, bool live,
             mu = group_sum<G>(mu);
             mu /= (double)rows;
             if (run) {
-                const double dscale = fmax(qscale, zmax);
                 EMP_QP_DEBUG("it %d rd %.3e rp %.3e mu %.3e zmax %.3e\n", iters, rd_max, rp_max, mu, zmax);
-                if (rd_max <= Q.eps_d_rel * dscale && rp_max <= Q.eps_p && mu <= Q.eps_mu) state = 0;
-                else if (!(mu == mu) || mu > 1e30 || (iters >= kQpStallIter && rp_max > kQpStallResidual)) state = 2;
-                // An infeasible problem shows long before that: its primal residual stalls while the multipliers grow
-                // without bound (x3..100 per iteration, 1e9 and more by iteration 8-12); those of the feasible benchmark
-                // problems stay below 250 Hessian diagonals.  Most of the batch's slowest problems were infeasible ones
-                // running into the iteration-16 rule above, and a kernel lasts as long as its slowest problem.
-                else if (rp_max > kQpStallResidual && zmax > kQpInfeasibleZ * pscale) state = 2;
-                else if (iters >= kQpMaxIter || iters >= iter_cap) state = acceptable ? 0 : 2;
-                const bool acc_now = rd_max <= 100.0 * Q.eps_d_rel * dscale && rp_max <= 10.0 * Q.eps_p && mu <= 1000.0 * Q.eps_mu;
-                if (acc_now) acceptable = true;
-                // Converged complementarity with the dual residual inside the acceptable band: at this mu the normal matrix
-                // carries weights z / s of 1e15 and more, another iteration adds rounding noise to the residual instead of
-                // removing it (benchmark scene 446: rd 5.6e-6, 1.1e-5 in another summation order, then 2e-2, 2e+4) - stop.
-                if (state == 1 && acc_now && rp_max <= Q.eps_p && mu <= Q.eps_mu) state = 0;
+                state = qp_stop_rule<true, true>(rd_max, rp_max, mu, zmax, qscale, pscale, iters, iter_cap, Q.eps_d_rel, Q.eps_p,
+                                                 Q.eps_mu, acceptable).state;
             }
         }
         if (!__any(state == 1)) break;          // nobody left to iterate: the rest of the pass would run fully masked (emp_qp_rows.h; one wavefront per block)
@@ -1128,8 +1110,8 @@ __device__ inline int box_qp_setup_group(BoxRangeQp& Q, const double* ref, int s
 // problem of a polyline on lanes 0-31 and its y problem on lanes 32-63.  The box QP has G = I (W = 1, F = 1,
 // off0 = 0): a station IS its unknown, so nothing is exchanged through LDS - neighbours for P u and for the
 // Cholesky / substitution sweeps come from lane shifts (a shift that crosses into the other group meets a band
-// entry that is exactly 0), norms and ratio tests from the group reductions.  Same algorithm, stopping rule and
-// constants as range_qp_solve_wave_fast with BoxRangeQp (emp_qp_core.h: box_qp_forms / box_qp_setup).
+// entry that is exactly 0), norms and ratio tests from the group reductions.  Same algorithm as
+// range_qp_solve_wave_fast; stopping rule: qp_stop_rule<false, false> (emp_qp_core.h) at box_qp_forms' thresholds of old.
 // r: this lane's reference coordinate (lanes >= m of the group: anything).  Returns 0 ok / 2 failed per group.
 // ---------------------------------------------------------------------------------------------
 // The same box QP by a primal-dual active set iteration (Hintermueller / Ito / Kunisch): fix the coordinates whose
@@ -1240,13 +1222,9 @@ __device__ inline int box_qp_lanes(double r, int m, const SmoothQpParams& prm, d
         const double rp_max = group_max<G>(has ? fmax(fabs(rpu), fabs(rpl)) : 0.0);
         const double zmax = group_max<G>(has ? fmax(zu, zl) : 0.0);
         const double mu = group_sum<G>(has ? su * zu + sl * zl : 0.0) / (double)rows;
-        if (state == 1) {
-            const double dscale = fmax(qscale, zmax);
-            if (rd_max <= eps_d_rel * dscale && rp_max <= eps_p && mu <= eps_mu) state = 0;
-            else if (!(mu == mu) || mu > 1e30 || (iters >= kQpStallIter && rp_max > kQpStallResidual)) state = 2;
-            else if (iters >= kQpMaxIter) state = acceptable ? 0 : 2;
-            if (rd_max <= 100.0 * eps_d_rel * dscale && rp_max <= 10.0 * eps_p && mu <= 1000.0 * eps_mu) acceptable = true;
-        }
+        if (state == 1)
+            state = qp_stop_rule<false, false>(rd_max, rp_max, mu, zmax, qscale, 0.0, iters, kQpMaxIter, eps_d_rel, eps_p, eps_mu,
+                                               acceptable).state;
         if (!__any(state == 1)) break;          // nobody left to iterate: the rest of the pass would run fully masked (emp_qp_rows.h; one wavefront per block)
         const bool go = state == 1;
         double fa[KD + 1], flow[KD + 1], frinv = 1.0;
@@ -1297,8 +1275,8 @@ __device__ inline int box_qp_lanes(double r, int m, const SmoothQpParams& prm, d
 // problem (same structure, independent data) run side by side in the same lanes so that their two serial
 // chains interleave.  The box QP has G = I (W = 1, F = 1, off0 = 0): a station IS its unknown, so the whole
 // interior-point iteration lives in registers - neighbours for P u and for the Cholesky / substitution sweeps
-// come from lane shifts, norms and ratio tests from butterflies.  Same algorithm, stopping rule and constants
-// as range_qp_solve_wave_fast with BoxRangeQp (emp_qp_core.h: box_qp_forms / box_qp_setup).
+// come from lane shifts, norms and ratio tests from butterflies.  box_qp_lanes with NP = 2 problems a lane, but
+// for the failed pivot: per problem here (rinv marked by band_chol_group_n), per group there.  tools/qp_box_test.hip runs both.
 // rx, ry: this lane's reference point (lanes >= m: anything).  Returns 0 ok / 2 failed (wave-uniform).
 // ---------------------------------------------------------------------------------------------
 __device__ inline int smooth_pair_lanes(double rx, double ry, int m, const SmoothQpParams& sx, const SmoothQpParams& sy,
@@ -1378,14 +1356,9 @@ __device__ inline int smooth_pair_lanes(double rx, double ry, int m, const Smoot
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             mu[p] = red[p][3] / (double)rows;
-            if (state[p] == 1) {
-                const double rd_max = red[p][0], rp_max = red[p][1], dscale = fmax(qscale[p], red[p][2]);
-                if (rd_max <= eps_d_rel * dscale && rp_max <= eps_p && mu[p] <= eps_mu) state[p] = 0;
-                else if (!(mu[p] == mu[p]) || mu[p] > 1e30 || (iters[p] >= kQpStallIter && rp_max > kQpStallResidual)) state[p] = 2;
-                else if (iters[p] >= kQpMaxIter) state[p] = acceptable[p] ? 0 : 2;
-                if (rd_max <= 100.0 * eps_d_rel * dscale && rp_max <= 10.0 * eps_p && mu[p] <= 1000.0 * eps_mu)
-                    acceptable[p] = true;
-            }
+            if (state[p] == 1)
+                state[p] = qp_stop_rule<false, false>(red[p][0], red[p][1], mu[p], red[p][2], qscale[p], 0.0, iters[p], kQpMaxIter,
+                                                      eps_d_rel, eps_p, eps_mu, acceptable[p]).state;
             go[p] = state[p] == 1;
         }
         if (!go[0] && !go[1]) break;

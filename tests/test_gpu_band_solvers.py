@@ -2,7 +2,9 @@
 per lane, emp_qp_rows.h, half bandwidth 3 and 2) and tools/qp_group_test.hip (one row per lane, emp_qp_wave.h, the two-problem
 form included) solve random SPD band systems - problems of 0, 1, 2, KD rows and a full group side by side in one wavefront - and
 compare with the scalar band_chol / band_solve of emp_qp_core.h: relative error below 1e-11, no NaN in a factor entry outside a
-problem.  A copy of the sweep that drifts shows in no parity test until two problems of unlike size share a wavefront."""
+problem.  A copy of the sweep that drifts shows in no parity test until two problems of unlike size share a wavefront.
+tools/qp_box_test.hip calls the interior-point fallback of the smoothing QP (box_qp_lanes<32> and smooth_pair_lanes), which no scene
+reaches behind the active-set solver, and holds it against the scalar solver on the host (its header lists cases and checks)."""
 import os
 import re
 import shutil
@@ -24,7 +26,7 @@ def _flags(source):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tool", ["qp_rows_test", "qp_group_test"])
+@pytest.mark.parametrize("tool", ["qp_rows_test", "qp_group_test", "qp_box_test"])
 def test_band_solver_tool(tool, tmp_path):
     source = os.path.join(ROOT, "tools", tool + ".hip")
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

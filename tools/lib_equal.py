@@ -1,6 +1,9 @@
 """Bit-identity of two builds of the library on whole planning cycles (development aid for changes that must not change a bit:
 storage layouts, launch geometry): python tools/lib_equal.py A.so B.so [cfg2|cfg5|stationsNN] [scenes].  Each library plans the same scenes in
-a child process of its own; every output array must be equal bit for bit (padding beyond each scene's length excluded)."""
+a child process of its own; every output array must be equal bit for bit (padding beyond each scene's length excluded).
+Two more targets feed both libraries committed fixtures instead of planning cycles: `speed` (tests/golden/speed_backend.npz
+through the speed planner's QP stage - the fixture holds that stage's inputs, not a scene for Planner.speed_plan) and
+`control` (tests/golden/control/control.npz through mpc_lateral, mpc_ff_lateral and lqr_lateral)."""
 import os
 import subprocess
 import sys
@@ -11,10 +14,38 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = ("dp_rows", "dp_s", "dp_l", "dp_len", "path_s", "path_l", "path_len", "traj", "traj_len", "status")
 
 
+def fixture_child(name, out):
+    """every output of the speed QP or of the three lateral controllers on the committed fixture"""
+    from emplanner_carla_amd import api
+    g = np.load(os.path.join(ROOT, "tests", "golden", "speed_backend.npz" if name == "speed" else os.path.join("control", "control.npz")))
+    pl = api.Planner(0)
+    res = {}
+    if name == "speed":
+        sel = np.nonzero(g["qp_code"] >= 0)[0]
+        cs = g["cs_out"][sel]
+        r = pl.speed_qp(api.speed_qp_params(), g["v0"][sel], g["qp_a0"][sel], g["dp_s"][sel], g["dp_t"][sel], cs[:, 0], cs[:, 1], cs[:, 2],
+                        cs[:, 3])
+        res = {f"speed_qp_{i}": np.asarray(a) for i, a in enumerate(r)}
+    else:
+        para = tuple(float(v) for v in g["vehicle_para"])
+        args = (g["ff_path"], g["ff_n"].astype(np.int32), g["ff_state"], g["ff_Vx"], g["ff_min_index_in"].astype(np.int32))
+        for law, prm, kw in (("mpc_lateral", api.mpc_params, dict(qp_matrices=True)), ("mpc_ff_lateral", api.mpc_ff_params, dict(qp_matrices=True)),
+                             ("lqr_lateral", api.lqr_params, {})):
+            r = getattr(pl, law)(prm(vehicle_para=para), *args, **kw)
+            for k, v in vars(r).items():
+                if isinstance(v, np.ndarray):
+                    res[f"{law}_{k}"] = v
+    pl.close()
+    assert res, "no outputs"
+    np.savez(out, **res)
+
+
 def child(lib, cfg_name, scenes, out):
     sys.path.insert(0, ROOT)
     from emplanner_carla_amd import _lib
     _lib.LIB_PATH = os.path.abspath(lib)
+    if cfg_name in ("speed", "control"):
+        return fixture_child(cfg_name, out)
     from emplanner_carla_amd import scenes as S
     from emplanner_carla_amd.api import Planner, dp_params_from_cfg, qp_params, smooth_params
     extra = {}
@@ -57,6 +88,9 @@ if __name__ == "__main__":
         subprocess.run([sys.executable, os.path.abspath(__file__), "--child", lib, cfg, str(n), out], check=True)
         outs.append(np.load(out))
     bad = [k for k in outs[0].files if not np.array_equal(outs[0][k], outs[1][k], equal_nan=True)]
+    if cfg in ("speed", "control"):
+        print(f"{cfg} fixture, {len(outs[0].files)} arrays: {'BIT-IDENTICAL' if not bad else 'DIFFERENT: ' + ', '.join(bad)} ({a} vs {b})")
+        sys.exit(1 if bad else 0)
     ok = ((outs[0]["bench_status"] & ~1) == 0).mean()
     if "--diff" in sys.argv:            # builds that may differ by rounding (solver arithmetic): how far apart, scene statuses first
         for tag in ("bench", "tight"):
