@@ -12,6 +12,9 @@ pass.  Here, at B = 64 and 151 (speed QP: two 32-lane scenes per block, so 151 l
   with statuses equal to the exception the port raises, speed QP at 1e-6, increase points as test_back_end_fuzz_vs_port;
 - batch invariance (tests/batch_check.invariant: alone, reversed, shifted by one, host == device), bit for bit;
 - the count contract of path_len and n_init (clamped to [0, max_path]) with raw guarded device calls.
+
+The speed QP on hard corridors (standstill, v0 = 60, walls, caps, tubes, crossing and non-finite bounds, 2 to 15 columns) and the
+stages behind it on a profile that stands still: tests/test_gpu_speed_qp_cases.py.
 """
 import functools
 
