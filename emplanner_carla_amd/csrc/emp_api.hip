@@ -43,7 +43,6 @@ static int launch(emp_ctx* ctx, const char* name, K kern, dim3 grid, dim3 block,
     return EMP_OK;
 }
 
-constexpr const char* kQpTooLarge = "problem too large for the LDS-resident QP solver";
 // Dynamic LDS of a kernel: refused with the caller's own text beyond a compute unit's 160 KB, opted in beyond the default 48 KB.
 template <typename K>
 static int set_lds(emp_ctx* ctx, K kernel, size_t bytes, const char* too_large) {
@@ -100,8 +99,15 @@ static int make_dp_dev(emp_ctx* ctx, const emp_dp_params* p, int B, int max_obs,
 
 // elements of the edge tensor the DP kernels exchange between themselves: tiled up to 32 rows, canonical beyond (emp_dp_launch.h)
 static size_t tiled_elems(const DpDev& d) { return edge_tensor_elems(d.row, d.col, d.B, true); }
-// a plan emp_dp_launch.h refused, as the call's error
+// a plan emp_dp_launch.h or emp_tail_launch.h refused, as the call's error
 static int plan_refused(emp_ctx* ctx, const char* error) { return error ? fail(ctx, EMP_ERR_INVALID, error) : EMP_OK; }
+// A kernel launched as emp_tail_launch.h plans it: refused with the plan's text, else opted in to its LDS and launched on its grid.
+template <typename K, typename... A>
+static int launch_plan(emp_ctx* ctx, const char* name, const TailPlan& p, K kern, A... args) {
+    if (const int rc = plan_refused(ctx, p.error)) return rc;
+    if (const int rc = set_lds(ctx, kern, p.lds, "internal: a launch plan beyond the LDS")) return rc;
+    return launch(ctx, name, kern, dim3(p.grid, p.grid_y), dim3(p.block), p.lds, args...);
+}
 
 // ---- device-level stage launchers (all pointers are device memory; nothing synchronises) -----
 // pair table of the lattice (emp_dp_kernels.h dp_pair_table_kernel): rebuilt only when the lattice parameters change,
@@ -940,24 +946,17 @@ static int dev_project(emp_ctx* ctx, int B, int max_ref, int max_obs, const doub
                        const double* obs_xy, const int* n_obs, double* s_map, double* obs_s, double* obs_l,
                        double* begin_sl, double* start, int obs_cap = -1, const double* dyn = nullptr,
                        int* n_obs_out = nullptr) {
-    if (B == 0) return EMP_OK;
-    const size_t lds = (size_t)7 * max_ref * sizeof(double);
-    if (const int rc = set_lds(ctx, frenet_project_wave_kernel, lds, "reference line too long for the LDS-resident projection kernel")) return rc;
-    return launch(ctx, "project", frenet_project_wave_kernel, dim3(B), dim3(64), lds, B, max_ref, max_obs, ref_line, n_ref, origin_xy,
-                  start_xy, start_v, start_a, obs_xy, n_obs, s_map, obs_s, obs_l, begin_sl, start, obs_cap < 0 ? max_obs : obs_cap, dyn,
-                  n_obs_out);
+    return launch_plan(ctx, "project", plan_project(B, max_ref), frenet_project_wave_kernel, B, max_ref, max_obs, ref_line, n_ref,
+                       origin_xy, start_xy, start_v, start_a, obs_xy, n_obs, s_map, obs_s, obs_l, begin_sl, start,
+                       obs_cap < 0 ? max_obs : obs_cap, dyn, n_obs_out);
 }
 
 // smooth_reference_line, one wavefront per scene (emp_reference_line, and the front end of emp_plan_cycle)
 template <typename... A>
 static int dev_reference_line(emp_ctx* ctx, const emp_smooth_params* sp, int B, int max_global, A... args) {
-    if (B == 0) return EMP_OK;
     const SmoothQpParams sx{sp->w_smooth, sp->w_length, sp->w_ref, sp->x_thre};
     const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
-    const size_t lds = (2 * (size_t)kRefLinePoints + 2 * (size_t)BoxRangeQp::words(kRefLinePoints, kRefLinePoints) +
-                        (size_t)kRefLinePoints) * sizeof(double);
-    if (const int rc = set_lds(ctx, reference_line_wave_kernel, lds, kQpTooLarge)) return rc;
-    return launch(ctx, "reference_line", reference_line_wave_kernel, dim3(B), dim3(64), lds, B, max_global, sx, sy, args...);
+    return launch_plan(ctx, "reference_line", plan_reference_line(B), reference_line_wave_kernel, B, max_global, sx, sy, args...);
 }
 
 static int dev_cycle_qp(emp_ctx* ctx, int B, int max_pts, int max_obs, const QpDev& Q, const double* dp_s,
@@ -965,37 +964,16 @@ static int dev_cycle_qp(emp_ctx* ctx, int B, int max_pts, int max_obs, const QpD
                         const int* n_obs, const double* start, double* path_s, double* path_l, int* path_len,
                         int* status, CycleSched* cs) {
     if (B == 0) return EMP_OK;
+    // which kernel, how many scenes per wavefront and why: emp_tail_launch.h plan_cycle_qp
+    const TailPlan p = plan_cycle_qp(B, max_pts, max_obs, Q.decimate, ctx->opt[EMP_OPT_PATH_QP_FORM], EMP_QP_LDS_PAD);
+    if (const int rc = plan_refused(ctx, p.error)) return rc;
     const int cap = (max_pts + Q.decimate - 1) / Q.decimate;          // most stations a scene can have
-    const size_t per_group = ((size_t)5 * cap + 4 * (size_t)max_obs + path_qp_words(cap)) * sizeof(double);
-    int rc;
+    auto kern = p.r == 0 ? (p.gp == 32 ? cycle_qp_wave_kernel<32> : cycle_qp_wave_kernel<64>)
+                         : p.gp == 16 ? cycle_qp_rows_kernel<16, 4> : p.r == 3 ? cycle_qp_rows_kernel<8, 3> : cycle_qp_rows_kernel<8, 4>;
     KernelTimer t(ctx, "path_qp");
-    // Eight scenes per wavefront (emp_qp_rows.h) up to 34 stations, four up to 66.  EMP_OPT_PATH_QP_FORM = 1 (emp_set_option)
-    // selects the kernels of rounds 1-2 (two scenes per wavefront up to 34 stations, one beyond): an interior-point iteration
-    // of that kernel is 2500 instructions against 3000, for the slower of two scenes instead of eight - the form for a caller
-    // who plans a handful of scenes and counts microseconds.  The two associate their sums differently (~2e-9) and only the
-    // rows solver restores its last acceptable iterate on a fallback exit, so the choice is the CALLER's and never follows
-    // the batch size (round 3 switched below 1024 scenes: a 512-scene shard then differed from its slice of a 4096-scene call).
-    const bool pair_form = ctx->opt[EMP_OPT_PATH_QP_FORM] == 1;
-    if (cap <= 66 && !pair_form) {                                    // 8 (4) scenes per wavefront on groups of 8 (16) lanes
-        const int gp = cap <= 34 ? 8 : 16;
-        // the kernel's own carve-up (PathQpRowsLayout, emp_qp_core.h: cycle_qp_group_words doubles between two groups)
-        const size_t per_wave = (cap <= 26 ? PathQpRowsLayout<8, 3>::wave_bytes(max_obs) : cap <= 34 ? PathQpRowsLayout<8, 4>::wave_bytes(max_obs)
-                                                                                          : PathQpRowsLayout<16, 4>::wave_bytes(max_obs)) + EMP_QP_LDS_PAD;
-        auto kern = cap <= 26 ? cycle_qp_rows_kernel<8, 3> : cap <= 34 ? cycle_qp_rows_kernel<8, 4> : cycle_qp_rows_kernel<16, 4>;
-        if ((rc = set_lds(ctx, kern, per_wave, kQpTooLarge))) return rc;
-        const int spw = 64 / gp;
-        return launch_attaching(ctx, cs, t.stop != nullptr, kern, dim3((B + spw - 1) / spw), dim3(64), per_wave, B, max_pts,
-                                max_obs, cap, Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
-    } else if (cap <= 34) {                                           // N, ns <= 32: two scenes per wavefront
-        const size_t per_pair = 2 * ((size_t)5 * cap + 4 * (size_t)max_obs + path_qp_words_pair()) * sizeof(double);
-        auto kern = cycle_qp_wave_kernel<32>;
-        if ((rc = set_lds(ctx, kern, per_pair, kQpTooLarge))) return rc;
-        return launch_attaching(ctx, cs, t.stop != nullptr, kern, dim3((B + 1) / 2), dim3(64), per_pair, B, max_pts,
-                                max_obs, cap, Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
-    }
-    if ((rc = set_lds(ctx, cycle_qp_wave_kernel<64>, per_group, kQpTooLarge))) return rc;
-    return launch_attaching(ctx, cs, t.stop != nullptr, cycle_qp_wave_kernel<64>, dim3(B), dim3(64), per_group, B, max_pts, max_obs, cap,
-                            Q, dp_s, dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
+    if (const int rc = set_lds(ctx, kern, p.lds, kQpTooLarge)) return rc;
+    return launch_attaching(ctx, cs, t.stop != nullptr, kern, dim3(p.grid), dim3(p.block), p.lds, B, max_pts, max_obs, cap, Q, dp_s,
+                            dp_l, dp_len, obs_s, obs_l, n_obs, start, path_s, path_l, path_len, status);
 }
 
 static int dev_cycle_cartesian(emp_ctx* ctx, int B, int max_ref, int max_pts, int path_cap, const emp_smooth_params* sp,
@@ -1006,23 +984,17 @@ static int dev_cycle_cartesian(emp_ctx* ctx, int B, int max_ref, int max_pts, in
     const SmoothQpParams sx{sp->w_smooth, sp->w_length, sp->w_ref, sp->x_thre};
     const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
     const int cap = path_cap + 1;                                        // trajectory = planning start + path points
-    const size_t lds = ((size_t)max_ref + 3 * (size_t)cap + 2 * (size_t)BoxRangeQp::words(cap, cap)) * sizeof(double);
-    // Four scenes per wavefront up to 32 trajectory points, two up to 64 (emp_tail_kernels.h, cycle_cartesian_rows_kernel);
-    // EMP_OPT_CARTESIAN_FORM = 1 (A/B runs) keeps the one-scene-per-wavefront kernels of rounds 1-2 (bit-identical results).
-    const bool wave_form = ctx->opt[EMP_OPT_CARTESIAN_FORM] == 1;
-    if (cap <= 64 && !wave_form) {
-        const int spw = cap <= 32 ? 4 : 2;
-        const size_t lds4 = ((size_t)spw * ((size_t)max_ref + 5 * (size_t)cap) + 2 * (size_t)BoxRangeQp::words(cap, cap)) * sizeof(double);
-        auto k4 = cap <= 24 ? cycle_cartesian_rows_kernel<8, 3> : cap <= 32 ? cycle_cartesian_rows_kernel<8, 4> : cycle_cartesian_rows_kernel<16, 4>;
-        if (const int rc = set_lds(ctx, k4, lds4, kQpTooLarge)) return rc;
+    // which kernel and how many scenes per wavefront: emp_tail_launch.h plan_cycle_cartesian
+    const TailPlan p = plan_cycle_cartesian(B, max_ref, max_pts, path_cap, ctx->opt[EMP_OPT_CARTESIAN_FORM]);
+    if (p.r) {
+        auto k4 = p.gp == 16 ? cycle_cartesian_rows_kernel<16, 4> : p.r == 3 ? cycle_cartesian_rows_kernel<8, 3> : cycle_cartesian_rows_kernel<8, 4>;
         const int force_fb = ctx->opt[EMP_OPT_SMOOTH_FORCE_FALLBACK] ? 1 : 0;                        // test hook
-        return launch(ctx, "to_cartesian", k4, dim3((B + spw - 1) / spw), dim3(64), lds4, B, max_ref, max_pts, cap, sx, sy, ref_line,
-                      s_map, n_ref, begin_sl, path_s, path_l, path_len, traj, traj_len, status, force_fb);
+        return launch_plan(ctx, "to_cartesian", p, k4, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref, begin_sl, path_s, path_l,
+                           path_len, traj, traj_len, status, force_fb);
     }
-    auto kern = cap > 32 ? cycle_cartesian_wave_kernel_wide : cycle_cartesian_wave_kernel_narrow;
-    if (const int rc = set_lds(ctx, kern, lds, kQpTooLarge)) return rc;
-    return launch(ctx, "to_cartesian", kern, dim3(B), dim3(64), lds, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref,
-                  begin_sl, path_s, path_l, path_len, traj, traj_len, status);
+    auto kern = p.wide ? cycle_cartesian_wave_kernel_wide : cycle_cartesian_wave_kernel_narrow;
+    return launch_plan(ctx, "to_cartesian", p, kern, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref, begin_sl, path_s, path_l,
+                       path_len, traj, traj_len, status);
 }
 
 // ---- emp_plan_cycle's pipeline lane and cycle graph -------------------------------------------------------------------
@@ -1377,13 +1349,9 @@ int emp_path_qp(emp_ctx* ctx, const emp_qp_params* q, int32_t B, int32_t max_pts
     int* d_it = st.out(iters, (size_t)B);
     int* d_st = st.out(status, (size_t)B);
     if (const int rc = st.ready()) return rc;
-    if (B) {
-        const size_t lds = (size_t)path_qp_words(max_pts) * sizeof(double);
-        if (const int rc = set_lds(ctx, path_qp_wave_kernel, lds, kQpTooLarge)) return rc;
-        if (const int rc = launch(ctx, "path_qp", path_qp_wave_kernel, dim3(B), dim3(64), lds, B, max_pts, max_pts, make_qp_dev(q),
-                                  d_lo, d_hi, d_np, d_s3, d_l, d_dl, d_ddl, d_it, d_st))
-            return rc;
-    }
+    if (const int rc = launch_plan(ctx, "path_qp", plan_path_qp(B, max_pts), path_qp_wave_kernel, B, max_pts, max_pts, make_qp_dev(q), d_lo,
+                                   d_hi, d_np, d_s3, d_l, d_dl, d_ddl, d_it, d_st))
+        return rc;
     return st.finish();
 }
 
@@ -1399,15 +1367,12 @@ int emp_smooth_line(emp_ctx* ctx, const emp_smooth_params* sp, int32_t B, int32_
     int* d_it = st.out(iters, (size_t)B);
     int* d_st = st.out(status, (size_t)B);
     if (const int rc = st.ready()) return rc;
-    if (B) {
-        const SmoothQpParams sx{sp->w_smooth, sp->w_length, sp->w_ref, sp->x_thre};
-        const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
-        const size_t lds = (2 * (size_t)BoxRangeQp::words(max_pts, max_pts) + (size_t)max_pts) * sizeof(double);
-        auto kern = max_pts > 32 ? smooth_wave_kernel<true> : smooth_wave_kernel<false>;
-        if (const int rc = set_lds(ctx, kern, lds, kQpTooLarge)) return rc;
-        if (const int rc = launch(ctx, "smooth", kern, dim3(B), dim3(64), lds, B, max_pts, max_pts, sx, sy, d_xy, d_np, d_out, d_it, d_st))
-            return rc;
-    }
+    const SmoothQpParams sx{sp->w_smooth, sp->w_length, sp->w_ref, sp->x_thre};
+    const SmoothQpParams sy{sp->w_smooth, sp->w_length, sp->w_ref, sp->y_thre};
+    const TailPlan plan = plan_smooth(B, max_pts);
+    if (const int rc = launch_plan(ctx, "smooth", plan, plan.wide ? smooth_wave_kernel<true> : smooth_wave_kernel<false>, B, max_pts, max_pts,
+                                   sx, sy, d_xy, d_np, d_out, d_it, d_st))
+        return rc;
     return st.finish();
 }
 
@@ -1923,9 +1888,9 @@ static int dev_speed_dp(emp_ctx* ctx, const emp_speed_dp_params* p, int B, int m
         hipLaunchKernelGGL(st_scatter_kernel, grid1(B, 256), dim3(256), 0, ctx->stream, B, o.key, o.hist, o.hist + kStKeys, o.order);
         EMP_LAUNCH_CHECK(ctx);
     }
-    return launch(ctx, "speed_dp", max_obs <= 32 ? speed_dp_kernel<uint32_t> : speed_dp_kernel<uint64_t>, dim3(B), dim3(kStBlock),
-                  speed_dp_lds_bytes(max_obs), make_st_dev(p, B, max_obs), s_in, s_out, t_in, t_out, v_start, cost, s_dot, node,
-                  end_node, speed_s, speed_t, (const int*)o.order);
+    const TailPlan plan = plan_speed_dp(B, max_obs);
+    return launch_plan(ctx, "speed_dp", plan, plan.m32 ? speed_dp_kernel<uint32_t> : speed_dp_kernel<uint64_t>, make_st_dev(p, B, max_obs),
+                       s_in, s_out, t_in, t_out, v_start, cost, s_dot, node, end_node, speed_s, speed_t, (const int*)o.order);
 }
 
 constexpr double kDefaultMaxLateralAccel = 0.2 * 9.8;       // ref: generate_convex_space's default, speed_planning_test.py:309
@@ -1941,9 +1906,8 @@ static int dev_speed_qp(emp_ctx* ctx, const emp_speed_qp_params* p, int B, const
                         const double* dp_t, const double* s_lb, const double* s_ub, const double* sd_lb, const double* sd_ub,
                         double* qs, double* qv, double* qa, double* qt, int* iters, int* status) {
     const stb::SpeedQpParams prm{p->w_cost_s_dot2, p->w_cost_v_ref, p->w_cost_jerk, p->reference_speed};
-    const size_t lds = 2 * (size_t)(stb::speed_qp_words(stb::kQp) + 1) * sizeof(double);
-    return launch(ctx, "speed_qp", stb::speed_qp_kernel<32>, dim3((B + 1) / 2) /* two scenes per wavefront */, dim3(64), lds, B, prm, v0, a0, dp_s, dp_t, s_lb, s_ub,
-                  sd_lb, sd_ub, qs, qv, qa, qt, iters, status);
+    return launch_plan(ctx, "speed_qp", plan_speed_qp(B), stb::speed_qp_kernel<32>, B, prm, v0, a0, dp_s, dp_t, s_lb, s_ub, sd_lb, sd_ub,
+                       qs, qv, qa, qt, iters, status);
 }
 
 static int dev_speed_increase_points(emp_ctx* ctx, int B, const double* qs, const double* qv, const double* qa, const double* qt,
@@ -1951,17 +1915,11 @@ static int dev_speed_increase_points(emp_ctx* ctx, int B, const double* qs, cons
     return launch(ctx, "speed_increase_points", stb::densify_kernel, dim3(B), dim3(64), 0, B, qs, qv, qa, qt, s, v, a, t, status);
 }
 
-constexpr const char* kMergeTooLong = "path too long for the LDS-resident merge kernel";
-static size_t merge_lds_bytes(int max_path) { return (size_t)5 * max_path * sizeof(double); }
-
 static int dev_path_speed_merge(emp_ctx* ctx, int B, int max_path, const double* s, const double* v, const double* a, const double* t,
                                 const double* now, const double* path_s, const double* x, const double* y, const double* heading,
                                 const double* kappa, const int* n_init, double* trajectory, int* status) {
-    if (B == 0) return EMP_OK;
-    const size_t lds = merge_lds_bytes(max_path);
-    if (const int rc = set_lds(ctx, stb::merge_kernel, lds, kMergeTooLong)) return rc;
-    return launch(ctx, "path_speed_merge", stb::merge_kernel, dim3(B), dim3(64), lds, B, max_path, s, v, a, t, now, path_s, x, y,
-                  heading, kappa, n_init, trajectory, status);
+    return launch_plan(ctx, "path_speed_merge", plan_merge(B, max_path), stb::merge_kernel, B, max_path, s, v, a, t, now, path_s, x, y,
+                       heading, kappa, n_init, trajectory, status);
 }
 
 int emp_st_graph(emp_ctx* ctx, int32_t B, int32_t max_obs, const double* obs_s, const double* obs_l,
@@ -2034,8 +1992,8 @@ int emp_st_edge_costs(emp_ctx* ctx, const emp_speed_dp_params* p, int32_t B, int
     double* d_t = st.out(total, ne, false);
     double* d_o = st.out(obs, ne, false);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, nullptr, st_edge_cost_kernel, dim3((n_edges + 63) / 64, B), dim3(64), 7 * (size_t)max_obs * sizeof(double),
-                              make_st_dev(p, B, max_obs), n_edges, d_e, d_si, d_so, d_ti, d_to, d_t, d_o))
+    if (const int rc = launch_plan(ctx, nullptr, plan_st_edge_cost(B, n_edges, max_obs), st_edge_cost_kernel, make_st_dev(p, B, max_obs),
+                                   n_edges, d_e, d_si, d_so, d_ti, d_to, d_t, d_o))
         return rc;
     return st.finish();
 }
@@ -2173,7 +2131,7 @@ int emp_path_speed_merge(emp_ctx* ctx, int32_t B, int32_t max_path, const double
     EMP_REQUIRE(ctx, B >= 0 && max_path >= 1, "bad sizes");
     EMP_REQUIRE(ctx, s && s_dot && s_dot2 && relative_time && current_time && path_s && x_init && y_init && heading_init &&
                          kappa_init && n_init && trajectory && status, "NULL argument");
-    EMP_REQUIRE(ctx, merge_lds_bytes(max_path) <= 64 * 1024, kMergeTooLong);     // this entry's own limit, before anything is staged
+    if (const int rc = plan_refused(ctx, plan_merge(B, max_path).error)) return rc;      // (kMergeLdsBytes) before anything is staged
     EMP_STAGE(st, where);
     const double* d_s = st.in(s, (size_t)B * stb::kDense);
     const double* d_v = st.in(s_dot, (size_t)B * stb::kDense);
@@ -2241,8 +2199,8 @@ int SpeedHalf::run(emp_ctx* ctx, Stage& st, int B, int max_pts, const double* d_
     double *ds = dp_speed, *dt = dp_speed + n16;
     const double* kappa = rows + 3 * bw;
     int rc;
-    if ((rc = launch(ctx, "speed_front", speed_front_wave_kernel, dim3(B), dim3(64), 2 * (size_t)W * sizeof(double), B, max_pts, W,
-                     max_dyn, d_traj, d_tlen, d_v, d_a, heading, dyn, n_dyn, pre, rows, i2s, v0, a0, seg, width, st_front)))
+    if ((rc = launch_plan(ctx, "speed_front", plan_speed_front(B, W), speed_front_wave_kernel, B, max_pts, W, max_dyn, d_traj, d_tlen,
+                          d_v, d_a, heading, dyn, n_dyn, pre, rows, i2s, v0, a0, seg, width, st_front)))
         return rc;
     if ((rc = dev_speed_dp(ctx, dp, B, max_dyn, si, so, ti, to, v0, nullptr, nullptr, nullptr, end_node, ds, dt, order))) return rc;
     // generate_convex_space on the W-wide rows; path_len = merge width: W, or 0 for a scene that already raised

@@ -652,7 +652,11 @@ EMP_HD void path_qp_finish(const double* cc, int n, double ds, double* out_l, do
 
 // doubles of scratch path_qp_solve_scalar needs for n stations
 // two scenes per wavefront (n <= 34 stations: N, ns <= 32): fixed layout, 36 coefficient slots + the solver's arrays
-EMP_HD constexpr int path_qp_words_pair() { return 36 + PathRangeQp::words_fast(32, 32); }
+constexpr int kPathQpPairUnknowns = 32;                                   // one unknown, one station row per lane of a 32-lane group
+constexpr int kPathQpPairStations = kPathQpPairUnknowns + 2;
+EMP_HD constexpr int path_qp_words_pair() {
+    return kPathQpPairStations + 2 + PathRangeQp::words_fast(kPathQpPairUnknowns, kPathQpPairUnknowns);
+}
 EMP_HD constexpr int path_qp_words(int n) { return PathRangeQp::words(n - 4 > 0 ? n - 4 : 0, n - 2 > 0 ? n - 2 : 0) + n + 2; }
 
 // ---------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@
 
 namespace emp {
 
-// dynamic LDS: 2 * W doubles.  traj [B][max_pts + 1][4] and traj_len [B] are emp_plan_cycle's outputs; W = max_pts + 2.
+// dynamic LDS: SpeedFrontLds (emp_tail_launch.h).  traj [B][max_pts + 1][4] and traj_len [B] are emp_plan_cycle's outputs; W = max_pts + 2.
 // Outputs: rows [4][B][W] = x, y, heading, kappa (NaN from traj_len on), index2s [B][W], s_dot0 / s_dot20 [B] (the speed
 // planner's start condition), seg [4][B][max_dyn] = s_in, s_out, t_in, t_out, merge_width [B] (W, or 0 for a scene whose
 // obstacle match leaves the trajectory: path_speed_merge then NaN-fills it), front_status [B] (EMP_STB_INDEX or 0).
@@ -28,8 +28,9 @@ __global__ __launch_bounds__(64) void speed_front_wave_kernel(
     double* __restrict__ rows, double* __restrict__ index2s, double* __restrict__ s_dot0, double* __restrict__ s_dot20,
     double* __restrict__ seg, int* __restrict__ merge_width, int* __restrict__ front_status) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    double* chord = lds;             // [W] chord i = |point i - point i-1|
-    double* i2s = lds + W;           // [W] trajectory_index2s of the scene
+    const SpeedFrontLds<double*> L = speed_front_lds(lds, W);
+    double* chord = L.chord;         // [W] chord i = |point i - point i-1|
+    double* i2s = L.i2s;             // [W] trajectory_index2s of the scene
     const int b = blockIdx.x, lane = threadIdx.x & 63;
     const int cap = max_pts + 1;
     const double* line = traj + (size_t)b * cap * 4;

@@ -13,6 +13,7 @@
 
 #include "emp_qp_wave.h"
 #include "emp_st_backend_core.h"
+#include "emp_tail_launch.h"
 
 namespace emp {
 namespace stb {
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(64) void convex_space_kernel(
     status[b] = st;
 }
 
-// dynamic LDS: (64 / G) groups x (speed_qp_words(kQp) + 1) doubles
+// dynamic LDS: (64 / G) groups of a SpeedQpLds (emp_tail_launch.h)
 template <int G>
 __global__ __launch_bounds__(64) void speed_qp_kernel(int B, SpeedQpParams prm, const double* __restrict__ v0,
                                                       const double* __restrict__ a0, const double* __restrict__ dp_s,
@@ -65,17 +66,17 @@ __global__ __launch_bounds__(64) void speed_qp_kernel(int B, SpeedQpParams prm, 
     const int lane = threadIdx.x & 63, grp = lane / G, gl = lane & (G - 1);
     const int b = blockIdx.x * GPW + grp;
     const bool present = b < B;
-    double* lds = lds_all + (size_t)grp * (speed_qp_words(kQp) + 1);
+    const SpeedQpLds<double*> L = speed_qp_lds(lds_all + (size_t)grp * speed_qp_lds(0).end);
     const size_t o16 = (size_t)(present ? b : 0) * kDp, o17 = (size_t)(present ? b : 0) * kQp;
     const int nq = present ? speed_qp_size(dp_s + o16) : -kStbQpFailed;
     bool live = nq >= 2;
     const int n = live ? nq : 2;
     const double dt = live ? dp_t[o16 + n - 1] / (double)(n - 1) : 1.0;       // ref :437, :449
     SpeedRangeQp Q;
-    double* cc = lds;
-    Q.bind(lds + kQp + 2, live ? n - 1 : 0, live ? n - 1 : 0);
+    double* cc = L.cc;
+    Q.bind(L.qmem, live ? n - 1 : 0, live ? n - 1 : 0);
     speed_qp_forms(Q, dt);
-    int* flag = reinterpret_cast<int*>(lds + speed_qp_words(kQp));            // set-up result of lane 0
+    int* flag = reinterpret_cast<int*>(L.flag);            // set-up result of lane 0
     if (gl == 0) {
         int rc0 = 0;
         if (live) rc0 = speed_qp_setup(Q, cc, n, dt, v0[b], a0[b], s_lb + o16, s_ub + o16, sd_lb + o16, sd_ub + o16, prm);
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(64) void densify_kernel(int B, const double* __rest
     if (lane == 0) status[b] = 0;
 }
 
-// dynamic LDS: 5 * max_path doubles.  out [B][7][401]: x, y, heading, kappa, speed, accel, time
+// dynamic LDS: MergeLds (emp_tail_launch.h).  out [B][7][401]: x, y, heading, kappa, speed, accel, time
 __global__ __launch_bounds__(64) void merge_kernel(int B, int max_path, const double* __restrict__ s,
                                                    const double* __restrict__ v, const double* __restrict__ a,
                                                    const double* __restrict__ t, const double* __restrict__ now,
@@ -182,11 +183,8 @@ __global__ __launch_bounds__(64) void merge_kernel(int B, int max_path, const do
                                                    double* __restrict__ out, int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = blockIdx.x, lane = threadIdx.x & 63;
-    double* ps = lds;
-    double* px = ps + max_path;
-    double* py = px + max_path;
-    double* ph = py + max_path;
-    double* pk = ph + max_path;
+    const MergeLds<double*> L = merge_lds(lds, max_path);
+    double *ps = L.ps, *px = L.px, *py = L.py, *ph = L.ph, *pk = L.pk;
     int width = n_init[b];
     width = width < 0 ? 0 : (width > max_path ? max_path : width);
     const size_t po = (size_t)b * max_path;

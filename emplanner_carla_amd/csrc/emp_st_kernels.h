@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "emp_st_core.h"
+#include "emp_tail_launch.h"
 
 namespace emp {
 
@@ -25,8 +26,6 @@ struct StDev {
     int B, max_obs;
     st::Weights w;
 };
-
-constexpr int kStBlock = 320;
 
 // ---- speed_dp_kernel (round 3): near pairs found by interval tests, costed on compacted lists --------------------
 //
@@ -51,7 +50,6 @@ constexpr int kStBlock = 320;
 #define EMP_ST_WAVES 5          // wavefronts per SIMD the register allocation aims for.  Round 6, per 4096 scenes alone: 4 (128 VGPRs) 2.6 ms,
                               // 5 (96) 2.02 ms, 6 (80) 2.02 ms and the same configs[4] step (round 3's kernel: 3.2 / 2.4 / 2.3 ms)
 #endif
-constexpr int kStListCap = 256;   // list entries per wavefront (a longer list is processed in windows)
 // Development builds only (tools/st_phase_probe.py; results of a gutted kernel mean nothing, durations do): -DEMP_ST_PROBE=
 //   1  no obstacle reaches any column (interval tests, node sums, pair lists all empty: the kinematic DP alone)
 //   2  interval tests and node sums run, no pair is emitted or costed
@@ -60,8 +58,6 @@ constexpr int kStListCap = 256;   // list entries per wavefront (a longer list i
 #ifndef EMP_ST_PROBE
 #define EMP_ST_PROBE 0
 #endif
-constexpr int kStWaves = kStBlock / 64;
-constexpr int kStParts = kStBlock / st::kRows;   // 8 partial minima per destination row
 
 __device__ __forceinline__ int st_wave_incl_sum(int v) {
     // inclusive prefix sum over the 64 lanes: Hillis-Steele inside the 16-lane rows, then the row totals travel
@@ -87,7 +83,7 @@ __device__ __forceinline__ unsigned long long st_uniform64(unsigned long long v)
            (unsigned)__builtin_amdgcn_readfirstlane((int)v);
 }
 
-struct StLds {   // carve-up of the dynamic LDS of speed_dp_kernel
+struct StLds {   // the dynamic LDS of speed_dp_kernel: pointers to the arrays SpeedDpLds (emp_tail_launch.h) lays out
     double *o_s_in, *o_s_out, *o_t_in, *o_t_out, *o_ux, *o_uy, *o_len;   // [max_obs] each, squeezed
     double* iv;       // [2][max_obs][5][2]  reach intervals (lo, hi) per class (0 = regular edges, 1 = edges from the origin), obstacle
                       //                     and sample: the eight bounds an edge tests against one obstacle are 80 contiguous bytes,
@@ -105,33 +101,30 @@ struct StLds {   // carve-up of the dynamic LDS of speed_dp_kernel
     unsigned char* part_k;  // [8][40]
     unsigned char* t_node;  // [40][16]
 };
-inline size_t speed_dp_lds_bytes(int max_obs) {
-    return ((27 + st::kRows) * (size_t)max_obs + 10 + st::kRows + kStParts * st::kRows + 4 * st::kRows + st::kCols + 4 +
-            kStWaves * (kStListCap + 1)) * sizeof(double) +
-           kStWaves * (kStListCap + 1) * sizeof(uint32_t) + 4 + kStParts * st::kRows + st::kRows * st::kCols;
-}
 __device__ __forceinline__ StLds st_carve(double* lds, int max_obs) {
+    const SpeedDpLds<unsigned char*> O = speed_dp_lds(reinterpret_cast<unsigned char*>(lds), max_obs);
+    auto doubles = [](unsigned char* at) { return reinterpret_cast<double*>(at); };
     StLds L;
-    L.o_s_in = lds;
-    L.o_s_out = L.o_s_in + max_obs;
-    L.o_t_in = L.o_s_out + max_obs;
-    L.o_t_out = L.o_t_in + max_obs;
-    L.o_ux = L.o_t_out + max_obs;
-    L.o_uy = L.o_ux + max_obs;
-    L.o_len = L.o_uy + max_obs;
-    L.iv = L.o_len + max_obs;
-    L.node_c = L.iv + 20 * max_obs;
-    L.t_tab = L.node_c + st::kRows * max_obs;
-    L.s_tab = L.t_tab + 10;
-    L.part_c = L.s_tab + st::kRows;
-    L.p_cost = L.part_c + kStParts * st::kRows;
-    L.p_sdot = L.p_cost + 2 * st::kRows;
-    L.row0 = L.p_sdot + 2 * st::kRows;
-    L.colmask = reinterpret_cast<unsigned long long*>(L.row0 + st::kCols);
-    L.list_s = L.row0 + st::kCols + 4;
-    L.list_c = reinterpret_cast<uint32_t*>(L.list_s + kStWaves * (kStListCap + 1));
-    L.part_k = reinterpret_cast<unsigned char*>(L.list_c + kStWaves * (kStListCap + 1));
-    L.t_node = L.part_k + kStParts * st::kRows;
+    L.o_s_in = doubles(O.o_s_in);
+    L.o_s_out = doubles(O.o_s_out);
+    L.o_t_in = doubles(O.o_t_in);
+    L.o_t_out = doubles(O.o_t_out);
+    L.o_ux = doubles(O.o_ux);
+    L.o_uy = doubles(O.o_uy);
+    L.o_len = doubles(O.o_len);
+    L.iv = doubles(O.iv);
+    L.node_c = doubles(O.node_c);
+    L.t_tab = doubles(O.t_tab);
+    L.s_tab = doubles(O.s_tab);
+    L.part_c = doubles(O.part_c);
+    L.p_cost = doubles(O.p_cost);
+    L.p_sdot = doubles(O.p_sdot);
+    L.row0 = doubles(O.row0);
+    L.colmask = reinterpret_cast<unsigned long long*>(O.colmask);
+    L.list_s = doubles(O.list_s);
+    L.list_c = reinterpret_cast<uint32_t*>(O.list_c);
+    L.part_k = O.part_k;
+    L.t_node = O.t_node;
     return L;
 }
 
@@ -479,7 +472,7 @@ __global__ void st_graph_kernel(int B, int n, const double* __restrict__ obs_s, 
 }
 
 // ref :191-271 - arbitrary edges (s0, t0, v0, s1, t1) against the scene's obstacles; one edge per lane,
-// blockIdx.y = scene; the obstacle frames of the scene are built once per block in LDS (7 * max_obs doubles)
+// blockIdx.y = scene; the obstacle frames of the scene are built once per block in LDS (StEdgeLds, emp_tail_launch.h)
 __global__ void st_edge_cost_kernel(StDev d, int n_edges, const double* __restrict__ edges,
                                     const double* __restrict__ s_in, const double* __restrict__ s_out,
                                     const double* __restrict__ t_in, const double* __restrict__ t_out,
@@ -488,18 +481,18 @@ __global__ void st_edge_cost_kernel(StDev d, int n_edges, const double* __restri
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     const size_t o = (size_t)b * d.max_obs;
-    double* f = lds;
     const int K = d.max_obs;
+    const StEdgeLds<double*> f = st_edge_lds(lds, K);
     for (int j = threadIdx.x; j < K; j += blockDim.x) {
-        f[j] = s_in[o + j];
-        f[K + j] = s_out[o + j];
-        f[2 * K + j] = t_in[o + j];
-        f[3 * K + j] = t_out[o + j];
-        st::obs_frame(f[j], f[2 * K + j], f[K + j], f[3 * K + j], &f[4 * K + j], &f[5 * K + j], &f[6 * K + j]);
+        f.s_in[j] = s_in[o + j];
+        f.s_out[j] = s_out[o + j];
+        f.t_in[j] = t_in[o + j];
+        f.t_out[j] = t_out[o + j];
+        st::obs_frame(f.s_in[j], f.t_in[j], f.s_out[j], f.t_out[j], &f.ux[j], &f.uy[j], &f.len[j]);
     }
     __syncthreads();
     if (e >= n_edges) return;
-    const st::ObsSet set{K, f, f + K, f + 2 * K, f + 3 * K, f + 4 * K, f + 5 * K, f + 6 * K};
+    const st::ObsSet set{K, f.s_in, f.s_out, f.t_in, f.t_out, f.ux, f.uy, f.len};
     const double* q = edges + ((size_t)b * n_edges + e) * 5;
     double oc;
     const double c = st::edge_cost(d.w, q[0], q[1], q[2], q[3], q[4], set, &oc);

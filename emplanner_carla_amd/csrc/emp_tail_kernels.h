@@ -14,6 +14,7 @@
 #include "emp_qp_wave.h"
 #include "emp_qp_rows.h"
 #include "emp_smooth_rows.h"
+#include "emp_tail_launch.h"
 
 namespace emp {
 
@@ -132,7 +133,7 @@ __device__ inline int match_scan_wave(const double* lx, const double* ly, int P,
     return ci;
 }
 
-// dynamic LDS (doubles): 7 * max_ref
+// dynamic LDS: ProjectLds (emp_tail_launch.h)
 __global__ __launch_bounds__(64) void frenet_project_wave_kernel(
     int B, int max_ref, int max_obs, const double* __restrict__ ref_line, const int* __restrict__ n_ref,
     const double* __restrict__ origin_xy, const double* __restrict__ start_xy, const double* __restrict__ start_v,
@@ -144,13 +145,10 @@ __global__ __launch_bounds__(64) void frenet_project_wave_kernel(
     // obstacles of test_9.py:137-169 are appended behind the projected ones and n_obs_out gets the total)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = blockIdx.x, lane = threadIdx.x & 63;
-    double* lx = lds;
-    double* ly = lx + max_ref;
-    double* lth = ly + max_ref;
-    double* lk = lth + max_ref;
-    double* sm = lk + max_ref;
-    double* lcos = sm + max_ref;                        // cos / sin of every node's heading: each node one lane, once per
-    double* lsin = lcos + max_ref;                      // scene - the ten projections below read them instead of calling
+    const ProjectLds<double*> L = project_lds(lds, max_ref);
+    double *lx = L.lx, *ly = L.ly, *lth = L.lth, *lk = L.lk, *sm = L.sm;
+    double *lcos = L.lcos, *lsin = L.lsin;              // cos / sin of every node's heading: each node one lane, once per
+                                                        // scene - the ten projections below read them instead of calling
     const double* line = ref_line + (size_t)b * max_ref * 4;   // cos / sin again (half of this kernel's instructions were those calls)
     const int P = min(max(n_ref[b], 0), max_ref);       // clamped to the row's capacity
     // Every coordinate the ten match scans below start from is fetched HERE, next to the reference line: one round trip
@@ -459,7 +457,7 @@ __device__ inline void heading_kappa_wave(const double* px, const double* py, in
 
 // ---------------------------------------------------------------------------------------------
 // ref: Quadratic_planning, path_planning.py:78-219 (stand-alone stage): one wavefront per scene
-// dynamic LDS: path_qp_words(cap) doubles
+// dynamic LDS: PathQpLds (emp_tail_launch.h)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void path_qp_wave_kernel(int B, int max_pts, int cap, QpDev Q,
                                                           const double* __restrict__ l_min,
@@ -476,7 +474,7 @@ __global__ __launch_bounds__(64) void path_qp_wave_kernel(int B, int max_pts, in
     int it = 0;
     int rc = 2;
     const bool fits = n <= cap;                         // (fewer than 4 stations: path_qp_setup_group refuses, EMP_ST_QP_FAILED)
-    rc = path_qp_group<64>(lds, l_min + o, l_max + o, n, start_l3[3 * b], start_l3[3 * b + 1], start_l3[3 * b + 2], Q.qp,
+    rc = path_qp_group<64>(path_qp_lds(lds, cap).qmem, l_min + o, l_max + o, n, start_l3[3 * b], start_l3[3 * b + 1], start_l3[3 * b + 2], Q.qp,
                            qp_l + o, qp_dl + o, qp_ddl + o, &it, fits);
     if ((threadIdx.x & 63) == 0) {
         if (iters) iters[b] = it;
@@ -487,7 +485,7 @@ __global__ __launch_bounds__(64) void path_qp_wave_kernel(int B, int max_pts, in
 // ---------------------------------------------------------------------------------------------
 // ref: smooth_reference_line, planning_utils.py:262-361 (stand-alone stage): one wavefront per polyline,
 // x on lanes 0-31, y on lanes 32-63, then heading / curvature one point per lane.
-// dynamic LDS: 2 * BoxRangeQp::words(cap, cap) + cap doubles
+// dynamic LDS: SmoothLds of cap points (emp_tail_launch.h); the headings sit behind the solver arrays of the scene's own m points
 // ---------------------------------------------------------------------------------------------
 template <bool WIDE>
 __global__ __launch_bounds__(64) void smooth_wave_kernel(int B, int max_pts, int cap, SmoothQpParams sx,
@@ -499,8 +497,8 @@ __global__ __launch_bounds__(64) void smooth_wave_kernel(int B, int max_pts, int
     const int m = min(max(n_pts[b], 0), max_pts);       // a count beyond the row's capacity is clamped, never followed
     int it = 0, rc = 2;
     double *px = nullptr, *py = nullptr;
-    if (m <= cap) rc = smooth_pair_wave<WIDE>(lds, xy + (size_t)b * max_pts * 2, 2, m, sx, sy, &px, &py, &it);
-    if (rc == 0) heading_kappa_wave(px, py, m, lds + 2 * BoxRangeQp::words(m, m), out + (size_t)b * max_pts * 4, 4);
+    if (m <= cap) rc = smooth_pair_wave<WIDE>(smooth_lds(lds, m).qmem, xy + (size_t)b * max_pts * 2, 2, m, sx, sy, &px, &py, &it);
+    if (rc == 0) heading_kappa_wave(px, py, m, smooth_lds(lds, m).theta, out + (size_t)b * max_pts * 4, 4);
     if ((threadIdx.x & 63) == 0) {
         if (iters) iters[b] = it;
         status[b] = rc ? kStSmoothFailed : 0;
@@ -512,10 +510,8 @@ __global__ __launch_bounds__(64) void smooth_wave_kernel(int B, int max_pts, int
 // GLOBAL path (planning_utils.py:49-182: windowed from the previous match unless is_first_run) -> sampling
 // (:231-259: 10 nodes back, 40 forward, shifted at either end of the path, 51 nodes) -> smooth_reference_line
 // (:262-361) -> the reference line of the cycle.  One wavefront per scene.
-// dynamic LDS: 2 * kRefLinePoints (gathered xy) + 2 * BoxRangeQp::words(51, 51) + 51 doubles
+// dynamic LDS: RefLineLds (emp_tail_launch.h)
 // ---------------------------------------------------------------------------------------------
-constexpr int kRefLinePoints = 51;
-
 __global__ __launch_bounds__(64) void reference_line_wave_kernel(int B, int max_global, SmoothQpParams sx, SmoothQpParams sy,
                                                                  const double* __restrict__ global_path,
                                                                  const int* __restrict__ n_global,
@@ -529,8 +525,9 @@ __global__ __launch_bounds__(64) void reference_line_wave_kernel(int B, int max_
     const int b = blockIdx.x, lane = threadIdx.x & 63;
     const double* line = global_path + (size_t)b * max_global * 4;
     const int P = min(n_global[b], max_global);          // a count beyond the row's capacity is clamped, never followed
-    double* gxy = lds;                                   // [51][2]
-    double* qmem = gxy + 2 * kRefLinePoints;
+    const RefLineLds<double*> L = ref_line_lds(lds);
+    double* gxy = L.gxy;                                 // [51][2]
+    double* qmem = L.smooth.qmem;
     double* out = ref_line + (size_t)b * kRefLinePoints * 4;
     int m = 0, first = 0, fail = 0;
     if (lane == 0) {
@@ -572,7 +569,7 @@ __global__ __launch_bounds__(64) void reference_line_wave_kernel(int B, int max_
         double *px = nullptr, *py = nullptr;
         const int rc = smooth_pair_wave<true>(qmem, gxy, 2, kRefLinePoints, sx, sy, &px, &py, &it);
         if (rc) fail = kStSmoothFailed;
-        else heading_kappa_wave(px, py, kRefLinePoints, qmem + 2 * BoxRangeQp::words(kRefLinePoints, kRefLinePoints), out, 4);
+        else heading_kappa_wave(px, py, kRefLinePoints, L.smooth.theta, out, 4);
     }
     if (fail)
         for (int i = lane; i < kRefLinePoints * 4; i += 64) out[i] = 0.0;
@@ -643,7 +640,7 @@ __global__ void path_to_xy_kernel(int B, int max_ref, int max_pts, const double*
 // ---------------------------------------------------------------------------------------------
 // One cycle, middle part (ref test_9.py:187-210): decimate -> bounds -> path QP -> midpoints.
 // One scene per GROUP of G lanes (G = 32: two scenes per wavefront when cap <= 34 stations, else G = 64).
-// dynamic LDS (doubles), per group: 5*cap + 4*max_obs + path_qp_words(cap)  (G = 32: + path_qp_words_pair() instead)
+// dynamic LDS, per group: CycleQpLds (emp_tail_launch.h)
 // ---------------------------------------------------------------------------------------------
 // R > 0: eight scenes per wavefront (G = 8), R stations per lane (emp_qp_rows.h; cap <= 8 R + 2 stations).
 // doubles of LDS per group (scene)
@@ -654,7 +651,7 @@ __host__ __device__ constexpr int cycle_qp_group_words(int cap, int max_obs) {
     // R = 3: the station and Hessian arrays at 2-4 times their conflict-free cost, 14.5 % of the kernel's wavefront cycles in
     // SQ_LDS_BANK_CONFLICT, profiles/r06a_sq.csv) - an odd stride walks the groups across the banks.
     if (R > 0) return PathQpRowsLayout<(R > 0 ? G : 8), (R > 0 ? R : 3)>::stride(max_obs);
-    return 5 * cap + 4 * max_obs + (G == 32 ? path_qp_words_pair() : path_qp_words(cap));
+    return cycle_qp_lds(0, G == 32, cap, max_obs).end;
 }
 template <int G, int R = 0>
 __device__ __forceinline__ void cycle_qp_body(int B, int max_pts, int max_obs, int cap, const QpDev& Q,
@@ -698,12 +695,13 @@ __device__ __forceinline__ void cycle_qp_body(int B, int max_pts, int max_obs, i
         // or behind the group's other arrays when the obstacle rows are wider than that
         otab = qmem + (max_obs <= L::C ? L::obstacles : L::words);
     } else {
-        ld = sd + cap;                // decimated DP l        [cap]
-        lmin = ld + cap;              // [cap]
-        lmax = lmin + cap;            // [cap]
-        ql = lmax + cap;              // QP result l           [cap]
-        otab = ql + cap;              // per obstacle: lo, hi, below, bound   [4*max_obs]
-        qmem = otab + 4 * max_obs;
+        const CycleQpLds<double*> L = cycle_qp_lds(lds, G == 32, cap, max_obs);
+        ld = L.ld;                    // decimated DP l        [cap]
+        lmin = L.lmin;                // [cap]
+        lmax = L.lmax;                // [cap]
+        ql = L.ql;                    // QP result l           [cap]
+        otab = L.otab;                // per obstacle: lo, hi, below, bound   [4*max_obs]
+        qmem = L.qmem;
     }
 #ifdef EMP_QP_PROBE_EMPTY
     if (Q.debug_stage == 4) return;                 // development timing: the launch alone (tools/qp_phase_probe.py)
@@ -893,7 +891,7 @@ __device__ inline int walk_from_zero(const double* sm, int P, double s, bool* of
 // ---------------------------------------------------------------------------------------------
 // One cycle, last part (ref path_planning.py:15-49): Frenet->Cartesian one point per lane, x / y smoothing
 // on the two half-waves, heading / curvature one point per lane.  One wavefront per scene.
-// dynamic LDS (doubles): max_ref + 3*cap + 2 * BoxRangeQp::words(cap, cap)
+// dynamic LDS: CartesianLds (emp_tail_launch.h)
 // The reference walks the s_map index monotonically from the previous point (:42-43); with a non-decreasing
 // s_map (what cal_s_map_fun produces) that equals a running maximum of independent walks from index 0.
 // ---------------------------------------------------------------------------------------------
@@ -908,10 +906,11 @@ __device__ __forceinline__ void cycle_cartesian_body(
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __builtin_amdgcn_s_setprio(EMP_PRIO_CART);          // as in the path QP kernel
     const int b = blockIdx.x, lane = threadIdx.x & 63;
-    double* sm = lds;                       // [max_ref]
-    double* txy = sm + max_ref;             // [cap][2] interleaved x, y
-    double* th = txy + 2 * cap;             // [cap]
-    double* qmem = th + cap;
+    const CartesianLds<double*> L = cartesian_lds(lds, max_ref, cap);
+    double* sm = L.sm;                      // [max_ref]
+    double* txy = L.txy;                    // [cap][2] interleaved x, y
+    double* th = L.th;                      // [cap]
+    double* qmem = L.qmem;
     const int st = status[b];
     double* out_rows = traj + (size_t)b * (max_pts + 1) * 4;
     auto body = [&]() -> int {          // returns the number of trajectory points (0 = none); wave-uniform control flow
@@ -1021,7 +1020,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 // is shared by four scenes here.  A problem whose active-set classification does not settle (none on any test or
 // benchmark scene) is solved by the whole wavefront with the half-wave solvers of the narrow kernel, one scene at a time.
 // With GP = 16 a scene takes 32 lanes and trajectories of up to 64 points fit (BASELINE configs[4]'s 63): two per wavefront.
-// dynamic LDS (doubles): (32 / GP) * (max_ref + 5 * cap) + 2 * BoxRangeQp::words(cap, cap)
+// dynamic LDS: a CartesianSceneLds per scene, then the fall-back solver's storage (emp_tail_launch.h cartesian_rows_words)
 // ---------------------------------------------------------------------------------------------
 template <int GP, int R>
 __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
@@ -1036,12 +1035,13 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
     const int b = blockIdx.x * SPW + sc;
     const bool present = b < B;
     const size_t bb = present ? (size_t)b : 0;
-    const int per_scene = max_ref + 5 * cap;
-    double* sm = lds + (size_t)sc * per_scene;   // [max_ref]
-    double* txy = sm + max_ref;                  // [cap][2] interleaved x, y
-    double* th = txy + 2 * cap;                  // [cap]
-    double* px = th + cap;                       // [cap] smoothed x
-    double* py = px + cap;                       // [cap] smoothed y
+    const int per_scene = cartesian_scene_lds(0, max_ref, cap).end;
+    const CartesianSceneLds<double*> L = cartesian_scene_lds(lds + (size_t)sc * per_scene, max_ref, cap);
+    double* sm = L.sm;                           // [max_ref]
+    double* txy = L.txy;                         // [cap][2] interleaved x, y
+    double* th = L.th;                           // [cap]
+    double* px = L.px;                           // [cap] smoothed x
+    double* py = L.py;                           // [cap] smoothed y
     double* qmem = lds + (size_t)SPW * per_scene;  // the fall-back solver's storage (whole wavefront)
     const int st = present ? status[bb] : 0;
     int add = 0;                                 // status bits this kernel adds (scene-uniform)
@@ -1140,14 +1140,14 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
         for (int s2 = 0; s2 < SPW; ++s2) {
             if (((unsettled >> (SL * s2)) & kSceneMask) == 0ull) continue;
             const int m2 = __builtin_amdgcn_readlane(m, SL * s2);
-            double* base2 = lds + (size_t)s2 * per_scene;
+            const CartesianSceneLds<double*> L2 = cartesian_scene_lds(lds + (size_t)s2 * per_scene, max_ref, cap);
             double *qx = nullptr, *qy = nullptr;
             int it2 = 0;
-            const int rc2 = smooth_pair_wave<(GP * R > 32)>(qmem, base2 + max_ref, 2, m2, sx, sy, &qx, &qy, &it2);
+            const int rc2 = smooth_pair_wave<(GP * R > kHalfWave)>(qmem, L2.txy, 2, m2, sx, sy, &qx, &qy, &it2);
             if (rc2 == 0) {
                 for (int i = lane; i < m2; i += 64) {
-                    base2[max_ref + 3 * cap + i] = qx[i];
-                    base2[max_ref + 4 * cap + i] = qy[i];
+                    L2.px[i] = qx[i];
+                    L2.py[i] = qy[i];
                 }
             } else if (sc == s2) {
                 add = kStSmoothFailed;

@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "..", "..", "emplanner_carla_amd", "csrc")
 
 
 def load():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("emp_core.h", "emp_dp_launch.h", "emp_frenet_core.h", "emp_qp_core.h", "emp_st_core.h", "emp_st_backend_core.h")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("emp_core.h", "emp_dp_launch.h", "emp_tail_launch.h", "emp_frenet_core.h", "emp_qp_core.h", "emp_st_core.h", "emp_st_backend_core.h")]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", SRC, "-o", OUT],
@@ -65,4 +65,13 @@ def load():
     lib.hc_edge_tensor_elems.argtypes = [i] * 4
     lib.hc_edge_ring_constants.restype = None
     lib.hc_edge_ring_constants.argtypes = [i, p]
+    for name, n_args in (("project", 2), ("reference_line", 1), ("cycle_qp", 5), ("cycle_cartesian", 5), ("path_qp", 2), ("smooth", 2),
+                         ("speed_front", 2), ("speed_dp", 2), ("st_edge_cost", 3), ("speed_qp", 1), ("merge", 2)):
+        fn = getattr(lib, "hc_plan_" + name)
+        fn.restype = C.c_char_p
+        fn.argtypes = [i] * n_args + [p]
+    lib.hc_tail_layout.restype = i
+    lib.hc_tail_layout.argtypes = [C.c_char_p, i, i, i, p]
+    lib.hc_tail_constants.restype = None
+    lib.hc_tail_constants.argtypes = [i, i, p]
     return lib

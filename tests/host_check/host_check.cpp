@@ -8,6 +8,10 @@
 #include "../../emplanner_carla_amd/csrc/emp_qp_core.h"
 #include "../../emplanner_carla_amd/csrc/emp_st_core.h"
 #include "../../emplanner_carla_amd/csrc/emp_st_backend_core.h"
+#include "../../emplanner_carla_amd/csrc/emp_tail_launch.h"
+
+#include <initializer_list>
+#include <string_view>
 
 using namespace emp;
 
@@ -198,6 +202,77 @@ void hc_edge_ring_constants(int max_obs, long long* out) {
     out[1] = kRingSlots;
     out[2] = kRingMaxCol;
     out[3] = edge_ring_bytes(max_obs);
+}
+
+// ---- launch plans and LDS layouts of every other kernel with dynamic LDS (emp_tail_launch.h) -------------------------------
+// A plan: its nine fields into `out` (zeros when refused), the refusal text or NULL returned.
+static const char* hc_put(const TailPlan& p, long long* out) {
+    const long long v[9] = {p.gp, p.r, p.wide, p.m32, p.spw, p.grid, p.grid_y, p.block, (long long)p.lds};
+    for (int i = 0; i < 9; ++i) out[i] = p.error ? 0 : v[i];
+    return p.error;
+}
+const char* hc_plan_project(int B, int max_ref, long long* out) { return hc_put(plan_project(B, max_ref), out); }
+const char* hc_plan_reference_line(int B, long long* out) { return hc_put(plan_reference_line(B), out); }
+const char* hc_plan_cycle_qp(int B, int max_pts, int max_obs, int decimate, int form, long long* out) {
+    return hc_put(plan_cycle_qp(B, max_pts, max_obs, decimate, form, 0), out);
+}
+const char* hc_plan_cycle_cartesian(int B, int max_ref, int max_pts, int path_cap, int form, long long* out) {
+    return hc_put(plan_cycle_cartesian(B, max_ref, max_pts, path_cap, form), out);
+}
+const char* hc_plan_path_qp(int B, int max_pts, long long* out) { return hc_put(plan_path_qp(B, max_pts), out); }
+const char* hc_plan_smooth(int B, int max_pts, long long* out) { return hc_put(plan_smooth(B, max_pts), out); }
+const char* hc_plan_speed_front(int B, int W, long long* out) { return hc_put(plan_speed_front(B, W), out); }
+const char* hc_plan_speed_dp(int B, int max_obs, long long* out) { return hc_put(plan_speed_dp(B, max_obs), out); }
+const char* hc_plan_st_edge_cost(int B, int n_edges, int max_obs, long long* out) {
+    return hc_put(plan_st_edge_cost(B, n_edges, max_obs), out);
+}
+const char* hc_plan_speed_qp(int B, long long* out) { return hc_put(plan_speed_qp(B), out); }
+const char* hc_plan_merge(int B, int max_path, long long* out) { return hc_put(plan_merge(B, max_path), out); }
+
+// A layout: its positions counted from 0, in the struct's order, `end` last; returns how many.  a, b, c are the layout
+// function's own arguments, in its order.
+int hc_tail_layout(const char* name, int a, int b, int c, long long* out) {
+    const LdsCount z = 0;
+    const std::string_view n(name);
+    int k = 0;
+    auto put = [&](std::initializer_list<LdsCount> v) {
+        for (LdsCount x : v) out[k++] = (long long)x;
+        return k;
+    };
+    if (n == "project") { const auto L = project_lds(z, a); return put({L.lx, L.ly, L.lth, L.lk, L.sm, L.lcos, L.lsin, L.end}); }
+    if (n == "smooth") { const auto L = smooth_lds(z, a); return put({L.qmem, L.theta, L.end}); }
+    if (n == "ref_line") { const auto L = ref_line_lds(z); return put({L.gxy, L.smooth.qmem, L.smooth.theta, L.end}); }
+    if (n == "path_qp") { const auto L = path_qp_lds(z, a); return put({L.qmem, L.end}); }
+    if (n == "cycle_qp") { const auto L = cycle_qp_lds(z, a != 0, b, c); return put({L.sd, L.ld, L.lmin, L.lmax, L.ql, L.otab, L.qmem, L.end}); }
+    if (n == "cartesian") { const auto L = cartesian_lds(z, a, b); return put({L.sm, L.txy, L.th, L.qmem, L.end}); }
+    if (n == "cartesian_scene") { const auto L = cartesian_scene_lds(z, a, b); return put({L.sm, L.txy, L.th, L.px, L.py, L.end}); }
+    if (n == "cartesian_rows") return put({cartesian_rows_words(a, b, c)});
+    if (n == "speed_qp") { const auto L = speed_qp_lds(z); return put({L.cc, L.qmem, L.flag, L.end}); }
+    if (n == "merge") { const auto L = merge_lds(z, a); return put({L.ps, L.px, L.py, L.ph, L.pk, L.end}); }
+    if (n == "speed_front") { const auto L = speed_front_lds(z, a); return put({L.chord, L.i2s, L.end}); }
+    if (n == "st_edge") { const auto L = st_edge_lds(z, a); return put({L.s_in, L.s_out, L.t_in, L.t_out, L.ux, L.uy, L.len, L.end}); }
+    if (n == "speed_dp") {
+        const auto L = speed_dp_lds(z, a);
+        return put({L.o_s_in, L.o_s_out, L.o_t_in, L.o_t_out, L.o_ux, L.o_uy, L.o_len, L.iv, L.node_c, L.t_tab, L.s_tab, L.part_c, L.p_cost,
+                    L.p_sdot, L.row0, L.colmask, L.list_s, L.list_c, L.part_k, L.t_node, L.end});
+    }
+    return 0;
+}
+
+// what the layouts are made of: the solvers' storage for n stations / points, and the rows path QP's stride and capacity
+void hc_tail_constants(int n, int max_obs, long long* out) {
+    out[0] = path_qp_words(n);
+    out[1] = path_qp_words_pair();
+    out[2] = kPathQpPairStations;
+    out[3] = BoxRangeQp::words(n, n);
+    out[4] = stb::speed_qp_words(stb::kQp);
+    out[5] = kHalfWave;
+    out[6] = kRefLinePoints;
+    out[7] = PathQpRowsLayout<8, 3>::stride(max_obs);
+    out[8] = PathQpRowsLayout<8, 4>::stride(max_obs);
+    out[9] = PathQpRowsLayout<16, 4>::stride(max_obs);
+    out[10] = kStWaves * (kStListCap + 1);
+    out[11] = kStParts;
 }
 
 }  // extern "C"

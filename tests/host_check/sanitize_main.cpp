@@ -1,5 +1,5 @@
 // sanitize_main.cpp - the host-side logic of the library (the scalar cores the kernels are built from: emp_core.h,
-// emp_frenet_core.h, emp_qp_core.h, emp_st_core.h, emp_st_backend_core.h, and the launch plans of emp_dp_launch.h, reached
+// emp_frenet_core.h, emp_qp_core.h, emp_st_core.h, emp_st_backend_core.h, and the launch plans of emp_dp_launch.h and emp_tail_launch.h, reached
 // through host_check.cpp's entry points) driven with deterministic random and hostile inputs under -fsanitize=address,undefined.  Test tool only:
 // tests/test_host_logic.py builds and runs it; any sanitizer report makes it exit non-zero.
 //
@@ -35,6 +35,15 @@ const char* hc_plan_sweep(int, int, int, int, long long*);
 const char* hc_plan_fused(int, int, int, int, long long*);
 const char* hc_plan_enrich(int, int, int, int, int, long long*);
 long long hc_edge_tensor_elems(int, int, int, int);
+const char* hc_plan_project(int, int, long long*);
+const char* hc_plan_cycle_qp(int, int, int, int, int, long long*);
+const char* hc_plan_cycle_cartesian(int, int, int, int, int, long long*);
+const char* hc_plan_path_qp(int, int, long long*);
+const char* hc_plan_smooth(int, int, long long*);
+const char* hc_plan_speed_front(int, int, long long*);
+const char* hc_plan_speed_dp(int, int, long long*);
+const char* hc_plan_st_edge_cost(int, int, int, long long*);
+const char* hc_plan_merge(int, int, long long*);
 }
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ull;
@@ -160,6 +169,29 @@ int main() {
                     sink += (double)(hc_edge_tensor_elems(row, col, B, 0) & 1) + (double)(hc_edge_tensor_elems(row, col, B, 1) & 1);
                     calls += 18;
                 }
+    // ---- the other launch plans (emp_tail_launch.h): every capacity at its entry point's limits, and the two no entry point
+    // bounds (max_ref, max_path) up to 2^31 - 1
+    for (int B : {0, 1, 9, 4096, 2147483647})
+        for (int big : {1, 2, 51, 256, 4096, 20480, 20481, 2147483647}) {
+            long long out[9];
+            sink += hc_plan_project(B, big, out) != nullptr;
+            sink += hc_plan_merge(B, big, out) != nullptr;
+            for (int max_pts : {1, 2, 26, 34, 66, 67, 255, 256}) {
+                sink += hc_plan_path_qp(B, max_pts, out) != nullptr;
+                sink += hc_plan_smooth(B, max_pts, out) != nullptr;
+                sink += hc_plan_speed_front(B, max_pts + 2, out) != nullptr;
+                for (int v = 0; v < 4; ++v) {
+                    sink += hc_plan_cycle_qp(B, max_pts, v ? 259 : 1, 1 + (v & 1), v >> 1, out) != nullptr;
+                    sink += hc_plan_cycle_cartesian(B, big, max_pts, (max_pts + (v & 1)) / (1 + (v & 1)) + 1, v >> 1, out) != nullptr;
+                }
+                calls += 11;
+            }
+            for (int slots : {1, 32, 33, 64}) {
+                sink += hc_plan_speed_dp(B, slots, out) != nullptr;
+                sink += hc_plan_st_edge_cost(B < 65536 ? B : 65535, big, slots, out) != nullptr;
+            }
+            calls += 10;
+        }
     std::printf("sanitize_main: %ld calls, checksum %d\n", calls, (int)std::fmod(std::fabs(sink), 1000.0));
     return 0;
 }

@@ -833,23 +833,41 @@ def test_full_cycle_on_the_wide_lattice_stage_by_stage(planner):
     assert checked >= 4
 
 
-@pytest.mark.parametrize("col,max_pts,stations", [(33, None, 33), (34, 68, 34), (34, None, 34)])
+#: (lattice columns, max_pts or None for the default 2 col + 1, stations of a scene at size): the launch classes these reach are
+#: asserted on the CPU, tests/test_host_logic.py::test_path_qp_size_limit_cases_reach_every_launch_class
+PATH_QP_LIMIT_CASES = [(33, None, 33), (34, 68, 34), (34, None, 34), (26, 52, 26), (26, None, 26), (35, None, 35), (66, 132, 66),
+                       (66, None, 66), (67, None, 67), (21, None, 21), (22, None, 22)]
+#: seeds 300 .. 315, but 300 .. 331 where max_pts cuts off the scenes with one station more (16 seeds leave 9 of them)
+PATH_QP_LIMIT_SEEDS = {(26, 52): 32}
+
+
+@pytest.mark.parametrize("col,max_pts,stations", PATH_QP_LIMIT_CASES)
 def test_path_qp_at_its_size_limits(planner, col, max_pts, stations):
     """The cycle's path QP packs eight scenes into a wavefront while a scene has at most 34 stations (R = 4 stations per lane
-    of an 8-lane group: every lane busy), four up to 66 (16-lane groups); the two-scenes-per-wavefront form
-    (EMP_OPT_PATH_QP_FORM = 1, the child run of tests/test_gpu_fuzz.py) holds 34 stations per half-wave, with LDS arrays
-    addressed by fixed strides and unclamped neighbour indices.  33 and 34 stations through the narrow kernel, 34 through the
-    wide one (the output capacity decides), each against oracle/ref_port.plan_cycle."""
+    of an 8-lane group: every lane busy; R = 3 up to 26), four up to 66 (16-lane groups), one beyond; the
+    two-scenes-per-wavefront form (EMP_OPT_PATH_QP_FORM = 1, the child run of tests/test_gpu_fuzz.py) holds 34 stations per
+    half-wave, with LDS arrays addressed by fixed strides and unclamped neighbour indices.  The output capacity max_pts decides
+    (emp_tail_launch.h plan_cycle_qp: ceil(max_pts / 2) stations), and the Cartesian tail's kernel follows it too
+    (plan_cycle_cartesian: that many + 2 points): the cases put a launch at and next to every capacity at which the path QP's
+    plan changes the kernel - 26 | 27, 34 | 35, 66 | 67 stations - and the Cartesian tail's at 24 | 25 points and on both sides of
+    32 | 33 (29, 36) and 64 | 65 (38, 68), with scenes of `col` stations (a few have one more: truncated where max_pts cuts them
+    off), each against oracle/ref_port.plan_cycle.  The first
+    nine scenes planned alone - a last wavefront with one scene in it, whichever kernel - must give the same bits."""
     from emplanner_carla_amd.api import dp_params_from_cfg, qp_params, smooth_params
     cfg = S.LatticeConfig(f"limits_{col}x5", row=5, col=col, sample_s=2.0, sample_l=1.0, sampling_res=1, n_obs=4)
-    seeds = list(range(300, 316))
+    seeds = list(range(300, 300 + PATH_QP_LIMIT_SEEDS.get((col, max_pts), 16)))
     b = S.make_batch(seeds, cfg)
     B, P = b.ref.shape[:2]
     kwargs = {} if max_pts is None else {"max_pts": max_pts}
-    r = planner.plan_cycle(dp_params_from_cfg(cfg), qp_params(obs_length=cfg.obs_length, obs_width=cfg.obs_width),
-                           smooth_params(), ref_line=b.ref, n_ref=np.full(B, P, np.int32), origin_xy=b.origin_xy,
-                           start_xy=b.start_xy, start_v=b.start_v, start_a=b.start_a, obs_xy=b.obs_xy, n_obs=b.n_obs,
-                           **kwargs)
+
+    def plan(n):
+        return planner.plan_cycle(dp_params_from_cfg(cfg), qp_params(obs_length=cfg.obs_length, obs_width=cfg.obs_width),
+                                  smooth_params(), ref_line=b.ref[:n], n_ref=np.full(n, P, np.int32), origin_xy=b.origin_xy[:n],
+                                  start_xy=b.start_xy[:n], start_v=b.start_v[:n], start_a=b.start_a[:n], obs_xy=b.obs_xy[:n],
+                                  n_obs=b.n_obs[:n], **kwargs)
+    r, r9 = plan(B), plan(9)
+    for k in ("dp_rows", "dp_len", "path_s", "path_l", "path_len", "traj", "traj_len", "status"):
+        assert np.array_equal(np.asarray(getattr(r9, k)), np.asarray(getattr(r, k))[:9], equal_nan=True), f"nine scenes alone: {k}"
     kw = dict(sampling_res=cfg.sampling_res, row=cfg.row, col=cfg.col, sample_s=cfg.sample_s, sample_l=cfg.sample_l)
     compared = at_size = 0
     for i in range(B):

@@ -499,3 +499,234 @@ def test_edge_tensor_elems_is_the_size_of_the_tiled_tensor(hc):
                 assert hc.hc_edge_tensor_elems(row, col, B, 1) == tile_edges(canonical, row).size
                 assert hc.hc_edge_tensor_elems(row, col, B, 0) == canonical.size
     assert hc.hc_edge_tensor_elems(33, 4, 5, 1) == 5 * 3 * 33 * 33         # beyond 32 rows: canonical whatever is asked
+
+
+# ---- launch plans and LDS layouts of the other kernels with dynamic LDS (csrc/emp_tail_launch.h) -----------------------------
+# per plan: how many inputs lead a row of tests/golden/tail_launch_plans.npz (the hc_plan_* arguments, in order)
+TAIL_PLANS = {"project": 2, "reference_line": 1, "cycle_qp": 5, "cycle_cartesian": 5, "path_qp": 2, "smooth": 2, "speed_front": 2,
+              "speed_dp": 2, "st_edge_cost": 3, "speed_qp": 1, "merge": 2}
+TAIL_FIELDS = ("gp", "r", "wide", "m32", "spw", "grid", "grid_y", "block", "lds")
+LDS_CU, LDS_DEFAULT = 160 * 1024, 48 * 1024
+
+
+def _tail_plan(hc, name, args):
+    """(refusal text or None, the plan's fields by name)"""
+    out = np.zeros(len(TAIL_FIELDS), dtype=np.int64)
+    err = getattr(hc, "hc_plan_" + name)(*args, out.ctypes.data)
+    return (None if err is None else err.decode()), dict(zip(TAIL_FIELDS, out.tolist()))
+
+
+def _tail_layout(hc, name, a=0, b=0, c=0):
+    out = np.zeros(24, dtype=np.int64)
+    n = hc.hc_tail_layout(name.encode(), a, b, c, out.ctypes.data)
+    assert n > 0, name
+    return out[:n].tolist()
+
+
+def _tail_constants(hc, n, max_obs=0):
+    out = np.zeros(12, dtype=np.int64)
+    hc.hc_tail_constants(n, max_obs, out.ctypes.data)
+    return dict(zip(("path_qp_words", "pair_words", "pair_stations", "box_words", "speed_qp_words", "half_wave", "ref_points",
+                     "stride_8_3", "stride_8_4", "stride_16_4", "st_list", "st_parts"), out.tolist()))
+
+
+def test_tail_launch_plans_match_the_pinned_table(hc):
+    """Every launch plan of emp_tail_launch.h on the points of tests/golden/tail_launch_plans.npz: max_pts {2, 8, 23 .. 27, 32 ..
+    35, 51 .. 53, 64 .. 68, 128, 255, 256} x obstacle slots {1, 8, 32, 33, 64, 65, 253, 256} x max_ref {51, 61, 64, 65, 256, 4096,
+    5000} x decimate {1, 2} x midpoint {0, 1} x B {0, 1, 7, 9, 64, 4096} x both values of path_qp_form and cartesian_form, less what an
+    entry point rejects before it launches (max_ref < 2; max_pts = 256 in a cycle; more than 64 slots in the speed stages); the
+    merge at path lengths either side of its entry point's 64 KB.  Kernel instantiation, grid, block, LDS bytes and refusals with
+    their text are compared.  The table holds what the launchers computed inline before the plans existed (commit 429a7cf: those
+    lines, unchanged, behind a stub context that records each launch) - a slip in them shows in no parity test at the sizes the
+    suite runs, only as an LDS access out of bounds at a capacity nobody runs."""
+    g = load_golden("tail_launch_plans.npz")
+    messages, fields = [str(m) for m in g["messages"]], [str(f) for f in g["fields"]]
+    assert set(TAIL_PLANS) == set(g.files) - {"messages", "fields"}
+    assert len(g["cycle_qp"]) == 6 * 21 * 8 * 2 * 2 and len(g["cycle_cartesian"]) == 6 * 21 * 7 * 2 * 2 * 2
+    for name, n_in in TAIL_PLANS.items():
+        for row in g[name].tolist():
+            err, p = _tail_plan(hc, name, row[:n_in])
+            got = [0 if err is None else 1 + messages.index(err)] + [p[f] for f in fields[1:]]
+            assert got == row[n_in:], f"{name}{tuple(row[:n_in])}: {dict(zip(fields, got))} != {dict(zip(fields, row[n_in:]))}"
+
+
+def test_tail_plan_invariants(hc):
+    """What every plan on the pinned grid must satisfy, whatever the tuning: the LDS bytes are the layout's total times the scenes
+    (groups) per block and fit a compute unit, or the plan is refused; the chosen instantiation holds the capacity (GP R + 2
+    stations for the rows path QP, 34 for the pair form, GP R points for the rows Cartesian tail, the narrow smoothers up to 32
+    points); the grid covers the batch.  The four speed-stage launches had no LDS opt-in before the plans: three stay below
+    the default 48 KB over everything their entry points accept (speed_front: max_pts <= 255; st_edge_cost and speed_qp: <= 64
+    slots), the speed DP does not from 53 slots on - which is why every plan's launch goes through set_lds."""
+    g = load_golden("tail_launch_plans.npz")
+    rows_cap = {(8, 3): 24, (8, 4): 32, (16, 4): 64}
+    seen = set()
+    for name, n_in in TAIL_PLANS.items():
+        for row in g[name].tolist():
+            args = row[:n_in]
+            err, p = _tail_plan(hc, name, args)
+            what = f"{name}{tuple(args)}"
+            B = args[0]
+            if B == 0 or (name == "st_edge_cost" and args[1] == 0):
+                # nothing to launch: all zeros, and never refused - but by emp_path_speed_merge, which checks before it stages
+                assert not any(p.values()) and (err is None or name == "merge"), what
+                continue
+            if err is not None:
+                continue
+            assert 0 < p["lds"] <= LDS_CU and p["spw"] >= 1 and p["block"] % 64 == 0, what
+            if name == "st_edge_cost":
+                assert p["grid"] * 64 >= args[1] and p["grid_y"] == B, what
+            else:
+                assert p["grid"] * p["spw"] >= B > (p["grid"] - 1) * p["spw"] and p["grid_y"] == 1, what
+            if name == "cycle_qp":
+                _, max_pts, mo, dec, form = args
+                cap = (max_pts + dec - 1) // dec
+                k = _tail_constants(hc, cap, mo)
+                if p["r"]:
+                    assert form == 0 and (p["gp"], p["r"]) in rows_cap and p["spw"] == 64 // p["gp"], what
+                    assert cap <= rows_cap[p["gp"], p["r"]] + 2, what
+                    assert all(cap > c + 2 for (gp, r), c in rows_cap.items() if c < rows_cap[p["gp"], p["r"]]), what   # the smallest that holds it
+                    assert p["lds"] == p["spw"] * k[f"stride_{p['gp']}_{p['r']}"] * 8, what
+                else:
+                    assert form == 1 or cap > 66, what
+                    assert (p["gp"], p["spw"]) == ((32, 2) if cap <= 34 and form == 1 else (64, 1)), what
+                    assert k["pair_stations"] == 34, what
+                    assert p["lds"] == p["spw"] * _tail_layout(hc, "cycle_qp", p["gp"] == 32, cap, mo)[-1] * 8, what
+                seen.add(("qp", p["gp"], p["r"]))
+            elif name == "cycle_cartesian":
+                _, max_ref, max_pts, path_cap, form = args
+                cap = path_cap + 1
+                if p["r"]:
+                    assert form == 0 and cap <= rows_cap[p["gp"], p["r"]] and p["spw"] == 32 // p["gp"], what
+                    assert all(cap > c for c in rows_cap.values() if c < rows_cap[p["gp"], p["r"]]), what
+                    assert p["lds"] == _tail_layout(hc, "cartesian_rows", p["spw"], max_ref, cap)[0] * 8, what
+                else:
+                    assert (form == 1 or cap > 64) and p["spw"] == 1 and p["wide"] == (cap > 32), what
+                    assert p["lds"] == _tail_layout(hc, "cartesian", max_ref, cap)[-1] * 8, what
+                seen.add(("cart", p["gp"], p["r"], p["wide"]))
+            else:
+                layout, largs, groups = {"project": ("project", args[1:], 1), "reference_line": ("ref_line", [], 1),
+                                         "path_qp": ("path_qp", args[1:], 1), "smooth": ("smooth", args[1:], 1),
+                                         "speed_front": ("speed_front", args[1:], 1), "speed_dp": ("speed_dp", args[1:], 1),
+                                         "st_edge_cost": ("st_edge", args[2:], 1), "speed_qp": ("speed_qp", [], 2),
+                                         "merge": ("merge", args[1:], 1)}[name]
+                total = _tail_layout(hc, layout, *largs)[-1]
+                assert p["spw"] == groups, what
+                if name == "speed_dp":
+                    assert p["lds"] == (total + 7) // 8 * 8 and p["block"] == 320 and p["m32"] == (args[1] <= 32), what     # (bytes)
+                else:
+                    assert p["lds"] == groups * total * 8 and p["block"] == 64, what
+                if name == "smooth":
+                    assert p["wide"] == (args[1] > 32), what
+                if name == "merge":
+                    assert p["lds"] <= 64 * 1024, what
+    assert seen >= {("qp", 8, 3), ("qp", 8, 4), ("qp", 16, 4), ("qp", 32, 0), ("qp", 64, 0), ("cart", 8, 3, 0), ("cart", 8, 4, 0),
+                    ("cart", 16, 4, 0), ("cart", 0, 0, 0), ("cart", 0, 0, 1)}
+    # the speed stages over the whole range of their entry points, not the grid's points alone
+    for B in (1, 9, 4096):
+        for max_pts in range(2, 256):
+            err, p = _tail_plan(hc, "speed_front", [B, max_pts + 2])
+            assert err is None and p["lds"] <= LDS_DEFAULT
+        for slots in range(1, 65):
+            for name, args in (("st_edge_cost", [B, 1000, slots]), ("speed_dp", [B, slots])):
+                err, p = _tail_plan(hc, name, args)
+                assert err is None and (p["lds"] <= LDS_DEFAULT or (name == "speed_dp" and slots >= 53))
+        err, p = _tail_plan(hc, "speed_qp", [B])
+        assert err is None and p["lds"] <= LDS_DEFAULT
+    assert _tail_plan(hc, "speed_dp", [1, 52])[1]["lds"] <= LDS_DEFAULT < _tail_plan(hc, "speed_dp", [1, 53])[1]["lds"]
+
+
+def _in_order(pos, sizes):
+    """positions (the last one `end`) of arrays of these sizes: in order, none overlapping, nothing behind the last"""
+    assert len(pos) == len(sizes) + 1 and pos[0] == 0
+    assert [b - a for a, b in zip(pos, pos[1:])] == list(sizes), (pos, sizes)
+
+
+def test_tail_layouts_hold_what_the_kernels_index(hc):
+    """The LDS layouts of emp_tail_launch.h against the loops of the kernels that use them: arrays in order, none overlapping,
+    each as long as the kernel indexes it.  The bounds, read from the kernels:
+      frenet_project_wave_kernel   all seven arrays at i < P <= max_ref (and entry 0 for an empty line; max_ref >= 2)
+      smooth_wave_kernel           smooth_pair_wave binds x and y to BoxRangeQp::words(m, m) doubles each from `qmem`;
+                                   heading_kappa_wave writes theta [i], i < m, from `theta` TAKEN AT m <= cap
+      reference_line_wave_kernel   gxy [2 lane + 1], lane < 51; then as smooth_wave_kernel with m = 51
+      path_qp_wave_kernel          path_qp_group<64> takes path_qp_words(n) doubles, n <= cap
+      cycle_qp_body, R == 0        sd, ld [i], i < n <= cap; lmin, lmax [i], i < n; ql [i], i < n; otab [4 k + 3], k < max_obs;
+                                   qmem: path_qp_words(n) (one scene per wavefront), path_qp_words_pair() with n <= 34 (two)
+      cycle_cartesian_body         sm [i], i < P <= max_ref; txy [2 q + 1], q < cap; th [i], i < m <= cap; qmem 2 words(m, m)
+      cycle_cartesian_rows_kernel  the same per scene, px / py [j], j < m <= cap; the fall-back's 2 words(m2, m2) behind the scenes
+      stb::speed_qp_kernel         cc [kQp + 2]; the solver's speed_qp_words(17) - 19 doubles; one flag word
+      stb::merge_kernel            five arrays at i < width <= max_path
+      speed_front_wave_kernel      chord [i], i2s [i], i < W
+      st_edge_cost_kernel          seven arrays at j < max_obs
+      speed_dp_kernel              see emp_st_kernels.h StLds: [max_obs] x 7, iv [2][max_obs][5][2], node_c [40][max_obs], t_tab
+                                   [10], s_tab [40], part_c [8][40], p_cost and p_sdot [2][40], row0 [16], colmask [2][2] 64-bit,
+                                   list_s [5][257] doubles, list_c [5][257] 32-bit, part_k [8][40] and t_node [40][16] bytes"""
+    for n in (1, 2, 51, 64, 65, 256, 4096):
+        _in_order(_tail_layout(hc, "project", n), [n] * 7)
+        _in_order(_tail_layout(hc, "merge", n), [n] * 5)
+        _in_order(_tail_layout(hc, "speed_front", n), [n] * 2)
+    for k in (1, 8, 32, 33, 64):
+        _in_order(_tail_layout(hc, "st_edge", k), [k] * 7)
+        c = _tail_constants(hc, 4)
+        assert (c["st_list"], c["st_parts"]) == (5 * 257, 8)
+        pos = _tail_layout(hc, "speed_dp", k)                                                   # bytes
+        _in_order(pos, [8 * k] * 7 + [8 * 20 * k, 8 * 40 * k, 80, 320, 8 * 8 * 40, 640, 640, 128, 32, 8 * c["st_list"], 4 * c["st_list"],
+                        8 * 40, 40 * 16])
+        assert all(p % 8 == 0 for p in pos[:17]) and pos[17] % 4 == 0                          # doubles and codes aligned
+    words = lambda m: _tail_constants(hc, m)["box_words"]
+    theta_prev = -1
+    for cap in range(2, 257):
+        c = _tail_constants(hc, cap)
+        _in_order(_tail_layout(hc, "smooth", cap), [2 * c["box_words"], cap])
+        _in_order(_tail_layout(hc, "path_qp", cap), [c["path_qp_words"]])
+        # theta at the scene's own m: never behind theta at the capacity, and its m headings end inside the capacity's total
+        q, theta, end = _tail_layout(hc, "smooth", cap)
+        assert theta > theta_prev
+        theta_prev = theta
+        for m in (2, cap // 2 + 1, cap - 1, cap):
+            qm, tm, em = _tail_layout(hc, "smooth", m)
+            assert tm <= theta and em <= end and words(m) <= words(cap)
+        assert _tail_constants(hc, cap - 1)["path_qp_words"] <= c["path_qp_words"]           # a scene with n <= cap stations fits
+    assert _tail_layout(hc, "ref_line") == [0, 102, 102 + 2 * words(51), 102 + 2 * words(51) + 51]
+    sq = _tail_constants(hc, 4)["speed_qp_words"]
+    _in_order(_tail_layout(hc, "speed_qp"), [19, sq - 19, 1])
+    for cap in (1, 2, 8, 26, 27, 34, 35, 66, 67, 128, 255):
+        for mo in (1, 8, 33, 64, 65, 256, 259):
+            c = _tail_constants(hc, cap)
+            _in_order(_tail_layout(hc, "cycle_qp", 0, cap, mo), [cap] * 5 + [4 * mo, c["path_qp_words"]])
+            if cap <= c["pair_stations"]:
+                _in_order(_tail_layout(hc, "cycle_qp", 1, cap, mo), [cap] * 5 + [4 * mo, c["pair_words"]])
+    for cap in (3, 24, 25, 32, 33, 64, 65, 129, 257):
+        for max_ref in (2, 51, 61, 256, 4096):
+            _in_order(_tail_layout(hc, "cartesian", max_ref, cap), [max_ref, 2 * cap, cap, 2 * words(cap)])
+            scene = _tail_layout(hc, "cartesian_scene", max_ref, cap)
+            _in_order(scene, [max_ref, 2 * cap, cap, cap, cap])
+            for spw in (2, 4):
+                assert _tail_layout(hc, "cartesian_rows", spw, max_ref, cap) == [spw * scene[-1] + 2 * words(cap)]
+
+
+def test_path_qp_size_limit_cases_reach_every_launch_class(hc):
+    """tests/test_gpu_cycle.py::test_path_qp_at_its_size_limits plans scenes at these (columns, max_pts) with the default
+    decimation (2) and midpoints (1): which kernels the plans give each case - asserted here, on the CPU - and that together the
+    cases stand on both sides of every capacity at which a plan changes the kernel."""
+    from tests.test_gpu_cycle import PATH_QP_LIMIT_CASES, PATH_QP_LIMIT_SEEDS
+    want = {(33, None): ((8, 4, 34), (16, 4, 36)), (34, 68): ((8, 4, 34), (16, 4, 36)), (34, None): ((16, 4, 35), (16, 4, 37)),
+            (26, 52): ((8, 3, 26), (8, 4, 28)), (26, None): ((8, 4, 27), (8, 4, 29)), (35, None): ((16, 4, 36), (16, 4, 38)),
+            (66, 132): ((16, 4, 66), (0, 0, 68)), (66, None): ((64, 0, 67), (0, 0, 69)), (67, None): ((64, 0, 68), (0, 0, 70)),
+            (21, None): ((8, 3, 22), (8, 3, 24)), (22, None): ((8, 3, 23), (8, 4, 25))}
+    assert {(c, m) for c, m, _ in PATH_QP_LIMIT_CASES} == set(want)
+    caps_qp, caps_cart = set(), set()
+    for col, max_pts, at_size in PATH_QP_LIMIT_CASES:
+        n_seeds = PATH_QP_LIMIT_SEEDS.get((col, max_pts), 16)
+        assert at_size == col
+        M = max_pts or 2 * col + 1                      # api.max_path_points: sample_s = 2, sampling_res = 1
+        stations, points = (M + 1) // 2, (M + 1) // 2 + 2
+        for B in (n_seeds, 9):
+            err, q = _tail_plan(hc, "cycle_qp", [B, M, 4, 2, 0])
+            err2, c = _tail_plan(hc, "cycle_cartesian", [B, 61, M, stations + 1, 0])
+            assert err is None and err2 is None
+            assert ((q["gp"], q["r"], stations), (c["gp"], c["r"], points)) == want[col, max_pts], (col, max_pts)
+            assert q["grid"] == -(-B // q["spw"]) and c["grid"] == -(-B // c["spw"])
+        assert B % q["spw"] == 1 % q["spw"] and B % c["spw"] == 1 % c["spw"]       # nine scenes: one in the last wavefront
+        caps_qp.add(stations)
+        caps_cart.add(points)
+    assert caps_qp >= {26, 27, 34, 35, 66, 67} and caps_cart >= {24, 25, 36, 37, 68}

@@ -39,6 +39,8 @@ GENERATORS = {
 PINNED = {
     "dp_launch_plans.npz": "the launch plans of csrc/emp_dp_launch.h as the launchers computed them at commit b1fe952 "
                            "(tests/test_host_logic.py::test_dp_launch_plans_match_the_pinned_table)",
+    "tail_launch_plans.npz": "the launch plans of csrc/emp_tail_launch.h as the launchers computed them at commit 429a7cf "
+                             "(tests/test_host_logic.py::test_tail_launch_plans_match_the_pinned_table)",
 }
 
 
