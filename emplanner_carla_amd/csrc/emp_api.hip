@@ -986,15 +986,13 @@ static int dev_cycle_cartesian(emp_ctx* ctx, int B, int max_ref, int max_pts, in
     const int cap = path_cap + 1;                                        // trajectory = planning start + path points
     // which kernel and how many scenes per wavefront: emp_tail_launch.h plan_cycle_cartesian
     const TailPlan p = plan_cycle_cartesian(B, max_ref, max_pts, path_cap, ctx->opt[EMP_OPT_CARTESIAN_FORM]);
-    if (p.r) {
-        auto k4 = p.gp == 16 ? cycle_cartesian_rows_kernel<16, 4> : p.r == 3 ? cycle_cartesian_rows_kernel<8, 3> : cycle_cartesian_rows_kernel<8, 4>;
-        const int force_fb = ctx->opt[EMP_OPT_SMOOTH_FORCE_FALLBACK] ? 1 : 0;                        // test hook
-        return launch_plan(ctx, "to_cartesian", p, k4, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref, begin_sl, path_s, path_l,
-                           path_len, traj, traj_len, status, force_fb);
-    }
-    auto kern = p.wide ? cycle_cartesian_wave_kernel_wide : cycle_cartesian_wave_kernel_narrow;
-    return launch_plan(ctx, "to_cartesian", p, kern, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref, begin_sl, path_s, path_l,
-                       path_len, traj, traj_len, status);
+    auto go = [&](auto kern, auto... hook) {
+        return launch_plan(ctx, "to_cartesian", p, kern, B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref, begin_sl, path_s, path_l,
+                           path_len, traj, traj_len, status, hook...);
+    };
+    if (p.r == 0) return go(p.wide ? cycle_cartesian_wave_kernel_wide : cycle_cartesian_wave_kernel_narrow);
+    return go(p.gp == 16 ? cycle_cartesian_rows_kernel<16, 4> : p.r == 3 ? cycle_cartesian_rows_kernel<8, 3> : cycle_cartesian_rows_kernel<8, 4>,
+              ctx->opt[EMP_OPT_SMOOTH_FORCE_FALLBACK] ? 1 : 0);                                      // (the rows smoother's test hook)
 }
 
 // ---- emp_plan_cycle's pipeline lane and cycle graph -------------------------------------------------------------------

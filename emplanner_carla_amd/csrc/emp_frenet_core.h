@@ -55,18 +55,25 @@ EMP_HD void sincos_pair(double x, double* s, double* c) {
 #endif
 }
 
-// ref: planning_utils.py:414-424 - projection on the tangent line of a matched node
+// node m advanced by ds along its tangent, (c, s) = cos / sin of m.theta (ref planning_utils.py:419-424, path_planning.py:66-75)
+EMP_HD Node node_advanced(const Node& m, double ds, double c, double s) {
+    return Node{m.x + ds * c, m.y + ds * s, m.theta + m.kappa * ds, m.kappa};
+}
+// the point at offset l along the normal of (x, y), (c, s) = cos / sin of the heading there (ref path_planning.py:32-34, :44-46)
+EMP_HD void normal_offset(double x, double y, double l, double c, double s, double* ox, double* oy) {
+    *ox = x + l * (-s);
+    *oy = y + l * c;
+}
+
+// ref: planning_utils.py:414-424 - projection on the tangent line of a matched node, cos / sin of its heading supplied (the
+// projection kernel evaluates them once per node and scene)
+EMP_HD Node project_on_cs(const Node& m, double c, double s, double x, double y) {
+    return node_advanced(m, dot2(x - m.x, y - m.y, c, s), c, s);
+}
 EMP_HD Node project_on(const Node& m, double x, double y) {
     double c, s;
     sincos_pair(m.theta, &s, &c);
-    const double ds = dot2(x - m.x, y - m.y, c, s);
-    return Node{m.x + ds * c, m.y + ds * s, m.theta + m.kappa * ds, m.kappa};
-}
-
-// the same with cos / sin of the node's heading supplied (the projection kernel evaluates them once per node and scene)
-EMP_HD Node project_on_cs(const Node& m, double c, double s, double x, double y) {
-    const double ds = dot2(x - m.x, y - m.y, c, s);
-    return Node{m.x + ds * c, m.y + ds * s, m.theta + m.kappa * ds, m.kappa};
+    return project_on_cs(m, c, s, x, y);
 }
 EMP_HD double projection_s_cs(const Node& m, double c, double s, double s_at_m, double x, double y) {
     return s_at_m + dot2(x - m.x, y - m.y, c, s);
@@ -142,27 +149,27 @@ EMP_HD bool proj_point(const double* line, const double* s_map, int n_ref, doubl
     const double ds = s - s_map[i];
     double c, sn;
     sincos_pair(m.theta, &sn, &c);
-    *out = Node{m.x + ds * c, m.y + ds * sn, m.theta + m.kappa * ds, m.kappa};
+    *out = node_advanced(m, ds, c, sn);
     *idx = i;
     return true;
 }
 
+// Centred difference of v[0..m) (stride `stride`) at i: the mean of the forward differences on either side, the ends replicated
+// (ref planning_utils.py:193-203 and :213-222).  Needs m >= 2.
+EMP_HD double centred_diff(const double* v, int stride, int i, int m) {
+    const int a = (i - 1 > 0) ? i - 1 : 0, b = (i < m - 2) ? i : m - 2;
+    return ((v[(a + 1) * stride] - v[a * stride]) + (v[(b + 1) * stride] - v[b * stride])) / 2.0;
+}
+
 // ref: cal_heading_kappa, planning_utils.py:185-228.  xy interleaved [m][stride]; needs m >= 2.
 EMP_HD void heading_kappa(const double* xy, int stride, int m, double* theta, int tstride, double* kappa, int kstride) {
-    // theta first (node value = mean of adjacent forward differences, ends replicated)
     for (int i = 0; i < m; ++i) {
-        const int a = (i - 1 > 0) ? i - 1 : 0, b = (i < m - 2) ? i : m - 2;
-        const double dx = ((xy[(a + 1) * stride] - xy[a * stride]) + (xy[(b + 1) * stride] - xy[b * stride])) / 2.0;
-        const double dy = ((xy[(a + 1) * stride + 1] - xy[a * stride + 1]) + (xy[(b + 1) * stride + 1] - xy[b * stride + 1])) / 2.0;
+        const double dx = centred_diff(xy, stride, i, m), dy = centred_diff(xy + 1, stride, i, m);
         theta[i * tstride] = atan2(dy, dx);
     }
     for (int i = 0; i < m; ++i) {
-        const int a = (i - 1 > 0) ? i - 1 : 0, b = (i < m - 2) ? i : m - 2;
-        const double dx = ((xy[(a + 1) * stride] - xy[a * stride]) + (xy[(b + 1) * stride] - xy[b * stride])) / 2.0;
-        const double dy = ((xy[(a + 1) * stride + 1] - xy[a * stride + 1]) + (xy[(b + 1) * stride + 1] - xy[b * stride + 1])) / 2.0;
-        const double dpre = theta[(a + 1) * tstride] - theta[a * tstride];
-        const double daft = theta[(b + 1) * tstride] - theta[b * tstride];
-        kappa[i * kstride] = sin((dpre + daft) / 2.0) / sqrt(dx * dx + dy * dy);
+        const double dx = centred_diff(xy, stride, i, m), dy = centred_diff(xy + 1, stride, i, m);
+        kappa[i * kstride] = sin(centred_diff(theta, tstride, i, m)) / sqrt(dx * dx + dy * dy);
     }
 }
 

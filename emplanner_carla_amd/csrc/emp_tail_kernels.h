@@ -428,31 +428,26 @@ __global__ void lmin_lmax_kernel(int B, int max_pts, int max_obs, const double* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// heading / curvature of m points held in LDS (px, py), one point per lane (ref planning_utils.py:185-228)
-// th: LDS scratch [m].  out[i*ostride + 0..3] = x, y, theta, kappa.  Contains barriers: whole wavefront calls.
+// heading / curvature of a scene's m points held in LDS (px, py), one point per lane of the scene's SL (ref planning_utils.py:185-228)
+// th: LDS scratch [m].  out[i*ostride + 0..3] = x, y, theta, kappa.  Contains a barrier: whole wavefront calls (m = 0: no point).
 // ---------------------------------------------------------------------------------------------
-__device__ inline void heading_kappa_wave(const double* px, const double* py, int m, double* th, double* out,
-                                          int ostride) {
-    const int lane = threadIdx.x & 63;
-    for (int i = lane; i < m; i += 64) {
-        const int a = (i - 1 > 0) ? i - 1 : 0, b = (i < m - 2) ? i : m - 2;
-        const double dx = ((px[a + 1] - px[a]) + (px[b + 1] - px[b])) / 2.0;
-        const double dy = ((py[a + 1] - py[a]) + (py[b + 1] - py[b])) / 2.0;
+template <int SL>
+__device__ __forceinline__ void heading_kappa_lanes(const double* px, const double* py, int m, double* th, double* out,
+                                                    int ostride) {
+    const int sl = threadIdx.x & (SL - 1);
+    for (int i = sl; i < m; i += SL) {
+        const double dx = centred_diff(px, 1, i, m), dy = centred_diff(py, 1, i, m);
         th[i] = atan2(dy, dx);
     }
     __syncthreads();
-    for (int i = lane; i < m; i += 64) {
-        const int a = (i - 1 > 0) ? i - 1 : 0, b = (i < m - 2) ? i : m - 2;
-        const double dx = ((px[a + 1] - px[a]) + (px[b + 1] - px[b])) / 2.0;
-        const double dy = ((py[a + 1] - py[a]) + (py[b + 1] - py[b])) / 2.0;
-        const double dpre = th[a + 1] - th[a], daft = th[b + 1] - th[b];
+    for (int i = sl; i < m; i += SL) {
+        const double dx = centred_diff(px, 1, i, m), dy = centred_diff(py, 1, i, m);
         double* o = out + (size_t)i * ostride;
         o[0] = px[i];
         o[1] = py[i];
         o[2] = th[i];
-        o[3] = sin((dpre + daft) / 2.0) / sqrt(dx * dx + dy * dy);
+        o[3] = sin(centred_diff(th, 1, i, m)) / sqrt(dx * dx + dy * dy);
     }
-    __syncthreads();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -498,7 +493,7 @@ __global__ __launch_bounds__(64) void smooth_wave_kernel(int B, int max_pts, int
     int it = 0, rc = 2;
     double *px = nullptr, *py = nullptr;
     if (m <= cap) rc = smooth_pair_wave<WIDE>(smooth_lds(lds, m).qmem, xy + (size_t)b * max_pts * 2, 2, m, sx, sy, &px, &py, &it);
-    if (rc == 0) heading_kappa_wave(px, py, m, smooth_lds(lds, m).theta, out + (size_t)b * max_pts * 4, 4);
+    if (rc == 0) heading_kappa_lanes<64>(px, py, m, smooth_lds(lds, m).theta, out + (size_t)b * max_pts * 4, 4);
     if ((threadIdx.x & 63) == 0) {
         if (iters) iters[b] = it;
         status[b] = rc ? kStSmoothFailed : 0;
@@ -535,12 +530,8 @@ __global__ __launch_bounds__(64) void reference_line_wave_kernel(int B, int max_
         const int st = pre_match_index[b];
         if (P < 1 || ((!is_first_run || !is_first_run[b]) && (st < 0 || st >= P))) {
             fail = kStSOutOfRange;                       // the reference raises IndexError
-        } else if (is_first_run && is_first_run[b]) {
-            m = match_scan(line, P, x, y, 0, 1, 50);     // ref :72-92
         } else {
-            const Node pm = node_at(line, st);           // ref :123-167
-            const double flag = dot2(x - pm.x, y - pm.y, cos(pm.theta), sin(pm.theta));   // ref :139 np.dot
-            m = match_scan(line, P, x, y, st, flag > 0.0 ? 1 : -1, 5);
+            m = find_match_one(line, P, x, y, !(is_first_run && is_first_run[b]), st);
         }
         // sampling (ref :244-259): the arguments are overwritten with 10 back / 40 forward
         int back = 10, fwd = 40;
@@ -569,7 +560,7 @@ __global__ __launch_bounds__(64) void reference_line_wave_kernel(int B, int max_
         double *px = nullptr, *py = nullptr;
         const int rc = smooth_pair_wave<true>(qmem, gxy, 2, kRefLinePoints, sx, sy, &px, &py, &it);
         if (rc) fail = kStSmoothFailed;
-        else heading_kappa_wave(px, py, kRefLinePoints, L.smooth.theta, out, 4);
+        else heading_kappa_lanes<64>(px, py, kRefLinePoints, L.smooth.theta, out, 4);
     }
     if (fail)
         for (int i = lane; i < kRefLinePoints * 4; i += 64) out[i] = 0.0;
@@ -597,8 +588,7 @@ __device__ inline int frenet_path_to_xy(const double* line, const double* s_map,
     }
     double pc, psn;
     sincos_pair(pr.theta, &psn, &pc);
-    target_xy[0] = pr.x + begin_l * (-psn);                                       // ref :32-34
-    target_xy[1] = pr.y + begin_l * pc;
+    normal_offset(pr.x, pr.y, begin_l, pc, psn, &target_xy[0], &target_xy[1]);    // ref :32-34
     m = 1;
     for (int i = 0; i < n; ++i) {
         const double s = path_s[i];
@@ -612,8 +602,7 @@ __device__ inline int frenet_path_to_xy(const double* line, const double* s_map,
             break;
         }
         sincos_pair(pr.theta, &psn, &pc);
-        target_xy[2 * m] = pr.x + path_l[i] * (-psn);                              // ref :44-46
-        target_xy[2 * m + 1] = pr.y + path_l[i] * pc;
+        normal_offset(pr.x, pr.y, path_l[i], pc, psn, &target_xy[2 * m], &target_xy[2 * m + 1]);   // ref :44-46
         ++m;
     }
     return m;
@@ -889,160 +878,53 @@ __device__ inline int walk_from_zero(const double* sm, int P, double s, bool* of
 }
 
 // ---------------------------------------------------------------------------------------------
-// One cycle, last part (ref path_planning.py:15-49): Frenet->Cartesian one point per lane, x / y smoothing
-// on the two half-waves, heading / curvature one point per lane.  One wavefront per scene.
-// dynamic LDS: CartesianLds (emp_tail_launch.h)
-// The reference walks the s_map index monotonically from the previous point (:42-43); with a non-decreasing
-// s_map (what cal_s_map_fun produces) that equals a running maximum of independent walks from index 0.
+// One cycle, last part (ref path_planning.py:15-49): Frenet->Cartesian one point per lane, x / y smoothing, heading / curvature
+// one point per lane.  One scene per SL lanes, 64 / SL scenes per wavefront:
+//   R == 0 (SL = 64): one scene per wavefront, smoothing on the two half-waves (smooth_pair_wave<WIDE>; WIDE == false, cap <= 32,
+//     compiles the half-wave register path only, which fits four wavefronts per SIMD).  dynamic LDS: CartesianLds.
+//   R > 0 (SL = 2 GP = 16 or 32): the x and the y smoothing problem on the scene's two GP-lane groups with R points per lane
+//     (emp_smooth_rows.h; trajectories of at most GP R points: <8, 3> the benchmark's 23, <8, 4> up to 32, <16, 4> up to 64, BASELINE
+//     configs[4]'s 63).  What the one-scene form spends per scene on 23 of 64 lanes (trigonometry) and on sweeps for two problems
+//     (smoothing) is shared by four scenes here.  A problem whose active-set classification does not settle (none on any test or
+//     benchmark scene) is solved by the whole wavefront with the half-wave solvers, one scene at a time.  dynamic LDS: a
+//     CartesianSceneLds per scene, then the fall-back solver's storage (emp_tail_launch.h cartesian_rows_words).
+// The reference walks the s_map index monotonically from the previous point (:42-43); with a non-decreasing s_map (what
+// cal_s_map_fun produces) that equals a running maximum of independent walks from index 0.
 // ---------------------------------------------------------------------------------------------
-// WIDE == false (cap <= 32, the benchmark's 23-point trajectories): only the half-wave smoothing path is
-// compiled, which fits four wavefronts per SIMD - all 4096 scenes of a batch are resident at once.
-template <bool WIDE>
-__device__ __forceinline__ void cycle_cartesian_body(
-    int B, int max_ref, int max_pts, int cap, SmoothQpParams sx, SmoothQpParams sy, const double* __restrict__ ref_line,
-    const double* __restrict__ s_map, const int* __restrict__ n_ref, const double* __restrict__ begin_sl,
-    const double* __restrict__ path_s, const double* __restrict__ path_l, const int* __restrict__ path_len,
-    double* __restrict__ traj, int* __restrict__ traj_len, int* __restrict__ status) {
+#define EMP_CARTESIAN_PARAMS                                                                                                       \
+    int B, int max_ref, int max_pts, int cap, SmoothQpParams sx, SmoothQpParams sy, const double *__restrict__ ref_line,            \
+        const double *__restrict__ s_map, const int *__restrict__ n_ref, const double *__restrict__ begin_sl,                       \
+        const double *__restrict__ path_s, const double *__restrict__ path_l, const int *__restrict__ path_len,                     \
+        double *__restrict__ traj, int *__restrict__ traj_len, int *__restrict__ status
+#define EMP_CARTESIAN_ARGS B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref, begin_sl, path_s, path_l, path_len, traj, traj_len, status
+template <int SL, int R, bool WIDE>
+__device__ __forceinline__ void cycle_cartesian_body(EMP_CARTESIAN_PARAMS, int force_fallback) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __builtin_amdgcn_s_setprio(EMP_PRIO_CART);          // as in the path QP kernel
-    const int b = blockIdx.x, lane = threadIdx.x & 63;
-    const CartesianLds<double*> L = cartesian_lds(lds, max_ref, cap);
-    double* sm = L.sm;                      // [max_ref]
-    double* txy = L.txy;                    // [cap][2] interleaved x, y
-    double* th = L.th;                      // [cap]
-    double* qmem = L.qmem;
-    const int st = status[b];
-    double* out_rows = traj + (size_t)b * (max_pts + 1) * 4;
-    auto body = [&]() -> int {          // returns the number of trajectory points (0 = none); wave-uniform control flow
-    const double* line = ref_line + (size_t)b * max_ref * 4;
-    const int P = min(max(n_ref[b], 0), max_ref);       // clamped to the row's capacity
-    const int n = path_len[b];
-    for (int i = lane; i < P; i += 64) sm[i] = s_map[(size_t)b * max_ref + i];
-    __syncthreads();
-    // planning start (ref :31-34).  Checked for a scene the path QP has refused as well: the reference ignores its solver's
-    // status (path_planning.py:211-218) and raises IndexError here all the same
-    bool off = false;
-    const double bs = begin_sl[2 * b], bl = begin_sl[2 * b + 1];
-    const int idx0 = walk_from_zero(sm, P, bs, &off);
-    if (off || P < 2) {
-        if (lane == 0) status[b] = st | kStSOutOfRange;
-        return 0;
-    }
-    if (st & (kStQpFailed | kStBoundIndex | kStTruncated)) return 0;
-    if (lane == 0) {
-        const Node m0 = node_at(line, idx0);
-        const double ds = bs - sm[idx0];
-        const double th0 = m0.theta + m0.kappa * ds;
-        double mc, msn, pc, psn;
-        sincos_pair(m0.theta, &msn, &mc);
-        sincos_pair(th0, &psn, &pc);
-        txy[0] = (m0.x + ds * mc) + bl * (-psn);
-        txy[1] = (m0.y + ds * msn) + bl * pc;
-    }
-    // path points: count = leading points with s <= s_map[-1] (ref :40-41), index = running max of walks
-    const double s_last = sm[P - 1];
-    int carry = idx0, count = n;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool in = i < n;
-        const double s = in ? path_s[(size_t)b * max_pts + i] : 0.0;
-        const int first_bad = __builtin_ffsll((long long)__ballot(in && s > s_last));   // 1-based lane, 0 if none
-        if (first_bad) count = min(count, base + first_bad - 1);
-        bool o2 = false;
-        int k = in ? walk_from_zero(sm, P, fmin(s, s_last), &o2) : 0;
-        for (int d = 1; d < 64; d <<= 1) {                 // inclusive running maximum across lanes
-            const int v = __shfl_up(k, d, 64);
-            if (lane >= d) k = max(k, v);
-        }
-        k = max(k, carry);
-        carry = __shfl(k, 63, 64);
-        if (in && i < count && i + 1 < cap) {
-            const Node mm = node_at(line, k);
-            const double ds = s - sm[k];
-            const double thp = mm.theta + mm.kappa * ds;
-            const double l = path_l[(size_t)b * max_pts + i];
-            double mc, msn, pc, psn;
-            sincos_pair(mm.theta, &msn, &mc);
-            sincos_pair(thp, &psn, &pc);
-            txy[2 * (i + 1)] = (mm.x + ds * mc) + l * (-psn);                        // ref :44-46
-            txy[2 * (i + 1) + 1] = (mm.y + ds * msn) + l * pc;
-        }
-        if (first_bad) break;
-    }
-    const int m = count + 1;
-    __syncthreads();
-    if (m > cap || m > max_pts + 1) {
-        if (lane == 0) status[b] = st | kStTruncated;
-        return 0;
-    }
-    if (m < 2) {
-        if (lane == 0) status[b] = st | kStSmoothFailed;
-        return 0;
-    }
-    int it = 0;
-    double *px = nullptr, *py = nullptr;
-    const int rc = smooth_pair_wave<WIDE>(qmem, txy, 2, m, sx, sy, &px, &py, &it);
-    if (rc) {
-        if (lane == 0) status[b] = st | kStSmoothFailed;
-        return 0;
-    }
-    heading_kappa_wave(px, py, m, th, out_rows, 4);
-    return m;
-    };
-    const int m_out = body();
-    for (int i = m_out * 4 + lane; i < (max_pts + 1) * 4; i += 64) out_rows[i] = 0.0;       // padding reads as 0
-    if (lane == 0) traj_len[b] = m_out;
-}
-
-#define EMP_CARTESIAN_ARGS B, max_ref, max_pts, cap, sx, sy, ref_line, s_map, n_ref, begin_sl, path_s, path_l, path_len, traj, traj_len, status
-__global__ __launch_bounds__(64) void cycle_cartesian_wave_kernel_wide(
-    int B, int max_ref, int max_pts, int cap, SmoothQpParams sx, SmoothQpParams sy, const double* __restrict__ ref_line,
-    const double* __restrict__ s_map, const int* __restrict__ n_ref, const double* __restrict__ begin_sl,
-    const double* __restrict__ path_s, const double* __restrict__ path_l, const int* __restrict__ path_len,
-    double* __restrict__ traj, int* __restrict__ traj_len, int* __restrict__ status) {
-    cycle_cartesian_body<true>(EMP_CARTESIAN_ARGS);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void cycle_cartesian_wave_kernel_narrow(
-    int B, int max_ref, int max_pts, int cap, SmoothQpParams sx, SmoothQpParams sy, const double* __restrict__ ref_line,
-    const double* __restrict__ s_map, const int* __restrict__ n_ref, const double* __restrict__ begin_sl,
-    const double* __restrict__ path_s, const double* __restrict__ path_l, const int* __restrict__ path_len,
-    double* __restrict__ traj, int* __restrict__ traj_len, int* __restrict__ status) {
-    cycle_cartesian_body<false>(EMP_CARTESIAN_ARGS);
-}
-#undef EMP_CARTESIAN_ARGS
-
-// ---------------------------------------------------------------------------------------------
-// The same last part of the cycle with FOUR scenes per wavefront (trajectories of at most 8 R points: R = 3 the
-// benchmark's 23, R = 4 up to 32): 16 lanes per scene - Frenet -> Cartesian one point per lane in passes of 16, the x
-// and the y smoothing problem on the scene's two 8-lane groups with R points per lane (emp_smooth_rows.h), heading /
-// curvature one point per lane again.  A quarter of the wavefronts of cycle_cartesian_wave_kernel_narrow for the same
-// work: what that kernel spends per scene on 23 of 64 lanes (trigonometry) and on sweeps for two problems (smoothing)
-// is shared by four scenes here.  A problem whose active-set classification does not settle (none on any test or
-// benchmark scene) is solved by the whole wavefront with the half-wave solvers of the narrow kernel, one scene at a time.
-// With GP = 16 a scene takes 32 lanes and trajectories of up to 64 points fit (BASELINE configs[4]'s 63): two per wavefront.
-// dynamic LDS: a CartesianSceneLds per scene, then the fall-back solver's storage (emp_tail_launch.h cartesian_rows_words)
-// ---------------------------------------------------------------------------------------------
-template <int GP, int R>
-__global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
-    int B, int max_ref, int max_pts, int cap, SmoothQpParams sx, SmoothQpParams sy, const double* __restrict__ ref_line,
-    const double* __restrict__ s_map, const int* __restrict__ n_ref, const double* __restrict__ begin_sl,
-    const double* __restrict__ path_s, const double* __restrict__ path_l, const int* __restrict__ path_len,
-    double* __restrict__ traj, int* __restrict__ traj_len, int* __restrict__ status, int force_fallback) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    __builtin_amdgcn_s_setprio(EMP_PRIO_CART);
-    constexpr int SL = 2 * GP, SPW = 64 / SL;     // lanes per scene, scenes per wavefront
+    constexpr int GP = SL / 2, SPW = 64 / SL;     // lanes per smoothing problem, scenes per wavefront
+    static_assert(R > 0 ? (SL == 16 || SL == 32) : SL == 64, "rows smoother: 16 or 32 lanes per scene; else the whole wavefront");
     const int lane = threadIdx.x & 63, sc = lane / SL, sl = lane & (SL - 1);
     const int b = blockIdx.x * SPW + sc;
     const bool present = b < B;
     const size_t bb = present ? (size_t)b : 0;
     const int per_scene = cartesian_scene_lds(0, max_ref, cap).end;
-    const CartesianSceneLds<double*> L = cartesian_scene_lds(lds + (size_t)sc * per_scene, max_ref, cap);
-    double* sm = L.sm;                           // [max_ref]
-    double* txy = L.txy;                         // [cap][2] interleaved x, y
-    double* th = L.th;                           // [cap]
-    double* px = L.px;                           // [cap] smoothed x
-    double* py = L.py;                           // [cap] smoothed y
-    double* qmem = lds + (size_t)SPW * per_scene;  // the fall-back solver's storage (whole wavefront)
+    double *sm, *txy, *th, *px, *py, *qmem;
+    if constexpr (R > 0) {
+        const CartesianSceneLds<double*> L = cartesian_scene_lds(lds + (size_t)sc * per_scene, max_ref, cap);
+        sm = L.sm;                                   // [max_ref]
+        txy = L.txy;                                 // [cap][2] interleaved x, y
+        th = L.th;                                   // [cap]
+        px = L.px;                                   // [cap] smoothed x
+        py = L.py;                                   // [cap] smoothed y
+        qmem = lds + (size_t)SPW * per_scene;        // the fall-back solver's storage (whole wavefront)
+    } else {
+        const CartesianLds<double*> L = cartesian_lds(lds, max_ref, cap);
+        sm = L.sm;
+        txy = L.txy;
+        th = L.th;
+        qmem = L.qmem;                               // the two smoothing problems; px, py: where the solver leaves its results
+        px = py = nullptr;
+    }
     const int st = present ? status[bb] : 0;
     int add = 0;                                 // status bits this kernel adds (scene-uniform)
     bool alive = present && !(st & (kStQpFailed | kStBoundIndex | kStTruncated));
@@ -1070,14 +952,14 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
     int qmax = 0;
 #pragma unroll
     for (int g = 0; g < SPW; ++g) qmax = max(qmax, __builtin_amdgcn_readlane(alive ? n + 1 : 0, SL * g));
-    constexpr unsigned long long kSceneMask = (SL == 32) ? 0xffffffffull : 0xffffull;
+    constexpr unsigned long long kSceneMask = ~0ull >> (64 - SL);
     for (int base = 0; base < qmax; base += SL) {
         const int q = base + sl, i = q - 1;
         const bool is0 = alive && q == 0;
         const bool in = !stop && i >= 0 && i < n;
         const double s = in ? path_s[bb * max_pts + i] : 0.0;
-        const unsigned bad16 = (unsigned)((__ballot(in && s > s_last) >> (SL * sc)) & kSceneMask);
-        const int first_bad = __builtin_ffs((int)bad16);                               // 1-based lane of the scene, 0 if none
+        const unsigned long long bad = (__ballot(in && s > s_last) >> (SL * sc)) & kSceneMask;
+        const int first_bad = SL == 64 ? __builtin_ffsll((long long)bad) : __builtin_ffs((int)bad);   // 1-based lane of the scene, 0 if none
         if (!stop && first_bad) count = min(count, base + first_bad - 2);              // (lane first_bad - 1 holds path point base + first_bad - 2)
         bool o2 = false;
         int k = in ? walk_from_zero(sm, P, fmin(s, s_last), &o2) : 0;
@@ -1089,20 +971,18 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
         carry = __shfl(k, SL - 1, SL);
         if (is0 || (in && i < count && i + 1 < cap)) {
             const Node mm = node_at(line, k);
-            const double ds = (is0 ? bs : s) - sm[k];
-            const double thp = mm.theta + mm.kappa * ds;
-            const double l = is0 ? bl : path_l[bb * max_pts + i];
+            const double ds = (is0 ? bs : s) - sm[k], l = is0 ? bl : path_l[bb * max_pts + i];
             double mc, msn, pc, psn;
             sincos_pair(mm.theta, &msn, &mc);
-            sincos_pair(thp, &psn, &pc);
-            txy[2 * q] = (mm.x + ds * mc) + l * (-psn);                              // ref :32-34 and :44-46
-            txy[2 * q + 1] = (mm.y + ds * msn) + l * pc;
+            const Node pr = node_advanced(mm, ds, mc, msn);
+            sincos_pair(pr.theta, &psn, &pc);
+            normal_offset(pr.x, pr.y, l, pc, psn, &txy[2 * q], &txy[2 * q + 1]);     // ref :32-34 and :44-46
         }
         if (first_bad) stop = true;
     }
     int m = count + 1;
     __syncthreads();
-    if (alive && (m > cap || m > max_pts + 1 || m > GP * R)) {
+    if (alive && (m > cap || m > max_pts + 1 || (R > 0 && m > GP * R))) {
         add = kStTruncated;
         alive = false;
     }
@@ -1110,73 +990,64 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
         add = kStSmoothFailed;
         alive = false;
     }
-    // smoothing (ref planning_utils.py:262-361): x on the scene's first GP lanes, y on the other GP, R points per lane
-    const int grp = sl / GP, gl = sl & (GP - 1);
-    double ref[R], u[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int j = gl * R + r;
-        const double v = txy[2 * (j < cap ? j : 0) + grp];
-        ref[r] = (alive && j < m) ? v : 0.0;
-    }
-    int it = 0;
-    int rc = box_qp_active_set_rows<GP, R>(ref, alive ? m : 0, grp ? sy : sx, u, &it);
-    if (force_fallback && rc == 0) rc = -1;          // test hook (EMP_SMOOTH_FORCE_FALLBACK=1): every scene takes the fall-back
-    const unsigned long long unsettled = __ballot(alive && rc < 0), wrong = __ballot(alive && rc > 0);
-    const bool need_fb = ((unsettled >> (SL * sc)) & kSceneMask) != 0ull;
-    if (((wrong >> (SL * sc)) & kSceneMask) != 0ull) {
-        add = kStSmoothFailed;
-        alive = false;
-    }
-    if (alive && !need_fb) {
+    if constexpr (R > 0) {
+        // smoothing (ref planning_utils.py:262-361): x on the scene's first GP lanes, y on the other GP, R points per lane
+        const int grp = sl / GP, gl = sl & (GP - 1);
+        double ref[R], u[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int j = gl * R + r;
-            if (j < m) (grp ? py : px)[j] = u[r];
+            const double v = txy[2 * (j < cap ? j : 0) + grp];
+            ref[r] = (alive && j < m) ? v : 0.0;
         }
-    }
-    __syncthreads();
-    if (unsettled != 0ull) {             // wave-uniform; never taken on the test and benchmark scenes
-        for (int s2 = 0; s2 < SPW; ++s2) {
-            if (((unsettled >> (SL * s2)) & kSceneMask) == 0ull) continue;
-            const int m2 = __builtin_amdgcn_readlane(m, SL * s2);
-            const CartesianSceneLds<double*> L2 = cartesian_scene_lds(lds + (size_t)s2 * per_scene, max_ref, cap);
-            double *qx = nullptr, *qy = nullptr;
-            int it2 = 0;
-            const int rc2 = smooth_pair_wave<(GP * R > kHalfWave)>(qmem, L2.txy, 2, m2, sx, sy, &qx, &qy, &it2);
-            if (rc2 == 0) {
-                for (int i = lane; i < m2; i += 64) {
-                    L2.px[i] = qx[i];
-                    L2.py[i] = qy[i];
-                }
-            } else if (sc == s2) {
-                add = kStSmoothFailed;
-                alive = false;
+        int it = 0;
+        int rc = box_qp_active_set_rows<GP, R>(ref, alive ? m : 0, grp ? sy : sx, u, &it);
+        if (force_fallback && rc == 0) rc = -1;          // test hook (EMP_SMOOTH_FORCE_FALLBACK=1): every scene takes the fall-back
+        const unsigned long long unsettled = __ballot(alive && rc < 0), wrong = __ballot(alive && rc > 0);
+        const bool need_fb = ((unsettled >> (SL * sc)) & kSceneMask) != 0ull;
+        if (((wrong >> (SL * sc)) & kSceneMask) != 0ull) {
+            add = kStSmoothFailed;
+            alive = false;
+        }
+        if (alive && !need_fb) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int j = gl * R + r;
+                if (j < m) (grp ? py : px)[j] = u[r];
             }
-            __syncthreads();
+        }
+        __syncthreads();
+        if (unsettled != 0ull) {             // wave-uniform; never taken on the test and benchmark scenes
+            for (int s2 = 0; s2 < SPW; ++s2) {
+                if (((unsettled >> (SL * s2)) & kSceneMask) == 0ull) continue;
+                const int m2 = __builtin_amdgcn_readlane(m, SL * s2);
+                const CartesianSceneLds<double*> L2 = cartesian_scene_lds(lds + (size_t)s2 * per_scene, max_ref, cap);
+                double *qx = nullptr, *qy = nullptr;
+                int it2 = 0;
+                const int rc2 = smooth_pair_wave<WIDE>(qmem, L2.txy, 2, m2, sx, sy, &qx, &qy, &it2);
+                if (rc2 == 0) {
+                    for (int i = lane; i < m2; i += 64) {
+                        L2.px[i] = qx[i];
+                        L2.py[i] = qy[i];
+                    }
+                } else if (sc == s2) {
+                    add = kStSmoothFailed;
+                    alive = false;
+                }
+                __syncthreads();
+            }
+        }
+    } else {
+        // smoothing on the two half-waves (alive is wave-uniform: the scene is the wavefront)
+        int it = 0;
+        if (alive && smooth_pair_wave<WIDE>(qmem, txy, 2, m, sx, sy, &px, &py, &it)) {
+            add = kStSmoothFailed;
+            alive = false;
         }
     }
-    // heading / curvature (ref planning_utils.py:185-228), one point per lane
     double* out_rows = traj + bb * (max_pts + 1) * 4;
     const int mm = alive ? m : 0;
-    for (int i = sl; i < mm; i += SL) {
-        const int a = (i - 1 > 0) ? i - 1 : 0, c = (i < mm - 2) ? i : mm - 2;
-        const double dx = ((px[a + 1] - px[a]) + (px[c + 1] - px[c])) / 2.0;
-        const double dy = ((py[a + 1] - py[a]) + (py[c + 1] - py[c])) / 2.0;
-        th[i] = atan2(dy, dx);
-    }
-    __syncthreads();
-    for (int i = sl; i < mm; i += SL) {
-        const int a = (i - 1 > 0) ? i - 1 : 0, c = (i < mm - 2) ? i : mm - 2;
-        const double dx = ((px[a + 1] - px[a]) + (px[c + 1] - px[c])) / 2.0;
-        const double dy = ((py[a + 1] - py[a]) + (py[c + 1] - py[c])) / 2.0;
-        const double dpre = th[a + 1] - th[a], daft = th[c + 1] - th[c];
-        double* o = out_rows + (size_t)i * 4;
-        o[0] = px[i];
-        o[1] = py[i];
-        o[2] = th[i];
-        o[3] = sin((dpre + daft) / 2.0) / sqrt(dx * dx + dy * dy);
-    }
+    heading_kappa_lanes<SL>(px, py, mm, th, out_rows, 4);
     if (present) {
         for (int i = mm * 4 + sl; i < (max_pts + 1) * 4; i += SL) out_rows[i] = 0.0;       // padding reads as 0
         if (sl == 0) {
@@ -1185,6 +1056,19 @@ __global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(
         }
     }
 }
+
+__global__ __launch_bounds__(64) void cycle_cartesian_wave_kernel_wide(EMP_CARTESIAN_PARAMS) {
+    cycle_cartesian_body<64, 0, true>(EMP_CARTESIAN_ARGS, 0);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void cycle_cartesian_wave_kernel_narrow(EMP_CARTESIAN_PARAMS) {
+    cycle_cartesian_body<64, 0, false>(EMP_CARTESIAN_ARGS, 0);
+}
+template <int GP, int R>
+__global__ __launch_bounds__(64) void cycle_cartesian_rows_kernel(EMP_CARTESIAN_PARAMS, int force_fallback) {
+    cycle_cartesian_body<2 * GP, R, (GP * R > kHalfWave)>(EMP_CARTESIAN_ARGS, force_fallback);
+}
+#undef EMP_CARTESIAN_PARAMS
+#undef EMP_CARTESIAN_ARGS
 
 // ---------------------------------------------------------------------------------------------
 // stand-alone forms of the projection helpers (one lane per scene, points in order)
@@ -1337,17 +1221,16 @@ __global__ void frenet2cartesian_kernel(int B, int max_ref, int max_pts, const d
         const double ds = v[0] - sm[idx];
         double mc, msn;
         sincos_pair(m.theta, &msn, &mc);
-        const double px = m.x + ds * mc, py = m.y + ds * msn;
-        const double ph = m.theta + ds * m.kappa, pk = m.kappa;
+        const Node pr = node_advanced(m, ds, mc, msn);
+        const double ph = pr.theta, pk = pr.kappa;
         if (proj_only) {
-            o[0] = px; o[1] = py; o[2] = ph; o[3] = pk;
+            o[0] = pr.x; o[1] = pr.y; o[2] = ph; o[3] = pk;
             continue;
         }
         const double l = v[1], dl = v[2], ddl = v[3];
         double pc, psn;
         sincos_pair(ph, &psn, &pc);
-        o[0] = px + l * (-psn);
-        o[1] = py + l * pc;
+        normal_offset(pr.x, pr.y, l, pc, psn, &o[0], &o[1]);
         const double hd = ph + atan(dl / (1.0 - pk * l));                                   // ref :727
         const double dth = hd - ph;
         o[2] = hd;

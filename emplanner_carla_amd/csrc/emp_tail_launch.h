@@ -52,7 +52,7 @@ EMP_HD ProjectLds<P> project_lds(P at, int max_ref) {
 }
 
 // smooth_wave_kernel, and the tail of every kernel that smooths a polyline on the whole wavefront: the x and the y problem
-// (smooth_pair_wave, emp_qp_wave.h), then the headings heading_kappa_wave exchanges.  The kernels take `theta` at the scene's
+// (smooth_pair_wave, emp_qp_wave.h), then the headings heading_kappa_lanes<64> exchanges.  The kernels take `theta` at the scene's
 // OWN point count m <= cap (the solver binds its arrays to m): BoxRangeQp::words grows with m, so theta(m) + m <= end(cap).
 template <class P>
 struct SmoothLds {
@@ -111,8 +111,8 @@ EMP_HD CycleQpLds<P> cycle_qp_lds(P at, bool pair, int cap, int max_obs) {
     return L;
 }
 
-// cycle_cartesian_body: s_map [max_ref], trajectory x, y interleaved [cap][2], headings [cap], the two smoothing problems (the
-// headings live in `th`, not behind the solver)
+// cycle_cartesian_body<64, 0, WIDE> (one scene per wavefront): s_map [max_ref], trajectory x, y interleaved [cap][2], headings
+// [cap], the two smoothing problems (the headings live in `th`, not behind the solver)
 template <class P>
 struct CartesianLds {
     P sm, txy, th, qmem, end;
@@ -128,7 +128,7 @@ EMP_HD CartesianLds<P> cartesian_lds(P at, int max_ref, int cap) {
     return L;
 }
 
-// cycle_cartesian_rows_kernel: a scene's share (as above, then the smoothed x and y [cap] each, no solver) ...
+// cycle_cartesian_body<2 GP, R, .> (cycle_cartesian_rows_kernel): a scene's share (as above, then the smoothed x and y [cap] each, no solver) ...
 template <class P>
 struct CartesianSceneLds {
     P sm, txy, th, px, py, end;
@@ -342,7 +342,8 @@ static inline TailPlan plan_cycle_qp(int B, int max_pts, int max_obs, int decima
 // The Cartesian tail of a cycle; cap = path_cap + 1 trajectory points (planning start + path points).  cartesian_form 0 (default):
 // cycle_cartesian_rows_kernel, the smallest of <8, 3>, <8, 4>, <16, 4> whose GP R points hold the trajectory - a scene takes
 // 2 GP lanes, so four (two) per wavefront.  EMP_OPT_CARTESIAN_FORM = 1 (A/B runs), and anything longer, takes the
-// one-scene-per-wavefront kernels of rounds 1-2 (bit-identical results).  (max_pts: the kernels' row stride, no part of the plan.)
+// one-scene-per-wavefront kernels cycle_cartesian_wave_kernel_narrow / _wide: the same cycle_cartesian_body on 64 lanes per scene
+// (bit-identical results).  (max_pts: the kernels' row stride, no part of the plan.)
 template <int GP, int R>
 static inline bool cartesian_rows_holds(int B, int max_ref, int cap, TailPlan* p) {
     if (cap > GP * R) return false;

@@ -1,4 +1,4 @@
-"""The Cartesian rows kernel indexes its passes by TRAJECTORY point (emp_tail_kernels.h, cycle_cartesian_rows_kernel): point 0 is
+"""The Cartesian tail indexes its passes by TRAJECTORY point (emp_tail_kernels.h, cycle_cartesian_body): point 0 is
 the planning start, point q >= 1 path point q - 1, so that the start shares the first pass's trigonometry.  Reached through
 plan_cycle like tests/test_gpu_cycle.py::test_path_qp_at_its_size_limits; the lattice's column count sets the output capacity
 and with it the instantiation: 21 columns <8, 3> (24 points), 29 columns <8, 4> (32), 60 columns <16, 4> (63).
@@ -9,7 +9,11 @@ is decided by a last bit.  m = 15 / 16 (31 / 32 on the 32-lane scenes) are the l
 and at the first point of the second.  Path point 0 has the planning start's own s (the densified DP path begins there), so a path
 that passes the end of the line at its FIRST point is the scene whose start lies beyond the line: EMP_ST_S_OUT_OF_RANGE.
 A scene the path QP has refused and the lanes of scenes that are not there (batches of 1, 3 and 5) share wavefronts with live
-scenes.  Everything is compared with oracle/ref_port.plan_cycle on the cut line, and alone against in the batch bit for bit."""
+scenes.  Everything is compared with oracle/ref_port.plan_cycle on the cut line, and alone against in the batch bit for bit.
+
+The same body runs one scene per wavefront under cartesian_form = 1 (64 lanes per scene: the passes end at 64 points, not at 16 or
+32, the scene's ballots are the whole wavefront's): 24 and 32 points reach cycle_cartesian_wave_kernel_narrow, 63
+cycle_cartesian_wave_kernel_wide.  Every batch again in that form, bit for bit against the default form."""
 import functools
 
 import numpy as np
@@ -79,6 +83,21 @@ def _plan(planner, cfg, inputs, idx):
                               **{k: v[idx] for k, v in inputs.items()})
 
 
+@pytest.fixture(scope="module")
+def hc():
+    from tests import host_check
+    return host_check.load()
+
+
+def _cartesian_plan(hc, B, max_ref, max_pts, form):
+    """emp_tail_launch.h plan_cycle_cartesian as emp_plan_cycle calls it (stations decimated by two, midpoints, planning start)"""
+    fields = ("gp", "r", "wide", "m32", "spw", "grid", "grid_y", "block", "lds")
+    out = np.zeros(len(fields), dtype=np.int64)
+    err = hc.hc_plan_cycle_cartesian(B, max_ref, max_pts, (max_pts + 1) // 2 + 1, form, out.ctypes.data)
+    assert err is None, err
+    return dict(zip(fields, out.tolist()))
+
+
 @pytest.mark.parametrize("col", [21, 29, 60], ids=["rows_8x3", "rows_8x4", "rows_16x4"])
 def test_planning_start_is_point_zero_of_the_first_pass(planner, col):
     cfg, inputs, want = case(col)
@@ -105,3 +124,31 @@ def test_planning_start_is_point_zero_of_the_first_pass(planner, col):
         for j, i in enumerate(idx):
             for f in ("traj", "traj_len", "status"):
                 assert np.array_equal(getattr(sub, f)[j], getattr(r, f)[i], equal_nan=True), f"scene {i} {f}: batch of {len(idx)} differs"
+
+
+@pytest.mark.parametrize("col", [21, 29, 60], ids=["narrow_24", "narrow_32", "wide_63"])
+def test_one_scene_per_wavefront_gives_the_bits_of_the_default_form(planner, hc, col):
+    cfg, inputs, want = case(col)
+    N = len(want)
+    r = _plan(planner, cfg, inputs, range(N))
+    max_ref, max_pts = inputs["ref_line"].shape[1], r.traj.shape[1] - 1
+    rows = _cartesian_plan(hc, N, max_ref, max_pts, 0)
+    assert (rows["gp"], rows["r"]) == {21: (8, 3), 29: (8, 4), 60: (16, 4)}[col]          # what r came from
+    old = planner.get_option("cartesian_form")
+    planner.set_option("cartesian_form", 1)
+    planner.set_timing(True, only="to_cartesian")
+    try:
+        for idx in [range(N)] + [[i] for i in range(N)] + [range(3)] + ([range(5)] if N >= 5 else []):
+            # which kernel: one launch of the stage, planned as one scene per wavefront, narrow up to 32 points and wide beyond
+            p = _cartesian_plan(hc, len(idx), max_ref, max_pts, 1)
+            assert (p["r"], p["spw"], p["grid"], p["block"], p["wide"]) == (0, 1, len(idx), 64, int(col == 60)), p
+            at = planner.kernel_launches("to_cartesian")
+            sub = _plan(planner, cfg, inputs, idx)
+            assert planner.kernel_launches("to_cartesian") == at + 1
+            for j, i in enumerate(idx):
+                for f in ("traj", "traj_len", "status"):
+                    assert np.array_equal(getattr(sub, f)[j], getattr(r, f)[i], equal_nan=True), \
+                        f"scene {i} {f}: cartesian_form 1 in a batch of {len(idx)} differs from the default form"
+    finally:
+        planner.set_timing(False)
+        planner.set_option("cartesian_form", old)

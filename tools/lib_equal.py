@@ -3,7 +3,9 @@ storage layouts, launch geometry): python tools/lib_equal.py A.so B.so [cfg2|cfg
 a child process of its own; every output array must be equal bit for bit (padding beyond each scene's length excluded).
 Two more targets feed both libraries committed fixtures instead of planning cycles: `speed` (tests/golden/speed_backend.npz
 through the speed planner's QP stage - the fixture holds that stage's inputs, not a scene for Planner.speed_plan) and
-`control` (tests/golden/control/control.npz through mpc_lateral, mpc_ff_lateral and lqr_lateral)."""
+`control` (tests/golden/control/control.npz through mpc_lateral, mpc_ff_lateral and lqr_lateral).  `tail` runs the stand-alone
+Frenet entry points (frenet_path_to_xy, frenet2cartesian, proj_point, match_projection, heading_kappa, smooth_line,
+reference_line) on the ragged hostile batch of tests/cycle_ragged.py."""
 import os
 import subprocess
 import sys
@@ -40,12 +42,56 @@ def fixture_child(name, out):
     np.savez(out, **res)
 
 
+def tail_child(out):
+    """every output of the stand-alone entry points that share the Cartesian tail's helpers (emp_frenet_core.h point transform and
+    centred difference, heading_kappa_lanes, find_match_one), on the ragged hostile batch of tests/cycle_ragged.py"""
+    from emplanner_carla_amd import api
+    from tests import cycle_ragged as CR
+    cfg, seeds, seed = CR.EXACT_CASES["cfg2"]
+    r = CR.ragged_batch(cfg, seeds, seed, "hostile")
+    b, B, P = r.batch, len(r), r.ref.shape[1]
+    rng = np.random.default_rng(7)
+    pl = api.Planner(0)
+    sp = api.smooth_params()
+    res = {}
+
+    def keep(name, outs):
+        for i, a in enumerate(outs):
+            res[f"{name}_{i}"] = np.array(a)
+
+    sm = pl.s_map(r.ref, r.n_ref, b.origin_xy)
+    # a path of M stations from each scene's planning start, 1.3 m apart: it runs past the end of the shorter lines
+    M = 30
+    n_pts = rng.integers(0, M + 1, B).astype(np.int32)
+    n_pts[[0, B - 1]] = M
+    path_s = b.sl_start[:, :1] + 0.4 + 1.3 * np.arange(M)[None, :]
+    path_l = b.sl_start[:, 1:2] + 0.8 * np.sin(0.3 * np.arange(M)[None, :] + np.arange(B)[:, None])
+    txy, n_out, st = pl.frenet_path_to_xy(r.ref, sm, r.n_ref, np.ascontiguousarray(b.sl_start[:, :2]), path_s, path_l, n_pts)
+    keep("frenet_path_to_xy", (txy, n_out, st))
+    sl = np.stack([path_s, path_l, 0.05 * np.cos(path_s), 0.01 * np.sin(path_s)], axis=2)
+    for proj_only in (False, True):
+        keep(f"frenet2cartesian_{int(proj_only)}", pl.frenet2cartesian(r.ref, sm, r.n_ref, sl, n_pts, proj_only=proj_only))
+    keep("proj_point", pl.proj_point(r.ref, sm, r.n_ref, np.ascontiguousarray(path_s[:, 3]), np.zeros(B, np.int32)))
+    keep("match_projection", pl.match_projection(r.ref, r.n_ref, r.obs_xy, r.n_obs))
+    keep("heading_kappa", pl.heading_kappa(txy, n_out))
+    for cap in (30, P):                         # row capacities of at most 32 points and of more: smooth_wave_kernel<false> / <true>
+        keep(f"smooth_line_{cap}", pl.smooth_line(sp, np.ascontiguousarray(r.ref[:, :cap, :2]), np.minimum(r.n_ref, cap).astype(np.int32)))
+    first = pl.reference_line(sp, r.ref, r.n_ref, b.start_xy, np.zeros(B, np.int32), is_first_run=np.ones(B, np.int32))
+    keep("reference_line_first", first)
+    pre = (np.asarray(first[2]) + np.where(np.arange(B) % 2 == 0, -2, 2)).clip(0, P - 1).astype(np.int32)   # windowed, both directions
+    keep("reference_line_windowed", pl.reference_line(sp, r.ref, r.n_ref, b.start_xy, pre, is_first_run=np.zeros(B, np.int32)))
+    pl.close()
+    np.savez(out, **res)
+
+
 def child(lib, cfg_name, scenes, out):
     sys.path.insert(0, ROOT)
     from emplanner_carla_amd import _lib
     _lib.LIB_PATH = os.path.abspath(lib)
     if cfg_name in ("speed", "control"):
         return fixture_child(cfg_name, out)
+    if cfg_name == "tail":
+        return tail_child(out)
     from emplanner_carla_amd import scenes as S
     from emplanner_carla_amd.api import Planner, dp_params_from_cfg, qp_params, smooth_params
     extra = {}
@@ -88,8 +134,9 @@ if __name__ == "__main__":
         subprocess.run([sys.executable, os.path.abspath(__file__), "--child", lib, cfg, str(n), out], check=True)
         outs.append(np.load(out))
     bad = [k for k in outs[0].files if not np.array_equal(outs[0][k], outs[1][k], equal_nan=True)]
-    if cfg in ("speed", "control"):
-        print(f"{cfg} fixture, {len(outs[0].files)} arrays: {'BIT-IDENTICAL' if not bad else 'DIFFERENT: ' + ', '.join(bad)} ({a} vs {b})")
+    if cfg in ("speed", "control", "tail"):
+        what = "stand-alone entry points on the ragged hostile batch" if cfg == "tail" else "fixture"
+        print(f"{cfg} {what}, {len(outs[0].files)} arrays: {'BIT-IDENTICAL' if not bad else 'DIFFERENT: ' + ', '.join(bad)} ({a} vs {b})")
         sys.exit(1 if bad else 0)
     ok = ((outs[0]["bench_status"] & ~1) == 0).mean()
     if "--diff" in sys.argv:            # builds that may differ by rounding (solver arithmetic): how far apart, scene statuses first
