@@ -59,7 +59,14 @@ __device__ inline bool inverse4(const M4& A, M4* out) {
                 best = fabs(w[r][c]);
                 piv = r;
             }
-        if (!(best > 0.0)) return false;
+        if (!(best > 0.0)) {
+            // singular or non-finite: NaN, not whatever *out held - the callers still form A_bar, H, f and K from it for the outputs
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) out->a[i][j] = __builtin_nan("");
+            return false;
+        }
 #pragma unroll
         for (int r = c + 1; r < 4; ++r)
             if (r == piv) {

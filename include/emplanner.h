@@ -597,7 +597,13 @@ int emp_reference_line(emp_ctx* ctx, const emp_smooth_params* sp, int32_t B, int
  * -> cal_control_para_fun (:253-311): condensed MPC with N = 6 steps x P = 2 controls, box |u| <= 1.
  * steer [B] = first control (res['x'][0]); optional outputs (NULL to skip): u [B][12], e_rr [B][4], k_r [B],
  * pre_pro [B][4] = predicted x, y and projected x, y, H [B][12][12] and f [B][12] of the QP, iters [B].
- * status: EMP_ST_S_OUT_OF_RANGE for a bad min_index / empty path (IndexError in the reference), EMP_ST_QP_FAILED. */
+ * status: EMP_ST_S_OUT_OF_RANGE for a bad min_index / empty path (IndexError in the reference), EMP_ST_QP_FAILED.
+ * Non-finite and singular input: a vehicle with NaN or +-inf in a state entry, in vx or in theta or kappa of its matched path
+ * point, or exactly at its path's centre of curvature (1 - k_r e_d == 0, which divides e_fi_dot by zero), gets
+ * EMP_ST_QP_FAILED (EMP_ST_S_OUT_OF_RANGE where the index rule above fires first), steer 0 and u all zero after at most one
+ * iteration; H and f are written as computed (NaN where the input reaches them).  The other vehicles of the call are unaffected, bit for bit.  A path
+ * point whose x or y is not finite is at no distance `<` another's: the match passes over it, as the reference's does, and
+ * the vehicle is answered from the nearest finite point.  No vehicle takes more than 60 iterations. */
 typedef struct emp_mpc_params {
     double a, b, Cf, Cr, m, Iz;            /* (a, b, Cf, Cr, m, Iz) = vehicle_para (controller.py:132); the drivers pass
                                             * (1.015, 1.895, 1412, -148970, -82204, 1537) (test_9.py:316) in THIS order */
@@ -615,7 +621,16 @@ int emp_mpc_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
  * max|dP| < 0.1 or 5000 sweeps) -> cal_error_k_fun(ts = 0.1) (:488-567) -> forward_control_fun (:569-583) ->
  * steer = -K e_rr + delta_f (:606; the raw command, not clipped).  p->q_diag / p->r are Q and R (:592-598: (200, 1, 50,
  * 1), 1; emp_lqr_params_default sets them), p->f_diag is unused.  Optional outputs (NULL to skip): K [B][4],
- * e_rr [B][4], k_r [B], pre_pro [B][4], sweeps [B] (Riccati sweeps performed). */
+ * e_rr [B][4], k_r [B], pre_pro [B][4], sweeps [B] (Riccati sweeps performed).
+ * Non-finite and singular input.  This law has no QP to fail.  With a finite model - vx finite, or +-inf, which only zeroes the
+ * model's quotients - a vehicle with NaN or +-inf in a state entry, in vx or in theta or kappa of its matched path point, or
+ * with 1 - k_r e_d == 0, gets status 0 and the IEEE result of the reference's expression: steer NaN (+-inf at the singular
+ * point), with the K and the sweeps of its model; emp_vehicle_control then actuates NaN as full lock -1 (see there).  A pose
+ * that is not finite matches nothing and keeps min_index; a path point whose x or y is not finite is passed over as in
+ * emp_mpc_lateral.  Where the model itself is not finite - vx NaN, or vx + 0.0001 == 0 - the discretisation has no inverse:
+ * EMP_ST_QP_FAILED, steer 0, K all NaN, and sweeps = 1, because the loop's NaN-dropping fmax sees max|dP| = 0 (the reference
+ * raises ZeroDivisionError for the zero velocity and spins all 5000 sweeps on NaN).  No vehicle holds its wavefront longer than
+ * the 5000 sweeps a creeping one needs. */
 void emp_lqr_params_default(emp_mpc_params* p);
 int emp_lqr_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t max_path, const double* target_path,
                     const int32_t* n_path, const double* state, const double* vx, const int32_t* min_index,
@@ -650,7 +665,10 @@ int emp_pid_longitudinal(emp_ctx* ctx, const emp_pid_params* p, int32_t B, const
  * only the first P steps' controls (:939-940), so H has a 2-D null space along u4 - u5 and u6 - u7: u0..u3 and the pair sums
  * u4 + u5, u6 + u7 are determined, the split of a pair is the interior point's.  p->q_diag / f_diag / r are Q, F, R
  * (emp_mpc_ff_params_default: (200, 1, 1, 1), (10, 10, 10, 10), 1; :974-979).  steer [B] = u[0] (:990); optional outputs (NULL to
- * skip): u [B][8], e_rr [B][4], k_r [B], pre_pro [B][4], H [B][8][8], f [B][8], iters [B]. */
+ * skip): u [B][8], e_rr [B][4], k_r [B], pre_pro [B][4], H [B][8][8], f [B][8], iters [B].
+ * Non-finite and singular input is answered as by emp_mpc_lateral (EMP_ST_QP_FAILED, steer 0, u all zero), and so is
+ * vx + 0.0001 == 0, which divides this law's model by zero.  Path points at exactly the same distance from the predicted pose -
+ * a standstill trajectory is a run of identical points - match at the lowest index, as the reference's strict `<` does. */
 #define EMP_MPC_FF_CONTROLS 8
 void emp_mpc_ff_params_default(emp_mpc_params* p);
 int emp_mpc_ff_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t max_path, const double* target_path,
