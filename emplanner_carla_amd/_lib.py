@@ -136,6 +136,16 @@ class SpeedDpParams(C.Structure):
 
 _vp, _i32, _f64, _u64 = C.c_void_p, C.c_int32, C.c_double, C.c_uint64
 
+ROUTE_MAX_NODES = 4096             # EMP_ROUTE_MAX_NODES
+ROUTE_MAX_LENGTH = 1 << 18         # EMP_ROUTE_MAX_LENGTH
+ROUTE_UNREACHABLE, ROUTE_TRUNCATED, ROUTE_BAD_QUERY = 1, 2, 4     # EMP_ROUTE_*
+
+
+class RouteGraph(C.Structure):
+    """emp_route_graph: the road graph of global routing (routing.RoadGraph fills it)."""
+    _fields_ = [(n, _vp) for n in ("vertex", "succ_off", "succ", "length", "wp_off", "wp")] + \
+               [("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("n_wp", C.c_int32), ("reserved", C.c_int32)]
+
 
 class CycleIO(C.Structure):
     _fields_ = [(n, _vp) for n in (
@@ -289,6 +299,8 @@ PROTOTYPES = {
     "emp_plan_trajectory": (C.c_int, [_vp, C.POINTER(DpParams), C.POINTER(QpParams), C.POINTER(SmoothParams),
                                       C.POINTER(SpeedDpParams), C.POINTER(SpeedQpParams), _i32, _i32, _i32, _i32, _i32,
                                       C.c_int, C.POINTER(CycleIO), C.POINTER(SpeedIO), C.c_int]),
+    "emp_route_search": (C.c_int, [_vp, C.POINTER(RouteGraph), _i32, _i32] + [_vp] * 5 + [C.c_int]),
+    "emp_route_paths": (C.c_int, [_vp, C.POINTER(RouteGraph), _i32, _i32, _i32] + [_vp] * 10 + [C.c_int]),
 }
 
 _lib = None

@@ -956,6 +956,49 @@ class Planner:
             a.where))
         return ref, nr, mi, it, st
 
+    # ---- global routing (reference planner/global_planning.py:153-272) -----------------------------
+    def _route_graph(self, a, graph):
+        """emp_route_graph of a routing.RoadGraph in the call's memory space (device tensors are made once per graph and kept)."""
+        if a.torch:
+            tensors = graph.on_device(a.device)
+            if not a.same_stream:        # the one-time copies ran on torch's current stream
+                self.torch_stream().wait_stream(a.t.cuda.current_stream(a.device))
+            a.keep.append(tensors)
+            return graph.struct([t.data_ptr() for t in tensors])
+        return graph.struct([x.ctypes.data for x in graph.arrays()])
+
+    def route_search(self, graph, start_node, end_edge, max_route: int):
+        """ref _route_search / _A_star for B queries over one routing.RoadGraph: start_node (B,), end_edge (B,) edge ids ->
+        RouteResult with route (B, max_route), route_len, status (EMP_ROUTE_* bits)."""
+        from .routing import RouteResult
+        a = self._args(start_node, end_edge)
+        B = int(start_node.shape[0])
+        g = self._route_graph(a, graph)
+        rt, rtp = a.out((B, int(max_route)), np.int32)
+        rl, rlp = a.out((B,), np.int32)
+        st, stp = a.out((B,), np.int32)
+        self._check(self._lib.emp_route_search(self._h, C.byref(g), B, int(max_route), a.inp(start_node, np.int32, (B,)),
+                                               a.inp(end_edge, np.int32, (B,)), rtp, rlp, stp, a.where))
+        return RouteResult(rt, rl, st)
+
+    def route(self, graph, start_node, end_edge, origin_wp, dest_wp, max_route: int, max_global: int):
+        """ref search_path_way + waypoint_list_2_target_path for B queries: origin_wp, dest_wp (B, 3) -> RouteResult; its
+        global_path (B, max_global, 4) / n_global are what reference_line, plan_cycle and drive take."""
+        from .routing import RouteResult
+        a = self._args(start_node, end_edge, origin_wp, dest_wp)
+        B = int(start_node.shape[0])
+        g = self._route_graph(a, graph)
+        rt, rtp = a.out((B, int(max_route)), np.int32)
+        rl, rlp = a.out((B,), np.int32)
+        wi, wip = a.out((B, int(max_global)), np.int32)
+        gp, gpp = a.out((B, int(max_global), 4), np.float64)
+        ng, ngp = a.out((B,), np.int32)
+        st, stp = a.out((B,), np.int32)
+        self._check(self._lib.emp_route_paths(
+            self._h, C.byref(g), B, int(max_route), int(max_global), a.inp(start_node, np.int32, (B,)), a.inp(end_edge, np.int32, (B,)),
+            a.inp(origin_wp, np.float64, (B, 3)), a.inp(dest_wp, np.float64, (B, 3)), rtp, rlp, wip, gpp, ngp, stp, a.where))
+        return RouteResult(rt, rl, st, wi, gp, ng)
+
     # ---- lateral MPC controller (reference controller/controller.py:65-337) -----------------------
     def mpc_lateral(self, p: MpcParams, target_path, n_path, state, vx, min_index, qp_matrices=False) -> MpcResult:
         """ref Lateral_MPC_controller._control for B vehicles: target_path (B,M,4), state (B,5) = x, y, fi, Vy, fi_dot,

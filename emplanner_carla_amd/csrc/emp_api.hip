@@ -21,6 +21,8 @@
 #include "emp_rollout_kernels.h"
 #include "emp_speed_front_kernels.h"
 #include "emp_drive_kernels.h"
+#include "emp_route_kernels.h"
+#include "emp_route_launch.h"
 
 namespace emp {
 thread_local std::string g_create_error;
@@ -3095,6 +3097,69 @@ int emp_drive_timed(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* 
     const DriveTimed tm{sdp, sqp, tp->plan_lead, plan_drive_clock(tick0, K, T), io};
     return drive_impl(ctx, dp, qp, smooth, drv, lateral, lat, pid, vp, B, max_global, max_obs, max_pts, max_act, max_dyn, K, T, target_speed,
                       &base, where, &tm);
+}
+
+}  // extern "C"
+
+// ---- global routing (emp_route_core.h, emp_route_kernels.h; the launch: emp_route_launch.h) -------------------------------------
+// origin_wp == nullptr: emp_route_search, A* only
+static int route_impl(emp_ctx* ctx, const emp_route_graph* g, int32_t B, int32_t max_route, int32_t max_global, const int32_t* start_node,
+                      const int32_t* end_edge, const double* origin_wp, const double* dest_wp, int32_t* route, int32_t* route_len,
+                      int32_t* wp_index, double* global_path, int32_t* n_global, int32_t* status, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, g != nullptr && g->reserved == 0, "route graph: NULL, or reserved != 0");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "routing takes EMP_HOST or EMP_DEVICE arrays");
+    const RoutePlan plan = plan_route(B, g->n_nodes, max_route, max_global);
+    if (const int rc = plan_refused(ctx, plan.error)) return rc;
+    EMP_REQUIRE(ctx, B >= 0 && g->n_edges >= 0 && g->n_wp >= 0, "bad sizes");
+    EMP_REQUIRE(ctx, g->vertex && g->succ_off && g->succ && g->length && g->wp_off && g->wp, "route graph: NULL array");
+    if (B == 0) return EMP_OK;
+    EMP_REQUIRE(ctx, start_node && end_edge && route && route_len && status, "NULL argument");
+    const route::Graph host = {g->vertex, g->succ_off, g->succ, g->length, g->wp_off, g->wp, g->n_nodes, g->n_edges, g->n_wp};
+    if (where == EMP_HOST)
+        if (const char* err = route::graph_error(host)) return fail(ctx, EMP_ERR_INVALID, err);
+    EMP_STAGE(st, where);
+    route::Graph d = host;
+    d.vertex = st.in(g->vertex, (size_t)g->n_nodes * 3);
+    d.succ_off = st.in(g->succ_off, (size_t)g->n_nodes + 1);
+    d.succ = st.in(g->succ, (size_t)g->n_edges);
+    d.length = st.in(g->length, (size_t)g->n_edges);
+    d.wp_off = st.in(g->wp_off, (size_t)g->n_edges + 1);
+    d.wp = st.in(g->wp, (size_t)g->n_wp * 3);
+    const int* d_start = st.in(start_node, (size_t)B);
+    const int* d_end = st.in(end_edge, (size_t)B);
+    const double* d_origin = st.in(origin_wp, (size_t)B * 3);
+    const double* d_dest = st.in(dest_wp, (size_t)B * 3);
+    int* d_route = st.out(route, (size_t)B * max_route);
+    int* d_len = st.out(route_len, (size_t)B);
+    int* d_wpi = st.out(wp_index, (size_t)B * max_global);
+    double* d_gp = st.out(global_path, (size_t)B * max_global * 4);
+    int* d_ng = st.out(n_global, (size_t)B);
+    int* d_st = st.out(status, (size_t)B);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = set_lds(ctx, route::route_kernel, plan.lds, kRouteTooManyNodes)) return rc;
+    if (const int rc = launch(ctx, "route", route::route_kernel, dim3(plan.grid), dim3(plan.block), plan.lds, d, (int)B, (int)max_route,
+                              (int)max_global, d_start, d_end, d_origin, d_dest, d_route, d_len, d_wpi, d_gp, d_ng, d_st))
+        return rc;
+    return st.finish();
+}
+
+extern "C" {
+
+int emp_route_search(emp_ctx* ctx, const emp_route_graph* graph, int32_t B, int32_t max_route, const int32_t* start_node,
+                     const int32_t* end_edge, int32_t* route, int32_t* route_len, int32_t* status, emp_mem where) {
+    return route_impl(ctx, graph, B, max_route, 1, start_node, end_edge, nullptr, nullptr, route, route_len, nullptr, nullptr, nullptr,
+                      status, where);
+}
+
+int emp_route_paths(emp_ctx* ctx, const emp_route_graph* graph, int32_t B, int32_t max_route, int32_t max_global,
+                    const int32_t* start_node, const int32_t* end_edge, const double* origin_wp, const double* dest_wp,
+                    int32_t* route, int32_t* route_len, int32_t* wp_index, double* global_path, int32_t* n_global, int32_t* status,
+                    emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, B == 0 || (origin_wp && dest_wp && wp_index && global_path && n_global), "NULL argument");
+    return route_impl(ctx, graph, B, max_route, max_global, start_node, end_edge, origin_wp, dest_wp, route, route_len, wp_index,
+                      global_path, n_global, status, where);
 }
 
 }  // extern "C"

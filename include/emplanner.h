@@ -1225,6 +1225,78 @@ int emp_drive_timed(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* 
                     int32_t max_dyn, int32_t K, int32_t T, int32_t tick0, const double* target_speed, const emp_drive_timed_io* io,
                     emp_mem where);
 
+/* ---- global routing: B queries over one road graph, routes expanded to global paths (additions: the ABI stays 13) -------------
+ * ref: planner/global_planning.py - _A_star (:168-214), _route_search (:153-166), search_path_way (:234-272) - and
+ * planning_utils.py waypoint_list_2_target_path (:29-46).  The PROCEDURE is the contract, not "a shortest path": the edge cost is
+ * a waypoint count, the heuristic a distance in metres (it over-estimates at the driver's 2 m resolution), and closed nodes are
+ * never reopened, so any other search order returns other routes.  One wavefront per query runs the reference's pop-and-relax
+ * loop; the lanes share the arg-min of a pop and the successors of the popped node.
+ *
+ * The graph (emp_route_graph, all arrays contiguous, shared by every query):
+ *   vertex [N][3]    the reference's 2-decimal rounded entry / exit positions, in node-id order (_build_graph's ids)
+ *   succ_off [N+1], succ [E]   CSR successor lists in the order DiGraph.successors yields them (first add_edge of a pair)
+ *                    a list names no node twice (one edge per (u, v), as in a DiGraph): the lanes of a wavefront relax the successors
+ *                    of a node side by side.  REQUIRED of EMP_DEVICE graphs too, where it cannot be checked: a repeated successor
+ *                    is memory-safe there, but which of its two edges sets g, parent and stamp is undefined
+ *   length [E]       edge costs, len(path) + 1;  0 <= length <= 2^18
+ *   wp_off [E+1], wp [W][3]    per edge: the entry waypoint, the path waypoints, the exit waypoint (at least 2)
+ * An edge id e is a position in succ; its ends are n_end (the node whose list holds e) and n_exit = succ[e].
+ *
+ * A query: start_node, end_edge, origin_wp [3], dest_wp [3] (the CARLA look-ups _find_location_edge / get_waypoint are the host's).
+ * Arithmetic, every operation rounded separately, IEEE sqrt:
+ *   dist(p, q) = sqrt(((dx dx) + (dy dy)) + (dz dz))
+ *   h(n) = dist(vertex[n], vertex[n_end]),  f(n) = (double) g[n] + h(n)      g int32; a NaN f orders as +inf
+ * Per node: NEW, OPEN or CLOSED, g, parent, stamp (the order of its FIRST insertion into the open set; an update keeps it).
+ *   start_node is OPEN with g = 0, parent = -1, stamp = 0.  Then, at most N times (each pop closes a node):
+ *     c = the OPEN node with the smallest f, equal f: the smallest stamp (Python's min over a dict).  None: EMP_ROUTE_UNREACHABLE
+ *     c == n_end: close it, stop
+ *     for every successor suc of c in CSR order, len its edge's length:
+ *       CLOSED: skipped;  OPEN: g[c] + len < g[suc] (integers) sets g and parent;  NEW: OPEN, g[c] + len, parent c, the next stamp
+ *     close c
+ *   route = the parents back from n_end, reversed, then n_exit;  route_len = its length (>= 2)
+ * Expansion (emp_route_paths).  The edge of (u, v) is the first e in u's list with succ[e] == v; closest(p, list) is the first
+ * index with the strictly smallest dist (a NaN or infinite distance never wins; none: index 0):
+ *   first edge (route[0], route[1]): its waypoints from closest(origin_wp, all of them) onwards
+ *   each further edge but the last, only when route_len > 3: its waypoints without the entry
+ *   last edge (route[-2], route[-1]): L = its waypoints without the entry, k = closest(dest_wp, L); L[0..k] when k != 0
+ * (kept quirks: a two-node route emits its one edge twice; the first edge is the one A* left start_node by, not the origin's own).
+ * wp_index [B][max_global] are positions in wp, global_path [B][max_global][4] = x, y, theta, kappa of those waypoints with theta
+ * and kappa bit for bit what emp_heading_kappa gives on the same xy (none below 2 points), n_global [B] the count.
+ * status [B]: 0, or EMP_ROUTE_UNREACHABLE (route_len = n_global = 0), or EMP_ROUTE_BAD_QUERY (start_node outside [0, N), end_edge
+ * outside [0, E), or - EMP_DEVICE only, where the graph cannot be checked - an offset or successor index out of range met on the
+ * way: never followed, route_len = n_global = 0), or EMP_ROUTE_TRUNCATED (route_len > max_route or n_global > max_global: the
+ * counts are the true lengths, only the capacity is written; a truncated route is still expanded in full).  Unused slots are 0.
+ * With EMP_HOST the graph is checked first (finite values, monotone offsets, indices in range, no repeated successor, the limits above): a violation is
+ * EMP_ERR_INVALID.  Refused as well: N > EMP_ROUTE_MAX_NODES, N < 1, max_route < 2, max_global < 1, reserved != 0,
+ * EMP_HOST_PINNED.  B == 0: EMP_OK. */
+#define EMP_ROUTE_MAX_NODES 4096
+#define EMP_ROUTE_MAX_LENGTH (1 << 18)
+#define EMP_ROUTE_UNREACHABLE 1
+#define EMP_ROUTE_TRUNCATED 2
+#define EMP_ROUTE_BAD_QUERY 4
+
+typedef struct emp_route_graph {
+    const double* vertex;           /* [n_nodes][3] */
+    const int32_t* succ_off;        /* [n_nodes + 1] */
+    const int32_t* succ;            /* [n_edges] */
+    const int32_t* length;          /* [n_edges] */
+    const int32_t* wp_off;          /* [n_edges + 1] */
+    const double* wp;               /* [n_wp][3] */
+    int32_t n_nodes, n_edges, n_wp;
+    int32_t reserved;               /* must be 0 */
+} emp_route_graph;
+
+/* A* only: start_node [B], end_edge [B] -> route [B][max_route], route_len [B], status [B]. */
+int emp_route_search(emp_ctx* ctx, const emp_route_graph* graph, int32_t B, int32_t max_route, const int32_t* start_node,
+                     const int32_t* end_edge, int32_t* route, int32_t* route_len, int32_t* status, emp_mem where);
+
+/* ... and the expansion: origin_wp [B][3], dest_wp [B][3] -> wp_index, global_path, n_global as above.  global_path / n_global are
+ * what emp_reference_line, emp_plan_cycle (io->global_path) and emp_drive take. */
+int emp_route_paths(emp_ctx* ctx, const emp_route_graph* graph, int32_t B, int32_t max_route, int32_t max_global,
+                    const int32_t* start_node, const int32_t* end_edge, const double* origin_wp, const double* dest_wp,
+                    int32_t* route, int32_t* route_len, int32_t* wp_index, double* global_path, int32_t* n_global, int32_t* status,
+                    emp_mem where);
+
 #ifdef __cplusplus
 }
 #endif
