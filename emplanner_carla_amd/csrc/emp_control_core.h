@@ -31,9 +31,13 @@ struct PidParams {
 //     Python's sum over the deque), derivative = (newest - previous) / dt
 //   - |e| > error_threshold: the integral is 0 and the buffer is cleared; the derivative term stays
 // dt = 0 gives IEEE inf / NaN where the reference raises ZeroDivisionError.
+// A NaN error enters the buffer as THE quiet NaN (0x7ff8000000000000): IEEE 754 leaves the sign of a NaN result open and the
+// compiler may carry the negation of `target - speed` across an operation, so the stored NaN had either sign bit depending on the
+// kernel this function was inlined into (emp_rollout's against emp_vehicle_control's, LQR) - and the two are bit-for-bit equal.
 EMP_HD double pid_step(const PidParams& p, double speed_kmh, double target_speed, const double* in, int n_in, double* out,
                        int* n_out) {
-    const double e = target_speed - speed_kmh;
+    const double diff = target_speed - speed_kmh;
+    const double e = (diff != diff) ? __builtin_nan("") : diff;
     const int n = n_in < 0 ? 0 : (n_in > kPidBuffer ? kPidBuffer : n_in);
     const int drop = (n == kPidBuffer) ? 1 : 0;
     const int m = n - drop + 1;                // entries after the append

@@ -648,7 +648,9 @@ int emp_lqr_lateral(emp_ctx* ctx, const emp_mpc_params* p, int32_t B, int32_t ma
  * integral and derivative are 0; |error| > error_threshold sets the integral to 0 and clears the buffer (the derivative term
  * stays).  command [B] = K_P e + K_I integral + K_D derivative.  err_out / n_err_out receive the buffer after the call (entries at
  * and past n_err_out are 0) and MAY be the same arrays as err_in / n_err_in: with EMP_DEVICE a fleet keeps its PID state on
- * the device across steps.  dt = 0 gives IEEE inf / NaN where the reference raises ZeroDivisionError. */
+ * the device across steps.  dt = 0 gives IEEE inf / NaN where the reference raises ZeroDivisionError.  A NaN error (a NaN speed or
+ * target) enters the buffer as the quiet NaN 0x7ff8000000000000 whatever the sign of the NaN it came from, so that every call
+ * that runs this rule (emp_vehicle_control, emp_rollout, emp_drive and their timed forms) stores the same bits. */
 #define EMP_PID_BUFFER 60
 typedef struct emp_pid_params {
     double K_P, K_I, K_D, dt, error_threshold;     /* controller.py:622, :638: 1.15, 0, 0, 0.01, 1 */
@@ -715,6 +717,11 @@ int emp_vehicle_control(emp_ctx* ctx, int32_t lateral, const emp_mpc_params* lat
  *   (the rule is A-stable: no speed makes the step blow up where the continuous model decays)
  *   the pose steps from the OLD values: x+ = x + dt * (Vx * cos fi - Vy * sin fi), y+ = y + dt * (Vx * sin fi + Vy * cos fi),
  *   fi+ = fi + dt * fi_dot;   Vx+ = max(Vx + dt * ax, 0): the model does not reverse.
+ *   Vx+ is `v > 0 ? v : 0` with v = Vx + dt * ax: never negative, never -0.0 (v = 0 exactly gives +0.0), and a NaN v steps to 0 -
+ *   a NaN Vx, a NaN throttle or brake, and an infinite Vx too (drag * inf is NaN with drag = 0, and inf - inf otherwise).  The speed
+ *   recovers from a NaN within the tick; x+ and y+, which use the OLD Vx, are NaN and stay so.  A NaN steer reaches Vy+ and fi_dot+
+ *   only, a NaN in x, y or fi only the pose.  The clamp keeps the sign of a Vx < 0 only: -0.0 and every |Vx| < 0.005 that is not
+ *   negative give Vxc = +0.005.  Controls are not clipped: values outside [0, 1] and [-1, 1] enter ax and delta as they are.
  * Optional outputs (NULL to skip) are the next emp_vehicle_control call's inputs, so a chain of calls never leaves the device:
  * ctl_state [B][5] = x, y, fi, Vy, fi_dot; vx_ctl [B] = the clamped Vx+; speed_kmh [B] = 3.6 * sqrt(Vx+ * Vx+ + Vy+ * Vy+).
  * state_out may alias state.  vp->reserved must be 0.
@@ -1022,6 +1029,20 @@ int emp_plan_trajectory(emp_ctx* ctx, const emp_dp_params* p, const emp_qp_param
  *                 beyond n_act copied unchanged; optional, may be `actors`
  * n_act is clamped to [0, max_act] and slots at or beyond it are never read.  Unused output slots are 0.  static_xy / static_dis
  * hold the max_obs nearest statics and dyn the max_dyn nearest dynamics; req_status is EMP_DRV_TRUNCATED when more were kept.
+ * On a threshold, tied and non-finite (each follows from the formulas above; tests/test_gpu_drive_request_cases.py pins them):
+ *   - `<` and `>` are strict and the gate is `<=`: an actor AT dis_limitation, AT +-lateral_band or AT `behind` is dropped, a
+ *     speed AT dynamic_speed is static, a nearest static AT static_gate opens the gate.
+ *   - actors of one class with bit-equal dis come out in actor-index order, a truncated list keeps the lowest indices, and the two
+ *     classes are ranked separately: an equal dis in the other class moves nothing.
+ *   - NaN compares false.  An actor with a NaN or infinite x_a or y_a is dropped.  A kept actor with a NaN vx_a or vy_a is STATIC
+ *     (speed > dynamic_speed is false; its actors_next position is NaN); an infinite velocity makes it dynamic with speed = inf,
+ *     and its advance is inf * advance_s.
+ *   - a NaN or infinite ego x or y keeps nothing (n_static = n_dyn = n_obs = 0, dyn_dis_speed = NaN) and origin_xy / start_xy carry
+ *     it: the prediction is not finite.  A NaN fi, Vy or Vx, and an infinite fi, make `along` NaN: nothing is kept, start_xy and
+ *     start_v (and start_heading) are NaN.  A NaN fi_dot reaches pred_fi only; a NaN accel reaches start_a only.
+ *   - zeros keep their signs and atan2 follows C Annex F: at fi = 0, Vy = +0 a speed Vx = -0.0 gives w = (-0, +0), start_heading =
+ *     pi and beta = pi; V = 0, so start_xy = (x, y).  A vehicle at rest (Vx = Vy = +0) has start_heading = +0, along = 0 for every
+ *     actor (all of them are "in front") and start_xy = (x, y).
  * Limits: 1 <= max_act <= 64, 1 <= max_obs <= 256, 1 <= max_dyn <= 64. */
 #define EMP_DRV_TRUNCATED 1
 #define EMP_DRIVE_MAX_PERIODS 4096

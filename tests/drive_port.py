@@ -5,7 +5,10 @@ This is what the GPU is compared with; tests/golden/drive/drive_request.npz hold
 same inputs.  Test tool only: the package never imports it.
 
 One known difference to the reference's text: it squares with ``** 2``, which CPython hands to libm's pow; pow(x, 2) is not always
-the correctly rounded product x * x (about 0.08 % of doubles differ in the last bit).  The library and this port multiply."""
+the correctly rounded product x * x (about 0.08 % of doubles differ in the last bit).  The library and this port multiply.
+
+Non-finite input goes through like any other (IEEE: NaN compares false, sin / cos of an infinity are NaN - math.sin raises there,
+hence `sin` and `cos` below); tests/drive_request_cases.py holds such vehicles."""
 from __future__ import annotations
 
 import math
@@ -20,9 +23,18 @@ def params(**kw):
     return dict(DEFAULTS, **kw)
 
 
+def cos(v):
+    """IEEE cos: NaN for an infinite argument, where math.cos raises."""
+    return math.cos(v) if math.isfinite(v) else math.nan
+
+
+def sin(v):
+    return math.sin(v) if math.isfinite(v) else math.nan
+
+
 def world_velocity(fi, Vy, Vx):
     """Body-frame (Vx, Vy) at heading fi -> world-frame (wx, wy)."""
-    c, s = math.cos(fi), math.sin(fi)
+    c, s = cos(fi), sin(fi)
     return Vx * c - Vy * s, Vx * s + Vy * c
 
 
@@ -30,7 +42,7 @@ def measure(state, actor):
     """dis, lat, along, speed of one actor (x, y, vx, vy) seen from one vehicle: the four decision variables."""
     x, y, fi, Vy, _, Vx = (float(v) for v in state)
     ax, ay, avx, avy = (float(v) for v in actor)
-    c, s = math.cos(fi), math.sin(fi)
+    c, s = cos(fi), sin(fi)
     wx, wy = world_velocity(fi, Vy, Vx)
     dx, dy = x - ax, y - ay
     dis = math.sqrt((dx * dx + dy * dy) + 0.0)
@@ -65,10 +77,10 @@ def predict(state, ts):
     wx, wy = world_velocity(fi, Vy, Vx)
     V = math.sqrt((wx * wx + wy * wy) + 0.0)
     beta = math.atan2(wy, wx) - fi
-    V_y = V * math.sin(beta)
-    V_x = V * math.cos(beta)
-    px = x + V_x * ts * math.cos(fi) - V_y * ts * math.sin(fi)
-    py = y + V_y * ts * math.cos(fi) + V_x * ts * math.sin(fi)
+    V_y = V * sin(beta)
+    V_x = V * cos(beta)
+    px = x + V_x * ts * cos(fi) - V_y * ts * sin(fi)
+    py = y + V_y * ts * cos(fi) + V_x * ts * sin(fi)
     return px, py, fi + fi_dot * ts
 
 
