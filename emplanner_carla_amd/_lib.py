@@ -147,6 +147,24 @@ class RouteGraph(C.Structure):
                [("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("n_wp", C.c_int32), ("reserved", C.c_int32)]
 
 
+AGENT_BUFFER = 10                  # EMP_AGENT_BUFFER: the agents' two error deques (agents/navigation/controller.py:124, :193)
+AGT_DONE = 1                       # EMP_AGT_DONE
+
+
+class AgentParams(C.Structure):
+    """emp_agent_params: the gains and limits of LocalPlanner / VehiclePIDController (local_planner.py:70-79)."""
+    _fields_ = [(n, C.c_double) for n in ("lat_K_P", "lat_K_I", "lat_K_D", "lon_K_P", "lon_K_I", "lon_K_D", "dt", "max_throttle",
+                                          "max_brake", "max_steer", "base_min_distance")] + [("reserved", C.c_int32)]
+
+
+class AgentRolloutIO(C.Structure):
+    """emp_agent_rollout_io: the path, the vehicle and agent state in and out, the logs."""
+    _fields_ = [(n, _vp) for n in (
+        "path", "n_path", "state", "target_speed", "head", "past_steer", "lon_err", "n_lon", "lat_err", "n_lat",
+        "state_out", "head_out", "past_steer_out", "lon_err_out", "n_lon_out", "lat_err_out", "n_lat_out", "status", "done_tick",
+        "actors_out", "log_state", "log_control", "log_head")] + [("reserved", C.c_int32)]
+
+
 class CycleIO(C.Structure):
     _fields_ = [(n, _vp) for n in (
         "ref_line", "n_ref", "origin_xy", "start_xy", "start_v", "start_a", "obs_xy", "n_obs",
@@ -301,6 +319,11 @@ PROTOTYPES = {
                                       C.c_int, C.POINTER(CycleIO), C.POINTER(SpeedIO), C.c_int]),
     "emp_route_search": (C.c_int, [_vp, C.POINTER(RouteGraph), _i32, _i32] + [_vp] * 5 + [C.c_int]),
     "emp_route_paths": (C.c_int, [_vp, C.POINTER(RouteGraph), _i32, _i32, _i32] + [_vp] * 10 + [C.c_int]),
+    "emp_agent_params_default": (None, [C.POINTER(AgentParams)]),
+    "emp_agent_observe": (C.c_int, [_vp, _i32] + [_vp] * 4 + [C.c_int]),
+    "emp_agent_control": (C.c_int, [_vp, C.POINTER(AgentParams), _i32, _i32] + [_vp] * 22 + [C.c_int]),
+    "emp_agent_rollout": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(VehicleParams), _i32, _i32, _i32, _i32,
+                                    C.POINTER(AgentRolloutIO), C.c_int]),
 }
 
 _lib = None

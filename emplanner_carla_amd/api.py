@@ -95,6 +95,65 @@ def vehicle_params(vehicle_para=(1.015, 2.910 - 1.015, 1412, -148970, -82204, 15
     return p
 
 
+#: (a, b, Cf, Cr, m, Iz) in physical order: the numbers of the reference drivers' vehicle_para, each under its own name
+AGENT_VEHICLE_PARA = (1.015, 2.910 - 1.015, -148970.0, -82204.0, 1412.0, 1537.0)
+
+
+def agent_params(lat_K_P=1.95, lat_K_I=0.05, lat_K_D=0.2, lon_K_P=1.0, lon_K_I=0.05, lon_K_D=0.0, dt=0.05, max_throttle=0.75,
+                 max_brake=0.3, max_steer=0.8, base_min_distance=3.0) -> L.AgentParams:
+    """Gains and limits of the reference's LocalPlanner / VehiclePIDController (agents/navigation/local_planner.py:70-79; its
+    defaults)."""
+    return L.AgentParams(float(lat_K_P), float(lat_K_I), float(lat_K_D), float(lon_K_P), float(lon_K_I), float(lon_K_D), float(dt),
+                         float(max_throttle), float(max_brake), float(max_steer), float(base_min_distance), 0)
+
+
+def agent_vehicle_params(vehicle_para=AGENT_VEHICLE_PARA, dt=0.05, **kw) -> VehicleParams:
+    """``vehicle_params`` for routed traffic: the tuple in PHYSICAL order and the agents' tick (0.05 s).  ``vehicle_params`` keeps the
+    order in which the reference's controllers unpack the drivers' tuple - (a, b, Cf, Cr, m, Iz) = (1.015, 1.895, 1412, -148970,
+    -82204, 1537) - so that plant and controller agree; read as physics that is a stiffness of +1412 and a mass of -82204, and the
+    plant barely yaws (about 0.03 rad/s per radian of wheel angle at 10 m/s).  The agents' law is a pursuit of waypoints round
+    corners: it needs a vehicle that turns, i.e. Cf = -148970, Cr = -82204, m = 1412, Iz = 1537."""
+    return vehicle_params(vehicle_para=vehicle_para, dt=dt, **kw)
+
+
+@dataclass
+class AgentObservation:
+    forward: object      # (A, 2) cos fi, sin fi: the transform's forward vector
+    speed_kmh: object    # (A,) get_speed
+    actors: object       # (A, 4) x, y, world-frame vx, vy: a row of drive's ``actors``
+
+
+@dataclass
+class AgentControlResult:
+    control: object      # (A, 3) throttle, steer, brake
+    status: object       # (A,) int32 EMP_AGT_DONE where the queue is empty
+    head: object         # (A,) int32 the waypoint queue's head after the purge
+    past_steer: object   # (A,)
+    lon_err: object      # (A, 10) the longitudinal deque, oldest first
+    n_lon: object        # (A,) int32
+    lat_err: object      # (A, 10) the lateral deque
+    n_lat: object        # (A,) int32
+    lat_error: object    # (A,) the signed angle to the head waypoint (0 where DONE)
+    lon_command: object  # (A,) the clipped longitudinal command (0 where DONE)
+
+
+@dataclass
+class AgentRolloutResult:
+    state: object        # (A, 6) after T ticks
+    head: object
+    past_steer: object
+    lon_err: object
+    n_lon: object
+    lat_err: object
+    n_lat: object
+    status: object       # (A,) int32 OR of the ticks' statuses
+    done_tick: object    # (A,) int32 first DONE tick, -1 if none
+    actors: object       # (A, 4) observe of the final state: drive's ``actors`` rows
+    log_state: object    # (n_log, A, 6) the state each logged tick saw; None without logs
+    log_control: object  # (n_log, A, 3)
+    log_head: object     # (n_log, A) int32 head after the tick's purge
+
+
 @dataclass
 class VehicleStepResult:
     state: object        # (B, 6) x, y, fi, Vy, fi_dot, Vx after the tick
@@ -998,6 +1057,74 @@ class Planner:
             self._h, C.byref(g), B, int(max_route), int(max_global), a.inp(start_node, np.int32, (B,)), a.inp(end_edge, np.int32, (B,)),
             a.inp(origin_wp, np.float64, (B, 3)), a.inp(dest_wp, np.float64, (B, 3)), rtp, rlp, wip, gpp, ngp, stp, a.where))
         return RouteResult(rt, rl, st, wi, gp, ng)
+
+    # ---- routed traffic: the agents' local planner and PID pair (reference agents/navigation/) -----------------
+    def agent_observe(self, state) -> AgentObservation:
+        """What the CARLA getters return for A vehicles of the project's model: state (A, 6) -> forward vector, km/h, actor rows."""
+        a = self._args(state)
+        A = int(state.shape[0])
+        fw, fwp = a.out((A, 2), np.float64)
+        kmh, kmhp = a.out((A,), np.float64)
+        act, actp = a.out((A, 4), np.float64)
+        self._check(self._lib.emp_agent_observe(self._h, A, a.inp(state, np.float64, (A, 6)), fwp, kmhp, actp, a.where))
+        return AgentObservation(fw, kmh, act)
+
+    @staticmethod
+    def _agent_state(a, A, head, past_steer, lon_err, n_lon, lat_err, n_lat, in_place):
+        """The six arrays of the agent state: the pointers of the inputs, and (array, pointer) of the outputs of their names."""
+        nb = L.AGENT_BUFFER
+        spec = ((head, np.int32, (A,)), (past_steer, np.float64, (A,)), (lon_err, np.float64, (A, nb)), (n_lon, np.int32, (A,)),
+                (lat_err, np.float64, (A, nb)), (n_lat, np.int32, (A,)))
+        ins = [a.inp(x, dt, shape) for x, dt, shape in spec]
+        outs = [a.out(shape, dt, into=_in_place(x, dt, in_place)) for x, dt, shape in spec]
+        return ins, outs
+
+    def agent_control(self, p, path, n_path, state, forward, speed_kmh, target_speed, head, past_steer, lon_err, n_lon, lat_err,
+                      n_lat, in_place=False) -> AgentControlResult:
+        """One tick of the agents' law (include/emplanner.h states it): path (A, M, 4) / n_path (A,) may be ``route``'s
+        global_path / n_global; forward (A, 2) and speed_kmh (A,) are ``agent_observe``'s.  in_place=True updates head,
+        past_steer and the two deques with their counts where they live."""
+        a = self._args(path, state, forward)
+        A, M = int(path.shape[0]), int(path.shape[1])
+        ins, outs = self._agent_state(a, A, head, past_steer, lon_err, n_lon, lat_err, n_lat, in_place)
+        ctl, ctlp = a.out((A, 3), np.float64)
+        st, stp = a.out((A,), np.int32)
+        le, lep = a.out((A,), np.float64)
+        lc, lcp = a.out((A,), np.float64)
+        self._check(self._lib.emp_agent_control(
+            self._h, C.byref(p), A, M, a.inp(path, np.float64, (A, M, 4)), a.inp(n_path, np.int32, (A,)),
+            a.inp(state, np.float64, (A, 6)), a.inp(forward, np.float64, (A, 2)), a.inp(speed_kmh, np.float64, (A,)),
+            a.inp(target_speed, np.float64, (A,)), *ins, ctlp, stp, *[o[1] for o in outs], lep, lcp, a.where))
+        return AgentControlResult(ctl, st, *[o[0] for o in outs], le, lc)
+
+    def agent_rollout(self, p, vp: VehicleParams, path, n_path, state, target_speed, head, past_steer, lon_err, n_lon, lat_err,
+                      n_lat, T, log_every=None, in_place=False) -> AgentRolloutResult:
+        """T ticks of [agent_observe, agent_control, vehicle_step(vp)] for A agents in ONE kernel launch, bit-identical to the
+        chain of the 3 T calls.  ``vp``: see ``agent_vehicle_params``.  log_every=k records ticks 0, k, 2k, ... (None: no logs).
+        in_place=True updates ``state`` and the agent state where they live.  ``actors`` of the result feeds ``drive``."""
+        T = int(T)
+        every = 1 if log_every is None else int(log_every)
+        n_log = (T + every - 1) // every if log_every is not None and every >= 1 and T >= 1 else None
+        a = self._args(path, state, lon_err)
+        A, M = int(path.shape[0]), int(path.shape[1])
+        io = L.AgentRolloutIO()
+        io.path, io.n_path = a.inp(path, np.float64, (A, M, 4)), a.inp(n_path, np.int32, (A,))
+        io.state, io.target_speed = a.inp(state, np.float64, (A, 6)), a.inp(target_speed, np.float64, (A,))
+        ins, outs = self._agent_state(a, A, head, past_steer, lon_err, n_lon, lat_err, n_lat, in_place)
+        io.head, io.past_steer, io.lon_err, io.n_lon, io.lat_err, io.n_lat = ins
+        so, io.state_out = a.out((A, 6), np.float64, into=_in_place(state, np.float64, in_place))
+        io.head_out, io.past_steer_out, io.lon_err_out, io.n_lon_out, io.lat_err_out, io.n_lat_out = [o[1] for o in outs]
+        st, io.status = a.out((A,), np.int32)
+        dn, io.done_tick = a.out((A,), np.int32)
+        act, io.actors_out = a.out((A, 4), np.float64)
+        ls = lc = lh = None
+        if n_log is not None:
+            ls, io.log_state = a.out((n_log, A, 6), np.float64)
+            lc, io.log_control = a.out((n_log, A, 3), np.float64)
+            lh, io.log_head = a.out((n_log, A), np.int32)
+        io.reserved = 0
+        self._check(self._lib.emp_agent_rollout(self._h, C.byref(p), C.byref(vp), A, M, T, every, C.byref(io), a.where))
+        return AgentRolloutResult(so, *[o[0] for o in outs], st, dn, act, ls, lc, lh)
 
     # ---- lateral MPC controller (reference controller/controller.py:65-337) -----------------------
     def mpc_lateral(self, p: MpcParams, target_path, n_path, state, vx, min_index, qp_matrices=False) -> MpcResult:

@@ -23,6 +23,7 @@
 #include "emp_drive_kernels.h"
 #include "emp_route_kernels.h"
 #include "emp_route_launch.h"
+#include "emp_agent_kernels.h"
 
 namespace emp {
 thread_local std::string g_create_error;
@@ -3160,6 +3161,150 @@ int emp_route_paths(emp_ctx* ctx, const emp_route_graph* graph, int32_t B, int32
     EMP_REQUIRE(ctx, B == 0 || (origin_wp && dest_wp && wp_index && global_path && n_global), "NULL argument");
     return route_impl(ctx, graph, B, max_route, max_global, start_node, end_edge, origin_wp, dest_wp, route, route_len, wp_index,
                       global_path, n_global, status, where);
+}
+
+}  // extern "C"
+
+// ---- routed traffic: the agents' local planner and PID pair (emp_agent_core.h, emp_agent_kernels.h) -----------------------------
+namespace {
+
+agt::Params agent_params(const emp_agent_params* p) {
+    return agt::Params{p->lat_K_P, p->lat_K_I, p->lat_K_D, p->lon_K_P, p->lon_K_I, p->lon_K_D, p->dt, p->max_throttle, p->max_brake,
+                       p->max_steer, p->base_min_distance};
+}
+
+// The caller's arrays of the agent state: six inputs and the six outputs of their names.
+struct AgentArrays {
+    const int32_t *head, *n_lon, *n_lat;
+    const double *past_steer, *lon_err, *lat_err;
+    int32_t *head_out, *n_lon_out, *n_lat_out;
+    double *past_steer_out, *lon_err_out, *lat_err_out;
+    bool complete() const {
+        return head && n_lon && n_lat && past_steer && lon_err && lat_err && head_out && n_lon_out && n_lat_out && past_steer_out &&
+               lon_err_out && lat_err_out;
+    }
+};
+void stage_agent_in(Stage& st, const AgentArrays& a, size_t nA, agt::StateIO* io) {
+    io->head_in = st.in(a.head, nA);
+    io->past_in = st.in(a.past_steer, nA);
+    io->lon_in = st.in(a.lon_err, nA * agt::kBuffer);
+    io->n_lon_in = st.in(a.n_lon, nA);
+    io->lat_in = st.in(a.lat_err, nA * agt::kBuffer);
+    io->n_lat_in = st.in(a.n_lat, nA);
+}
+void stage_agent_out(Stage& st, const AgentArrays& a, size_t nA, agt::StateIO* io) {
+    io->head_out = st.out(a.head_out, nA, false);
+    io->past_out = st.out(a.past_steer_out, nA, false);
+    io->lon_out = st.out(a.lon_err_out, nA * agt::kBuffer, false);
+    io->n_lon_out = st.out(a.n_lon_out, nA, false);
+    io->lat_out = st.out(a.lat_err_out, nA * agt::kBuffer, false);
+    io->n_lat_out = st.out(a.n_lat_out, nA, false);
+}
+
+}  // namespace
+
+extern "C" {
+
+void emp_agent_params_default(emp_agent_params* p) {
+    if (!p) return;
+    p->lat_K_P = 1.95; p->lat_K_I = 0.05; p->lat_K_D = 0.2;     // ref local_planner.py:73
+    p->lon_K_P = 1.0; p->lon_K_I = 0.05; p->lon_K_D = 0.0;      // :74
+    p->dt = 1.0 / 20.0;                                         // :70
+    p->max_throttle = 0.75;                                     // :75-77
+    p->max_brake = 0.3;
+    p->max_steer = 0.8;
+    p->base_min_distance = 3.0;                                 // :79
+    p->reserved = 0;
+}
+
+int emp_agent_observe(emp_ctx* ctx, int32_t A, const double* state, double* forward, double* speed_kmh, double* actors, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_agent_observe takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, A >= 0, "bad sizes");
+    EMP_REQUIRE(ctx, state && (forward || speed_kmh || actors), "NULL argument (state, and at least one output)");
+    EMP_STAGE(st, where);
+    const double* d_state = st.in(state, (size_t)A * 6);
+    double* d_fw = st.out(forward, (size_t)A * 2, false);
+    double* d_kmh = st.out(speed_kmh, (size_t)A, false);
+    double* d_act = st.out(actors, (size_t)A * 4, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "agent_observe", agt::agent_observe_kernel, grid1(A, 256), dim3(256), 0, (int)A, d_state, d_fw, d_kmh, d_act))
+        return rc;
+    return st.finish();
+}
+
+int emp_agent_control(emp_ctx* ctx, const emp_agent_params* p, int32_t A, int32_t max_path, const double* path, const int32_t* n_path,
+                      const double* state, const double* forward, const double* speed_kmh, const double* target_speed,
+                      const int32_t* head, const double* past_steer, const double* lon_err, const int32_t* n_lon,
+                      const double* lat_err, const int32_t* n_lat, double* control, int32_t* status, int32_t* head_out,
+                      double* past_steer_out, double* lon_err_out, int32_t* n_lon_out, double* lat_err_out, int32_t* n_lat_out,
+                      double* lat_error, double* lon_command, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_agent_control takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, p && A >= 0 && max_path >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, p->reserved == 0, "emp_agent_params.reserved must be 0");
+    const AgentArrays aa{head, n_lon, n_lat, past_steer, lon_err, lat_err, head_out, n_lon_out, n_lat_out, past_steer_out, lon_err_out, lat_err_out};
+    EMP_REQUIRE(ctx, path && n_path && state && forward && speed_kmh && target_speed && control && status && aa.complete(), "NULL argument");
+    const size_t nA = (size_t)A;
+    EMP_STAGE(st, where);
+    const double* d_path = st.in(path, nA * max_path * 4);
+    const int* d_np = st.in(n_path, nA);
+    const double* d_state = st.in(state, nA * 6);
+    const double* d_fw = st.in(forward, nA * 2);
+    const double* d_kmh = st.in(speed_kmh, nA);
+    const double* d_tgt = st.in(target_speed, nA);
+    agt::StateIO sio{};
+    stage_agent_in(st, aa, nA, &sio);
+    double* d_ctl = st.out(control, nA * 3, false);
+    int* d_st = st.out(status, nA, false);
+    stage_agent_out(st, aa, nA, &sio);
+    double* d_le = st.out(lat_error, nA, false);
+    double* d_lc = st.out(lon_command, nA, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "agent_control", agt::agent_control_kernel, grid1(A, 64), dim3(64), 0, (int)A, (int)max_path, agent_params(p),
+                              d_path, d_np, d_state, d_fw, d_kmh, d_tgt, sio, d_ctl, d_st, d_le, d_lc))
+        return rc;
+    return st.finish();
+}
+
+int emp_agent_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_vehicle_params* vp, int32_t A, int32_t max_path, int32_t T,
+                      int32_t log_every, const emp_agent_rollout_io* a, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_agent_rollout takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, p && vp && a, "NULL parameter struct");
+    EMP_REQUIRE(ctx, A >= 0 && max_path >= 1, "bad sizes");
+    EMP_REQUIRE(ctx, p->reserved == 0, "emp_agent_params.reserved must be 0");
+    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    EMP_REQUIRE(ctx, a->reserved == 0, "emp_agent_rollout_io.reserved must be 0");
+    EMP_REQUIRE(ctx, T >= 1 && T <= EMP_ROLLOUT_MAX_TICKS, "T must be in [1, 65536]");
+    EMP_REQUIRE(ctx, log_every >= 1, "log_every must be at least 1");
+    const AgentArrays aa{a->head, a->n_lon, a->n_lat, a->past_steer, a->lon_err, a->lat_err, a->head_out, a->n_lon_out, a->n_lat_out,
+                         a->past_steer_out, a->lon_err_out, a->lat_err_out};
+    EMP_REQUIRE(ctx, a->path && a->n_path && a->state && a->target_speed && a->state_out && a->status && a->done_tick && aa.complete(),
+                "NULL array");
+    const size_t nA = (size_t)A, n_log = rollout_log_rows(T, log_every);
+    EMP_STAGE(st, where);
+    const double* d_path = st.in(a->path, nA * max_path * 4);
+    const int* d_np = st.in(a->n_path, nA);
+    agt::RolloutIO io{};
+    io.T = T;
+    io.log_every = log_every;
+    io.state_in = st.in(a->state, nA * 6);
+    io.target_speed = st.in(a->target_speed, nA);
+    stage_agent_in(st, aa, nA, &io.st);
+    io.state_out = st.out(a->state_out, nA * 6, false);
+    stage_agent_out(st, aa, nA, &io.st);
+    io.status = st.out(a->status, nA, false);
+    io.done_tick = st.out(a->done_tick, nA, false);
+    io.actors_out = st.out(a->actors_out, nA * 4, false);
+    io.log_state = st.out(a->log_state, n_log * nA * 6, false);
+    io.log_control = st.out(a->log_control, n_log * nA * 3, false);
+    io.log_head = st.out(a->log_head, n_log * nA, false);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "agent_rollout", agt::agent_rollout_kernel, grid1(A, 64), dim3(64), 0, (int)A, (int)max_path, agent_params(p),
+                              vehicle_params(vp), d_path, d_np, io))
+        return rc;
+    return st.finish();
 }
 
 }  // extern "C"

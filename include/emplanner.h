@@ -1318,6 +1318,110 @@ int emp_route_paths(emp_ctx* ctx, const emp_route_graph* graph, int32_t B, int32
                     int32_t* route, int32_t* route_len, int32_t* wp_index, double* global_path, int32_t* n_global, int32_t* status,
                     emp_mem where);
 
+/* ---- routed traffic: the agents' local planner and PID pair (new with ABI 13's library; EMP_ABI_VERSION is unchanged) --------
+ * ref: the dynamic obstacle of the reference's drivers is a BehaviorAgent on a route (test_9.py:288-291), stepped once per control
+ * tick (test_9.py:344).  With no hazard in sight that step is LocalPlanner.run_step (agents/navigation/local_planner.py:208-260)
+ * and VehiclePIDController.run_step (agents/navigation/controller.py:54-92).  NOT reproduced: offset != 0; random waypoint
+ * creation (_stop_waypoint_creation is always true after set_global_plan); BehaviorAgent's traffic-light, pedestrian and
+ * car-following branches (they need CARLA's map queries); CARLA's float32 Location and its z coordinate.  The target speed is the
+ * caller's, as set_target_speed(30.0) is in the driver.
+ *
+ * The rule, per agent; every operation is rounded separately (no contraction), `/` and sqrt are IEEE, clip(v) = min(max(v, -1), 1)
+ * in NumPy's form (a NaN passes through).  It reads the pose x, y and the forward vector (c, s), speed_kmh and target_speed (both
+ * km/h), the path [max_path][4] in emp_route_paths' global_path layout (only x and y are read) and n_path (clamped to
+ * [0, max_path]).  It keeps head (int32, clamped to [0, n_path] on entry), past_steer, and two deques of EMP_AGENT_BUFFER doubles,
+ * oldest first, with counts n_lon and n_lat (clamped to [0, 10]).  Deque entries at and past the count are never read and come
+ * out as they went in.  One tick:
+ *   1. purge.  min_distance = base_min_distance + 0.5 * (speed_kmh / 3.6).  While head < n_path: (px, py) = path[head],
+ *      md = (n_path - head == 1) ? 1 : min_distance; if sqrt((x - px) * (x - px) + (y - py) * (y - py)) < md then ++head, else stop
+ *      (a NaN distance compares false and stops the purge).
+ *   2. empty queue.  head == n_path (n_path == 0 included): control = (0, 0, 1), status EMP_AGT_DONE, lat_error = lon_command = 0;
+ *      past_steer and both deques stay as they are (the reference does not call the controller).
+ *   3. longitudinal PID.  e = target_speed - speed_kmh is appended; a full deque drops its oldest entry.  With at least 2 entries
+ *      de = (e[-1] - e[-2]) / dt and ie = (the sum from +0, oldest first) * dt; with fewer, both are 0.
+ *      acc = clip((lon_K_P * e + lon_K_D * de) + lon_K_I * ie).
+ *   4. lateral PID and actuation.  (wx, wy) = (px - x, py - y) for path[head];  nn = sqrt(wx * wx + wy * wy) * sqrt((c * c + s * s) + 0).
+ *      nn == 0: dot = 1 (the reference's own value, one radian: kept).  Otherwise dot = acos(clip(((wx * c + wy * s) + 0) / nn)).
+ *      If c * wy - s * wx < 0 then dot = -dot.  dot is appended; de, ie and cs = clip(...) as in step 3 with the lat_ gains.
+ *      Rate limit: cs > past_steer + 0.1 gives past_steer + 0.1; else cs < past_steer - 0.1 gives past_steer - 0.1.
+ *      steer = cs >= 0 ? min(max_steer, cs) : max(-max_steer, cs).
+ *      acc >= 0: throttle = min(acc, max_throttle), brake = 0; otherwise throttle = 0, brake = min(|acc|, max_brake).
+ *      min / max are Python's: they keep their FIRST argument unless the second is strictly smaller / larger, so a NaN cs gives
+ *      steer = -max_steer, and a NaN acc throttle 0 and a NaN brake.  past_steer = steer.
+ *   A NaN enters a deque as the quiet NaN 0x7ff8000000000000.  acos is the one libm call of the law: outputs that depend on it
+ *   (lat_error, the newest lateral entry, a steer that neither limit binds) may differ from another libm's by its last bits times
+ *   about 6 (lat_K_P + lat_K_D / dt + lat_K_I * dt); every other output is determined to the bit.
+ *
+ * emp_agent_observe stands in for the CARLA getters, from state [A][6] = x, y, fi, Vy, fi_dot, Vx (emp_vehicle_step's):
+ *   (c, s) = (cos fi, sin fi), as emp_drive_request takes them;  (wx, wy) = (Vx * c - Vy * s, Vx * s + Vy * c);
+ *   forward [A][2] = c, s;  speed_kmh [A] = 3.6 * sqrt((wx * wx + wy * wy) + 0) (get_speed);  actors [A][4] = x, y, wx, wy: the
+ *   row emp_drive and emp_drive_timed take as an actor.  Each output is optional (NULL), at least one is required.
+ *   It exists so that the law's acos argument is made of data the caller can see: emp_agent_control takes (c, s) as data.
+ *
+ * emp_agent_control: one tick of the rule for A agents, one kernel.  Inputs: path [A][max_path][4], n_path [A], state [A][6] (x and
+ * y are read), forward [A][2], speed_kmh [A], target_speed [A], head [A], past_steer [A], lon_err [A][10], n_lon [A],
+ * lat_err [A][10], n_lat [A].  Outputs: control [A][3] = throttle, steer, brake; status [A]; head_out, past_steer_out, lon_err_out,
+ * n_lon_out, lat_err_out, n_lat_out (each may alias its input); optional lat_error [A] (the signed dot) and lon_command [A] (acc).
+ *
+ * emp_agent_rollout: T ticks in ONE launch.  Tick t is emp_agent_observe, then emp_agent_control, then emp_vehicle_step(vp) on its
+ * controls.  EVERY OUTPUT EQUALS, BIT FOR BIT, T iterations of those three calls on the same arrays, so a rollout cut in two
+ * resumes bit for bit.  A DONE agent keeps braking: its vehicle is stepped with (0, 0, 1) like any other.  T in
+ * [1, EMP_ROLLOUT_MAX_TICKS], log_every >= 1.  emp_agent_rollout_io: the inputs of emp_agent_control without forward and speed_kmh;
+ * outputs state_out [A][6] and the agent state (each may alias its input), status [A] (the OR over ticks), done_tick [A] (the first
+ * DONE tick, -1 if none), optional actors_out [A][4] (observe of the final state) and optional logs of n_log = ceil(T / log_every)
+ * rows, tick t logged when t % log_every == 0: log_state [n_log][A][6] (the state the tick saw), log_control [n_log][A][3],
+ * log_head [n_log][A] (head after the tick's purge).
+ * Use emp_vehicle_params with the tuple in physical order (a, b, Cf, Cr, m, Iz) = (1.015, 1.895, -148970, -82204, 1412, 1537) for a
+ * vehicle that takes corners: emp_vehicle_params_default keeps the controllers' unpacking order, whose plant barely yaws.
+ * Refused (EMP_ERR_INVALID): a NULL required pointer, max_path < 1, A < 0, T outside its range, log_every < 1, reserved != 0,
+ * EMP_HOST_PINNED.  A == 0: EMP_OK.  With a pipeline set the three calls fence like every non-cycle entry point. */
+#define EMP_AGENT_BUFFER 10
+#define EMP_AGT_DONE 1
+typedef struct emp_agent_params {
+    double lat_K_P, lat_K_I, lat_K_D;      /* 1.95, 0.05, 0.2 (local_planner.py:73) */
+    double lon_K_P, lon_K_I, lon_K_D;      /* 1.0, 0.05, 0.0 (:74) */
+    double dt;                             /* 0.05 (:70) */
+    double max_throttle, max_brake, max_steer; /* 0.75, 0.3, 0.8 (:75-77) */
+    double base_min_distance;              /* 3.0 (:79) */
+    int32_t reserved;                      /* must be 0 */
+} emp_agent_params;
+void emp_agent_params_default(emp_agent_params* p);
+int emp_agent_observe(emp_ctx* ctx, int32_t A, const double* state, double* forward, double* speed_kmh, double* actors, emp_mem where);
+int emp_agent_control(emp_ctx* ctx, const emp_agent_params* p, int32_t A, int32_t max_path, const double* path, const int32_t* n_path,
+                      const double* state, const double* forward, const double* speed_kmh, const double* target_speed,
+                      const int32_t* head, const double* past_steer, const double* lon_err, const int32_t* n_lon,
+                      const double* lat_err, const int32_t* n_lat, double* control, int32_t* status, int32_t* head_out,
+                      double* past_steer_out, double* lon_err_out, int32_t* n_lon_out, double* lat_err_out, int32_t* n_lat_out,
+                      double* lat_error, double* lon_command, emp_mem where);
+typedef struct emp_agent_rollout_io {
+    const double* path;                    /* [A][max_path][4] */
+    const int32_t* n_path;                 /* [A] */
+    const double* state;                   /* [A][6] */
+    const double* target_speed;            /* [A] km/h */
+    const int32_t* head;                   /* [A] */
+    const double* past_steer;              /* [A] */
+    const double* lon_err;                 /* [A][EMP_AGENT_BUFFER] */
+    const int32_t* n_lon;                  /* [A] */
+    const double* lat_err;                 /* [A][EMP_AGENT_BUFFER] */
+    const int32_t* n_lat;                  /* [A] */
+    double* state_out;
+    int32_t* head_out;
+    double* past_steer_out;
+    double* lon_err_out;
+    int32_t* n_lon_out;
+    double* lat_err_out;
+    int32_t* n_lat_out;
+    int32_t* status;
+    int32_t* done_tick;
+    double* actors_out;                    /* optional */
+    double* log_state;                     /* optional logs */
+    double* log_control;
+    int32_t* log_head;
+    int32_t reserved;                      /* must be 0 */
+} emp_agent_rollout_io;
+int emp_agent_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_vehicle_params* vp, int32_t A, int32_t max_path, int32_t T,
+                      int32_t log_every, const emp_agent_rollout_io* io, emp_mem where);
+
 #ifdef __cplusplus
 }
 #endif
