@@ -165,6 +165,28 @@ class AgentRolloutIO(C.Structure):
         "actors_out", "log_state", "log_control", "log_head")] + [("reserved", C.c_int32)]
 
 
+TRAFFIC_MAX_WORLD = 64             # EMP_TRAFFIC_MAX_WORLD: agents of a world, and others of a world
+BHV_NORMAL, BHV_SLOW, BHV_FOLLOW, BHV_CLEAR, BHV_EMERGENCY, BHV_DONE = range(6)       # EMP_BHV_*: the mode of a tick
+BHV_KINDS = {"cautious": 0, "normal": 1, "aggressive": 2}                            # EMP_BHV_CAUTIOUS, _KIND_NORMAL, _AGGRESSIVE
+
+
+class BehaviorParams(C.Structure):
+    """emp_behavior_params: behavior_types.py plus the constants of BehaviorAgent's car-following."""
+    _fields_ = [(n, C.c_double) for n in ("max_speed", "speed_lim_dist", "speed_decrease", "safety_time", "min_proximity_threshold",
+                                          "braking_distance", "min_speed", "emergency_brake", "up_angle")] + \
+               [("look_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BehaviorIO(C.Structure):
+    """emp_behavior_io: the arrays of emp_agent_behave and emp_traffic_rollout."""
+    _fields_ = [(n, _vp) for n in (
+        "n_world", "path", "n_path", "lane", "state", "forward", "speed_kmh", "speed_limit", "extent", "head", "past_steer", "lon_err",
+        "n_lon", "lat_err", "n_lat", "n_other", "other", "other_lane", "head_out", "past_steer_out", "lon_err_out", "n_lon_out",
+        "lat_err_out", "n_lat_out", "status", "control", "mode", "blocker", "distance", "ttc", "target_speed_out", "lat_error",
+        "lon_command", "state_out", "done_tick", "mode_ticks", "min_gap", "actors_out", "log_state", "log_control", "log_head",
+        "log_mode", "log_target")] + [("reserved", C.c_int32)]
+
+
 class CycleIO(C.Structure):
     _fields_ = [(n, _vp) for n in (
         "ref_line", "n_ref", "origin_xy", "start_xy", "start_v", "start_a", "obs_xy", "n_obs",
@@ -324,6 +346,11 @@ PROTOTYPES = {
     "emp_agent_control": (C.c_int, [_vp, C.POINTER(AgentParams), _i32, _i32] + [_vp] * 22 + [C.c_int]),
     "emp_agent_rollout": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(VehicleParams), _i32, _i32, _i32, _i32,
                                     C.POINTER(AgentRolloutIO), C.c_int]),
+    "emp_behavior_params_default": (None, [C.POINTER(BehaviorParams), _i32]),
+    "emp_agent_behave": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(BehaviorParams), _i32, _i32, _i32, _i32, C.c_int64,
+                                   C.POINTER(BehaviorIO), C.c_int]),
+    "emp_traffic_rollout": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(BehaviorParams), C.POINTER(VehicleParams), _i32, _i32, _i32,
+                                      _i32, _i32, _i32, C.c_int64, C.POINTER(BehaviorIO), C.c_int]),
 }
 
 _lib = None

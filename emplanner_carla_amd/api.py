@@ -116,6 +116,21 @@ def agent_vehicle_params(vehicle_para=AGENT_VEHICLE_PARA, dt=0.05, **kw) -> Vehi
     return vehicle_params(vehicle_para=vehicle_para, dt=dt, **kw)
 
 
+def behavior_params(kind="normal", **kw) -> L.BehaviorParams:
+    """The car-following constants of the reference's BehaviorAgent: ``kind`` is "cautious", "normal" or "aggressive"
+    (agents/navigation/behavior_types.py); keywords replace single fields (min_speed, emergency_brake, up_angle, look_steps too)."""
+    if kind not in L.BHV_KINDS:
+        raise ValueError(f"kind must be one of {sorted(L.BHV_KINDS)}, not {kind!r}")
+    p = L.BehaviorParams()
+    L.load().emp_behavior_params_default(C.byref(p), L.BHV_KINDS[kind])
+    names = {n for n, _ in L.BehaviorParams._fields_} - {"reserved"}
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError(f"behavior_params has no field {k!r}")
+        setattr(p, k, int(v) if k == "look_steps" else float(v))
+    return p
+
+
 @dataclass
 class AgentObservation:
     forward: object      # (A, 2) cos fi, sin fi: the transform's forward vector
@@ -152,6 +167,46 @@ class AgentRolloutResult:
     log_state: object    # (n_log, A, 6) the state each logged tick saw; None without logs
     log_control: object  # (n_log, A, 3)
     log_head: object     # (n_log, A) int32 head after the tick's purge
+
+
+@dataclass
+class BehaveResult:
+    control: object      # (W, N, 3) throttle, steer, brake
+    status: object       # (W, N) int32 EMP_AGT_DONE where the queue is empty
+    head: object         # the agent state after the tick, as AgentControlResult's, (W, N, ...)
+    past_steer: object
+    lon_err: object
+    n_lon: object
+    lat_err: object
+    n_lat: object
+    mode: object         # (W, N) int32 EMP_BHV_*
+    blocker: object      # (W, N) int32 position of the vehicle ahead in the scan order, -1 if none
+    distance: object     # (W, N) bumper distance to it, +inf if none
+    ttc: object          # (W, N) time to collision, +inf where the rule does not compute it
+    target_speed: object # (W, N) km/h the local planner holds after the tick
+    lat_error: object
+    lon_command: object
+
+
+@dataclass
+class TrafficRolloutResult:
+    state: object        # (W, N, 6) after T ticks
+    head: object
+    past_steer: object
+    lon_err: object
+    n_lon: object
+    lat_err: object
+    n_lat: object
+    status: object       # (W, N) int32 OR of the ticks' statuses
+    done_tick: object    # (W, N) int32 first DONE tick, -1 if none
+    mode_ticks: object   # (W, N, 5) int32 ticks spent in NORMAL, SLOW, FOLLOW, CLEAR, EMERGENCY
+    min_gap: object      # (W, N) the smallest bumper distance to a vehicle ahead, +inf if none was seen
+    actors: object       # (W, N, 4) observe of the final state
+    log_state: object    # (n_log, W, N, 6); None without logs
+    log_control: object  # (n_log, W, N, 3)
+    log_head: object     # (n_log, W, N) int32
+    log_mode: object     # (n_log, W, N) int32
+    log_target: object   # (n_log, W, N)
 
 
 @dataclass
@@ -1125,6 +1180,83 @@ class Planner:
         io.reserved = 0
         self._check(self._lib.emp_agent_rollout(self._h, C.byref(p), C.byref(vp), A, M, T, every, C.byref(io), a.where))
         return AgentRolloutResult(so, *[o[0] for o in outs], st, dn, act, ls, lc, lh)
+
+    # ---- traffic that reacts to traffic: BehaviorAgent's car-following (reference agents/navigation/behavior_agent.py) ----
+    def _behavior_io(self, a, n_world, path, n_path, lane, state, speed_limit, extent, agent_state, others, in_place):
+        """The fields both behaviour calls share: -> (io, W, N, M, max_other, the six agent-state outputs)."""
+        W, N, M = int(path.shape[0]), int(path.shape[1]), int(path.shape[2])
+        nb = L.AGENT_BUFFER
+        io = L.BehaviorIO()
+        io.n_world, io.path = a.inp(n_world, np.int32, (W,)), a.inp(path, np.float64, (W, N, M, 4))
+        io.n_path, io.lane = a.inp(n_path, np.int32, (W, N)), a.inp(lane, np.int32, (W, N, M))
+        io.state, io.speed_limit = a.inp(state, np.float64, (W, N, 6)), a.inp(speed_limit, np.float64, (W, N))
+        io.extent = a.inp(extent, np.float64, (W, N))
+        spec = list(zip(agent_state, (np.int32, np.float64, np.float64, np.int32, np.float64, np.int32),
+                        ((W, N), (W, N), (W, N, nb), (W, N), (W, N, nb), (W, N))))
+        io.head, io.past_steer, io.lon_err, io.n_lon, io.lat_err, io.n_lat = [a.inp(x, dt, shape) for x, dt, shape in spec]
+        outs = [a.out(shape, dt, into=_in_place(x, dt, in_place)) for x, dt, shape in spec]
+        io.head_out, io.past_steer_out, io.lon_err_out, io.n_lon_out, io.lat_err_out, io.n_lat_out = [o[1] for o in outs]
+        max_other = 0
+        if others is not None:
+            n_other, other, other_lane = others
+            max_other = int(other.shape[1])
+            if max_other > 0:
+                io.n_other, io.other = a.inp(n_other, np.int32, (W,)), a.inp(other, np.float64, (W, max_other, 5))
+                io.other_lane = a.inp(other_lane, np.int32, (W, max_other))
+        io.reserved = 0
+        return io, W, N, M, max_other, [o[0] for o in outs]
+
+    def agent_behave(self, p, bp, n_world, path, n_path, lane, state, forward, speed_kmh, speed_limit, extent, head, past_steer,
+                     lon_err, n_lon, lat_err, n_lat, others=None, tick0=0, in_place=False) -> BehaveResult:
+        """One tick of BehaviorAgent's car-following law (include/emplanner.h states it) for W worlds of up to N <= 64 agents:
+        n_world (W,), path (W, N, M, 4), n_path (W, N), lane (W, N, M) int32 keys (``RouteResult.lane_key()``), state (W, N, 6),
+        forward (W, N, 2) and speed_kmh (W, N) as ``agent_observe`` gives them, speed_limit and extent (W, N).  others:
+        (n_other (W,), other (W, K, 5) = x, y, vx, vy, half extent, other_lane (W, K)) vehicles the call does not drive, seen at
+        time tick0 * p.dt.  Agents see only their own world; padding slots are neither read nor written (host arrays: outputs come
+        back with 0 there)."""
+        a = self._args(path, state, forward)
+        io, W, N, M, K, outs = self._behavior_io(a, n_world, path, n_path, lane, state, speed_limit, extent,
+                                                 (head, past_steer, lon_err, n_lon, lat_err, n_lat), others, in_place)
+        io.forward, io.speed_kmh = a.inp(forward, np.float64, (W, N, 2)), a.inp(speed_kmh, np.float64, (W, N))
+        st, io.status = a.out((W, N), np.int32)
+        ctl, io.control = a.out((W, N, 3), np.float64)
+        mode, io.mode = a.out((W, N), np.int32)
+        blk, io.blocker = a.out((W, N), np.int32)
+        dist, io.distance = a.out((W, N), np.float64)
+        ttc, io.ttc = a.out((W, N), np.float64)
+        tgt, io.target_speed_out = a.out((W, N), np.float64)
+        le, io.lat_error = a.out((W, N), np.float64)
+        lc, io.lon_command = a.out((W, N), np.float64)
+        self._check(self._lib.emp_agent_behave(self._h, C.byref(p), C.byref(bp), W, N, M, K, int(tick0), C.byref(io), a.where))
+        return BehaveResult(ctl, st, *outs, mode, blk, dist, ttc, tgt, le, lc)
+
+    def traffic_rollout(self, p, bp, vp: VehicleParams, n_world, path, n_path, lane, state, speed_limit, extent, head, past_steer,
+                        lon_err, n_lon, lat_err, n_lat, T, others=None, tick0=0, log_every=None, in_place=False) -> TrafficRolloutResult:
+        """T ticks of [agent_observe, agent_behave, vehicle_step(vp)] in ONE kernel launch, bit-identical to the chain of the 3 T
+        calls; a rollout cut in two, with ``tick0`` advanced by the ticks done, resumes bit for bit.  Arrays as ``agent_behave``.
+        log_every=k records ticks 0, k, 2k, ... (None: no logs).  in_place=True updates ``state`` and the agent state where they live."""
+        T = int(T)
+        every = 1 if log_every is None else int(log_every)
+        n_log = (T + every - 1) // every if log_every is not None and every >= 1 and T >= 1 else None
+        a = self._args(path, state, lon_err)
+        io, W, N, M, K, outs = self._behavior_io(a, n_world, path, n_path, lane, state, speed_limit, extent,
+                                                 (head, past_steer, lon_err, n_lon, lat_err, n_lat), others, in_place)
+        so, io.state_out = a.out((W, N, 6), np.float64, into=_in_place(state, np.float64, in_place))
+        st, io.status = a.out((W, N), np.int32)
+        dn, io.done_tick = a.out((W, N), np.int32)
+        mt, io.mode_ticks = a.out((W, N, 5), np.int32)
+        mg, io.min_gap = a.out((W, N), np.float64)
+        act, io.actors_out = a.out((W, N, 4), np.float64)
+        ls = lc = lh = lm = lt = None
+        if n_log is not None:
+            ls, io.log_state = a.out((n_log, W, N, 6), np.float64)
+            lc, io.log_control = a.out((n_log, W, N, 3), np.float64)
+            lh, io.log_head = a.out((n_log, W, N), np.int32)
+            lm, io.log_mode = a.out((n_log, W, N), np.int32)
+            lt, io.log_target = a.out((n_log, W, N), np.float64)
+        self._check(self._lib.emp_traffic_rollout(self._h, C.byref(p), C.byref(bp), C.byref(vp), W, N, M, K, T, every, int(tick0),
+                                                  C.byref(io), a.where))
+        return TrafficRolloutResult(so, *outs, st, dn, mt, mg, act, ls, lc, lh, lm, lt)
 
     # ---- lateral MPC controller (reference controller/controller.py:65-337) -----------------------
     def mpc_lateral(self, p: MpcParams, target_path, n_path, state, vx, min_index, qp_matrices=False) -> MpcResult:

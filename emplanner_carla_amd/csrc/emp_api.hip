@@ -24,6 +24,7 @@
 #include "emp_route_kernels.h"
 #include "emp_route_launch.h"
 #include "emp_agent_kernels.h"
+#include "emp_behavior_kernels.h"
 
 namespace emp {
 thread_local std::string g_create_error;
@@ -3303,6 +3304,161 @@ int emp_agent_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_vehicle
     if (const int rc = st.ready()) return rc;
     if (const int rc = launch(ctx, "agent_rollout", agt::agent_rollout_kernel, grid1(A, 64), dim3(64), 0, (int)A, (int)max_path, agent_params(p),
                               vehicle_params(vp), d_path, d_np, io))
+        return rc;
+    return st.finish();
+}
+
+}  // extern "C"
+
+// ---- traffic that reacts to traffic: BehaviorAgent's car-following (emp_behavior_core.h, emp_behavior_kernels.h) ----------------
+namespace {
+
+bhv::Params behavior_params(const emp_behavior_params* p) {
+    return bhv::Params{p->max_speed, p->speed_lim_dist, p->speed_decrease, p->safety_time, p->min_proximity_threshold, p->braking_distance,
+                       p->min_speed, p->emergency_brake, p->up_angle, (int)p->look_steps};
+}
+
+AgentArrays behavior_agent_arrays(const emp_behavior_io* a) {
+    return AgentArrays{a->head, a->n_lon, a->n_lat, a->past_steer, a->lon_err, a->lat_err, a->head_out, a->n_lon_out, a->n_lat_out,
+                       a->past_steer_out, a->lon_err_out, a->lat_err_out};
+}
+
+// what both calls refuse, and the arrays both stage: the world, the agents' inputs and state.  A padding slot is never written in
+// the caller's device memory (EMP_DEVICE); staged outputs (EMP_HOST) are copied back whole, their padding slots as 0.
+int behavior_checks(emp_ctx* ctx, const char* who, const emp_agent_params* p, const emp_behavior_params* bp, const emp_behavior_io* a,
+                    int max_other, emp_mem where, const bhv::BehaviorPlan& plan) {
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "the behaviour calls take EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, p && bp && a, "NULL parameter struct");
+    (void)who;
+    EMP_REQUIRE(ctx, plan.error == nullptr, plan.error);
+    EMP_REQUIRE(ctx, p->reserved == 0, "emp_agent_params.reserved must be 0");
+    EMP_REQUIRE(ctx, bp->reserved == 0, "emp_behavior_params.reserved must be 0");
+    EMP_REQUIRE(ctx, a->reserved == 0, "emp_behavior_io.reserved must be 0");
+    EMP_REQUIRE(ctx, a->n_world && a->path && a->n_path && a->lane && a->state && a->speed_limit && a->extent && a->status &&
+                         behavior_agent_arrays(a).complete(), "NULL array");
+    EMP_REQUIRE(ctx, max_other == 0 || (a->n_other && a->other && a->other_lane), "max_other > 0 needs n_other, other and other_lane");
+    return EMP_OK;
+}
+
+void stage_world(Stage& st, const emp_behavior_io* a, size_t W, size_t max_world, size_t max_path, size_t max_other, int64_t tick0,
+                 bhv::WorldIO* io) {
+    const size_t nA = W * max_world;
+    io->max_world = (int)max_world;
+    io->max_path = (int)max_path;
+    io->max_other = (int)max_other;
+    io->tick0 = (long long)tick0;
+    io->n_world = st.in(a->n_world, W);
+    io->path = st.in(a->path, nA * max_path * 4);
+    io->n_path = st.in(a->n_path, nA);
+    io->lane = st.in(a->lane, nA * max_path);
+    io->state = st.in(a->state, nA * 6);
+    io->speed_limit = st.in(a->speed_limit, nA);
+    io->extent = st.in(a->extent, nA);
+    if (max_other > 0) {
+        io->n_other = st.in(a->n_other, W);
+        io->other = st.in(a->other, W * max_other * 5);
+        io->other_lane = st.in(a->other_lane, W * max_other);
+    }
+    stage_agent_in(st, behavior_agent_arrays(a), nA, &io->st);
+}
+
+void stage_behavior_state_out(Stage& st, const emp_behavior_io* a, size_t nA, bool z, bhv::WorldIO* io) {
+    io->st.head_out = st.out(a->head_out, nA, z);
+    io->st.past_out = st.out(a->past_steer_out, nA, z);
+    io->st.lon_out = st.out(a->lon_err_out, nA * agt::kBuffer, z);
+    io->st.n_lon_out = st.out(a->n_lon_out, nA, z);
+    io->st.lat_out = st.out(a->lat_err_out, nA * agt::kBuffer, z);
+    io->st.n_lat_out = st.out(a->n_lat_out, nA, z);
+    io->status = st.out(a->status, nA, z);
+}
+
+}  // namespace
+
+extern "C" {
+
+void emp_behavior_params_default(emp_behavior_params* p, int32_t kind) {
+    if (!p) return;
+    // ref behavior_types.py: Cautious, Normal, Aggressive
+    if (kind == EMP_BHV_CAUTIOUS) {
+        p->max_speed = 40.0; p->speed_lim_dist = 6.0; p->speed_decrease = 12.0; p->safety_time = 3.0;
+        p->min_proximity_threshold = 12.0; p->braking_distance = 6.0;
+    } else if (kind == EMP_BHV_AGGRESSIVE) {
+        p->max_speed = 70.0; p->speed_lim_dist = 1.0; p->speed_decrease = 8.0; p->safety_time = 3.0;
+        p->min_proximity_threshold = 8.0; p->braking_distance = 4.0;
+    } else {
+        p->max_speed = 50.0; p->speed_lim_dist = 3.0; p->speed_decrease = 10.0; p->safety_time = 3.0;
+        p->min_proximity_threshold = 10.0; p->braking_distance = 5.0;
+    }
+    p->min_speed = 5.0;                                         // behavior_agent.py:51
+    p->emergency_brake = 0.5;                                   // basic_agent.py:50
+    p->up_angle = 30.0;                                         // behavior_agent.py:215
+    p->look_steps = 5;                                          // :128
+    p->reserved = 0;
+}
+
+int emp_agent_behave(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, int32_t W, int32_t max_world,
+                     int32_t max_path, int32_t max_other, int64_t tick0, const emp_behavior_io* a, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    const bhv::BehaviorPlan plan = bhv::plan_behavior(W, max_world, max_other, max_path, 0, 1, tick0);
+    if (const int rc = behavior_checks(ctx, "emp_agent_behave", p, bp, a, max_other, where, plan)) return rc;
+    EMP_REQUIRE(ctx, a->forward && a->speed_kmh && a->control && a->mode && a->blocker && a->distance && a->ttc && a->target_speed_out,
+                "NULL array");
+    if (W == 0) return EMP_OK;
+    const size_t nA = (size_t)W * max_world;
+    EMP_STAGE(st, where);
+    const bool z = where == EMP_HOST;          // staged outputs start from 0; the caller's device memory is never filled
+    bhv::WorldIO io{};
+    stage_world(st, a, (size_t)W, (size_t)max_world, (size_t)max_path, (size_t)max_other, tick0, &io);
+    io.forward = st.in(a->forward, nA * 2);
+    io.speed_kmh = st.in(a->speed_kmh, nA);
+    stage_behavior_state_out(st, a, nA, z, &io);
+    io.control = st.out(a->control, nA * 3, z);
+    io.mode = st.out(a->mode, nA, z);
+    io.blocker = st.out(a->blocker, nA, z);
+    io.distance = st.out(a->distance, nA, z);
+    io.ttc = st.out(a->ttc, nA, z);
+    io.target_out = st.out(a->target_speed_out, nA, z);
+    io.lat_error = st.out(a->lat_error, nA, z);
+    io.lon_command = st.out(a->lon_command, nA, z);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "agent_behave", bhv::agent_behave_kernel, dim3(plan.grid), dim3(plan.block), 0, agent_params(p),
+                              behavior_params(bp), io))
+        return rc;
+    return st.finish();
+}
+
+int emp_traffic_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp, int32_t W,
+                        int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every, int64_t tick0,
+                        const emp_behavior_io* a, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, T >= 1, "T must be in [1, 65536]");
+    const bhv::BehaviorPlan plan = bhv::plan_behavior(W, max_world, max_other, max_path, T, log_every, tick0);
+    if (const int rc = behavior_checks(ctx, "emp_traffic_rollout", p, bp, a, max_other, where, plan)) return rc;
+    EMP_REQUIRE(ctx, vp != nullptr, "NULL parameter struct");
+    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    EMP_REQUIRE(ctx, a->state_out && a->done_tick && a->mode_ticks && a->min_gap, "NULL array");
+    if (W == 0) return EMP_OK;
+    const size_t nA = (size_t)W * max_world, n_log = plan.n_log;
+    EMP_STAGE(st, where);
+    const bool z = where == EMP_HOST;          // staged outputs start from 0; the caller's device memory is never filled
+    bhv::WorldIO io{};
+    stage_world(st, a, (size_t)W, (size_t)max_world, (size_t)max_path, (size_t)max_other, tick0, &io);
+    io.T = T;
+    io.log_every = log_every;
+    stage_behavior_state_out(st, a, nA, z, &io);
+    io.state_out = st.out(a->state_out, nA * 6, z);
+    io.done_tick = st.out(a->done_tick, nA, z);
+    io.mode_ticks = st.out(a->mode_ticks, nA * bhv::kCountedModes, z);
+    io.min_gap = st.out(a->min_gap, nA, z);
+    io.actors_out = st.out(a->actors_out, nA * 4, z);
+    io.log_state = st.out(a->log_state, n_log * nA * 6, z);
+    io.log_control = st.out(a->log_control, n_log * nA * 3, z);
+    io.log_head = st.out(a->log_head, n_log * nA, z);
+    io.log_mode = st.out(a->log_mode, n_log * nA, z);
+    io.log_target = st.out(a->log_target, n_log * nA, z);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "traffic_rollout", bhv::traffic_rollout_kernel, dim3(plan.grid), dim3(plan.block), 0, agent_params(p),
+                              behavior_params(bp), vehicle_params(vp), (int)nA, io))
         return rc;
     return st.finish();
 }

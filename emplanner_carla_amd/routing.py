@@ -57,6 +57,9 @@ class RoadGraph:
         if len(np.unique(self.edge_u.astype(np.int64) * N + self.succ)) != E:
             raise ValueError("a node lists the same successor twice (one edge per (u, v), as in a DiGraph)")
         self._device = {}
+        #: [E] int32 lane key of each edge: what stands in for CARLA's (road_id, lane_id) in the car-following law
+        #: (emp_agent_behave).  The edge id unless a builder knows better; a key below 0 never matches.
+        self.edge_key = np.arange(E, dtype=np.int32)
         # what from_segments / from_carla_map add
         self.seg_edge = None          # [S] the edge each segment became (a duplicate (u, v) shares its edge)
         self.edge_seg = None          # [E] the segment whose attributes the edge carries (the LAST add_edge of the pair)
@@ -180,6 +183,8 @@ class RoadGraph:
         for t, e in zip(topology, g.seg_edge):
             w = t["entry"]
             g.road_to_edge.setdefault(w.road_id, {}).setdefault(w.section_id, {})[w.lane_id] = (int(g.edge_u[e]), int(g.succ[e]))
+        g.edge_key = np.array([pack_lane_key(topology[s]["entry"].road_id, topology[s]["entry"].lane_id) for s in g.edge_seg],
+                              np.int32).reshape(g.n_edges)
         return g
 
     @classmethod
@@ -187,6 +192,15 @@ class RoadGraph:
         """``_build_topology`` then ``_build_graph`` on ``world_map.get_topology()``.  Duck-typed: a waypoint needs
         ``transform.location`` (``x``, ``y``, ``z``, ``distance``), ``next(d)``, ``road_id``, ``section_id``, ``lane_id``."""
         return cls.from_topology(cls.topology_of(world_map, sampling_resolution))
+
+
+def pack_lane_key(road_id: int, lane_id: int) -> int:
+    """(road_id, lane_id) as one non-negative int32: road_id * 256 + (lane_id + 128), lane ids in [-128, 127] and road ids below
+    2^23 (OpenDRIVE lanes are small signed numbers)."""
+    road_id, lane_id = int(road_id), int(lane_id)
+    if not (0 <= road_id < 1 << 23 and -128 <= lane_id <= 127):
+        raise ValueError(f"(road_id, lane_id) = ({road_id}, {lane_id}) does not fit a lane key")
+    return road_id * 256 + (lane_id + 128)
 
 
 @dataclass
@@ -198,6 +212,21 @@ class RouteResult:
     wp_index: object = None      # (B, max_global) int32 rows of graph.wp
     global_path: object = None   # (B, max_global, 4) x, y, theta, kappa
     n_global: object = None      # (B,)
+
+    def lane_key(self, graph: "RoadGraph"):
+        """(B, max_global) int32: the lane key (``graph.edge_key``) of the edge each waypoint of ``global_path`` lies on, -1 past
+        ``n_global`` - the ``lane`` array of ``Planner.agent_behave`` / ``traffic.BehaviorTraffic``, of the kind ``wp_index`` is."""
+        if self.wp_index is None:
+            raise ValueError("lane_key needs the wp_index of Planner.route")
+        torch_ = hasattr(self.wp_index, "data_ptr")
+        wi = self.wp_index.detach().cpu().numpy() if torch_ else np.asarray(self.wp_index)
+        ng = self.n_global.detach().cpu().numpy() if torch_ else np.asarray(self.n_global)
+        edge = np.clip(np.searchsorted(graph.wp_off, np.clip(wi, 0, max(graph.n_wp - 1, 0)), side="right") - 1, 0, max(graph.n_edges - 1, 0))
+        key = np.where(np.arange(wi.shape[1])[None, :] < ng[:, None], np.asarray(graph.edge_key, np.int32)[edge], -1).astype(np.int32)
+        if torch_:
+            import torch
+            return torch.from_numpy(key).to(self.wp_index.device)
+        return key
 
 
 UNREACHABLE, TRUNCATED, BAD_QUERY = L.ROUTE_UNREACHABLE, L.ROUTE_TRUNCATED, L.ROUTE_BAD_QUERY

@@ -12,6 +12,9 @@ whose queue is empty, ``set_speed()`` changes the target.  What the reference le
         res = planner.drive(..., actors=actors, n_act=n_act, K=1, T=T)
         traffic.rollout(round(T * vp_ego.dt / traffic.vp.dt))                       # the same span of time
 
+``BehaviorTraffic`` is the same fleet with the reference's BehaviorAgent on top: W worlds of up to 64 agents that see the vehicles
+of their own world - each other, and ``set_others()``'s, e.g. a planning fleet's egos - and follow, slow down or stop behind them.
+
 Include/emplanner.h states the law and what of the reference is not reproduced."""
 from __future__ import annotations
 
@@ -98,3 +101,108 @@ class TrafficAgents:
         """ref LocalPlanner.done per agent: (A,) bool, the waypoint queue is empty."""
         return self.head >= self.n_path.clamp(0, int(self.paths.shape[1])) if self._torch else \
             self.head >= np.clip(self.n_path, 0, self.paths.shape[1])
+
+
+class BehaviorTraffic(TrafficAgents):
+    """W worlds of up to N <= 64 agents with the reference's BehaviorAgent car-following law: paths (W, N, M, 4), n_path (W, N),
+    lane (W, N, M) int32 lane keys (``RouteResult.lane_key(graph)`` reshaped), state (W, N, 6), speed_limit km/h (a number, or
+    (W, N)), n_world (W,) the live agents of each world (None: all N), extent (W, N) half extents in metres (a number: all alike;
+    2.4 is a mid-size car's).  Arrays of one kind, as for ``TrafficAgents``.  The target speed is the law's own: it follows from the
+    speed limit and the vehicle ahead."""
+
+    def __init__(self, planner, paths, n_path, lane, state, speed_limit, n_world=None, extent=2.4, params=None, behavior=None,
+                 vehicle=None):
+        W, N = int(paths.shape[0]), int(paths.shape[1])
+        if tuple(paths.shape[3:]) != (4,) or tuple(state.shape) != (W, N, 6) or tuple(lane.shape) != tuple(paths.shape[:3]):
+            raise ValueError("paths must be (W, N, M, 4), lane (W, N, M) and state (W, N, 6)")
+        if not 1 <= N <= L.TRAFFIC_MAX_WORLD:
+            raise ValueError(f"a world holds 1 to {L.TRAFFIC_MAX_WORLD} agents, not {N}")
+        self.W, self.N = W, N
+        flat = lambda x: x.reshape((W * N,) + tuple(x.shape[2:]))
+        super().__init__(planner, flat(paths), flat(n_path), flat(state), 0.0, params=params, vehicle=vehicle)
+        self.behavior = behavior if behavior is not None else api.behavior_params()
+        self.lane = self._own(lane, np.int32)
+        self.speed_limit, self.extent = self._zeros((W, N), np.float64), self._zeros((W, N), np.float64)
+        self.n_world = self._zeros((W,), np.int32)
+        self._fill(self.n_world, N if n_world is None else n_world)
+        self._fill(self.extent, extent)
+        self.set_speed_limit(speed_limit)
+        self.others = None
+        self.tick = 0                  # ticks done: the clock of the others
+        self.mode = self._zeros((W, N), np.int32)
+        self.target_speed = self._zeros((W, N), np.float64)
+
+    def _fill(self, dst, value):
+        if self._torch:
+            import torch
+            dst.copy_(torch.as_tensor(value, dtype=dst.dtype).to(dst.device).expand(dst.shape))
+        else:
+            dst[...] = np.broadcast_to(np.asarray(value, dst.dtype), dst.shape)
+
+    def _world(self, x):
+        return x.reshape((self.W, self.N) + tuple(x.shape[1:]))
+
+    def _state_args(self):
+        v = self._world
+        return (v(self.head), v(self.past_steer), v(self.lon_err), v(self.n_lon), v(self.lat_err), v(self.n_lat))
+
+    def _adopt(self, r):
+        self.status = r.status.reshape(self.A)
+
+    # ---- the BehaviorAgent surface ----------------------------------------------------------------------------------------------
+    def set_speed(self, speed):
+        """The law sets its own target from the speed limit: use ``set_speed_limit``."""
+        if hasattr(self, "speed_limit"):
+            raise AttributeError("BehaviorTraffic takes its target from the speed limit: use set_speed_limit")
+
+    def set_speed_limit(self, limit):
+        """What get_speed_limit returns, km/h: one number, or (W, N)."""
+        self._fill(self.speed_limit, limit)
+
+    def set_others(self, other=None, other_lane=None, n_other=None):
+        """Vehicles the fleet does not drive: other (W, K, 5) = x, y, world-frame vx, vy, half extent (the first four columns are a
+        row of ``Planner.drive``'s actors), other_lane (W, K) their lane keys, n_other (W,) (None: all K).  Their positions are
+        those at the fleet's current tick: the clock restarts here.  None removes them."""
+        if other is None:
+            self.others = None
+            return
+        W, K = int(other.shape[0]), int(other.shape[1])
+        if W != self.W or tuple(other.shape[2:]) != (5,) or not K <= L.TRAFFIC_MAX_WORLD:
+            raise ValueError(f"other must be (W, K, 5) with K <= {L.TRAFFIC_MAX_WORLD}")
+        n = self._zeros((W,), np.int32)
+        self._fill(n, K if n_other is None else n_other)
+        self.others = (n, self._own(other, np.float64), self._own(other_lane, np.int32))
+        self.tick = 0
+
+    def run_step(self):
+        """ref BehaviorAgent.run_step for every agent: one tick's controls (W, N, 3).  The agent state advances, the vehicles do
+        not move, the others' clock stands."""
+        v = self._world
+        obs = self.planner.agent_observe(self.state)
+        r = self.planner.agent_behave(self.params, self.behavior, self.n_world, v(self.paths), v(self.n_path), self.lane, v(self.state),
+                                      v(obs.forward), v(obs.speed_kmh), self.speed_limit, self.extent, *self._state_args(),
+                                      others=self.others, tick0=self.tick, in_place=True)
+        self._adopt(r)
+        self.mode, self.target_speed = r.mode, r.target_speed
+        return r.control
+
+    def rollout(self, T, log_every=None):
+        """T ticks of run_step + the vehicle model in one launch; state, agent state and the others' clock advance."""
+        v = self._world
+        r = self.planner.traffic_rollout(self.params, self.behavior, self.vp, self.n_world, v(self.paths), v(self.n_path), self.lane,
+                                         v(self.state), self.speed_limit, self.extent, *self._state_args(), T, others=self.others,
+                                         tick0=self.tick, log_every=log_every, in_place=True)
+        self._adopt(r)
+        self.tick += int(T)
+        return r
+
+    def modes(self):
+        """(W, N) int32 EMP_BHV_* of the last ``run_step`` (a rollout reports ``mode_ticks`` and ``log_mode`` instead)."""
+        return self.mode
+
+    def actors(self):
+        """(W, N, 4) x, y, world-frame vx, vy; rows of padding slots are observations of whatever their state holds."""
+        return self._world(super().actors())
+
+    def done(self):
+        return self._world(super().done())

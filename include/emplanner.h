@@ -1322,9 +1322,10 @@ int emp_route_paths(emp_ctx* ctx, const emp_route_graph* graph, int32_t B, int32
  * ref: the dynamic obstacle of the reference's drivers is a BehaviorAgent on a route (test_9.py:288-291), stepped once per control
  * tick (test_9.py:344).  With no hazard in sight that step is LocalPlanner.run_step (agents/navigation/local_planner.py:208-260)
  * and VehiclePIDController.run_step (agents/navigation/controller.py:54-92).  NOT reproduced: offset != 0; random waypoint
- * creation (_stop_waypoint_creation is always true after set_global_plan); BehaviorAgent's traffic-light, pedestrian and
- * car-following branches (they need CARLA's map queries); CARLA's float32 Location and its z coordinate.  The target speed is the
- * caller's, as set_target_speed(30.0) is in the driver.
+ * creation (_stop_waypoint_creation is always true after set_global_plan); BehaviorAgent's traffic-light and pedestrian
+ * branches (they need CARLA's map queries); CARLA's float32 Location and its z coordinate.  The target speed is the
+ * caller's, as set_target_speed(30.0) is in the driver.  BehaviorAgent's car-following branch and its speed-limit target are
+ * reproduced by emp_agent_behave (the section after this one).
  *
  * The rule, per agent; every operation is rounded separately (no contraction), `/` and sqrt are IEEE, clip(v) = min(max(v, -1), 1)
  * in NumPy's form (a NaN passes through).  It reads the pose x, y and the forward vector (c, s), speed_kmh and target_speed (both
@@ -1421,6 +1422,144 @@ typedef struct emp_agent_rollout_io {
 } emp_agent_rollout_io;
 int emp_agent_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_vehicle_params* vp, int32_t A, int32_t max_path, int32_t T,
                       int32_t log_every, const emp_agent_rollout_io* io, emp_mem where);
+
+/* ---- traffic that reacts to traffic: BehaviorAgent's car-following (new with ABI 13's library; EMP_ABI_VERSION is unchanged) ----
+ * ref: BehaviorAgent.run_step (agents/navigation/behavior_agent.py:296-362) for the "normal", "cautious" and "aggressive" agents of
+ * behavior_types.py: the target speed from the speed limit (_update_information, :65-82), the vehicle-ahead detector
+ * (_vehicle_obstacle_detected, :84-138, with is_within_distance, agents/tools/misc.py:66-103), the time-to-collision rule
+ * (car_following_manager, :253-294) and the emergency stop (:364-375), on top of the local planner and PID pair of the section
+ * above, whose rule (one "agent tick" below) is called unchanged.
+ * NOT reproduced: traffic lights; pedestrians; tailgating and lane changes (the law is that of a road whose markings allow none:
+ * _tailgating then only looks behind); the junction branch (:347-352: it needs RoadOptions the router does not produce);
+ * BasicAgent.run_step; per-road speed limits (the limit is per agent and constant over a call).
+ * Stand-ins for CARLA's map: map.get_waypoint(location) compares (road_id, lane_id); here every path waypoint carries an int32
+ * lane key, lane [max_path] beside the path, and a vehicle IS ON the key of the waypoint behind its queue's head:
+ * lane[max(head - 1, 0)] with head as at the start of the tick, -1 (never matches) if it has no plan.  That holds for the ego
+ * (key_cur) and for every other agent.  A key below 0 never matches.  The 45 m pre-filter round the ego's lane waypoint (:201-202) is
+ * not a step of its own: the detector's own range is max(min_proximity_threshold, speed_limit / 3), so the filter cannot decide
+ * anything while speed_limit / 3 plus the agent's offset from its lane centre stays below 45 m (a limit under about 130 km/h).
+ *
+ * Worlds.  Agents are laid out [W][max_world]; world w holds n_world[w] agents (clamped to [0, max_world]), max_world <=
+ * EMP_TRAFFIC_MAX_WORLD.  Agents see only their own world.  Padding slots are never read and never written (EMP_HOST arrays are staged:
+ * an output array comes back whole, its padding slots as 0).  A world may also hold
+ * n_other[w] (clamped to [0, max_other], max_other <= 64) vehicles that the call does not drive: other [W][max_other][5] = x, y,
+ * world-frame vx, vy, half extent, and other_lane [W][max_other] their keys.  The first four columns are emp_drive's actor row.
+ * At tick t of a call an other stands at x + vx * ((tick0 + t) * dt), y + vy * ((tick0 + t) * dt) with emp_agent_params.dt: nothing
+ * accumulates (emp_drive_timed's clock rule).  Its km/h is 3.6 * sqrt((vx * vx + vy * vy) + 0).
+ * Per agent: the arrays of emp_agent_control without target_speed; speed_limit in km/h (get_speed_limit); extent, the half extent
+ * max(bounding_box.extent.x, .y); lane [max_path].
+ *
+ * One tick for agent i; every other vehicle is read as it stood at the start of the tick (the reference steps its agents one after
+ * another between two world ticks).  Rounding as in the section above; min([..]) and max(a, b) are Python's (the first argument
+ * is kept unless a later one is strictly smaller / larger).
+ *   1. head == n_path after the clamps: the DONE tick of the agent tick (control (0, 0, 1), status EMP_AGT_DONE), mode
+ *      EMP_BHV_DONE, target_speed_out = speed_limit.  (The reference raises here.)  A DONE agent stays visible to the others.
+ *   2. th = max(min_proximity_threshold, speed_limit / 3);  key_cur = lane[max(head - 1, 0)];
+ *      key_next = lane[min(head + look_steps, n_path - 1)] (get_incoming_waypoint_and_direction(steps=5)).
+ *   3. Scan the candidates in order: the world's agents by slot without i, then the others by index.  THE FIRST HIT WINS, not the
+ *      nearest.  A candidate whose key is below 0, or equals neither key_cur nor key_next, is passed over.  tv = (xj - xi, yj - yi),
+ *      norm = sqrt(tvx * tvx + tvy * tvy).  norm < 0.001: a hit.  norm > th: no hit.  Otherwise
+ *      angle = acos(clip((c * tvx + s * tvy) / norm)) * (180 / pi), a hit if and only if 0 < angle < up_angle, with (c, s)
+ *      emp_agent_observe's forward vector.  The lower bound is strict as in the reference: a vehicle exactly ahead (angle 0) is not seen.
+ *   4. No hit: mode NORMAL, target = min([max_speed, speed_limit - speed_lim_dist]), one agent tick with that target.
+ *   5. Hit on j: d = (sqrt((dx * dx + dy * dy) + 0) + 2^-52) - extent_j - extent_i with (dx, dy) = (xi - xj, yi - yj).
+ *      d < braking_distance: mode EMERGENCY, control = (0, 0, emergency_brake) (throttle, steer, brake: a fresh control, steer 0);
+ *      head, both deques and past_steer stay as they were, lat_error = lon_command = 0, target_speed_out = speed_limit.
+ *      Otherwise vs = j's km/h, dv = max(1, (kmh_i - vs) / 3.6), ttc = d / dv, and
+ *        safety_time > ttc > 0:                 mode SLOW,   target = min([positive(vs - speed_decrease), max_speed, speed_limit - speed_lim_dist])
+ *        2 * safety_time > ttc >= safety_time:  mode FOLLOW, target = min([max(min_speed, vs), max_speed, speed_limit - speed_lim_dist])
+ *        otherwise:                             mode CLEAR,  the target of step 4;
+ *      then TWO agent ticks with that target on the same observation, the second one's control returned: the reference steps its
+ *      local planner in car_following_manager (:275, :284, :292) and once more at the end of run_step (:360).  The second purge finds
+ *      nothing to do; both deques take the tick's error twice and the steering rate limit applies twice.
+ *   Outputs of a tick beside the agent tick's: mode, blocker (position in the scan order, -1 if none), distance (d) and ttc (+inf
+ *   where the rule does not compute them), target_speed_out (what the reference's local planner then holds).  distance and ttc need
+ *   no libm call; acos decides a hit only within its last bits of 0 and up_angle.
+ *
+ * emp_agent_behave: one tick for W worlds, one kernel.  forward [A][2] and speed_kmh [A] are data, as for emp_agent_control
+ * (A = W * max_world).  emp_traffic_rollout: T ticks in ONE launch; tick t is emp_agent_observe, emp_agent_behave (tick0 + t),
+ * emp_vehicle_step.  EVERY OUTPUT AND LOG ROW EQUALS, BIT FOR BIT, T iterations of those three calls; a rollout cut in two, with
+ * tick0 advanced, resumes bit for bit.  Logs as emp_agent_rollout's plus log_mode and log_target; mode_ticks [A][5] counts the ticks
+ * spent in NORMAL, SLOW, FOLLOW, CLEAR, EMERGENCY; min_gap [A] is the smallest d seen, +inf if none.  status is the OR over ticks.
+ * emp_behavior_io serves both calls; a field the call does not use is not looked at.  Each agent-state output may alias its input.
+ *   emp_agent_behave uses: n_world, path, n_path, lane, state, forward, speed_kmh, speed_limit, extent, the agent state in and out,
+ *     control, status, mode, blocker, distance, ttc, target_speed_out; optional n_other / other / other_lane (all three, or
+ *     max_other == 0), lat_error, lon_command.
+ *   emp_traffic_rollout uses: the same inputs without forward and speed_kmh; state_out (may alias state), the agent state out,
+ *     status, done_tick, mode_ticks, min_gap; optional actors_out and the five logs.
+ * Refused before any launch (EMP_ERR_INVALID): a NULL required pointer, max_world outside [1, 64], max_other outside [0, 64],
+ * max_path < 1, W < 0, T outside [1, EMP_ROLLOUT_MAX_TICKS], log_every < 1, tick0 < 0, reserved != 0, EMP_HOST_PINNED.  W == 0: EMP_OK. */
+#define EMP_TRAFFIC_MAX_WORLD 64
+#define EMP_BHV_NORMAL 0
+#define EMP_BHV_SLOW 1
+#define EMP_BHV_FOLLOW 2
+#define EMP_BHV_CLEAR 3
+#define EMP_BHV_EMERGENCY 4
+#define EMP_BHV_DONE 5
+#define EMP_BHV_CAUTIOUS 0
+#define EMP_BHV_KIND_NORMAL 1
+#define EMP_BHV_AGGRESSIVE 2
+typedef struct emp_behavior_params {
+    double max_speed, speed_lim_dist, speed_decrease, safety_time, min_proximity_threshold, braking_distance; /* behavior_types.py */
+    double min_speed;                      /* 5 (BehaviorAgent._min_speed) */
+    double emergency_brake;                /* 0.5 (BasicAgent._max_brake) */
+    double up_angle;                       /* 30 degrees */
+    int32_t look_steps;                    /* 5 */
+    int32_t reserved;                      /* must be 0 */
+} emp_behavior_params;
+/* kind: EMP_BHV_CAUTIOUS, EMP_BHV_KIND_NORMAL or EMP_BHV_AGGRESSIVE (anything else: normal) */
+void emp_behavior_params_default(emp_behavior_params* p, int32_t kind);
+typedef struct emp_behavior_io {
+    const int32_t* n_world;                /* [W] */
+    const double* path;                    /* [A][max_path][4], A = W * max_world */
+    const int32_t* n_path;                 /* [A] */
+    const int32_t* lane;                   /* [A][max_path] */
+    const double* state;                   /* [A][6] */
+    const double* forward;                 /* [A][2] (behave) */
+    const double* speed_kmh;               /* [A] (behave) */
+    const double* speed_limit;             /* [A] km/h */
+    const double* extent;                  /* [A] */
+    const int32_t* head;                   /* the agent state, as emp_agent_rollout_io's */
+    const double* past_steer;
+    const double* lon_err;
+    const int32_t* n_lon;
+    const double* lat_err;
+    const int32_t* n_lat;
+    const int32_t* n_other;                /* [W] */
+    const double* other;                   /* [W][max_other][5] */
+    const int32_t* other_lane;             /* [W][max_other] */
+    int32_t* head_out;
+    double* past_steer_out;
+    double* lon_err_out;
+    int32_t* n_lon_out;
+    double* lat_err_out;
+    int32_t* n_lat_out;
+    int32_t* status;                       /* [A] */
+    double* control;                       /* [A][3] (behave) */
+    int32_t* mode;                         /* [A] (behave) */
+    int32_t* blocker;                      /* [A] (behave) */
+    double* distance;                      /* [A] (behave) */
+    double* ttc;                           /* [A] (behave) */
+    double* target_speed_out;              /* [A] (behave) */
+    double* lat_error;                     /* [A] optional (behave) */
+    double* lon_command;                   /* [A] optional (behave) */
+    double* state_out;                     /* [A][6] (rollout) */
+    int32_t* done_tick;                    /* [A] (rollout) */
+    int32_t* mode_ticks;                   /* [A][5] (rollout) */
+    double* min_gap;                       /* [A] (rollout) */
+    double* actors_out;                    /* [A][4] optional (rollout) */
+    double* log_state;                     /* optional logs (rollout) */
+    double* log_control;
+    int32_t* log_head;
+    int32_t* log_mode;
+    double* log_target;
+    int32_t reserved;                      /* must be 0 */
+} emp_behavior_io;
+int emp_agent_behave(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, int32_t W, int32_t max_world,
+                     int32_t max_path, int32_t max_other, int64_t tick0, const emp_behavior_io* io, emp_mem where);
+int emp_traffic_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp, int32_t W,
+                        int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every, int64_t tick0,
+                        const emp_behavior_io* io, emp_mem where);
 
 #ifdef __cplusplus
 }
