@@ -37,7 +37,10 @@ struct QpDev {
 // The reference's nearest-node scan (planning_utils.py:383-402) is an ordered scan with an early exit after
 // 50 consecutive non-improvements; in parallel that is: L_i = first index achieving min(d_0..d_i) (a prefix
 // minimum that keeps the FIRST occurrence, because only a strict '<' counts as an improvement), stop at the first
-// i with i - L_i >= 50, answer L_i there (or L_{P-1} if the scan never stops early).
+// i with i - L_i >= 50, answer L_i there (or L_{P-1} if the scan never stops early).  A distance that is not `< inf` (NaN, +inf) never
+// improves and counts from node 0 on: until the first improvement L_i is "-1", so a line whose first 50 distances are all such
+// stops at node 49 with the scan's initial answer, node 0 (tests/match_cases.py holds the ties, stop boundaries and non-finite
+// lines that pin all of this against the serial match_scan).
 // ---------------------------------------------------------------------------------------------
 // Inclusive prefix minimum of (d, index) over the 64 lanes, the EARLIER lane winning ties, by DPP moves (no LDS
 // traffic, no address arithmetic): Hillis-Steele inside each row of 16 lanes (row_shr:1, 2, 4, 8; a lane without a
@@ -52,7 +55,8 @@ __device__ __forceinline__ void prefix_min_step(double& d, int& li) {
     r.w[1] = __builtin_amdgcn_update_dpp(inf.w[1], a.w[1], CTRL, ROW_MASK, 0xF, false);
     const int oi = __builtin_amdgcn_update_dpp(0, li, CTRL, ROW_MASK, 0xF, false);
     if (!(d < r.f)) {                  // the value from the earlier lanes wins unless mine is strictly smaller;
-        d = r.f;                       // a lane without a source sees +inf and keeps its own unless that is +inf / NaN
+        d = r.f;                       // a lane without a source sees +inf and keeps its own unless that is +inf (the caller
+                                       // hands in no NaN: it would win this comparison and travel down the prefix)
         li = oi;
     }
 }
@@ -88,6 +92,10 @@ __device__ inline int match_scan_wave64(const double* lx, const double* ly, int 
         const double dx = lx[lane] - x, dy = ly[lane] - y;
         d = sqrt(dx * dx + dy * dy);
     }
+    // A distance that is not `< inf` (NaN, or +inf itself) is a non-improvement from node 0 on: where none of the first `limit`
+    // nodes improves, the ordered scan has stopped at node limit - 1 with its initial answer, node 0.  The prefix below cannot
+    // see that stop (pm is +inf there, and a finite node `limit` differs from it).
+    if (P >= limit && !__ballot(lane < limit && d < __builtin_inf())) return 0;   // uniform
     double pm = d;
     pm = prefix_fmin_step<0x111, 0xF>(pm);   // row_shr:1
     pm = prefix_fmin_step<0x112, 0xF>(pm);   // row_shr:2
@@ -107,7 +115,8 @@ __device__ inline int match_scan_wave(const double* lx, const double* ly, int P,
     if (P <= 64 && limit >= 1) return match_scan_wave64(lx, ly, P, x, y, limit);   // uniform
     const int lane = threadIdx.x & 63;
     double cd = __builtin_inf();     // carry: prefix minimum and its first index over the previous chunks
-    int ci = 0;
+    int ci = -1;                     // -1: nothing has improved yet.  The ordered scan counts non-improvements from node 0, so
+                                     // it stops at node limit - 1 where no distance so far was `< inf` (NaN, +inf): answer 0
     for (int base = 0; base < P; base += 64) {
         const int i = base + lane;
         double d = __builtin_inf();
@@ -115,6 +124,9 @@ __device__ inline int match_scan_wave(const double* lx, const double* ly, int P,
         if (i < P) {
             const double dx = lx[i] - x, dy = ly[i] - y;
             d = sqrt(dx * dx + dy * dy);
+            // A NaN distance is passed over like +inf: it is never `<` another.  As NaN it would travel down the prefix instead -
+            // `!(d < NaN)` hands a later lane the NaN in place of its own strictly smaller distance.
+            if (!(d < __builtin_inf())) d = __builtin_inf();
         }
         prefix_min_first(d, li);                           // inclusive prefix-min keeping the earlier index on ties
         if (!(d < cd)) {                                   // fold the carry (earlier) in
@@ -124,13 +136,13 @@ __device__ inline int match_scan_wave(const double* lx, const double* ly, int P,
         const unsigned long long stop = __ballot(i < P && i - li >= limit);
         if (stop) {
             const int first = __builtin_ffsll((long long)stop) - 1;
-            return __shfl(li, first, 64);
+            return max(__shfl(li, first, 64), 0);
         }
         const int last = min(63, P - 1 - base);
         cd = __shfl(d, last, 64);
         ci = __shfl(li, last, 64);
     }
-    return ci;
+    return max(ci, 0);
 }
 
 // dynamic LDS: ProjectLds (emp_tail_launch.h)

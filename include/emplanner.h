@@ -447,7 +447,13 @@ int emp_proj_point(emp_ctx* ctx, int32_t n, int32_t max_ref, const double* ref_l
                    const int32_t* n_ref, const double* s, const int32_t* pre_match_index, double* out,
                    int32_t* index, int32_t* status, emp_mem where);
 
-/* ref: match_projection_points (planning_utils.py:364-426): [B][max_pts] points against one line per scene */
+/* ref: match_projection_points (planning_utils.py:364-426): [B][max_pts] points against one line per scene.
+ * The match rule, here and in every entry point that projects on a line (emp_frenet_project, emp_s_map, emp_s_l, emp_s_l_deri,
+ * emp_reference_line, emp_plan_cycle): the reference's ordered scan - only a strict `<` improves (the first of equal distances
+ * wins), and the scan stops after 50 consecutive non-improvements (5 in the windowed search), so a nearer node behind that is
+ * never seen.  A distance that is not finite (a NaN or infinite node or query coordinate) is never `<` another: such a node is
+ * passed over and counts as a non-improvement from node 0 on, so a line whose first 50 distances are not finite - or a query that
+ * is not finite - matches node 0 (in the windowed search too, wherever it started), and the projection on a NaN node is NaN. */
 int emp_match_projection(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_pts,
                          const double* ref_line, const int32_t* n_ref, const double* xy, const int32_t* n_pts,
                          int32_t* match_index, double* proj, emp_mem where);
