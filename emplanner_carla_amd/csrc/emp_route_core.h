@@ -213,7 +213,7 @@ EMP_HD int find_edge(const Graph& G, int u, int v) {
     return -1;
 }
 
-// _closest_index over the waypoints [a, b): relative to a
+// _closest_index over the waypoints [a, b): relative to a, -1 where no distance is below +inf (the reference's initial index)
 template <class W>
 EMP_HD int closest(const Graph& G, const double* p, int a, int b, const W& w) {
     double bd = INFINITY;
@@ -227,7 +227,7 @@ EMP_HD int closest(const Graph& G, const double* p, int a, int b, const W& w) {
     }
     int key = bj;
     w.argmin(bd, key, bj);
-    return bj < 0 ? 0 : bj - a;
+    return bj < 0 ? -1 : bj - a;
 }
 
 struct PathOut {
@@ -269,11 +269,15 @@ EMP_HD long long expand(const Graph& G, const State& S, int start, int count, in
         const bool last = i == count - 1;
         const int v = last ? n_exit : S.stamp[u];
         if (!edge_waypoints(G, u, v, &a, &b)) return -1;
-        if (i == 0) at = emit(G, o, at, a + closest(G, origin_wp, a, b, w), b, w);
-        else if (!last) at = emit(G, o, at, a + 1, b, w);
-        if (last) {
+        if (i == 0) {                             // path[k:], and path[-1:] is the exit alone
+            const int k = closest(G, origin_wp, a, b, w);
+            at = emit(G, o, at, k < 0 ? b - 1 : a + k, b, w);
+        } else if (!last) {
+            at = emit(G, o, at, a + 1, b, w);
+        }
+        if (last) {                               // path[:k + 1] when k != 0, and path[:0] is empty
             const int k = closest(G, dest_wp, a + 1, b, w);
-            if (k != 0) at = emit(G, o, at, a + 1, a + 1 + k + 1, w);
+            if (k > 0) at = emit(G, o, at, a + 1, a + 1 + k + 1, w);
         }
         u = v;
     }

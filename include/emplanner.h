@@ -1282,7 +1282,8 @@ int emp_drive_timed(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* 
  *     close c
  *   route = the parents back from n_end, reversed, then n_exit;  route_len = its length (>= 2)
  * Expansion (emp_route_paths).  The edge of (u, v) is the first e in u's list with succ[e] == v; closest(p, list) is the first
- * index with the strictly smallest dist (a NaN or infinite distance never wins; none: index 0):
+ * index with the strictly smallest dist (a NaN or infinite distance never wins; none: the reference's -1, read as Python reads
+ * it - list[-1:] on the first edge is its exit waypoint alone, L[:0] on the last edge is nothing):
  *   first edge (route[0], route[1]): its waypoints from closest(origin_wp, all of them) onwards
  *   each further edge but the last, only when route_len > 3: its waypoints without the entry
  *   last edge (route[-2], route[-1]): L = its waypoints without the entry, k = closest(dest_wp, L); L[0..k] when k != 0

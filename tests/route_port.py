@@ -24,33 +24,46 @@ def edge_ends(g, e):
     return int(np.searchsorted(g.succ_off, e, side="right")) - 1, int(g.succ[e])
 
 
-def astar(g, start, n_end, gaps=None):
+def astar(g, start, n_end, gaps=None, probe=None):
     """The route from start to n_end as a list of node ids, None when the open set runs empty.  ``gaps``: a list that receives,
-    per pop with at least two open nodes, the difference between the second-best and the best f."""
+    per pop with at least two open nodes, the difference between the second-best and the best f (0.0 for equal ones).  ``probe``:
+    a dict whose counters this search adds to - ``updates`` (an OPEN node took a smaller g), ``tie_pops`` (the best f was held by
+    two or more open nodes), ``max_open``, ``pops``, and ``popped_degree``, the set of out-degrees of the nodes it expanded.
+    The open nodes are kept as a list in the order of their first insertion - the order of their stamps - so the first strict
+    minimum of f over it is the header's "smallest f, then smallest stamp"."""
     N = len(g.vertex)
-    h = [dist3(g.vertex[n], g.vertex[n_end]) for n in range(N)]
+    h = [None] * N
     state = [0] * N                     # 0 NEW, 1 OPEN, 2 CLOSED
-    gc, parent, stamp = [0] * N, [-1] * N, [0] * N
-    state[start], next_stamp = 1, 1
+    gc, parent = [0] * N, [-1] * N
+    state[start], opened = 1, [start]
     for _ in range(N):
-        best = None
-        fs = []
-        for n in range(N):
-            if state[n] != 1:
-                continue
-            f = float(gc[n]) + h[n]
-            fs.append(f)
-            if best is None or f < best[0] or (f == best[0] and stamp[n] < best[1]):
-                best = (f, stamp[n], n)
-        if best is None:
+        if not opened:
             return None
-        if gaps is not None and len(fs) > 1:
+        best, at, fs = None, 0, []
+        for i, n in enumerate(opened):
+            if h[n] is None:
+                h[n] = dist3(g.vertex[n], g.vertex[n_end])
+            f = float(gc[n]) + h[n]
+            if f != f:                  # a NaN f orders as +inf
+                f = math.inf
+            fs.append(f)
+            if best is None or f < best:
+                best, at = f, i
+        if len(fs) > 1 and (gaps is not None or probe is not None):
             fs.sort()
-            gaps.append(fs[1] - fs[0])
-        c = best[2]
+            if gaps is not None:
+                gaps.append(0.0 if fs[1] == fs[0] else fs[1] - fs[0])
+            if probe is not None and fs[1] == fs[0]:
+                probe["tie_pops"] = probe.get("tie_pops", 0) + 1
+        if probe is not None:
+            probe["max_open"] = max(probe.get("max_open", 0), len(opened))
+            probe["pops"] = probe.get("pops", 0) + 1
+        c = opened.pop(at)
         if c == n_end:
             state[c] = 2
             break
+        if probe is not None:
+            probe.setdefault("popped_degree", set()).add(int(g.succ_off[c + 1]) - int(g.succ_off[c]))
         for e in range(g.succ_off[c], g.succ_off[c + 1]):
             suc, ng = int(g.succ[e]), gc[c] + int(g.length[e])
             if state[suc] == 2:
@@ -58,9 +71,11 @@ def astar(g, start, n_end, gaps=None):
             if state[suc] == 1:
                 if ng < gc[suc]:
                     gc[suc], parent[suc] = ng, c
+                    if probe is not None:
+                        probe["updates"] = probe.get("updates", 0) + 1
             else:
-                state[suc], gc[suc], parent[suc], stamp[suc] = 1, ng, c, next_stamp
-                next_stamp += 1
+                state[suc], gc[suc], parent[suc] = 1, ng, c
+                opened.append(suc)
         state[c] = 2
     else:
         return None
@@ -77,42 +92,52 @@ def find_edge(g, u, v):
     raise KeyError((u, v))
 
 
-def closest(g, p, a, b):
-    """The first index of wp[a:b] with the strictly smallest distance to p, relative to a; 0 when no distance is below inf."""
-    best, k = math.inf, 0
+def closest(g, p, a, b, tied=None):
+    """The first index of wp[a:b] with the strictly smallest distance to p, relative to a; -1 when no distance is below inf (the
+    reference's initial index).  ``tied``: a list that receives every relative index at which that smallest distance is attained."""
+    best, k = math.inf, -1
     for j in range(a, b):
         d = dist3(g.wp[j], p)
         if d < best:
             best, k = d, j - a
+            if tied is not None:
+                del tied[:]
+        if tied is not None and d == best and k >= 0:
+            tied.append(j - a)
     return k
 
 
-def expand(g, route, origin_wp, dest_wp):
-    """search_path_way's waypoints as rows of g.wp."""
+def expand(g, route, origin_wp, dest_wp, probe=None):
+    """search_path_way's waypoints as rows of g.wp.  An index of -1 is read as Python reads it: path[-1:] is the first edge's exit
+    alone, path[:0] nothing.  ``probe``: a dict that receives ``origin_tied`` and ``dest_tied`` (closest's tied indices)."""
     out = []
+    ot, dt = ([], []) if probe is not None else (None, None)
     e = find_edge(g, route[0], route[1])
     a, b = int(g.wp_off[e]), int(g.wp_off[e + 1])
-    out += range(a + closest(g, origin_wp, a, b), b)
+    k = closest(g, origin_wp, a, b, ot)
+    out += range(a + k if k >= 0 else b - 1, b)
     if len(route) > 3:
         for i in range(1, len(route) - 2):
             e = find_edge(g, route[i], route[i + 1])
             out += range(int(g.wp_off[e]) + 1, int(g.wp_off[e + 1]))
     e = find_edge(g, route[-2], route[-1])
     a, b = int(g.wp_off[e]) + 1, int(g.wp_off[e + 1])
-    k = closest(g, dest_wp, a, b)
-    if k != 0:
+    k = closest(g, dest_wp, a, b, dt)
+    if k > 0:
         out += range(a, a + k + 1)
+    if probe is not None:
+        probe["origin_tied"], probe["dest_tied"] = ot, dt
     return out
 
 
-def search_path_way(g, start_node, end_edge, origin_wp, dest_wp):
+def search_path_way(g, start_node, end_edge, origin_wp, dest_wp, gaps=None, probe=None):
     """(route, rows of g.wp), or (None, None) for an unreachable end.  The route ends with n_exit."""
     n_end, n_exit = edge_ends(g, end_edge)
-    route = astar(g, start_node, n_end)
+    route = astar(g, start_node, n_end, gaps, probe)
     if route is None:
         return None, None
     route = route + [n_exit]
-    return route, expand(g, route, origin_wp, dest_wp)
+    return route, expand(g, route, origin_wp, dest_wp, probe)
 
 
 def run(g, start_node, end_edge, origin_wp, dest_wp, max_route, max_global):
