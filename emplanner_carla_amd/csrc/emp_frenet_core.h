@@ -5,7 +5,16 @@
 
 #include "emp_core.h"
 
+#if !defined(__HIPCC__)
+#include <algorithm>
+#endif
+
 namespace emp {
+
+#if !defined(__HIPCC__)
+using std::max;      // the device compiler declares min / max itself
+using std::min;
+#endif
 
 struct Node {
     double x, y, theta, kappa;
@@ -151,6 +160,84 @@ EMP_HD bool proj_point(const double* line, const double* s_map, int n_ref, doubl
     sincos_pair(m.theta, &sn, &c);
     *out = node_advanced(m, ds, c, sn);
     *idx = i;
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The station lookups the kernels of emp_tail_kernels.h share, here so that the CPU checks (tests/host_check) run the same text.
+// ---------------------------------------------------------------------------------------------
+// monotone index walk of cal_proj_point from index 0 (ref path_planning.py:62-64: `while s_map[idx + 1] < s: idx += 1`);
+// *off_end when it runs past the end.  s_map is a cumulative chord length, i.e. non-decreasing, so the walk's stopping
+// index is found by bisection (6 LDS round trips instead of up to P).
+EMP_HD int walk_from_zero(const double* sm, int P, double s, bool* off_end) {
+    int lo = 0, hi = P - 1;                       // answer in [0, P-1]; P-1 = "no index stops the walk"
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sm[mid + 1] < s) lo = mid + 1;
+        else hi = mid;
+    }
+    *off_end = lo + 1 >= P;
+    return lo;
+}
+
+// ref: cal_lmin_lmax, path_planning.py:222-273.  lmin_lmax returns false where the reference raises IndexError.
+EMP_HD int argmin_abs(const double* s, int stride, int n, double target) {
+    int best = 0;
+    double bv = fabs(s[0] - target);
+    for (int j = 1; j < n; ++j) {
+        const double v = fabs(s[j * stride] - target);
+        if (v < bv) {
+            bv = v;
+            best = j;
+        }
+    }
+    return best;
+}
+
+// The three scans of one obstacle (ref path_planning.py:240, :241, :257) in ONE pass over the stations, four stations a step: the
+// same comparisons in the same order per target as three argmin_abs calls (strict '<': the first minimum), but the stations are
+// read once and four LDS reads are in flight at a time - the three separate loops were 3 n dependent LDS round trips of a wavefront
+// that has its SIMD to itself (round 6: 4 us of the path-QP kernel's 30 us set-up).  n >= 1.
+EMP_HD void argmin_abs3(const double* s, int n, double t0, double t1, double t2, int* i0, int* i1, int* i2) {
+    const double f = s[0];
+    double b0 = fabs(f - t0), b1 = fabs(f - t1), b2 = fabs(f - t2);
+    int k0 = 0, k1 = 0, k2 = 0;
+    for (int j0 = 1; j0 < n; j0 += 4) {
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = s[min(j0 + u, n - 1)];      // past the end: the last station again (never a strict improvement)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = j0 + u;
+            const double a0 = fabs(v[u] - t0), a1 = fabs(v[u] - t1), a2 = fabs(v[u] - t2);
+            if (a0 < b0) { b0 = a0; k0 = j; }
+            if (a1 < b1) { b1 = a1; k1 = j; }
+            if (a2 < b2) { b2 = a2; k2 = j; }
+        }
+    }
+    *i0 = min(k0, n - 1);      // (k never exceeds n - 1: a repeated last station is not strictly below itself; the clamp costs nothing)
+    *i1 = min(k1, n - 1);
+    *i2 = min(k2, n - 1);
+}
+
+EMP_HD bool lmin_lmax(const double* dp_s, const double* dp_l, int stride, int n, const double* obs_s,
+                                 const double* obs_l, int n_obs, double obs_length, double obs_width, double* l_min,
+                                 double* l_max) {
+    for (int j = 0; j < n; ++j) {
+        l_min[j] = -10.0;                                                          // ref :233-234
+        l_max[j] = 10.0;
+    }
+    for (int k = 0; k < n_obs; ++k) {
+        const int lo = argmin_abs(dp_s, stride, n, obs_s[k] - obs_length / 2.0) + 2;   // ref :240
+        const int hi = argmin_abs(dp_s, stride, n, obs_s[k] + obs_length / 2.0) + 2;   // ref :241
+        const int centre = argmin_abs(dp_s, stride, n, obs_s[k]);                      // ref :257
+        const bool below = dp_l[centre * stride] < obs_l[k];                           // ref :263
+        for (int j = lo; j <= hi; ++j) {
+            if (j >= n) return false;                                                  // IndexError in the reference
+            if (below) l_max[j] = fmin(l_max[j], obs_l[k] - obs_width / 2.0);
+            else l_min[j] = fmax(l_min[j], obs_l[k] + obs_width / 2.0);
+        }
+    }
     return true;
 }
 

@@ -440,6 +440,33 @@ int emp_s_l_deri(emp_ctx* ctx, int32_t B, int32_t max_ref, int32_t max_pts, cons
                  const int32_t* n_ref, const double* xy, const double* v_xy, const double* a_xy,
                  const int32_t* n_pts, const double* origin_xy, double* out, emp_mem where);
 
+/* The station lookups: which node (or station) belongs to an s.  The comparisons are the reference's, and where they are decided
+ * by equality the answers are these (tests/lookup_cases.py holds every one of them with ties that are equal in bits):
+ *   emp_proj_point, emp_frenet_path_to_xy, emp_plan_cycle (cal_proj_point: `while s_map[i + 1] < s: i += 1` from the previous
+ *     index, never backwards):
+ *       s on the knot s_map[i + 1]   the walk stays at node i (ds is the whole chord); one ulp above, it is node i + 1.  On a plateau
+ *                                    of equal entries (repeated nodes) s on or below the value stays in front of the plateau, one
+ *                                    ulp above passes all of it.
+ *       s on the end s_map[n - 1]    node n - 2, in range; a path station there is KEPT (the path stops at the first s > s_map[n - 1]),
+ *                                    one ulp above it is EMP_ST_S_OUT_OF_RANGE for emp_proj_point and for a planning start, and the
+ *                                    end of the path for a path station.  s below s_map[0]: node 0, ds negative.
+ *       s = NaN                      no comparison holds: the walk stays at the previous index, the point is NaN, status 0; in a path
+ *                                    the station is not past the end, its point is NaN and later points are unaffected.
+ *                                    s = -inf: as NaN, with an infinite point.  s = +inf: past the end.
+ *       a NaN entry of the s_map     stops the walk in front of it (emp_proj_point, emp_frenet_path_to_xy).
+ *       pre_match_index              n_ref - 1 or more: EMP_ST_S_OUT_OF_RANGE (s_map[i + 1] does not exist); negative: refused the
+ *                                    same way (the reference's index wraps round).  n_ref < 2: always EMP_ST_S_OUT_OF_RANGE.
+ *     emp_plan_cycle finds the indices by bisection with a running maximum; that equals the walk for a non-decreasing s_map and
+ *     finite stations, which is what it is given: a NaN node makes every later s_map entry NaN (a suffix, on which the bisection still
+ *     equals the walk), and a NaN planning start, origin or node in front of the start retires the scene with a status bit and
+ *     traj_len 0 before the stations are looked up ("The station lookups").
+ *   emp_frenet2cartesian (CalcProjPoint: from index 1, the first index2s[i] >= s): s on index2s[i] is node i with ds = 0; s at or
+ *     below index2s[1] - below index2s[0] too - is node 1 with ds <= 0; one ulp above index2s[n - 1], and every s where n_ref < 2, is
+ *     EMP_ST_S_OUT_OF_RANGE with that point and the rest of the scene NaN; a NaN s ends the scene the same way without a status.
+ *   emp_lmin_lmax, emp_plan_cycle (cal_lmin_lmax: numpy.argmin of |s_j - t|): of equally near stations the FIRST wins, so an
+ *     obstacle edge midway between stations j and j + 1 takes j, also where the last station is repeated; a NaN obs_s takes station 0
+ *     three times; dp_l[centre] == obs_l is "not below" (the l_min side), and so is a NaN obs_l, which bounds nothing.  An index range
+ *     lo..hi that is not empty and reaches n is EMP_ST_BOUND_INDEX; an empty one (lo > hi) is not, wherever it lies. */
 /* ref: cal_proj_point (path_planning.py:52-75; twin cal_proj_point_1, planning_utils.py:647-668): n independent
  * queries, each against its own line: s [n], pre_match_index [n] -> out [n][4] x,y,theta,kappa, index [n],
  * status [n] (EMP_ST_S_OUT_OF_RANGE where the reference raises IndexError) */

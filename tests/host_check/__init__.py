@@ -35,6 +35,14 @@ def load():
     lib.hc_dot2.argtypes = [i, p, p, p]
     lib.hc_match.restype = i
     lib.hc_match.argtypes = [p, i, d, d, i, i, i]
+    lib.hc_proj_point.restype = i
+    lib.hc_proj_point.argtypes = [p, p, i, d, p, p]
+    lib.hc_walk_from_zero.restype = i
+    lib.hc_walk_from_zero.argtypes = [p, i, d, p]
+    lib.hc_argmin_abs3.restype = None
+    lib.hc_argmin_abs3.argtypes = [p, i, p, p, p]
+    lib.hc_lmin_lmax.restype = i
+    lib.hc_lmin_lmax.argtypes = [p, p, i, p, p, i, d, d, p, p]
     lib.hc_st_edge_cost.restype = d
     lib.hc_st_edge_cost.argtypes = [p, p, i, p, p, p, p, p]
     lib.hc_st_reach.restype = None

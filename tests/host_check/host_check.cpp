@@ -73,6 +73,33 @@ int hc_match(const double* line, int n_ref, double x, double y, int first, int s
     return match_scan(line, n_ref, x, y, first, step, limit);
 }
 
+// ---- the station lookups (emp_frenet_core.h): the text the kernels of emp_tail_kernels.h run ------
+// cal_proj_point: out[4] = x, y, theta, kappa; *idx in: the previous index, out: the walk's; returns 1 where the walk stops in range
+int hc_proj_point(const double* line, const double* s_map, int n_ref, double s, int* idx, double* out) {
+    Node pr{0, 0, 0, 0};
+    const bool ok = proj_point(line, s_map, n_ref, s, idx, &pr);
+    out[0] = pr.x; out[1] = pr.y; out[2] = pr.theta; out[3] = pr.kappa;
+    return ok ? 1 : 0;
+}
+
+int hc_walk_from_zero(const double* s_map, int n_ref, double s, int* off_end) {
+    bool off = false;
+    const int k = walk_from_zero(s_map, n_ref, s, &off);
+    *off_end = off ? 1 : 0;
+    return k;
+}
+
+// one pass over the stations (one[3]) next to three argmin_abs calls (three[3]), targets t[3]
+void hc_argmin_abs3(const double* s, int n, const double* t, int* one, int* three) {
+    argmin_abs3(s, n, t[0], t[1], t[2], &one[0], &one[1], &one[2]);
+    for (int k = 0; k < 3; ++k) three[k] = argmin_abs(s, 1, n, t[k]);
+}
+
+int hc_lmin_lmax(const double* dp_s, const double* dp_l, int n, const double* obs_s, const double* obs_l, int n_obs,
+                 double obs_length, double obs_width, double* l_min, double* l_max) {
+    return lmin_lmax(dp_s, dp_l, 1, n, obs_s, obs_l, n_obs, obs_length, obs_width, l_min, l_max) ? 1 : 0;
+}
+
 // ---- S-T speed DP scalar pieces (emp_st_core.h) ---------------------------------------------------
 double hc_st_edge_cost(const double* w4, const double* edge5, int n_obs, const double* s_in, const double* s_out,
                        const double* t_in, const double* t_out, double* obs) {

@@ -44,6 +44,10 @@ const char* hc_plan_speed_front(int, int, long long*);
 const char* hc_plan_speed_dp(int, int, long long*);
 const char* hc_plan_st_edge_cost(int, int, int, long long*);
 const char* hc_plan_merge(int, int, long long*);
+int hc_proj_point(const double*, const double*, int, double, int*, double*);
+int hc_walk_from_zero(const double*, int, double, int*);
+void hc_argmin_abs3(const double*, int, const double*, int*, int*);
+int hc_lmin_lmax(const double*, const double*, int, const double*, const double*, int, double, double, double*, double*);
 }
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ull;
@@ -106,6 +110,30 @@ int main() {
                 sink += hc_match(line.data(), n, uni(0, 2.0 * n), uni(-5, 5), 0, 1, 50);
             }
             calls += 4;
+            // ---- the station lookups on the s_map just built (NaN where the origin was hostile) and on a sorted copy of it: stations
+            // at, beside and far outside the entries, every previous index from 0 to n - 1, 0..9 obstacles with hostile positions
+            std::vector<double> sorted(smap.begin(), smap.begin() + n), lmin(n + 1), lmax(n + 1), dl(n + 1), os(10), ol(10);
+            for (int i = 0; i < n; ++i) sorted[i] = 2.0 * i - 7.0;
+            sorted.push_back(0.0);
+            for (int q = 0; q < 12; ++q) {
+                const double* sm = (q & 1) ? smap.data() : sorted.data();
+                const double st = hostile((q % 3 == 0 && n >= 1) ? sm[(int)(u01() * n)] : uni(-12.0, 2.0 * n));
+                int idx = (int)(u01() * (n + 1)), off = 0, one[3], three[3];
+                if (idx > n - 1) idx = n > 0 ? n - 1 : 0;
+                double pt[4];
+                sink += hc_proj_point(line.data(), sm, n, st, &idx, pt);
+                sink += hc_walk_from_zero(sorted.data(), n, st, &off) + off;
+                if (n >= 1) {
+                    const double t3[3] = {hostile(st - 2.5), hostile(st + 2.5), st};
+                    hc_argmin_abs3(sm, n, t3, one, three);
+                    sink += one[0] + one[1] + one[2] + three[0];
+                    const int k = q % 10;
+                    for (int m = 0; m < k; ++m) { os[m] = hostile(uni(-12.0, 2.0 * n + 6.0)); ol[m] = hostile(uni(-4, 4)); }
+                    for (int i = 0; i < n; ++i) dl[i] = hostile(uni(-3, 3));
+                    sink += hc_lmin_lmax(sm, dl.data(), n, os.data(), ol.data(), k, 5.0, 5.0, lmin.data(), lmax.data());
+                }
+                calls += 4;
+            }
         }
         // ---- lattice edge cost with 0..64 obstacles, hostile positions
         for (int k : {0, 1, 3, 8, 16, 64}) {
