@@ -252,13 +252,15 @@ __global__ __launch_bounds__(1024, EMP_EDGE_WAVES) void dp_edge_kernel(DpDev P, 
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __builtin_amdgcn_s_setprio(EMP_PRIO_FRONT);
     const int row = ROW > 0 ? ROW : P.row, rr = row * row;
-    double* tab = lds;                                  // [kTableFields][rr], pair index = k*row + i
-    double* t_obs_s = lds + kTableFields * rr;          // [S][max_obs]
-    double* t_obs_l = t_obs_s + P.S * P.max_obs;
-    double* t_smp = t_obs_l + P.S * P.max_obs;          // [kTableTail] sample offsets t_n, sum t_n, sum t_n^2, unit quintic
+    constexpr int kMaskBits = (int)sizeof(MASK) * 8;
+    // (waves = 1, NOT the block's count: `box` is the last array, so only `end` counts the wavefronts, and the kernel never asks
+    // for it.  This holds only while nothing follows `box` in EdgeLds - an array appended there would get a wrong position here,
+    // and the CPU layout test, which calls the layout with the plan's count, would not see it: pass the real count then.)
+    const EdgeLds<double*> L = edge_lds(lds, row, P.S, P.max_obs, kMaskBits, 1);
+    double *tab = L.tab, *t_obs_s = L.obs_s, *t_obs_l = L.obs_l, *t_smp = L.smp;
     // per wavefront: [S][mask width] longitudinal box terms of the column it works on (dp_edge_column: box_dx2)
-    const int box_w = min(P.max_obs, (int)sizeof(MASK) * 8);
-    double* box_all = t_smp + kTableTail;
+    const int box_w = edge_box_width(P.max_obs, kMaskBits);
+    double* box_all = L.box;
     const int tile = blockIdx.x;
     const int tid = threadIdx.x;
 
@@ -303,6 +305,11 @@ __global__ __launch_bounds__(1024, EMP_EDGE_WAVES) void dp_edge_kernel(DpDev P, 
     const double* my_obs_s = t_obs_s + s * P.max_obs;
     const double* my_obs_l = t_obs_l + s * P.max_obs;
     double* my_box = box_all + ((size_t)(tid >> 6) * P.S + s) * box_w;
+    // (an optimisation hint only - an LDS address is never the null flat pointer: dp_edge_column's form without box terms is
+    // compiled away.  Where the compiler does not see it, the kernel carries a third copy of the scan, 270 instructions
+    // (profiles/dp_layouts/README.md); taking the line out changes the code's size, not its results, and whether it is
+    // needed depends on the toolchain.)
+    __builtin_assume(my_box != nullptr);
     for (int j = j_begin + (tid >> 6); j < j_end; j += (int)(blockDim.x >> 6)) {
         // (the sample offsets t_n are the same for every lane: read through the kernel argument they come back in scalar
         // registers, where the LDS copy costs a vector move and an LDS read per pair of them in every scan)
@@ -380,18 +387,15 @@ __global__ EMP_EDGE_RING_BOUNDS void dp_edge_ring_kernel(DpDev P, const double* 
     const unsigned long long probe_c0 = clock_probe ? clock64() : 0;       // the shader clock: what the chip holds under FP64 load
     constexpr int kMaskBits = (int)sizeof(MASK) * 8;
     const int row = ROW > 0 ? ROW : P.row, rr = row * row;
-    double* tab = lds;                                  // [kTableFields][rr], pair index = k*row + i
-    double* t_obs_s = lds + kTableFields * rr;          // [S][max_obs]
-    double* t_obs_l = t_obs_s + P.S * P.max_obs;
-    double* t_ps = t_obs_l + P.S * P.max_obs;           // [S] plan_start_s of the tile's scenes (S <= 64)
-    double* box_all = t_ps + ((P.S + 1) & ~1);          // per wavefront: [2][S][max_obs] lateral reach band of each obstacle in its column
     const int waves = (int)(blockDim.x >> 6);
-    unsigned char* rings = reinterpret_cast<unsigned char*>(box_all + (size_t)waves * 2 * P.S * P.max_obs);
     const int mask_bytes = edge_ring_mask_bytes(P.max_obs);
     // behind the rings, per wavefront: the jerk factor F of each of its columns, [columns per wavefront][S] - computed once per
     // (scene, column) in the dense pass, read back by whichever lane pops an entry of that column
     const int cpw = (cols_per_chunk + waves - 1) / waves;
-    double* f_all = reinterpret_cast<double*>(rings + (size_t)waves * edge_ring_bytes(P.max_obs));
+    const EdgeRingLds<unsigned char*> L = edge_ring_lds(reinterpret_cast<unsigned char*>(lds), row, P.S, P.max_obs, waves, cpw);
+    double *tab = reinterpret_cast<double*>(L.tab), *t_obs_s = reinterpret_cast<double*>(L.obs_s), *t_obs_l = reinterpret_cast<double*>(L.obs_l);
+    double *t_ps = reinterpret_cast<double*>(L.ps), *box_all = reinterpret_cast<double*>(L.band), *f_all = reinterpret_cast<double*>(L.f);
+    unsigned char* rings = L.rings;
     const double* t_smp = pair_tab + kTableFields * rr; // sample offsets through the kernel argument: scalar registers
     const int tile = blockIdx.x;
     const int tid = threadIdx.x;
@@ -722,7 +726,7 @@ __global__ __launch_bounds__(64 * WPB) void dp_sweep_kernel(DpDev P, const doubl
                                                        unsigned char* __restrict__ pre_out = nullptr,
                                                        int* __restrict__ term_out = nullptr,
                                                        unsigned long long* __restrict__ clock_probe = nullptr) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char pre_lds[];   // [WPB][64] doubles, then [WPB][col][64] bytes
+    extern __shared__ __attribute__((aligned(16))) unsigned char pre_lds[];   // SweepLds at WPB wavefronts (emp_dp_launch.h)
     // EMP_OPT_SWEEP_CLOCK_PROBE (measurement; a scalar branch when off): the shader-clock counter and the constant 100 MHz
     // reference counter at the wavefront's first and last instruction - their ratio is the clock this wavefront ran at,
     // whatever runs beside it (a counter pass of rocprofv3 would serialise the kernels of the staged step).
@@ -746,10 +750,11 @@ __global__ __launch_bounds__(64 * WPB) void dp_sweep_kernel(DpDev P, const doubl
     __builtin_amdgcn_s_setprio(EMP_PRIO_SWEEP);
     const int row = ROW > 0 ? ROW : P.row;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double* cost_lds = reinterpret_cast<double*>(pre_lds);
+    const SweepLds<double*> L = sweep_lds(reinterpret_cast<double*>(pre_lds), WPB, P.col);
+    double* cost_lds = L.front;
     const int tile = blockIdx.x * WPB + wave;
     if (tile >= P.tiles) return;                         // whole wavefront exits together
-    unsigned char* pre = pre_lds + (size_t)WPB * 64 * sizeof(double) + (size_t)wave * P.col * 64;
+    unsigned char* pre = reinterpret_cast<unsigned char*>(L.pre) + (size_t)wave * P.col * 64;
     const int s = lane / row, i = lane - s * row;
     const int b = tile * P.S + s;
     const bool live = (lane < P.S * row) && (b < P.B);
@@ -963,13 +968,14 @@ __global__ __launch_bounds__(256) void dp_sweep_wide_kernel(DpDev P, const doubl
                                                             const double* __restrict__ edge, const int* __restrict__ n_obs,
                                                             unsigned short* __restrict__ pre, double* __restrict__ rows_out,
                                                             double* __restrict__ min_cost_out, int* __restrict__ status_out) {
-    extern __shared__ double front_lds[];                 // [2][row]
+    extern __shared__ double front_lds[];                 // SweepWideLds (emp_dp_launch.h)
     const int row = P.row;
     const size_t rr = (size_t)P.row * P.row;
     const int b = blockIdx.x;
     const double INF = __builtin_inf();
-    double* cur = front_lds;
-    double* nxt = front_lds + row;
+    const SweepWideLds<double*> L = sweep_wide_lds(front_lds, row);
+    double* cur = L.cur;
+    double* nxt = L.nxt;
     for (int i = threadIdx.x; i < row; i += blockDim.x) {
         double c = start_cost[(size_t)b * row + i];
         if (i < (row >> 1)) c = c + kLanePenalty;         // ref :318
@@ -1043,7 +1049,7 @@ __global__ __launch_bounds__(256) void dp_sweep_wide_kernel(DpDev P, const doubl
 // lowest-k predecessor, first-minimum terminal), so rows, min_cost and status are bit-identical to the two-kernel
 // path.  Trade: no 8 E bytes per scene written and read back, against one block per tile - 586 blocks at 4096
 // scenes 40x9, two or three per CU instead of the edge kernel's sixteen wavefronts per CU (HISTORY.md section 3.2).
-// (FusedLds, fused_lds: the kernel's LDS carve-up, emp_dp_launch.h)
+// (FusedLds, fused_lds: the kernel's LDS layout, emp_dp_launch.h)
 
 template <int ROW>
 __global__ __launch_bounds__(256, 4) void dp_fused_kernel(DpDev P, const double* __restrict__ pair_tab,
@@ -1056,16 +1062,18 @@ __global__ __launch_bounds__(256, 4) void dp_fused_kernel(DpDev P, const double*
                                                           int* __restrict__ status_out, int nc) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int row = ROW > 0 ? ROW : P.row, rr = row * row;
-    const FusedLds L = fused_lds(row, P.col, P.S, P.max_obs, nc);
+    // (P = int: byte positions from 0, added to the base here.  Walked as pointers the same layout costs this kernel four to six
+    // vector registers more, and nine more spilled at 21 rows: profiles/dp_layouts/README.md)
+    const FusedLds<int> L = fused_lds(0, row, P.col, P.S, P.max_obs, nc);
     unsigned char* base_b = reinterpret_cast<unsigned char*>(lds);
-    double* tab = lds;
-    double* t_smp = reinterpret_cast<double*>(base_b + L.off_smp);
-    double* t_obs_s = reinterpret_cast<double*>(base_b + L.off_obs_s);
-    double* t_obs_l = reinterpret_cast<double*>(base_b + L.off_obs_l);
-    double* buf = reinterpret_cast<double*>(base_b + L.off_buf);                  // [2][nc][row][64]
-    double* front = reinterpret_cast<double*>(base_b + L.off_front);              // [64] cost front of the previous column
-    unsigned char* pre = base_b + L.off_pre;                                      // [col][64] predecessor rows
-    int* ctr = reinterpret_cast<int*>(base_b + L.off_ctr);                        // [2] column counters, one per buffer
+    double* tab = reinterpret_cast<double*>(base_b + L.tab);
+    double* t_smp = reinterpret_cast<double*>(base_b + L.smp);
+    double* t_obs_s = reinterpret_cast<double*>(base_b + L.obs_s);
+    double* t_obs_l = reinterpret_cast<double*>(base_b + L.obs_l);
+    double* buf = reinterpret_cast<double*>(base_b + L.buf);                  // [2][nc][row][64]
+    double* front = reinterpret_cast<double*>(base_b + L.front);              // [64] cost front of the previous column
+    unsigned char* pre = base_b + L.pre;                                      // [col][64] predecessor rows
+    int* ctr = reinterpret_cast<int*>(base_b + L.ctr);                        // [2] column counters, one per buffer
     const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -1234,7 +1242,8 @@ __global__ __launch_bounds__(64) void dp_enrich_wave_kernel(DpDev P, const doubl
                                                            const int* __restrict__ term = nullptr,
                                                            const int* __restrict__ n_obs = nullptr,
                                                            double* __restrict__ rows_out = nullptr) {
-    extern __shared__ __attribute__((aligned(16))) double enrich_lds[];
+    extern __shared__ __attribute__((aligned(16))) double enrich_mem[];                // EnrichLds (emp_dp_launch.h)
+    const EnrichLds<unsigned char*> L = enrich_lds(reinterpret_cast<unsigned char*>(enrich_mem), P.row, P.col, pre != nullptr);
     const int b = blockIdx.x, lane = threadIdx.x & 63;
     const double ps = start[b * 4 + 0];
     double* os = path_s + (size_t)b * max_pts;
@@ -1242,13 +1251,13 @@ __global__ __launch_bounds__(64) void dp_enrich_wave_kernel(DpDev P, const doubl
     // The scene's rows are read from LDS in BOTH forms (round 6): as a run-time choice between the device array and the LDS copy
     // the reads compiled to flat loads behind a select of two address spaces - the pattern that perturbed builds of the path-QP
     // kernel read wrong (emp_tail_kernels.h, sd_at).
-    double* lrows = enrich_lds;                                                       // [col]
+    double* lrows = reinterpret_cast<double*>(L.rows);                                // [col]
     const double* my_rows = lrows;
     if (pre == nullptr) {
         for (int j = lane; j < P.col; j += 64) lrows[j] = rows[(size_t)b * P.col + j];
         __syncthreads();
     } else {
-        unsigned char* bt = reinterpret_cast<unsigned char*>(lrows + P.col);          // [col][row]
+        unsigned char* bt = L.bt;                                                     // [col][row]
         const int tile = b / P.S, base = (b - tile * P.S) * P.row;
         const unsigned char* tp = pre + (size_t)tile * P.col * 64 + base;
         for (int j = 1 + lane; j < P.col; j += 64)

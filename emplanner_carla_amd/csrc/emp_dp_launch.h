@@ -56,20 +56,126 @@ constexpr int kMaxTiledRow = 32;       // the tiled kernels (scenes packed into 
 constexpr int kMaxWideRow = 1024;      // (round 5: predecessors of the wide sweep are 16-bit; until round 4 a byte, 256 rows.  The pair
                                        // table is 15 row^2 doubles - 126 MB at 1024 rows - and the tensor (col - 1) row^2 doubles per scene)
 
-struct FusedLds {
-    int off_smp, off_obs_s, off_obs_l, off_buf, off_front, off_pre, off_ctr, total;   // bytes
+// ---- layouts ------------------------------------------------------------------------------------------------------------
+// The dynamic LDS of every DP kernel, as in emp_tail_launch.h: a struct of positions, and ONE function that walks the arrays in
+// order from `at`.  The position type P is the kernel's own pointer on the device - the function then IS the kernel's carve-up -
+// and a plain count from 0 on the host (LdsCount), where `end` is the total the launch asks for: one sum, not two.  The
+// layouts of doubles alone count DOUBLES (edge_lds, sweep_lds - 64 predecessor bytes a column are 8 - and sweep_wide_lds); those
+// that also hold bytes or 32-bit words count BYTES, as emp_tail_launch.h's SpeedDpLds does (edge_ring_lds: the rings;
+// enrich_lds: col * row predecessor bytes; fused_lds: predecessor bytes and counters).  What varies per wavefront is an
+// argument (`waves`, `cpw`, `wpb`); a wavefront's own share of such an array is index arithmetic from its base, in the kernel.
+using LdsCount = size_t;
+
+// the lockstep kernel's box terms per scene: one per obstacle slot inside the kernel's reach mask (MASK: 32 or 64 bits)
+EMP_HD constexpr int edge_box_width(int max_obs, int mask_bits) { return max_obs < mask_bits ? max_obs : mask_bits; }
+
+template <class P>
+struct EdgeLds {         // dp_edge_kernel
+    P tab;               // [kTableFields][row^2], pair index = k * row + i
+    P obs_s, obs_l;      // [S][max_obs] each
+    P smp;               // [kTableTail] sample offsets t_n, sum t_n, sum t_n^2, unit quintic
+    P box;               // [waves][S][edge_box_width] longitudinal box terms of the column a wavefront works on.  Keep it the LAST
+                         // array: dp_edge_kernel asks for the layout of ONE wavefront (see there), right for everything up to `box`
+    P end;
 };
-EMP_HD FusedLds fused_lds(int row, int col, int S, int max_obs, int nc) {
-    FusedLds L;
-    int o = kTableFields * row * row * 8;
-    L.off_smp = o;   o += kTableTail * 8;
-    L.off_obs_s = o; o += S * max_obs * 8;
-    L.off_obs_l = o; o += S * max_obs * 8;
-    L.off_buf = o;   o += 2 * nc * row * 64 * 8;
-    L.off_front = o; o += 64 * 8;
-    L.off_pre = o;   o += ((col * 64 + 7) / 8) * 8;
-    L.off_ctr = o;   o += 8;
-    L.total = o;
+template <class P>
+EMP_HD EdgeLds<P> edge_lds(P at, int row, int S, int max_obs, int mask_bits, int waves) {
+    EdgeLds<P> L;
+    L.tab = at;   at += kTableFields * row * row;
+    L.obs_s = at; at += S * max_obs;
+    L.obs_l = at; at += S * max_obs;
+    L.smp = at;   at += kTableTail;
+    L.box = at;   at += (size_t)waves * S * edge_box_width(max_obs, mask_bits);
+    L.end = at;
+    return L;
+}
+
+template <class P>
+struct EdgeRingLds {     // dp_edge_ring_kernel, in BYTES
+    P tab;               // [kTableFields][row^2] doubles
+    P obs_s, obs_l;      // [S][max_obs] doubles each
+    P ps;                // [S rounded up to even] doubles: plan_start_s of the tile's scenes
+    P band;              // [waves][S][max_obs][2] doubles: lateral reach band (lo, hi) of each obstacle in the wavefront's column
+    P rings;             // [waves] of edge_ring_bytes(max_obs) bytes: code [2][kRingSlots], then a mask per slot
+    P f;                 // [waves][cpw][S] doubles: the jerk factor F of each of a wavefront's cpw columns
+    P end;
+};
+template <class P>
+EMP_HD EdgeRingLds<P> edge_ring_lds(P at, int row, int S, int max_obs, int waves, int cpw) {
+    EdgeRingLds<P> L;
+    L.tab = at;   at += kTableFields * row * row * 8;
+    L.obs_s = at; at += S * max_obs * 8;
+    L.obs_l = at; at += S * max_obs * 8;
+    L.ps = at;    at += ((S + 1) & ~1) * 8;
+    L.band = at;  at += (size_t)waves * 2 * S * max_obs * 8;
+    L.rings = at; at += (size_t)waves * edge_ring_bytes(max_obs);
+    L.f = at;     at += (size_t)waves * cpw * S * 8;
+    L.end = at;
+    return L;
+}
+
+template <class P>
+struct SweepLds {        // dp_sweep_kernel<ROW, PD, WPB, ., .>
+    P front;             // [wpb][64] the cost front of the previous column
+    P pre;               // [wpb][col][64] predecessor BYTES: 8 doubles a column
+    P end;
+};
+template <class P>
+EMP_HD SweepLds<P> sweep_lds(P at, int wpb, int col) {
+    SweepLds<P> L;
+    L.front = at; at += wpb * 64;
+    L.pre = at;   at += (size_t)wpb * col * 8;
+    L.end = at;
+    return L;
+}
+
+template <class P>
+struct SweepWideLds {    // dp_sweep_wide_kernel: the cost front of the previous column and the one being built, [row] each
+    P cur, nxt, end;
+};
+template <class P>
+EMP_HD SweepWideLds<P> sweep_wide_lds(P at, int row) {
+    return {at, at + row, at + row + row};
+}
+
+template <class P>
+struct EnrichLds {       // dp_enrich_wave_kernel, in BYTES (P: a byte pointer, or a count of bytes)
+    P rows;              // [col] doubles: the scene's rows
+    P bt;                // [col][row] predecessor bytes, where the kernel does the backtrack (with_pre)
+    P end;
+};
+template <class P>
+EMP_HD EnrichLds<P> enrich_lds(P at, int row, int col, bool with_pre) {
+    EnrichLds<P> L;
+    L.rows = at; at += (size_t)col * 8;
+    L.bt = at;   at += with_pre ? (size_t)col * row : 0;
+    L.end = at;
+    return L;
+}
+
+template <class P>
+struct FusedLds {        // dp_fused_kernel, in BYTES
+    P tab;               // [kTableFields][row^2] doubles
+    P smp;               // [kTableTail] doubles
+    P obs_s, obs_l;      // [S][max_obs] doubles each
+    P buf;               // [2][nc][row][64] doubles: the edge costs of two column chunks
+    P front;             // [64] doubles: cost front of the previous column
+    P pre;               // [col][64] predecessor bytes
+    P ctr;               // [2] 32-bit column counters, one per buffer
+    P end;
+};
+template <class P>
+EMP_HD FusedLds<P> fused_lds(P at, int row, int col, int S, int max_obs, int nc) {
+    FusedLds<P> L;
+    L.tab = at;   at += kTableFields * row * row * 8;
+    L.smp = at;   at += kTableTail * 8;
+    L.obs_s = at; at += S * max_obs * 8;
+    L.obs_l = at; at += S * max_obs * 8;
+    L.buf = at;   at += 2 * nc * row * 64 * 8;
+    L.front = at; at += 64 * 8;
+    L.pre = at;   at += col * 64;
+    L.ctr = at;   at += 2 * 4;
+    L.end = at;
     return L;
 }
 
@@ -131,11 +237,14 @@ static inline EdgePlan plan_edge(const DpDev& d, bool tiled, int opt_edge_form, 
     p.ring = ring;
     p.m32 = d.max_obs <= 32;
     p.row_inst = dp_row_inst(d.row);
-    const size_t lds_fixed = (ring ? ((size_t)kTableFields * d.row * d.row + 2 * (size_t)d.S * d.max_obs + ((d.S + 1) & ~1)) * sizeof(double)
-                                   : ((size_t)kTableFields * d.row * d.row + 2 * (size_t)d.S * d.max_obs + kTableTail) * sizeof(double)) + lds_pad;
-    const size_t lds_wave = ring ? 2 * (size_t)d.S * d.max_obs * sizeof(double) + (size_t)edge_ring_bytes(d.max_obs) + 4 * (size_t)d.S * sizeof(double)
-                                 : (size_t)d.S * (d.max_obs <= 32 ? d.max_obs : (d.max_obs < 64 ? d.max_obs : 64)) * sizeof(double);
-    size_t lds = lds_fixed + 2 * lds_wave;        // the block-size rule below prices a two-wavefront block; the launch its own
+    // the LDS of a block of w wavefronts: the kernel's own layout.  (cpw, ring form only: the columns a wavefront takes, which
+    // follow from the block size - the rules that choose the block size price kEdgeRingMaxCpw, the most a wavefront is ever given)
+    constexpr int kEdgeRingMaxCpw = 4;
+    const auto lds_of = [&](int w, int cpw) {
+        return (ring ? edge_ring_lds(LdsCount(0), d.row, d.S, d.max_obs, w, cpw).end
+                     : edge_lds(LdsCount(0), d.row, d.S, d.max_obs, p.m32 ? 32 : 64, w).end * sizeof(double)) + lds_pad;
+    };
+    size_t lds = lds_of(2, kEdgeRingMaxCpw);      // the block-size rule below prices a two-wavefront block; the launch its own
     if (lds > kLdsBytes) {
         p.error = "lattice too wide for the LDS pair table";
         return p;
@@ -163,12 +272,12 @@ static inline EdgePlan plan_edge(const DpDev& d, bool tiled, int opt_edge_form, 
         auto blocks_per_cu = [](size_t l) { return (size_t)128 / ((l + 1279) / 1280); };
         int best = 0;
         for (int w = 2; w <= 16; ++w) {
-            const size_t l = lds_fixed + (size_t)w * lds_wave;
+            const size_t l = lds_of(w, kEdgeRingMaxCpw);
             if (l > kLdsBytes) break;
             best = std::max(best, (int)std::min<size_t>(blocks_per_cu(l) * w, 20));
         }
         for (int w = 2; w <= 16; ++w) {
-            const size_t l = lds_fixed + (size_t)w * lds_wave;
+            const size_t l = lds_of(w, kEdgeRingMaxCpw);
             if (l > kLdsBytes) break;
             if ((int)std::min<size_t>(blocks_per_cu(l) * w, 20) >= std::min(best, 16)) {
                 wpb = w;
@@ -183,8 +292,8 @@ static inline EdgePlan plan_edge(const DpDev& d, bool tiled, int opt_edge_form, 
     if (opt_edge_block) wpb = opt_edge_block / 64;
     // (the rule above prices a two-wavefront block; a wide table with wide obstacle rows - 32 rows, 254+ obstacle slots: one block
     // of sixteen wavefronts per CU - may not hold sixteen per-wavefront scratch areas: fewer wavefronts, not a refusal)
-    while (wpb > 1 && lds_fixed + (size_t)wpb * lds_wave > kLdsBytes) --wpb;
-    lds = lds_fixed + (size_t)wpb * lds_wave;
+    while (wpb > 1 && lds_of(wpb, kEdgeRingMaxCpw) > kLdsBytes) --wpb;
+    lds = lds_of(wpb, kEdgeRingMaxCpw);
     if (lds > kLdsBytes) {
         p.error = "edge-cost block too large for the LDS";
         return p;
@@ -202,13 +311,11 @@ static inline EdgePlan plan_edge(const DpDev& d, bool tiled, int opt_edge_form, 
     int cols_per_chunk = ncol > 0 ? (ncol + chunks - 1) / chunks : 1;
     cols_per_chunk = cols_per_chunk >= wpb ? (cols_per_chunk / wpb) * wpb : wpb;
     chunks = ncol > 0 ? (ncol + cols_per_chunk - 1) / cols_per_chunk : 1;
-    if (ring) {       // the ring form's jerk-factor table: [columns per wavefront][S] per wavefront (priced above with four columns, the most the rule below gives a wavefront)
-        const size_t cpw_final = (size_t)(cols_per_chunk + wpb - 1) / wpb;
-        lds = lds_fixed + (size_t)wpb * (lds_wave - 4 * (size_t)d.S * sizeof(double) + cpw_final * d.S * sizeof(double));
-        if (lds > kLdsBytes) {
-            p.error = "edge-cost block too large for the LDS";
-            return p;
-        }
+    // the launch's LDS: the ring form's jerk-factor table holds the columns a wavefront really takes, as the kernel counts them
+    lds = lds_of(wpb, (cols_per_chunk + wpb - 1) / wpb);
+    if (lds > kLdsBytes) {
+        p.error = "edge-cost block too large for the LDS";
+        return p;
     }
     p.wpb = wpb;
     p.cols_per_chunk = cols_per_chunk;
@@ -234,7 +341,7 @@ static inline SweepPlan plan_sweep(const DpDev& d) {
     if (dp_wide(d)) {          // more than 32 rows: one block per scene, predecessors in device memory
         p.grid = d.B;
         p.block = std::min(((d.row + 63) / 64) * 64, 256);
-        p.lds = 2 * (size_t)d.row * sizeof(double);
+        p.lds = sweep_wide_lds(LdsCount(0), d.row).end * sizeof(double);
         return p;
     }
     // Ring depth PD (columns in flight per wavefront), measured at 4096 scenes: 2 is best for rows 5..12 (row 9:
@@ -261,7 +368,7 @@ static inline SweepPlan plan_sweep(const DpDev& d) {
     }
     p.grid = d.tiles;          // one wavefront a block
     p.block = 64;
-    p.lds = d.col * 64 + 64 * sizeof(double);      // the predecessor bytes [col][64], the front [64]
+    p.lds = sweep_lds(LdsCount(0), 1, d.col).end * sizeof(double);      // WPB = 1: the front [64], the predecessor bytes [col][64]
     if (p.lds > kLdsBytes) p.error = "too many columns for the predecessor table in LDS";
     return p;
 }
@@ -278,8 +385,9 @@ static inline FusedPlan plan_fused(const DpDev& d) {
     // columns per chunk: 4 (one per wavefront) while two buffers of them leave room for three blocks per CU, fewer on wide
     // lattices whose pair table fills the LDS
     p.nc = 4;
-    while (p.nc > 1 && fused_lds(d.row, d.col, d.S, d.max_obs, p.nc).total > 53 * 1024) p.nc /= 2;
-    p.lds = (size_t)fused_lds(d.row, d.col, d.S, d.max_obs, p.nc).total;
+    const auto lds_of = [&](int nc) { return fused_lds(LdsCount(0), d.row, d.col, d.S, d.max_obs, nc).end; };      // (bytes)
+    while (p.nc > 1 && lds_of(p.nc) > 53 * 1024) p.nc /= 2;
+    p.lds = lds_of(p.nc);
     if (p.lds > kLdsBytes) p.error = "lattice too wide for the fused DP kernel's LDS working set";
     return p;
 }
@@ -291,7 +399,7 @@ struct EnrichPlan {
 
 static inline EnrichPlan plan_enrich(const DpDev& d, bool with_pre) {
     EnrichPlan p;
-    p.lds = (size_t)d.col * sizeof(double) + (with_pre ? (size_t)d.col * d.row : 0);      // the rows [col], + the predecessor bytes
+    p.lds = enrich_lds(LdsCount(0), d.row, d.col, with_pre).end;      // (bytes)
     if (p.lds > kLdsBytes) p.error = "too many columns for the densification kernel's predecessor table in LDS";
     return p;
 }

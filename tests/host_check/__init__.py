@@ -73,6 +73,8 @@ def load():
     lib.hc_edge_tensor_elems.argtypes = [i] * 4
     lib.hc_edge_ring_constants.restype = None
     lib.hc_edge_ring_constants.argtypes = [i, p]
+    lib.hc_dp_layout.restype = i
+    lib.hc_dp_layout.argtypes = [C.c_char_p, i, i, i, i, i, p]
     for name, n_args in (("project", 2), ("reference_line", 1), ("cycle_qp", 5), ("cycle_cartesian", 5), ("path_qp", 2), ("smooth", 2),
                          ("speed_front", 2), ("speed_dp", 2), ("st_edge_cost", 3), ("speed_qp", 1), ("merge", 2)):
         fn = getattr(lib, "hc_plan_" + name)

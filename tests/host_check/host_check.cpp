@@ -231,6 +231,25 @@ void hc_edge_ring_constants(int max_obs, long long* out) {
     out[3] = edge_ring_bytes(max_obs);
 }
 
+// A DP kernel's LDS layout: its positions counted from 0, in the struct's order, `end` last; returns how many.  a .. e are the
+// layout function's own arguments, in its order.  Doubles, but bytes for "edge_ring", "enrich" and "fused".
+int hc_dp_layout(const char* name, int a, int b, int c, int d, int e, long long* out) {
+    const LdsCount z = 0;
+    const std::string_view n(name);
+    int k = 0;
+    auto put = [&](std::initializer_list<LdsCount> v) {
+        for (LdsCount x : v) out[k++] = (long long)x;
+        return k;
+    };
+    if (n == "edge") { const auto L = edge_lds(z, a, b, c, d, e); return put({L.tab, L.obs_s, L.obs_l, L.smp, L.box, L.end}); }
+    if (n == "edge_ring") { const auto L = edge_ring_lds(z, a, b, c, d, e); return put({L.tab, L.obs_s, L.obs_l, L.ps, L.band, L.rings, L.f, L.end}); }
+    if (n == "sweep") { const auto L = sweep_lds(z, a, b); return put({L.front, L.pre, L.end}); }
+    if (n == "sweep_wide") { const auto L = sweep_wide_lds(z, a); return put({L.cur, L.nxt, L.end}); }
+    if (n == "enrich") { const auto L = enrich_lds(z, a, b, c != 0); return put({L.rows, L.bt, L.end}); }
+    if (n == "fused") { const auto L = fused_lds(z, a, b, c, d, e); return put({L.tab, L.smp, L.obs_s, L.obs_l, L.buf, L.front, L.pre, L.ctr, L.end}); }
+    return 0;
+}
+
 // ---- launch plans and LDS layouts of every other kernel with dynamic LDS (emp_tail_launch.h) -------------------------------
 // A plan: its nine fields into `out` (zeros when refused), the refusal text or NULL returned.
 static const char* hc_put(const TailPlan& p, long long* out) {

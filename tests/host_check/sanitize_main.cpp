@@ -35,6 +35,7 @@ const char* hc_plan_sweep(int, int, int, int, long long*);
 const char* hc_plan_fused(int, int, int, int, long long*);
 const char* hc_plan_enrich(int, int, int, int, int, long long*);
 long long hc_edge_tensor_elems(int, int, int, int);
+int hc_dp_layout(const char*, int, int, int, int, int, long long*);
 const char* hc_plan_project(int, int, long long*);
 const char* hc_plan_cycle_qp(int, int, int, int, int, long long*);
 const char* hc_plan_cycle_cartesian(int, int, int, int, int, long long*);
@@ -195,7 +196,19 @@ int main() {
                     sink += hc_plan_enrich(row, col, B, mo, 0, out) != nullptr;
                     sink += hc_plan_enrich(row, col, B, mo, 1, out) != nullptr;
                     sink += (double)(hc_edge_tensor_elems(row, col, B, 0) & 1) + (double)(hc_edge_tensor_elems(row, col, B, 1) & 1);
-                    calls += 18;
+                    // the kernels' LDS layouts at this point: the edge forms from one to sixteen wavefronts and one to four columns
+                    // per wavefront, the fused kernel at every chunk size
+                    const int S = row <= 32 ? 64 / row : 1, slots = mo > 0 ? mo : 1;
+                    long long pos[9];
+                    for (int w : {1, 2, 5, 16}) {
+                        sink += hc_dp_layout("edge", row, S, slots, slots <= 32 ? 32 : 64, w, pos) + (double)(pos[5] & 1);
+                        sink += hc_dp_layout("edge_ring", row, S, slots, w, 1 + w % 4, pos) + (double)(pos[7] & 1);
+                        sink += hc_dp_layout("sweep", w, col, 0, 0, 0, pos) + (double)(pos[2] & 1);
+                    }
+                    for (int nc : {1, 2, 4}) sink += hc_dp_layout("fused", row, col, S, slots, nc, pos) + (double)(pos[8] & 1);
+                    sink += hc_dp_layout("sweep_wide", row, 0, 0, 0, 0, pos) + (double)(pos[2] & 1);
+                    sink += hc_dp_layout("enrich", row, col, 0, 0, 0, pos) + hc_dp_layout("enrich", row, col, 1, 0, 0, pos) + (double)(pos[2] & 1);
+                    calls += 36;
                 }
     // ---- the other launch plans (emp_tail_launch.h): every capacity at its entry point's limits, and the two no entry point
     // bounds (max_ref, max_path) up to 2^31 - 1

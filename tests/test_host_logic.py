@@ -488,6 +488,100 @@ def test_dp_edge_plan_invariants(hc):
     assert n_ring > 1000 and n_shrunk > 0                        # the grid reaches both (32 rows with 254 obstacle slots shrinks)
 
 
+def _dp_layout(hc, name, a=0, b=0, c=0, d=0, e=0):
+    out = np.zeros(12, dtype=np.int64)
+    n = hc.hc_dp_layout(name.encode(), a, b, c, d, e, out.ctypes.data)
+    assert n > 0, name
+    return out[:n].tolist()
+
+
+def test_dp_layouts_hold_what_the_kernels_index(hc):
+    """The LDS layouts of emp_dp_launch.h against the loops of the six kernels that carve with them, on every good plan of the
+    pinned grid: arrays in the struct's order, none overlapping, each aligned to its element and as long as the kernel indexes
+    it, `end` equal to the plan's `lds`.  Positions count doubles, but bytes for edge_ring, enrich and fused.  The bounds, read from
+    emp_dp_kernels.h (rr = row^2, S = 64 / row scenes a tile, F = kTableFields, T = kTableTail = 10 sample offsets + 2 moments
+    + 3 coefficients):
+      dp_edge_kernel        tab [f rr + p], f < F, p < rr (the scan's ten samples are fields 0..9); obs_s, obs_l [s max_obs + m],
+                            s < S, m < max_obs; smp [t], t < T; box [(wave S + s) w + m], wave < wavefronts, m < w =
+                            min(max_obs, mask bits)
+      dp_edge_ring_kernel   tab, obs_s, obs_l as above; ps [s], s < S; band [((wave S + s) max_obs + m) 2 + 1]; rings: a wavefront's
+                            share is edge_ring_bytes - 32-bit codes [2][kRingSlots], then kRingSlots masks of edge_ring_mask_bytes;
+                            f [(wave cpw + t) S + s], t < cpw = ceil(cols_per_chunk / wavefronts)
+      dp_sweep_kernel       front [wave 64 + lane]; pre bytes [(wave col + j) 64 + lane], j < col, copied out 16 bytes a lane;
+                            the plan launches WPB = 1
+      dp_sweep_wide_kernel  cur [i], nxt [i], i < row
+      dp_enrich_wave_kernel rows [j] doubles, j < col; with the backtrack bt [j row + r] bytes, r < row
+      dp_fused_kernel       tab, smp, obs_s, obs_l as the lockstep kernel; buf [((par nc + jj) row + k) 64 + lane] doubles, par < 2,
+                            jj < nc, k < row; front [lane]; pre bytes [j 64 + lane], j < col; ctr [2] 32-bit"""
+    g = load_golden("dp_launch_plans.npz")
+    T = 10 + 2 + 3
+    n_edge = n_ring = n_wide = n_fused = 0
+    seen_small = set()
+    for row, col, B, max_obs, tiled, form, block in np.unique(g["plans"][:, :7], axis=0).tolist():
+        what = f"row {row} col {col} B {B} max_obs {max_obs} tiled {tiled} form {form} block {block}"
+        mo = max(max_obs, 1)                                     # make_dp_dev: at least one slot
+        S = 64 // row if row <= 32 else 1
+        rr = row * row
+        c = np.zeros(4, dtype=np.int64)
+        hc.hc_edge_ring_constants(mo, c.ctypes.data)
+        F, ring_slots, _, ring_bytes = c.tolist()
+        mask_bytes = 1 if mo <= 8 else 2 if mo <= 16 else 4 if mo <= 32 else 8
+        e = np.zeros(10, dtype=np.int64)
+        if hc.hc_plan_edge(row, col, B, max_obs, tiled, form, block, e.ctypes.data) is None and not e[0]:
+            _, ring, m32, _, wpb, cpc, _, _, _, lds = e.tolist()
+            if ring:
+                cpw = (cpc + wpb - 1) // wpb
+                pos = _dp_layout(hc, "edge_ring", row, S, mo, wpb, cpw)                       # bytes
+                assert ring_bytes == 4 * 2 * ring_slots + mask_bytes * ring_slots, what
+                _in_order(pos, [8 * F * rr, 8 * S * mo, 8 * S * mo, 8 * ((S + 1) & ~1), 8 * wpb * S * mo * 2, wpb * ring_bytes,
+                                8 * wpb * cpw * S])
+                assert S <= (S + 1) & ~1 and all(p % 8 == 0 for p in pos), what                # the doubles, and the ones behind the rings
+                # a wavefront's codes at 4 bytes, its masks (behind 2 kRingSlots codes) at their own width
+                for wave in range(wpb):
+                    at = pos[5] + wave * ring_bytes
+                    assert at % 4 == 0 and (at + 4 * 2 * ring_slots) % mask_bytes == 0, what
+                assert pos[-1] == lds, what
+                n_ring += 1
+            else:
+                bits = 32 if m32 else 64
+                pos = _dp_layout(hc, "edge", row, S, mo, bits, wpb)
+                _in_order(pos, [F * rr, S * mo, S * mo, T, wpb * S * min(mo, bits)])
+                assert F >= 10 and m32 == (mo <= 32), what      # the scan's ten samples are the table's first fields
+                assert 8 * pos[-1] == lds, what
+                n_edge += 1
+        if (row, col, B, max_obs) in seen_small:
+            continue
+        seen_small.add((row, col, B, max_obs))
+        s = np.zeros(6, dtype=np.int64)
+        if hc.hc_plan_sweep(row, col, B, max_obs, s.ctypes.data) is None:
+            if row > 32:
+                pos = _dp_layout(hc, "sweep_wide", row)
+                _in_order(pos, [row, row])
+                n_wide += 1
+            else:
+                assert s[4] == 64, what                          # one wavefront a block: WPB = 1
+                pos = _dp_layout(hc, "sweep", 1, col)
+                _in_order(pos, [64, col * 64 // 8])
+                assert (8 * pos[1]) % 16 == 0, what              # the predecessor table leaves the kernel 16 bytes a lane
+                for wpb in (2, 4):                               # the kernel's other block sizes: a wavefront's share is col * 64 bytes
+                    _in_order(_dp_layout(hc, "sweep", wpb, col), [wpb * 64, wpb * col * 64 // 8])
+            assert 8 * pos[-1] == s[5], what
+        for with_pre in (0, 1):
+            n = np.zeros(1, dtype=np.int64)
+            if hc.hc_plan_enrich(row, col, B, max_obs, with_pre, n.ctypes.data) is None:
+                pos = _dp_layout(hc, "enrich", row, col, with_pre)                            # bytes
+                _in_order(pos, [8 * col, col * row if with_pre else 0])
+                assert pos[0] % 8 == 0 and pos[-1] == n[0], what
+        f = np.zeros(2, dtype=np.int64)
+        if hc.hc_plan_fused(row, col, B, max_obs, f.ctypes.data) is None:
+            nc = int(f[0])
+            pos = _dp_layout(hc, "fused", row, col, S, mo, nc)                                # bytes
+            _in_order(pos, [8 * F * rr, 8 * T, 8 * S * mo, 8 * S * mo, 8 * 2 * nc * row * 64, 8 * 64, col * 64, 2 * 4])
+            assert all(p % 8 == 0 for p in pos[:6]) and pos[7] % 4 == 0 and pos[-1] == f[1], what
+            n_fused += 1
+    assert n_ring > 1000 and n_edge > 1000 and n_wide > 0 and n_fused > 100
+
+
 def test_edge_tensor_elems_is_the_size_of_the_tiled_tensor(hc):
     """emp_dp_launch.h edge_tensor_elems against the package's own host-side tiling (api.tile_edges) and the canonical
     shape, on small lattices either side of every scenes-per-wavefront count."""
