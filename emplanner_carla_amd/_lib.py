@@ -187,6 +187,23 @@ class BehaviorIO(C.Structure):
         "log_mode", "log_target")] + [("reserved", C.c_int32)]
 
 
+HAZARD_MAX = 64                    # EMP_HAZARD_MAX: lights of a world, and walkers of a world
+HZ_NONE, HZ_LIGHT, HZ_WALKER, HZ_VEHICLE = range(4)      # EMP_HZ_*: why a tick is EMERGENCY
+
+
+class HazardParams(C.Structure):
+    """emp_hazard_params: the thresholds of BasicAgent._affected_by_traffic_light and pedestrian_avoid_manager."""
+    _fields_ = [(n, C.c_double) for n in ("tlight_threshold", "tlight_up_angle", "walker_radius", "walker_up_angle")] + \
+               [("reserved", C.c_int32)]
+
+
+class HazardIO(C.Structure):
+    """emp_hazard_io: what emp_agent_behave_hazards and emp_traffic_rollout_hazards add to emp_behavior_io."""
+    _fields_ = [(n, _vp) for n in (
+        "n_light", "light", "light_lane", "light_cycle", "n_walker", "walker", "walker_lane", "last_light", "last_light_out", "cause",
+        "light_hit", "walker_hit", "walker_distance", "cause_ticks", "min_walker_gap", "log_cause")] + [("reserved", C.c_int32)]
+
+
 class CycleIO(C.Structure):
     _fields_ = [(n, _vp) for n in (
         "ref_line", "n_ref", "origin_xy", "start_xy", "start_v", "start_a", "obs_xy", "n_obs",
@@ -351,6 +368,12 @@ PROTOTYPES = {
                                    C.POINTER(BehaviorIO), C.c_int]),
     "emp_traffic_rollout": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(BehaviorParams), C.POINTER(VehicleParams), _i32, _i32, _i32,
                                       _i32, _i32, _i32, C.c_int64, C.POINTER(BehaviorIO), C.c_int]),
+    "emp_hazard_params_default": (None, [C.POINTER(HazardParams)]),
+    "emp_agent_behave_hazards": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(BehaviorParams), _i32, _i32, _i32, _i32, C.c_int64,
+                                           C.POINTER(BehaviorIO), C.c_int, C.POINTER(HazardParams), _i32, _i32, C.POINTER(HazardIO)]),
+    "emp_traffic_rollout_hazards": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(BehaviorParams), C.POINTER(VehicleParams), _i32, _i32,
+                                              _i32, _i32, _i32, _i32, C.c_int64, C.POINTER(BehaviorIO), C.c_int, C.POINTER(HazardParams),
+                                              _i32, _i32, C.POINTER(HazardIO)]),
 }
 
 _lib = None

@@ -131,6 +131,19 @@ def behavior_params(kind="normal", **kw) -> L.BehaviorParams:
     return p
 
 
+def hazard_params(**kw) -> L.HazardParams:
+    """The thresholds of the reference's red-light and pedestrian checks (tlight_threshold 5 m, tlight_up_angle 90, walker_radius
+    10 m, walker_up_angle 60); keywords replace single fields."""
+    p = L.HazardParams()
+    L.load().emp_hazard_params_default(C.byref(p))
+    names = {n for n, _ in L.HazardParams._fields_} - {"reserved"}
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError(f"hazard_params has no field {k!r}")
+        setattr(p, k, float(v))
+    return p
+
+
 @dataclass
 class AgentObservation:
     forward: object      # (A, 2) cos fi, sin fi: the transform's forward vector
@@ -207,6 +220,23 @@ class TrafficRolloutResult:
     log_head: object     # (n_log, W, N) int32
     log_mode: object     # (n_log, W, N) int32
     log_target: object   # (n_log, W, N)
+
+
+@dataclass
+class HazardBehaveResult(BehaveResult):
+    last_light: object   # (W, N) int32 the light that holds the agent after the tick, -1 for none
+    cause: object        # (W, N) int32 EMP_HZ_*: why the tick is EMERGENCY, 0 for any other mode
+    light_hit: object    # (W, N) int32 index of the red light that affects the agent, -1 if none
+    walker_hit: object   # (W, N) int32 index of the walker seen (ignored ones too), -1 if none
+    walker_distance: object  # (W, N) distance to it less the two extents, +inf if none
+
+
+@dataclass
+class HazardRolloutResult(TrafficRolloutResult):
+    last_light: object   # (W, N) int32 after T ticks
+    cause_ticks: object  # (W, N, 3) int32 EMERGENCY ticks by light, walker, vehicle
+    min_walker_gap: object   # (W, N) the smallest walker_distance seen, +inf if none
+    log_cause: object    # (n_log, W, N) int32; None without logs
 
 
 @dataclass
@@ -1257,6 +1287,92 @@ class Planner:
         self._check(self._lib.emp_traffic_rollout(self._h, C.byref(p), C.byref(bp), C.byref(vp), W, N, M, K, T, every, int(tick0),
                                                   C.byref(io), a.where))
         return TrafficRolloutResult(so, *outs, st, dn, mt, mg, act, ls, lc, lh, lm, lt)
+
+    # ---- traffic that stops for red lights and pedestrians (reference behavior_agent.py:312-328, basic_agent.py:201-249) ----
+    def _hazard_io(self, a, W, N, last_light, lights, walkers, in_place):
+        """emp_hazard_io's inputs and last_light_out: -> (io, max_light, max_walker, last_light_out)."""
+        h = L.HazardIO()
+        max_light = max_walker = 0
+        if lights is not None:
+            n_light, light, light_lane, light_cycle = lights
+            max_light = int(light.shape[1])
+            if max_light > 0:
+                h.n_light, h.light = a.inp(n_light, np.int32, (W,)), a.inp(light, np.float64, (W, max_light, 4))
+                h.light_lane = a.inp(light_lane, np.int32, (W, max_light))
+                h.light_cycle = a.inp(light_cycle, np.int32, (W, max_light, 3))
+        if walkers is not None:
+            n_walker, walker, walker_lane = walkers
+            max_walker = int(walker.shape[1])
+            if max_walker > 0:
+                h.n_walker, h.walker = a.inp(n_walker, np.int32, (W,)), a.inp(walker, np.float64, (W, max_walker, 5))
+                h.walker_lane = a.inp(walker_lane, np.int32, (W, max_walker))
+        h.last_light = a.inp(last_light, np.int32, (W, N))
+        ll, h.last_light_out = a.out((W, N), np.int32, into=_in_place(last_light, np.int32, in_place))
+        h.reserved = 0
+        return h, max_light, max_walker, ll
+
+    def agent_behave_hazards(self, p, bp, hp, n_world, path, n_path, lane, state, forward, speed_kmh, speed_limit, extent, head,
+                             past_steer, lon_err, n_lon, lat_err, n_lat, last_light, lights=None, walkers=None, others=None, tick0=0,
+                             in_place=False) -> HazardBehaveResult:
+        """``agent_behave`` with the two checks the reference runs before car-following (include/emplanner.h states them): red
+        lights and pedestrians.  hp: ``hazard_params()``.  last_light (W, N) int32: the light that holds each agent, -1 for none.
+        lights: (n_light (W,), light (W, L, 4) = x, y, dx, dy of the trigger waypoint, light_lane (W, L), light_cycle (W, L, 3) =
+        period, red_from, red_to in ticks); walkers: (n_walker (W,), walker (W, K, 5) = x, y, vx, vy, half extent, walker_lane
+        (W, K)); both at tick index tick0.  L, K <= 64."""
+        a = self._args(path, state, forward)
+        io, W, N, M, K, outs = self._behavior_io(a, n_world, path, n_path, lane, state, speed_limit, extent,
+                                                 (head, past_steer, lon_err, n_lon, lat_err, n_lat), others, in_place)
+        io.forward, io.speed_kmh = a.inp(forward, np.float64, (W, N, 2)), a.inp(speed_kmh, np.float64, (W, N))
+        st, io.status = a.out((W, N), np.int32)
+        ctl, io.control = a.out((W, N, 3), np.float64)
+        mode, io.mode = a.out((W, N), np.int32)
+        blk, io.blocker = a.out((W, N), np.int32)
+        dist, io.distance = a.out((W, N), np.float64)
+        ttc, io.ttc = a.out((W, N), np.float64)
+        tgt, io.target_speed_out = a.out((W, N), np.float64)
+        le, io.lat_error = a.out((W, N), np.float64)
+        lc, io.lon_command = a.out((W, N), np.float64)
+        h, ML, MW, ll = self._hazard_io(a, W, N, last_light, lights, walkers, in_place)
+        cause, h.cause = a.out((W, N), np.int32)
+        lhit, h.light_hit = a.out((W, N), np.int32)
+        whit, h.walker_hit = a.out((W, N), np.int32)
+        wd, h.walker_distance = a.out((W, N), np.float64)
+        self._check(self._lib.emp_agent_behave_hazards(self._h, C.byref(p), C.byref(bp), W, N, M, K, int(tick0), C.byref(io), a.where,
+                                                       C.byref(hp), ML, MW, C.byref(h)))
+        return HazardBehaveResult(ctl, st, *outs, mode, blk, dist, ttc, tgt, le, lc, ll, cause, lhit, whit, wd)
+
+    def traffic_rollout_hazards(self, p, bp, hp, vp: VehicleParams, n_world, path, n_path, lane, state, speed_limit, extent, head,
+                                past_steer, lon_err, n_lon, lat_err, n_lat, last_light, T, lights=None, walkers=None, others=None,
+                                tick0=0, log_every=None, in_place=False) -> HazardRolloutResult:
+        """``traffic_rollout`` with red lights and pedestrians: T ticks of [agent_observe, agent_behave_hazards, vehicle_step(vp)] in
+        ONE kernel launch, bit-identical to the chain of the 3 T calls; cut in two, with ``tick0`` advanced and ``last_light``
+        carried, it resumes bit for bit.  Arrays as ``agent_behave_hazards``."""
+        T = int(T)
+        every = 1 if log_every is None else int(log_every)
+        n_log = (T + every - 1) // every if log_every is not None and every >= 1 and T >= 1 else None
+        a = self._args(path, state, lon_err)
+        io, W, N, M, K, outs = self._behavior_io(a, n_world, path, n_path, lane, state, speed_limit, extent,
+                                                 (head, past_steer, lon_err, n_lon, lat_err, n_lat), others, in_place)
+        so, io.state_out = a.out((W, N, 6), np.float64, into=_in_place(state, np.float64, in_place))
+        st, io.status = a.out((W, N), np.int32)
+        dn, io.done_tick = a.out((W, N), np.int32)
+        mt, io.mode_ticks = a.out((W, N, 5), np.int32)
+        mg, io.min_gap = a.out((W, N), np.float64)
+        act, io.actors_out = a.out((W, N, 4), np.float64)
+        h, ML, MW, ll = self._hazard_io(a, W, N, last_light, lights, walkers, in_place)
+        ct, h.cause_ticks = a.out((W, N, 3), np.int32)
+        wg, h.min_walker_gap = a.out((W, N), np.float64)
+        ls = lc = lh = lm = lt = lcs = None
+        if n_log is not None:
+            ls, io.log_state = a.out((n_log, W, N, 6), np.float64)
+            lc, io.log_control = a.out((n_log, W, N, 3), np.float64)
+            lh, io.log_head = a.out((n_log, W, N), np.int32)
+            lm, io.log_mode = a.out((n_log, W, N), np.int32)
+            lt, io.log_target = a.out((n_log, W, N), np.float64)
+            lcs, h.log_cause = a.out((n_log, W, N), np.int32)
+        self._check(self._lib.emp_traffic_rollout_hazards(self._h, C.byref(p), C.byref(bp), C.byref(vp), W, N, M, K, T, every, int(tick0),
+                                                          C.byref(io), a.where, C.byref(hp), ML, MW, C.byref(h)))
+        return HazardRolloutResult(so, *outs, st, dn, mt, mg, act, ls, lc, lh, lm, lt, ll, ct, wg, lcs)
 
     # ---- lateral MPC controller (reference controller/controller.py:65-337) -----------------------
     def mpc_lateral(self, p: MpcParams, target_path, n_path, state, vx, min_index, qp_matrices=False) -> MpcResult:

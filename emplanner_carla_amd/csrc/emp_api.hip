@@ -25,6 +25,7 @@
 #include "emp_route_launch.h"
 #include "emp_agent_kernels.h"
 #include "emp_behavior_kernels.h"
+#include "emp_hazard_kernels.h"
 
 namespace emp {
 thread_local std::string g_create_error;
@@ -3459,6 +3460,142 @@ int emp_traffic_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_behav
     if (const int rc = st.ready()) return rc;
     if (const int rc = launch(ctx, "traffic_rollout", bhv::traffic_rollout_kernel, dim3(plan.grid), dim3(plan.block), 0, agent_params(p),
                               behavior_params(bp), vehicle_params(vp), (int)nA, io))
+        return rc;
+    return st.finish();
+}
+
+}  // extern "C"
+
+// ---- traffic that stops for red lights and pedestrians (emp_hazard_core.h, emp_hazard_kernels.h) ------------------------------------
+namespace {
+
+hz::Params hazard_params(const emp_hazard_params* p) {
+    return hz::Params{p->tlight_threshold, p->tlight_up_angle, p->walker_radius, p->walker_up_angle};
+}
+
+// what both hazard calls refuse beyond behavior_checks
+int hazard_checks(emp_ctx* ctx, const emp_hazard_params* hp, const emp_hazard_io* h, int max_light, int max_walker) {
+    EMP_REQUIRE(ctx, hp && h, "NULL parameter struct");
+    EMP_REQUIRE(ctx, hp->reserved == 0, "emp_hazard_params.reserved must be 0");
+    EMP_REQUIRE(ctx, h->reserved == 0, "emp_hazard_io.reserved must be 0");
+    EMP_REQUIRE(ctx, h->last_light && h->last_light_out, "NULL array");
+    EMP_REQUIRE(ctx, max_light == 0 || (h->n_light && h->light && h->light_lane && h->light_cycle),
+                "max_light > 0 needs n_light, light, light_lane and light_cycle");
+    EMP_REQUIRE(ctx, max_walker == 0 || (h->n_walker && h->walker && h->walker_lane), "max_walker > 0 needs n_walker, walker and walker_lane");
+    return EMP_OK;
+}
+
+void stage_hazards(Stage& st, const emp_hazard_io* h, size_t W, size_t nA, size_t max_light, size_t max_walker, bool z, hz::HazardIO* io) {
+    io->max_light = (int)max_light;
+    io->max_walker = (int)max_walker;
+    if (max_light > 0) {
+        io->n_light = st.in(h->n_light, W);
+        io->light = st.in(h->light, W * max_light * 4);
+        io->light_lane = st.in(h->light_lane, W * max_light);
+        io->light_cycle = st.in(h->light_cycle, W * max_light * 3);
+    }
+    if (max_walker > 0) {
+        io->n_walker = st.in(h->n_walker, W);
+        io->walker = st.in(h->walker, W * max_walker * 5);
+        io->walker_lane = st.in(h->walker_lane, W * max_walker);
+    }
+    io->last_light = st.in(h->last_light, nA);
+    io->last_light_out = st.out(h->last_light_out, nA, z);
+}
+
+}  // namespace
+
+extern "C" {
+
+void emp_hazard_params_default(emp_hazard_params* p) {
+    if (!p) return;
+    p->tlight_threshold = 5.0;                                  // basic_agent.py:47
+    p->tlight_up_angle = 90.0;                                  // :245
+    p->walker_radius = 10.0;                                    // behavior_agent.py:239
+    p->walker_up_angle = 60.0;                                  // :249
+    p->reserved = 0;
+}
+
+int emp_agent_behave_hazards(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, int32_t W, int32_t max_world,
+                             int32_t max_path, int32_t max_other, int64_t tick0, const emp_behavior_io* a, emp_mem where,
+                             const emp_hazard_params* hp, int32_t max_light, int32_t max_walker, const emp_hazard_io* h) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    const bhv::BehaviorPlan plan = hz::plan_hazards(W, max_world, max_other, max_light, max_walker, max_path, 0, 1, tick0);
+    if (const int rc = behavior_checks(ctx, "emp_agent_behave_hazards", p, bp, a, max_other, where, plan)) return rc;
+    EMP_REQUIRE(ctx, a->forward && a->speed_kmh && a->control && a->mode && a->blocker && a->distance && a->ttc && a->target_speed_out,
+                "NULL array");
+    if (const int rc = hazard_checks(ctx, hp, h, max_light, max_walker)) return rc;
+    EMP_REQUIRE(ctx, h->cause && h->light_hit && h->walker_hit && h->walker_distance, "NULL array");
+    if (W == 0) return EMP_OK;
+    const size_t nA = (size_t)W * max_world;
+    EMP_STAGE(st, where);
+    const bool z = where == EMP_HOST;          // staged outputs start from 0; the caller's device memory is never filled
+    bhv::WorldIO io{};
+    hz::HazardIO hio{};
+    stage_world(st, a, (size_t)W, (size_t)max_world, (size_t)max_path, (size_t)max_other, tick0, &io);
+    io.forward = st.in(a->forward, nA * 2);
+    io.speed_kmh = st.in(a->speed_kmh, nA);
+    stage_behavior_state_out(st, a, nA, z, &io);
+    io.control = st.out(a->control, nA * 3, z);
+    io.mode = st.out(a->mode, nA, z);
+    io.blocker = st.out(a->blocker, nA, z);
+    io.distance = st.out(a->distance, nA, z);
+    io.ttc = st.out(a->ttc, nA, z);
+    io.target_out = st.out(a->target_speed_out, nA, z);
+    io.lat_error = st.out(a->lat_error, nA, z);
+    io.lon_command = st.out(a->lon_command, nA, z);
+    stage_hazards(st, h, (size_t)W, nA, (size_t)max_light, (size_t)max_walker, z, &hio);
+    hio.cause = st.out(h->cause, nA, z);
+    hio.light_hit = st.out(h->light_hit, nA, z);
+    hio.walker_hit = st.out(h->walker_hit, nA, z);
+    hio.walker_distance = st.out(h->walker_distance, nA, z);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "agent_behave_hazards", hz::agent_behave_hazards_kernel, dim3(plan.grid), dim3(plan.block), 0,
+                              agent_params(p), behavior_params(bp), hazard_params(hp), io, hio))
+        return rc;
+    return st.finish();
+}
+
+int emp_traffic_rollout_hazards(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp,
+                                int32_t W, int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every,
+                                int64_t tick0, const emp_behavior_io* a, emp_mem where, const emp_hazard_params* hp, int32_t max_light,
+                                int32_t max_walker, const emp_hazard_io* h) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, T >= 1, "T must be in [1, 65536]");
+    const bhv::BehaviorPlan plan = hz::plan_hazards(W, max_world, max_other, max_light, max_walker, max_path, T, log_every, tick0);
+    if (const int rc = behavior_checks(ctx, "emp_traffic_rollout_hazards", p, bp, a, max_other, where, plan)) return rc;
+    EMP_REQUIRE(ctx, vp != nullptr, "NULL parameter struct");
+    EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
+    EMP_REQUIRE(ctx, a->state_out && a->done_tick && a->mode_ticks && a->min_gap, "NULL array");
+    if (const int rc = hazard_checks(ctx, hp, h, max_light, max_walker)) return rc;
+    EMP_REQUIRE(ctx, h->cause_ticks && h->min_walker_gap, "NULL array");
+    if (W == 0) return EMP_OK;
+    const size_t nA = (size_t)W * max_world, n_log = plan.n_log;
+    EMP_STAGE(st, where);
+    const bool z = where == EMP_HOST;          // staged outputs start from 0; the caller's device memory is never filled
+    bhv::WorldIO io{};
+    hz::HazardIO hio{};
+    stage_world(st, a, (size_t)W, (size_t)max_world, (size_t)max_path, (size_t)max_other, tick0, &io);
+    io.T = T;
+    io.log_every = log_every;
+    stage_behavior_state_out(st, a, nA, z, &io);
+    io.state_out = st.out(a->state_out, nA * 6, z);
+    io.done_tick = st.out(a->done_tick, nA, z);
+    io.mode_ticks = st.out(a->mode_ticks, nA * bhv::kCountedModes, z);
+    io.min_gap = st.out(a->min_gap, nA, z);
+    io.actors_out = st.out(a->actors_out, nA * 4, z);
+    io.log_state = st.out(a->log_state, n_log * nA * 6, z);
+    io.log_control = st.out(a->log_control, n_log * nA * 3, z);
+    io.log_head = st.out(a->log_head, n_log * nA, z);
+    io.log_mode = st.out(a->log_mode, n_log * nA, z);
+    io.log_target = st.out(a->log_target, n_log * nA, z);
+    stage_hazards(st, h, (size_t)W, nA, (size_t)max_light, (size_t)max_walker, z, &hio);
+    hio.cause_ticks = st.out(h->cause_ticks, nA * hz::kCountedCauses, z);
+    hio.min_walker_gap = st.out(h->min_walker_gap, nA, z);
+    hio.log_cause = st.out(h->log_cause, n_log * nA, z);
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch(ctx, "traffic_rollout_hazards", hz::traffic_rollout_hazards_kernel, dim3(plan.grid), dim3(plan.block), 0,
+                              agent_params(p), behavior_params(bp), hazard_params(hp), vehicle_params(vp), (int)nA, io, hio))
         return rc;
     return st.finish();
 }

@@ -42,6 +42,15 @@ EMP_HD bool within(const Params& p, double th, double c, double s, double tvx, d
     return 0.0 < angle && angle < p.up_angle;           // a NaN angle (a NaN norm passes both tests above) is no hit
 }
 
+// The same arithmetic with the cone as an argument (emp_hazard_core.h: 90 degrees for a traffic light, 60 for a walker)
+EMP_HD bool within(double up_angle, double th, double c, double s, double tvx, double tvy) {
+    const double norm = sqrt(tvx * tvx + tvy * tvy);
+    if (norm < 0.001) return true;
+    if (norm > th) return false;
+    const double angle = acos(agt::clip1((c * tvx + s * tvy) / norm)) * kRadToDeg;
+    return 0.0 < angle && angle < up_angle;
+}
+
 // The vehicles an agent may see, as the start of the tick left them.  Agents: n_agents slots of ax / ay / akmh / aext / akey (the
 // agent's own slot `self` is passed over); others: n_others rows of other[5] = x, y, vx, vy, half extent with keys okey, moved to
 // time tau.  Any memory: LDS in the kernels.

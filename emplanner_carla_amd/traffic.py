@@ -131,6 +131,11 @@ class BehaviorTraffic(TrafficAgents):
         self.tick = 0                  # ticks done: the clock of the others
         self.mode = self._zeros((W, N), np.int32)
         self.target_speed = self._zeros((W, N), np.float64)
+        self.lights = self.walkers = None
+        self.hazard = None             # emp_hazard_params, made when lights or walkers are first used
+        self.last_light = self._zeros((W, N), np.int32)       # the light that holds each agent (_last_traffic_light), -1 for none
+        self._fill(self.last_light, -1)
+        self.cause = self._zeros((W, N), np.int32)
 
     def _fill(self, dst, value):
         if self._torch:
@@ -174,11 +179,65 @@ class BehaviorTraffic(TrafficAgents):
         self.others = (n, self._own(other, np.float64), self._own(other_lane, np.int32))
         self.tick = 0
 
+    def set_lights(self, light=None, light_lane=None, light_cycle=None, n_light=None):
+        """Traffic lights: light (W, L, 4) = x, y, dx, dy, the location and forward vector of the lane waypoint under each light's
+        trigger volume; light_lane (W, L) that waypoint's lane key (a light that governs several keys is listed once per key);
+        light_cycle (W, L, 3) int32 = period, red_from, red_to in ticks: red while red_from <= tick mod period < red_to, on the
+        fleet's clock ``tick``.  n_light (W,) (None: all L).  No agent is held by a light afterwards.  None removes them."""
+        self._fill(self.last_light, -1)
+        if light is None:
+            self.lights = None
+            return
+        W, K = int(light.shape[0]), int(light.shape[1])
+        if W != self.W or tuple(light.shape[2:]) != (4,) or not K <= L.HAZARD_MAX:
+            raise ValueError(f"light must be (W, L, 4) with L <= {L.HAZARD_MAX}")
+        n = self._zeros((W,), np.int32)
+        self._fill(n, K if n_light is None else n_light)
+        self.lights = (n, self._own(light, np.float64), self._own(light_lane, np.int32), self._own(light_cycle, np.int32))
+
+    def set_walkers(self, walker=None, walker_lane=None, n_walker=None):
+        """Pedestrians: walker (W, K, 5) = x, y, world-frame vx, vy, half extent, as they stand at the fleet's tick 0 (they move by
+        the clock ``tick``, as the others do); walker_lane (W, K) their lane keys; n_walker (W,) (None: all K).  None removes them."""
+        if walker is None:
+            self.walkers = None
+            return
+        W, K = int(walker.shape[0]), int(walker.shape[1])
+        if W != self.W or tuple(walker.shape[2:]) != (5,) or not K <= L.HAZARD_MAX:
+            raise ValueError(f"walker must be (W, K, 5) with K <= {L.HAZARD_MAX}")
+        n = self._zeros((W,), np.int32)
+        self._fill(n, K if n_walker is None else n_walker)
+        self.walkers = (n, self._own(walker, np.float64), self._own(walker_lane, np.int32))
+
+    def _hazards(self):
+        return self.lights is not None or self.walkers is not None
+
+    def causes(self):
+        """(W, N) int32 EMP_HZ_* of the last ``run_step``: why an agent made an emergency stop (light, walker, vehicle), 0 where it
+        made none.  (A rollout reports ``cause_ticks`` and ``log_cause`` instead.)  Without lights and walkers: EMP_HZ_VEHICLE where
+        the mode is EMERGENCY."""
+        if self._hazards():
+            return self.cause
+        return (self.mode == L.BHV_EMERGENCY) * L.HZ_VEHICLE
+
+    def _hazard_params(self):
+        if self.hazard is None:
+            self.hazard = api.hazard_params()
+        return self.hazard
+
     def run_step(self):
         """ref BehaviorAgent.run_step for every agent: one tick's controls (W, N, 3).  The agent state advances, the vehicles do
         not move, the others' clock stands."""
         v = self._world
         obs = self.planner.agent_observe(self.state)
+        if self._hazards():
+            r = self.planner.agent_behave_hazards(self.params, self.behavior, self._hazard_params(), self.n_world, v(self.paths),
+                                                  v(self.n_path), self.lane, v(self.state), v(obs.forward), v(obs.speed_kmh),
+                                                  self.speed_limit, self.extent, *self._state_args(), self.last_light,
+                                                  lights=self.lights, walkers=self.walkers,
+                                                  others=self.others, tick0=self.tick, in_place=True)
+            self._adopt(r)
+            self.mode, self.target_speed, self.cause = r.mode, r.target_speed, r.cause
+            return r.control
         r = self.planner.agent_behave(self.params, self.behavior, self.n_world, v(self.paths), v(self.n_path), self.lane, v(self.state),
                                       v(obs.forward), v(obs.speed_kmh), self.speed_limit, self.extent, *self._state_args(),
                                       others=self.others, tick0=self.tick, in_place=True)
@@ -189,6 +248,14 @@ class BehaviorTraffic(TrafficAgents):
     def rollout(self, T, log_every=None):
         """T ticks of run_step + the vehicle model in one launch; state, agent state and the others' clock advance."""
         v = self._world
+        if self._hazards():
+            r = self.planner.traffic_rollout_hazards(self.params, self.behavior, self._hazard_params(), self.vp, self.n_world, v(self.paths),
+                                                     v(self.n_path), self.lane, v(self.state), self.speed_limit, self.extent,
+                                                     *self._state_args(), self.last_light, T, lights=self.lights, walkers=self.walkers,
+                                                     others=self.others, tick0=self.tick, log_every=log_every, in_place=True)
+            self._adopt(r)
+            self.tick += int(T)
+            return r
         r = self.planner.traffic_rollout(self.params, self.behavior, self.vp, self.n_world, v(self.paths), v(self.n_path), self.lane,
                                          v(self.state), self.speed_limit, self.extent, *self._state_args(), T, others=self.others,
                                          tick0=self.tick, log_every=log_every, in_place=True)

@@ -1463,7 +1463,8 @@ int emp_agent_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_vehicle
  * (_vehicle_obstacle_detected, :84-138, with is_within_distance, agents/tools/misc.py:66-103), the time-to-collision rule
  * (car_following_manager, :253-294) and the emergency stop (:364-375), on top of the local planner and PID pair of the section
  * above, whose rule (one "agent tick" below) is called unchanged.
- * NOT reproduced: traffic lights; pedestrians; tailgating and lane changes (the law is that of a road whose markings allow none:
+ * NOT reproduced: traffic lights and pedestrians (the section after this one puts them in front of this rule: emp_agent_behave_hazards);
+ * tailgating and lane changes (the law is that of a road whose markings allow none:
  * _tailgating then only looks behind); the junction branch (:347-352: it needs RoadOptions the router does not produce);
  * BasicAgent.run_step; per-road speed limits (the limit is per agent and constant over a call).
  * Stand-ins for CARLA's map: map.get_waypoint(location) compares (road_id, lane_id); here every path waypoint carries an int32
@@ -1594,6 +1595,108 @@ int emp_agent_behave(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior
 int emp_traffic_rollout(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp, int32_t W,
                         int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every, int64_t tick0,
                         const emp_behavior_io* io, emp_mem where);
+
+/* ---- traffic that stops for red lights and pedestrians (new with ABI 13's library; EMP_ABI_VERSION is unchanged) ----------------
+ * ref: the two checks BehaviorAgent.run_step runs before car-following on every tick (agents/navigation/behavior_agent.py:312-328):
+ * red lights (traffic_light_manager, :140-148 -> BasicAgent._affected_by_traffic_light, agents/navigation/basic_agent.py:201-249,
+ * with its sticky _last_traffic_light) and pedestrians (pedestrian_avoid_manager, :225-251), in front of the rule of the section
+ * above, which is called unchanged.  emp_agent_behave and emp_traffic_rollout stay what they are; these calls are theirs plus
+ * lights and walkers.
+ * NOT reproduced: the lane-change variants of the walker detector (:241-246); ignore_traffic_lights; stop signs; and, as before,
+ * the junction branch, tailgating and lane changes.
+ * Stand-ins for CARLA's map, beside those of the section above: the ego's lane waypoint (map.get_waypoint(ego location)) has the
+ * key key_cur = lane[max(head - 1, 0)], the location path[max(head - 1, 0)] x, y, and a forward vector ve that is the chord
+ * path[i0 + 1] - path[i0], i0 = min(max(head - 1, 0), n_path - 2); (0, 0) if n_path == 1.  Only the sign of a dot product with ve is
+ * used, so it is not normalised.
+ *
+ * Worlds as above.  A world also holds
+ *   n_light[w] lights (clamped to [0, max_light], max_light <= EMP_HAZARD_MAX): light [W][max_light][4] = x, y, dx, dy, the location
+ *     and forward vector of the map waypoint under the light's trigger volume (get_waypoint(get_trafficlight_trigger_location(l)));
+ *     light_lane [W][max_light] that waypoint's key (the reference compares road_id only; a light that governs several lane keys is
+ *     listed once per key); light_cycle [W][max_light][3] = period, red_from, red_to in ticks.  The light IS RED at tick index k iff
+ *     period >= 1 and red_from <= (k mod period) < red_to, in int64 arithmetic: nothing accumulates;
+ *   n_walker[w] walkers (clamped to [0, max_walker], max_walker <= EMP_HAZARD_MAX): walker [W][max_walker][5] = x, y, world-frame
+ *     vx, vy, half extent, walker_lane [W][max_walker] their keys.  At tick index k a walker stands at x + vx * (k * dt),
+ *     y + vy * (k * dt): the clock rule of `other`.
+ * Per agent: last_light [A] int32 in and out, the index of the light that holds the agent (_last_traffic_light), -1 for none; any
+ * value outside [0, n_light) counts as -1.
+ *
+ * One tick for agent i at tick index k = tick0 + t.  Rounding as in the section above; libm enters through acos only.
+ *   0. head == n_path after the clamps: the DONE tick of the section above.  (The reference raises there, before it looks at a
+ *      light.)  last_light_out = last_light as given, cause 0, light_hit = walker_hit = -1, walker_distance = +inf.
+ *   1. Red lights.  If last_light >= 0 and that light is red at k: AFFECTED by it, no geometry is looked at.  If it is not red:
+ *      last_light = -1.  Then scan the lights in index order, THE FIRST HIT WINS.  A light is passed over if its key is below 0 or
+ *      differs from key_cur (key_next plays no part); if ve.x * dx + ve.y * dy < 0; if it is not red at k.  Otherwise it is a hit iff
+ *      is_within_distance(light waypoint, vehicle, tlight_threshold, [0, tlight_up_angle]): tv = (x - xi, y - yi),
+ *      norm = sqrt(tvx * tvx + tvy * tvy); norm < 0.001: a hit; norm > tlight_threshold: no hit; otherwise
+ *      angle = acos(clip((c * tvx + s * tvy) / norm)) * (180 / pi), a hit iff 0 < angle < tlight_up_angle.  A hit sets last_light.
+ *      AFFECTED is emergency_stop(): mode EMERGENCY, cause EMP_HZ_LIGHT, control (0, 0, emergency_brake); head, both deques and
+ *      past_steer stay, lat_error = lon_command = 0, target_speed_out = speed_limit, distance = ttc = +inf, blocker = -1.
+ *      light_hit is the light's index (the sticky one too), -1 if none.
+ *   2. Walkers, in index order, THE FIRST HIT WINS.  A walker at (wx, wy) (the clock rule) is a hit iff all of
+ *      (a) sqrt((ex * ex + ey * ey) + 0) < walker_radius with (ex, ey) = (wx - px, wy - py), (px, py) the ego's lane waypoint
+ *          (:238-239).  Unlike the 45 m vehicle filter this one decides: the detector's own range is
+ *          max(min_proximity_threshold, speed_limit / 3) >= walker_radius for the three behaviours;
+ *      (b) its key is >= 0 and equals key_cur or key_next;
+ *      (c) the `within` of step 3 above with th = max(min_proximity_threshold, speed_limit / 3), tv = (wx - xi, wy - yi) and the
+ *          cone 0 < angle < walker_up_angle.
+ *      On a hit d = (sqrt((dx * dx + dy * dy) + 0) + 2^-52) - extent_walker - extent_i with (dx, dy) = (xi - wx, yi - wy);
+ *      walker_hit and walker_distance = d are reported.  d < braking_distance: emergency_stop() as in step 1, cause EMP_HZ_WALKER.
+ *      Otherwise the walker is IGNORED, as in the reference: the tick goes on as if no walker were there.
+ *   3. Vehicles: the rule of the section above, unchanged.  Its EMERGENCY has cause EMP_HZ_VEHICLE; every other mode has cause 0.
+ *
+ * emp_agent_behave_hazards / emp_traffic_rollout_hazards take the arguments of emp_agent_behave / emp_traffic_rollout, then the
+ * hazard parameters, max_light, max_walker and emp_hazard_io, which serves both calls.  Everything the counterparts return comes
+ * back as they define it.  The rollout: tick t is emp_agent_observe, emp_agent_behave_hazards (tick0 + t), emp_vehicle_step; EVERY
+ * OUTPUT AND LOG ROW EQUALS, BIT FOR BIT, T iterations of those three calls, and a rollout cut in two, with tick0 advanced and
+ * last_light carried, resumes bit for bit.  cause_ticks [A][3] counts the EMERGENCY ticks by light, walker and vehicle;
+ * min_walker_gap [A] is the smallest walker_distance seen (ignored walkers too), +inf if none; log_cause is laid out as log_mode.
+ *   emp_agent_behave_hazards uses: last_light, last_light_out (may alias), cause, light_hit, walker_hit, walker_distance; optional
+ *     n_light / light / light_lane / light_cycle (all four, or max_light == 0), n_walker / walker / walker_lane (all three, or
+ *     max_walker == 0).
+ *   emp_traffic_rollout_hazards uses: last_light, last_light_out, cause_ticks, min_walker_gap; optional lights and walkers as
+ *     above, log_cause.
+ * Refused before any launch (EMP_ERR_INVALID): everything the counterpart refuses; max_light or max_walker outside
+ * [0, EMP_HAZARD_MAX]; a NULL required pointer; reserved != 0.  W == 0: EMP_OK. */
+#define EMP_HAZARD_MAX 64
+#define EMP_HZ_NONE 0
+#define EMP_HZ_LIGHT 1
+#define EMP_HZ_WALKER 2
+#define EMP_HZ_VEHICLE 3
+typedef struct emp_hazard_params {
+    double tlight_threshold;               /* 5 m (BasicAgent._base_tlight_threshold) */
+    double tlight_up_angle;                /* 90 degrees */
+    double walker_radius;                  /* 10 m */
+    double walker_up_angle;                /* 60 degrees */
+    int32_t reserved;                      /* must be 0 */
+} emp_hazard_params;
+void emp_hazard_params_default(emp_hazard_params* p);
+typedef struct emp_hazard_io {
+    const int32_t* n_light;                /* [W] */
+    const double* light;                   /* [W][max_light][4] */
+    const int32_t* light_lane;             /* [W][max_light] */
+    const int32_t* light_cycle;            /* [W][max_light][3] */
+    const int32_t* n_walker;               /* [W] */
+    const double* walker;                  /* [W][max_walker][5] */
+    const int32_t* walker_lane;            /* [W][max_walker] */
+    const int32_t* last_light;             /* [A] */
+    int32_t* last_light_out;               /* [A] */
+    int32_t* cause;                        /* [A] (behave) */
+    int32_t* light_hit;                    /* [A] (behave) */
+    int32_t* walker_hit;                   /* [A] (behave) */
+    double* walker_distance;               /* [A] (behave) */
+    int32_t* cause_ticks;                  /* [A][3] (rollout) */
+    double* min_walker_gap;                /* [A] (rollout) */
+    int32_t* log_cause;                    /* optional log (rollout) */
+    int32_t reserved;                      /* must be 0 */
+} emp_hazard_io;
+int emp_agent_behave_hazards(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, int32_t W, int32_t max_world,
+                             int32_t max_path, int32_t max_other, int64_t tick0, const emp_behavior_io* io, emp_mem where,
+                             const emp_hazard_params* hp, int32_t max_light, int32_t max_walker, const emp_hazard_io* hio);
+int emp_traffic_rollout_hazards(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp,
+                                int32_t W, int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every,
+                                int64_t tick0, const emp_behavior_io* io, emp_mem where, const emp_hazard_params* hp, int32_t max_light,
+                                int32_t max_walker, const emp_hazard_io* hio);
 
 #ifdef __cplusplus
 }
