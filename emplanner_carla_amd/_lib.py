@@ -204,6 +204,36 @@ class HazardIO(C.Structure):
         "light_hit", "walker_hit", "walker_distance", "cause_ticks", "min_walker_gap", "log_cause")] + [("reserved", C.c_int32)]
 
 
+WX_ACT_TRUNCATED, WX_NOT_LISTED, WX_NO_WORLD = 1, 2, 4       # EMP_WX_*: bits of emp_world_exchange's wx_status
+
+
+class WorldExchangeIO(C.Structure):
+    """emp_world_exchange_io: both fleets' states in, who sees whom out."""
+    _fields_ = [(n, _vp) for n in (
+        "n_world", "agent_state", "ego_off", "ego_state", "ego_extent", "global_path", "n_global", "ego_lane", "pre_match_index",
+        "actors", "n_act", "other", "other_lane", "n_other", "wx_status")] + [("reserved", C.c_int32)]
+
+
+class WorldParams(C.Structure):
+    """emp_world_params: the traffic's sizes, the agents' clock and the exchange's two settings in emp_world_drive."""
+    _fields_ = [(n, C.c_int32) for n in ("W", "max_world", "max_path", "max_other", "max_light", "max_walker", "Ta", "lane_window",
+                                         "see_egos", "reserved")] + [("atick0", C.c_int64)]
+
+
+class WorldIO(C.Structure):
+    """emp_world_io: emp_drive_timed_io without actors and n_act, the exchange's ego arrays, the traffic's two structs, the logs."""
+    _fields_ = [(n, _vp) for n in (
+        "global_path", "n_global", "state", "accel", "pre_match_index", "track", "track_len", "held", "t0", "profile", "cursor",
+        "speed_held", "ego_off", "ego_extent", "ego_lane",
+        "state_out", "accel_out", "actors_out", "pre_match_index_out", "track_out", "track_len_out", "held_out", "profile_out",
+        "cursor_out", "speed_held_out",
+        "log_state", "log_plan_status", "log_roll_status", "log_held", "log_counts", "log_traj", "log_traj_len", "log_speed_status",
+        "log_speed_held", "log_tgt_status", "log_cursor", "log_profile")] + \
+        [("agents", C.POINTER(BehaviorIO)), ("hazards", C.POINTER(HazardIO))] + \
+        [(n, _vp) for n in ("log_wx_status", "log_n_act", "log_agent_state", "log_agent_status", "log_done_tick", "log_mode_ticks",
+                            "log_cause_ticks", "log_min_gap", "log_min_walker_gap")] + [("reserved", C.c_int32)]
+
+
 class CycleIO(C.Structure):
     _fields_ = [(n, _vp) for n in (
         "ref_line", "n_ref", "origin_xy", "start_xy", "start_v", "start_a", "obs_xy", "n_obs",
@@ -374,6 +404,16 @@ PROTOTYPES = {
     "emp_traffic_rollout_hazards": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(BehaviorParams), C.POINTER(VehicleParams), _i32, _i32,
                                               _i32, _i32, _i32, _i32, C.c_int64, C.POINTER(BehaviorIO), C.c_int, C.POINTER(HazardParams),
                                               _i32, _i32, C.POINTER(HazardIO)]),
+    "emp_world_exchange": (C.c_int, [_vp] + [_i32] * 8 + [C.POINTER(WorldExchangeIO), C.c_int]),
+    "emp_traffic_rollout_epoch": (C.c_int, [_vp, C.POINTER(AgentParams), C.POINTER(BehaviorParams), C.POINTER(VehicleParams), _i32, _i32,
+                                            _i32, _i32, _i32, _i32, C.c_int64, C.POINTER(BehaviorIO), C.c_int, C.POINTER(HazardParams),
+                                            _i32, _i32, C.POINTER(HazardIO), C.c_int64]),
+    "emp_world_params_default": (None, [C.POINTER(WorldParams)]),
+    "emp_world_drive": (C.c_int, [_vp, C.POINTER(DpParams), C.POINTER(QpParams), C.POINTER(SmoothParams), C.POINTER(SpeedDpParams),
+                                  C.POINTER(SpeedQpParams), C.POINTER(DriveParams), C.POINTER(DriveTimedParams), _i32,
+                                  C.POINTER(MpcParams), C.POINTER(PidParams), C.POINTER(VehicleParams), C.POINTER(AgentParams),
+                                  C.POINTER(BehaviorParams), C.POINTER(VehicleParams), C.POINTER(HazardParams), C.POINTER(WorldParams)]
+                        + [_i32] * 9 + [_vp, C.POINTER(WorldIO), C.c_int]),
 }
 
 _lib = None

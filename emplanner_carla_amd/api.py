@@ -359,6 +359,54 @@ class TimedDriveResult(DriveResult):
 
 
 @dataclass
+class WorldExchangeResult:
+    """Outputs of ``Planner.world_exchange``: who sees whom at the start of a period."""
+    actors: object        # (B, max_act, 4) ``drive_timed``'s actors: the world's live agents, then (see_egos) its other egos
+    n_act: object         # (B,) int32
+    other: object         # (W, max_other, 5) ``traffic_rollout_epoch``'s others: the world's egos; None with max_other == 0
+    other_lane: object    # (W, max_other) int32 the lane key each ego shows
+    n_other: object       # (W,) int32
+    wx_status: object     # (B,) int32 WX_ACT_TRUNCATED | WX_NOT_LISTED | WX_NO_WORLD
+
+
+@dataclass
+class WorldTrafficResult:
+    """The traffic's side of ``Planner.world_drive``: the agents' state after K periods and the last period's rollout outputs."""
+    state: object         # (W, N, 6)
+    head: object
+    past_steer: object
+    lon_err: object
+    n_lon: object
+    lat_err: object
+    n_lat: object
+    last_light: object    # (W, N) int32
+    status: object        # (W, N) int32, the last period's, as the five below
+    done_tick: object
+    mode_ticks: object    # (W, N, 5) int32
+    min_gap: object       # (W, N)
+    actors: object        # (W, N, 4) observe of the final state
+    cause_ticks: object   # (W, N, 3) int32
+    min_walker_gap: object  # (W, N)
+
+
+@dataclass
+class WorldDriveResult:
+    """Outputs of ``Planner.world_drive``: the egos' ``TimedDriveResult``, the traffic, and the world's per-period logs (None
+    without logs), each row that period's call output."""
+    egos: object                # TimedDriveResult (log_profile is not kept)
+    traffic: object             # WorldTrafficResult
+    log_wx_status: object       # (K, B) int32
+    log_n_act: object           # (K, B) int32
+    log_agent_state: object     # (K, W, N, 6) the agents' state at the start of each period
+    log_agent_status: object    # (K, W, N) int32
+    log_done_tick: object       # (K, W, N) int32
+    log_mode_ticks: object      # (K, W, N, 5) int32
+    log_cause_ticks: object     # (K, W, N, 3) int32
+    log_min_gap: object         # (K, W, N)
+    log_min_walker_gap: object  # (K, W, N)
+
+
+@dataclass
 class PidResult:
     command: object      # (B,) K_P e + K_I integral + K_D derivative
     err: object          # (B, 60) the error buffer after the call, oldest first; entries past n_err are 0
@@ -1343,10 +1391,10 @@ class Planner:
 
     def traffic_rollout_hazards(self, p, bp, hp, vp: VehicleParams, n_world, path, n_path, lane, state, speed_limit, extent, head,
                                 past_steer, lon_err, n_lon, lat_err, n_lat, last_light, T, lights=None, walkers=None, others=None,
-                                tick0=0, log_every=None, in_place=False) -> HazardRolloutResult:
+                                tick0=0, log_every=None, in_place=False, other_tick0=None) -> HazardRolloutResult:
         """``traffic_rollout`` with red lights and pedestrians: T ticks of [agent_observe, agent_behave_hazards, vehicle_step(vp)] in
         ONE kernel launch, bit-identical to the chain of the 3 T calls; cut in two, with ``tick0`` advanced and ``last_light``
-        carried, it resumes bit for bit.  Arrays as ``agent_behave_hazards``."""
+        carried, it resumes bit for bit.  Arrays as ``agent_behave_hazards``.  (other_tick0: ``traffic_rollout_epoch``.)"""
         T = int(T)
         every = 1 if log_every is None else int(log_every)
         n_log = (T + every - 1) // every if log_every is not None and every >= 1 and T >= 1 else None
@@ -1370,9 +1418,139 @@ class Planner:
             lm, io.log_mode = a.out((n_log, W, N), np.int32)
             lt, io.log_target = a.out((n_log, W, N), np.float64)
             lcs, h.log_cause = a.out((n_log, W, N), np.int32)
-        self._check(self._lib.emp_traffic_rollout_hazards(self._h, C.byref(p), C.byref(bp), C.byref(vp), W, N, M, K, T, every, int(tick0),
-                                                          C.byref(io), a.where, C.byref(hp), ML, MW, C.byref(h)))
+        if other_tick0 is None:
+            self._check(self._lib.emp_traffic_rollout_hazards(self._h, C.byref(p), C.byref(bp), C.byref(vp), W, N, M, K, T, every,
+                                                              int(tick0), C.byref(io), a.where, C.byref(hp), ML, MW, C.byref(h)))
+        else:
+            self._check(self._lib.emp_traffic_rollout_epoch(self._h, C.byref(p), C.byref(bp), C.byref(vp), W, N, M, K, T, every,
+                                                            int(tick0), C.byref(io), a.where, C.byref(hp), ML, MW, C.byref(h),
+                                                            int(other_tick0)))
         return HazardRolloutResult(so, *outs, st, dn, mt, mg, act, ls, lc, lh, lm, lt, ll, ct, wg, lcs)
+
+    def traffic_rollout_epoch(self, p, bp, hp, vp: VehicleParams, n_world, path, n_path, lane, state, speed_limit, extent, head,
+                              past_steer, lon_err, n_lon, lat_err, n_lat, last_light, T, other_tick0, lights=None, walkers=None,
+                              others=None, tick0=0, log_every=None, in_place=False) -> HazardRolloutResult:
+        """``traffic_rollout_hazards`` with the others' own epoch: ``others`` holds their rows as they were at tick index
+        ``other_tick0`` (0 <= other_tick0 <= tick0), so at tick k they stand at x + vx * ((k - other_tick0) * dt), while lights
+        and walkers stay on k.  ``world_exchange``'s others with other_tick0 = tick0 are the egos as they are now, and the
+        fleet's tick clock is left alone.  other_tick0 = 0 is ``traffic_rollout_hazards`` bit for bit."""
+        return self.traffic_rollout_hazards(p, bp, hp, vp, n_world, path, n_path, lane, state, speed_limit, extent, head, past_steer,
+                                            lon_err, n_lon, lat_err, n_lat, last_light, T, lights=lights, walkers=walkers,
+                                            others=others, tick0=tick0, log_every=log_every, in_place=in_place,
+                                            other_tick0=int(other_tick0))
+
+    # ---- one world for a planning fleet and reacting traffic ------------------------------------------------------------------------
+    def world_exchange(self, n_world, agent_state, ego_off, ego_state, ego_extent, global_path, n_global, ego_lane, pre_match_index,
+                       max_act: int, max_other: int, see_egos=False, lane_window=50) -> WorldExchangeResult:
+        """Who sees whom in W worlds: world w holds the agents of n_world (W,) / agent_state (W, N, 6) and the egos
+        ego_off[w] <= b < ego_off[w + 1] (ego_off (W + 1,) int32, non-decreasing) of ego_state (B, 6).  -> actors (B, max_act, 4) /
+        n_act (B,) for ``drive_timed``: ``agent_observe``'s rows of the world's live agents, then (see_egos) of its other egos;
+        other (W, max_other, 5) / other_lane / n_other for ``traffic_rollout_epoch``: each ego's row with ego_extent (B,) and the
+        lane key it shows - ego_lane (B, G) (``RouteResult.lane_key(graph)``) at the global waypoint nearest to it within
+        lane_window waypoints of pre_match_index; wx_status (B,) WX_* bits.  An ego in no world sees nothing and is not seen."""
+        a = self._args(agent_state, ego_state, global_path)
+        W, N = int(agent_state.shape[0]), int(agent_state.shape[1])
+        B, G = int(global_path.shape[0]), int(global_path.shape[1])
+        ma, mo = int(max_act), int(max_other)
+        io = L.WorldExchangeIO()
+        io.n_world, io.agent_state = a.inp(n_world, np.int32, (W,)), a.inp(agent_state, np.float64, (W, N, 6))
+        io.ego_off, io.ego_state = a.inp(ego_off, np.int32, (W + 1,)), a.inp(ego_state, np.float64, (B, 6))
+        io.ego_extent, io.global_path = a.inp(ego_extent, np.float64, (B,)), a.inp(global_path, np.float64, (B, G, 4))
+        io.n_global, io.ego_lane = a.inp(n_global, np.int32, (B,)), a.inp(ego_lane, np.int32, (B, G))
+        io.pre_match_index = a.inp(pre_match_index, np.int32, (B,))
+        act, io.actors = a.out((B, ma, 4), np.float64)
+        na, io.n_act = a.out((B,), np.int32)
+        oth = okey = no = None
+        if mo > 0:
+            oth, io.other = a.out((W, mo, 5), np.float64)
+            okey, io.other_lane = a.out((W, mo), np.int32)
+            no, io.n_other = a.out((W,), np.int32)
+        ws, io.wx_status = a.out((B,), np.int32)
+        io.reserved = 0
+        self._check(self._lib.emp_world_exchange(self._h, W, N, B, G, ma, mo, int(lane_window), int(see_egos), C.byref(io), a.where))
+        return WorldExchangeResult(act, na, oth, okey, no, ws)
+
+    def world_drive(self, p: DpParams, q: QpParams, sp: SmoothParams, sdp: SpeedDpParams, sqp: SpeedQpParams, dp: DriveParams,
+                    lat: MpcParams, pid: PidParams, vp: VehicleParams, ap, bp, hp, avp: VehicleParams,
+                    global_path, n_global, state, accel, pre_match_index, track, track_len, held, t0, profile, cursor, speed_held,
+                    target_speed, ego_off, ego_extent, ego_lane,
+                    n_world, path, n_path, lane, agent_state, speed_limit, extent, head, past_steer, lon_err, n_lon, lat_err, n_lat,
+                    last_light, K, T, Ta, max_obs: int, max_act: int, max_other: int, max_dyn: int = 8, tick0=0, atick0=0,
+                    lights=None, walkers=None, see_egos=False, lane_window=50, tp: DriveTimedParams = None, max_pts=None,
+                    lateral="mpc", logs=True, in_place=False) -> WorldDriveResult:
+        """K periods of a planning fleet and reacting traffic in ONE call, nothing leaving the device in between: per period
+        ``world_exchange``, the period of ``drive_timed`` on the exchanged actors at ego tick tick0 + k * T, and
+        ``traffic_rollout_epoch`` of Ta agent ticks at atick0 + k * Ta with the exchanged others (other_tick0 = that tick).
+        T * vp.dt must equal Ta * ap.dt.  The egos' arrays as ``drive_timed`` (without actors and n_act) and ``world_exchange``;
+        the agents' as ``traffic_rollout_hazards`` (ap, bp, hp, avp: its p, bp, hp, vp).  in_place=True updates both fleets'
+        state where it lives.  Equals the chain of the three calls bit for bit; resumes bit for bit with tick0 advanced by K * T
+        and atick0 by K * Ta."""
+        law = _lateral_law(lateral)
+        K, T = int(K), int(T)
+        tp = tp if tp is not None else drive_timed_params()
+        a = self._args(global_path, state, track, profile, path, agent_state)
+        B, G, A = int(global_path.shape[0]), int(global_path.shape[1]), int(max_act)
+        M, N = (int(max_pts) if max_pts else max_path_points(p)), L.TIMED_POINTS
+        io = L.WorldIO()
+        for name, src, shape, dt in (("global_path", global_path, (B, G, 4), np.float64), ("n_global", n_global, (B,), np.int32),
+                                     ("state", state, (B, 6), np.float64), ("accel", accel, (B, 2), np.float64),
+                                     ("pre_match_index", pre_match_index, (B,), np.int32), ("track", track, (B, M + 1, 4), np.float64),
+                                     ("track_len", track_len, (B,), np.int32), ("held", held, (B,), np.int32),
+                                     ("t0", t0, (B,), np.float64), ("profile", profile, (B, 7, N), np.float64),
+                                     ("cursor", cursor, (B,), np.int32), ("speed_held", speed_held, (B,), np.int32),
+                                     ("ego_extent", ego_extent, (B,), np.float64), ("ego_lane", ego_lane, (B, G), np.int32)):
+            setattr(io, name, a.inp(src, dt, shape))
+        tsp = a.inp(target_speed, np.float64, (B,))
+        res = {}
+        for name, src, shape, dt in (("state", state, (B, 6), np.float64), ("accel", accel, (B, 2), np.float64),
+                                     ("actors", None, (B, A, 4), np.float64), ("pre_match_index", pre_match_index, (B,), np.int32),
+                                     ("track", track, (B, M + 1, 4), np.float64), ("track_len", track_len, (B,), np.int32),
+                                     ("held", held, (B,), np.int32), ("profile", profile, (B, 7, N), np.float64),
+                                     ("cursor", cursor, (B,), np.int32), ("speed_held", speed_held, (B,), np.int32)):
+            res[name], ptr = a.out(shape, dt, into=_in_place(src, dt, in_place and src is not None))
+            setattr(io, name + "_out", ptr)
+        for name, shape, dt in (("log_state", (K, B, 6), np.float64), ("log_plan_status", (K, B), np.int32),
+                                ("log_roll_status", (K, B), np.int32), ("log_held", (K, B), np.int32),
+                                ("log_counts", (K, B, 2), np.int32), ("log_traj", (K, B, M + 1, 4), np.float64),
+                                ("log_traj_len", (K, B), np.int32), ("log_speed_status", (K, B), np.int32),
+                                ("log_speed_held", (K, B), np.int32), ("log_tgt_status", (K, B), np.int32),
+                                ("log_cursor", (K, B), np.int32)):
+            res[name] = None
+            if logs and K >= 1:
+                res[name], ptr = a.out(shape, dt)
+                setattr(io, name, ptr)
+        # the traffic, as traffic_rollout_hazards stages it
+        bio, W, NW, MP, _, outs = self._behavior_io(a, n_world, path, n_path, lane, agent_state, speed_limit, extent,
+                                                    (head, past_steer, lon_err, n_lon, lat_err, n_lat), None, in_place)
+        io.ego_off = a.inp(ego_off, np.int32, (W + 1,))
+        tr = dict(zip(("head", "past_steer", "lon_err", "n_lon", "lat_err", "n_lat"), outs))
+        tr["state"], bio.state_out = a.out((W, NW, 6), np.float64, into=_in_place(agent_state, np.float64, in_place))
+        tr["status"], bio.status = a.out((W, NW), np.int32)
+        tr["done_tick"], bio.done_tick = a.out((W, NW), np.int32)
+        tr["mode_ticks"], bio.mode_ticks = a.out((W, NW, 5), np.int32)
+        tr["min_gap"], bio.min_gap = a.out((W, NW), np.float64)
+        tr["actors"], bio.actors_out = a.out((W, NW, 4), np.float64)
+        h, ML, MW, tr["last_light"] = self._hazard_io(a, W, NW, last_light, lights, walkers, in_place)
+        tr["cause_ticks"], h.cause_ticks = a.out((W, NW, 3), np.int32)
+        tr["min_walker_gap"], h.min_walker_gap = a.out((W, NW), np.float64)
+        io.agents, io.hazards = C.pointer(bio), C.pointer(h)
+        wl = {}
+        for name, shape, dt in (("log_wx_status", (K, B), np.int32), ("log_n_act", (K, B), np.int32),
+                                ("log_agent_state", (K, W, NW, 6), np.float64), ("log_agent_status", (K, W, NW), np.int32),
+                                ("log_done_tick", (K, W, NW), np.int32), ("log_mode_ticks", (K, W, NW, 5), np.int32),
+                                ("log_cause_ticks", (K, W, NW, 3), np.int32), ("log_min_gap", (K, W, NW), np.float64),
+                                ("log_min_walker_gap", (K, W, NW), np.float64)):
+            wl[name] = None
+            if logs and K >= 1:
+                wl[name], ptr = a.out(shape, dt)
+                setattr(io, name, ptr)
+        io.reserved = 0
+        wp = L.WorldParams(W, NW, MP, int(max_other), ML, MW, int(Ta), int(lane_window), int(see_egos), 0, int(atick0))
+        self._check(self._lib.emp_world_drive(self._h, C.byref(p), C.byref(q), C.byref(sp), C.byref(sdp), C.byref(sqp), C.byref(dp),
+                                              C.byref(tp), law, C.byref(lat), C.byref(pid), C.byref(vp), C.byref(ap), C.byref(bp),
+                                              C.byref(avp), C.byref(hp), C.byref(wp), B, G, int(max_obs), M, A, int(max_dyn), K, T,
+                                              int(tick0), tsp, C.byref(io), a.where))
+        return WorldDriveResult(TimedDriveResult(log_profile=None, **res), WorldTrafficResult(**tr), **wl)
 
     # ---- lateral MPC controller (reference controller/controller.py:65-337) -----------------------
     def mpc_lateral(self, p: MpcParams, target_path, n_path, state, vx, min_index, qp_matrices=False) -> MpcResult:

@@ -22,7 +22,8 @@ HEADERS = ["emp_core.h", "emp_context.h", "emp_dp_launch.h", "emp_tail_launch.h"
            "emp_st_backend_core.h", "emp_st_backend_kernels.h", "emp_control_core.h", "emp_speed_front_kernels.h", "emp_rollout_kernels.h", "emp_drive_kernels.h",
            "emp_route_core.h", "emp_route_kernels.h", "emp_route_launch.h", "emp_agent_core.h", "emp_agent_kernels.h",
            "emp_behavior_core.h", "emp_behavior_launch.h", "emp_behavior_kernels.h",
-           "emp_hazard_core.h", "emp_hazard_launch.h", "emp_hazard_kernels.h"]
+           "emp_hazard_core.h", "emp_hazard_launch.h", "emp_hazard_kernels.h",
+           "emp_world_core.h", "emp_world_kernels.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 

@@ -26,6 +26,7 @@
 #include "emp_agent_kernels.h"
 #include "emp_behavior_kernels.h"
 #include "emp_hazard_kernels.h"
+#include "emp_world_kernels.h"
 
 namespace emp {
 thread_local std::string g_create_error;
@@ -2779,19 +2780,33 @@ struct DriveTimed {
     const emp_drive_timed_io* io;
 };
 
+// What emp_world_drive puts around each period of the loop below (its body is with the traffic calls): the exchange in front,
+// whose actors and n_act the period's request reads in place of the caller's, and the agents' ticks behind.  The arrays are staged
+// with the drive's own, inputs among its inputs and outputs among its outputs.
+struct DriveWorld {
+    const double* actors = nullptr;             // [B][max_act][4] on the device: the period's exchanged rows
+    const int* n_act = nullptr;                 // [B]
+    virtual void stage_in(Stage& st) = 0;
+    virtual void stage_out(Stage& st, size_t nK) = 0;
+    virtual int exchange(int k, const double* global_path, const int* n_global, const double* state, const int* pre_match_index) = 0;
+    virtual int traffic(int k) = 0;
+    virtual ~DriveWorld() {}
+};
+
 // emp_drive's body behind its own checks of ctx, NULL structs and `where`; with `tm` emp_drive_timed's: the same periods with the
-// timed request, the speed half behind the cycle, the profile adopted beside the track, the timed rollout
+// timed request, the speed half behind the cycle, the profile adopted beside the track, the timed rollout; with `wd` as well
+// emp_world_drive's: the same periods again, between the exchange and the agents' ticks
 int drive_impl(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth, const emp_drive_params* drv,
                int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid, const emp_vehicle_params* vp, int32_t B,
                int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act, int32_t max_dyn, int32_t K, int32_t T,
-               const double* target_speed, const emp_drive_io* io, emp_mem where, const DriveTimed* tm) {
+               const double* target_speed, const emp_drive_io* io, emp_mem where, const DriveTimed* tm, DriveWorld* wd = nullptr) {
     EMP_REQUIRE(ctx, B >= 0 && max_global >= 1, "bad sizes");
     EMP_REQUIRE(ctx, K >= 1 && K <= EMP_DRIVE_MAX_PERIODS, "K must be in [1, 4096]");
     EMP_REQUIRE(ctx, max_act >= 1 && max_act <= 64, "max_act must be in [1, 64]");
     EMP_REQUIRE(ctx, max_obs >= 1 && max_obs <= 253 && max_dyn >= 1 && max_dyn <= 64, "max_obs must be in [1, 253], max_dyn in [1, 64]");
     EMP_REQUIRE(ctx, max_pts >= 2 && max_pts <= 255, "2 <= max_pts <= 255 required");
     EMP_REQUIRE(ctx, qp->ds > 0, "ds must be > 0");
-    EMP_REQUIRE(ctx, target_speed && io->global_path && io->n_global && io->state && io->actors && io->n_act && io->pre_match_index &&
+    EMP_REQUIRE(ctx, target_speed && io->global_path && io->n_global && io->state && (wd || (io->actors && io->n_act)) && io->pre_match_index &&
                          io->track && io->track_len && io->held,
                 "NULL input array");
     EMP_REQUIRE(ctx, io->state_out && io->accel_out && io->actors_out && io->pre_match_index_out && io->track_out && io->track_len_out &&
@@ -2817,8 +2832,8 @@ int drive_impl(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, c
     const int* d_nglob = st.in(io->n_global, nB);
     const double* d_state = st.in(io->state, nB * 6);
     const double* d_accel = st.in(io->accel, nB * 2);
-    const double* d_actors = st.in(io->actors, nB * max_act * 4);
-    const int* d_nact = st.in(io->n_act, nB);
+    const double* d_actors = wd ? nullptr : st.in(io->actors, nB * max_act * 4);
+    const int* d_nact = wd ? nullptr : st.in(io->n_act, nB);
     const int* d_prem = st.in(io->pre_match_index, nB);
     const double* d_track = st.in(io->track, nB * row);
     const int* d_tlen = st.in(io->track_len, nB);
@@ -2828,6 +2843,7 @@ int drive_impl(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, c
     const double* d_prof = tm ? st.in(tm->io->profile, nB * prof) : nullptr;
     const int* d_cur = tm ? st.in(tm->io->cursor, nB) : nullptr;
     const int* d_sheld = tm ? st.in(tm->io->speed_held, nB) : nullptr;
+    if (wd) wd->stage_in(st);
     double* o_state = st.out(io->state_out, nB * 6, false);
     double* o_accel = st.out(io->accel_out, nB * 2, false);
     double* o_actors = st.out(io->actors_out, nB * max_act * 4, false);
@@ -2854,6 +2870,7 @@ int drive_impl(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, c
         l_cur = st.out(tm->io->log_cursor, nK * nB, false);
         l_prof = st.out(tm->io->log_profile, nK * nB * prof, false);
     }
+    if (wd) wd->stage_out(st, nK);
     // the request's outputs, the cycle's, the rollout's: temporaries of the drive pool, the same for every period
     drive::RequestIO rq{};
     rq.n_act = d_nact;
@@ -2948,6 +2965,11 @@ int drive_impl(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, c
         rq.state = k ? o_state : d_state;
         rq.accel = k ? o_accel : d_accel;
         rq.actors = k ? o_actors : d_actors;
+        if (wd) {
+            if (const int rc = wd->exchange(k, d_glob, d_nglob, rq.state, k ? o_prem : d_prem)) return rc;
+            rq.actors = wd->actors;
+            rq.n_act = wd->n_act;
+        }
         rq.log_state = l_state ? l_state + kB * 6 : nullptr;
         rq.log_counts = l_counts ? l_counts + kB * 2 : nullptr;
         ck.tick = tm ? tm->clock.tick(k) : 0;
@@ -2991,9 +3013,49 @@ int drive_impl(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, c
         if (const int rc = launch(ctx, "drive_accel", drive::drive_accel_kernel, grid1(B, 256), dim3(256), 0, B, vp->dt, (const double*)o_state,
                                   last_seen, o_accel))
             return rc;
+        if (wd)
+            if (const int rc = wd->traffic(k)) return rc;
     }
     ctx->pipe_mode = scope.pipe_mode;
     return st.finish();
+}
+
+// emp_drive_timed behind its own checks; with `wd` emp_world_drive's (io->actors and io->n_act are then not looked at)
+int drive_timed_impl(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
+                     const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp, const emp_drive_params* drv,
+                     const emp_drive_timed_params* tp, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
+                     const emp_vehicle_params* vp, int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act,
+                     int32_t max_dyn, int32_t K, int32_t T, int32_t tick0, const double* target_speed, const emp_drive_timed_io* io,
+                     emp_mem where, DriveWorld* wd) {
+    // emp_drive's arrays under their names
+    emp_drive_io base{};
+    base.global_path = io->global_path;
+    base.n_global = io->n_global;
+    base.state = io->state;
+    base.accel = io->accel;
+    base.actors = io->actors;
+    base.n_act = io->n_act;
+    base.pre_match_index = io->pre_match_index;
+    base.track = io->track;
+    base.track_len = io->track_len;
+    base.held = io->held;
+    base.state_out = io->state_out;
+    base.accel_out = io->accel_out;
+    base.actors_out = io->actors_out;
+    base.pre_match_index_out = io->pre_match_index_out;
+    base.track_out = io->track_out;
+    base.track_len_out = io->track_len_out;
+    base.held_out = io->held_out;
+    base.log_state = io->log_state;
+    base.log_plan_status = io->log_plan_status;
+    base.log_roll_status = io->log_roll_status;
+    base.log_held = io->log_held;
+    base.log_counts = io->log_counts;
+    base.log_traj = io->log_traj;
+    base.log_traj_len = io->log_traj_len;
+    const DriveTimed tm{sdp, sqp, tp->plan_lead, plan_drive_clock(tick0, K, T), io};
+    return drive_impl(ctx, dp, qp, smooth, drv, lateral, lat, pid, vp, B, max_global, max_obs, max_pts, max_act, max_dyn, K, T, target_speed,
+                      &base, where, &tm, wd);
 }
 
 }  // namespace
@@ -3071,35 +3133,8 @@ int emp_drive_timed(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* 
     EMP_REQUIRE(ctx, qp_reserved_ok(qp), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
     EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE,
                 "emp_drive_timed takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
-    // emp_drive's arrays under their names
-    emp_drive_io base{};
-    base.global_path = io->global_path;
-    base.n_global = io->n_global;
-    base.state = io->state;
-    base.accel = io->accel;
-    base.actors = io->actors;
-    base.n_act = io->n_act;
-    base.pre_match_index = io->pre_match_index;
-    base.track = io->track;
-    base.track_len = io->track_len;
-    base.held = io->held;
-    base.state_out = io->state_out;
-    base.accel_out = io->accel_out;
-    base.actors_out = io->actors_out;
-    base.pre_match_index_out = io->pre_match_index_out;
-    base.track_out = io->track_out;
-    base.track_len_out = io->track_len_out;
-    base.held_out = io->held_out;
-    base.log_state = io->log_state;
-    base.log_plan_status = io->log_plan_status;
-    base.log_roll_status = io->log_roll_status;
-    base.log_held = io->log_held;
-    base.log_counts = io->log_counts;
-    base.log_traj = io->log_traj;
-    base.log_traj_len = io->log_traj_len;
-    const DriveTimed tm{sdp, sqp, tp->plan_lead, plan_drive_clock(tick0, K, T), io};
-    return drive_impl(ctx, dp, qp, smooth, drv, lateral, lat, pid, vp, B, max_global, max_obs, max_pts, max_act, max_dyn, K, T, target_speed,
-                      &base, where, &tm);
+    return drive_timed_impl(ctx, dp, qp, smooth, sdp, sqp, drv, tp, lateral, lat, pid, vp, B, max_global, max_obs, max_pts, max_act, max_dyn, K, T,
+                            tick0, target_speed, io, where, nullptr);
 }
 
 }  // extern "C"
@@ -3556,48 +3591,357 @@ int emp_agent_behave_hazards(emp_ctx* ctx, const emp_agent_params* p, const emp_
     return st.finish();
 }
 
-int emp_traffic_rollout_hazards(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp,
-                                int32_t W, int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every,
-                                int64_t tick0, const emp_behavior_io* a, emp_mem where, const emp_hazard_params* hp, int32_t max_light,
-                                int32_t max_walker, const emp_hazard_io* h) {
-    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
-    EMP_REQUIRE(ctx, T >= 1, "T must be in [1, 65536]");
-    const bhv::BehaviorPlan plan = hz::plan_hazards(W, max_world, max_other, max_light, max_walker, max_path, T, log_every, tick0);
+}  // extern "C"
+
+namespace {
+
+// what emp_traffic_rollout_hazards refuses (emp_traffic_rollout_epoch and emp_world_drive with it)
+int traffic_hazards_checks(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp,
+                           const emp_behavior_io* a, int max_other, emp_mem where, const bhv::BehaviorPlan& plan, const emp_hazard_params* hp,
+                           int max_light, int max_walker, const emp_hazard_io* h) {
     if (const int rc = behavior_checks(ctx, "emp_traffic_rollout_hazards", p, bp, a, max_other, where, plan)) return rc;
     EMP_REQUIRE(ctx, vp != nullptr, "NULL parameter struct");
     EMP_REQUIRE(ctx, vp->reserved == 0, "emp_vehicle_params.reserved must be 0");
     EMP_REQUIRE(ctx, a->state_out && a->done_tick && a->mode_ticks && a->min_gap, "NULL array");
     if (const int rc = hazard_checks(ctx, hp, h, max_light, max_walker)) return rc;
     EMP_REQUIRE(ctx, h->cause_ticks && h->min_walker_gap, "NULL array");
+    return EMP_OK;
+}
+
+// ... and the arrays it stages, but for its logs
+void stage_traffic_hazards(Stage& st, const emp_behavior_io* a, const emp_hazard_io* h, size_t W, size_t max_world, size_t max_path,
+                           size_t max_other, size_t max_light, size_t max_walker, int64_t tick0, bool z, bhv::WorldIO* io, hz::HazardIO* hio) {
+    const size_t nA = W * max_world;
+    stage_world(st, a, W, max_world, max_path, max_other, tick0, io);
+    stage_behavior_state_out(st, a, nA, z, io);
+    io->state_out = st.out(a->state_out, nA * 6, z);
+    io->done_tick = st.out(a->done_tick, nA, z);
+    io->mode_ticks = st.out(a->mode_ticks, nA * bhv::kCountedModes, z);
+    io->min_gap = st.out(a->min_gap, nA, z);
+    io->actors_out = st.out(a->actors_out, nA * 4, z);
+    stage_hazards(st, h, W, nA, max_light, max_walker, z, hio);
+    hio->cause_ticks = st.out(h->cause_ticks, nA * hz::kCountedCauses, z);
+    hio->min_walker_gap = st.out(h->min_walker_gap, nA, z);
+}
+
+int launch_traffic_hazards(emp_ctx* ctx, const bhv::BehaviorPlan& plan, const emp_agent_params* p, const emp_behavior_params* bp,
+                           const emp_hazard_params* hp, const emp_vehicle_params* vp, size_t nA, const bhv::WorldIO& io,
+                           const hz::HazardIO& hio) {
+    return launch(ctx, "traffic_rollout_hazards", hz::traffic_rollout_hazards_kernel, dim3(plan.grid), dim3(plan.block), 0, agent_params(p),
+                  behavior_params(bp), hazard_params(hp), vehicle_params(vp), (int)nA, io, hio);
+}
+
+// emp_traffic_rollout_hazards is other_tick0 == 0
+int traffic_rollout_hazards_impl(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp,
+                                 int32_t W, int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every,
+                                 int64_t tick0, const emp_behavior_io* a, emp_mem where, const emp_hazard_params* hp, int32_t max_light,
+                                 int32_t max_walker, const emp_hazard_io* h, int64_t other_tick0) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, T >= 1, "T must be in [1, 65536]");
+    const bhv::BehaviorPlan plan = hz::plan_hazards(W, max_world, max_other, max_light, max_walker, max_path, T, log_every, tick0);
+    if (const int rc = traffic_hazards_checks(ctx, p, bp, vp, a, max_other, where, plan, hp, max_light, max_walker, h)) return rc;
+    if (const int rc = plan_refused(ctx, wx::epoch_error(tick0, other_tick0))) return rc;
     if (W == 0) return EMP_OK;
     const size_t nA = (size_t)W * max_world, n_log = plan.n_log;
     EMP_STAGE(st, where);
     const bool z = where == EMP_HOST;          // staged outputs start from 0; the caller's device memory is never filled
     bhv::WorldIO io{};
     hz::HazardIO hio{};
-    stage_world(st, a, (size_t)W, (size_t)max_world, (size_t)max_path, (size_t)max_other, tick0, &io);
+    stage_traffic_hazards(st, a, h, (size_t)W, (size_t)max_world, (size_t)max_path, (size_t)max_other, (size_t)max_light, (size_t)max_walker,
+                          tick0, z, &io, &hio);
+    io.other_tick0 = (long long)other_tick0;
     io.T = T;
     io.log_every = log_every;
-    stage_behavior_state_out(st, a, nA, z, &io);
-    io.state_out = st.out(a->state_out, nA * 6, z);
-    io.done_tick = st.out(a->done_tick, nA, z);
-    io.mode_ticks = st.out(a->mode_ticks, nA * bhv::kCountedModes, z);
-    io.min_gap = st.out(a->min_gap, nA, z);
-    io.actors_out = st.out(a->actors_out, nA * 4, z);
     io.log_state = st.out(a->log_state, n_log * nA * 6, z);
     io.log_control = st.out(a->log_control, n_log * nA * 3, z);
     io.log_head = st.out(a->log_head, n_log * nA, z);
     io.log_mode = st.out(a->log_mode, n_log * nA, z);
     io.log_target = st.out(a->log_target, n_log * nA, z);
-    stage_hazards(st, h, (size_t)W, nA, (size_t)max_light, (size_t)max_walker, z, &hio);
-    hio.cause_ticks = st.out(h->cause_ticks, nA * hz::kCountedCauses, z);
-    hio.min_walker_gap = st.out(h->min_walker_gap, nA, z);
     hio.log_cause = st.out(h->log_cause, n_log * nA, z);
     if (const int rc = st.ready()) return rc;
-    if (const int rc = launch(ctx, "traffic_rollout_hazards", hz::traffic_rollout_hazards_kernel, dim3(plan.grid), dim3(plan.block), 0,
-                              agent_params(p), behavior_params(bp), hazard_params(hp), vehicle_params(vp), (int)nA, io, hio))
+    if (const int rc = launch_traffic_hazards(ctx, plan, p, bp, hp, vp, nA, io, hio)) return rc;
+    return st.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int emp_traffic_rollout_hazards(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp,
+                                int32_t W, int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every,
+                                int64_t tick0, const emp_behavior_io* a, emp_mem where, const emp_hazard_params* hp, int32_t max_light,
+                                int32_t max_walker, const emp_hazard_io* h) {
+    return traffic_rollout_hazards_impl(ctx, p, bp, vp, W, max_world, max_path, max_other, T, log_every, tick0, a, where, hp, max_light,
+                                        max_walker, h, 0);
+}
+
+int emp_traffic_rollout_epoch(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp,
+                              int32_t W, int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every,
+                              int64_t tick0, const emp_behavior_io* a, emp_mem where, const emp_hazard_params* hp, int32_t max_light,
+                              int32_t max_walker, const emp_hazard_io* h, int64_t other_tick0) {
+    return traffic_rollout_hazards_impl(ctx, p, bp, vp, W, max_world, max_path, max_other, T, log_every, tick0, a, where, hp, max_light,
+                                        max_walker, h, other_tick0);
+}
+
+}  // extern "C"
+
+// ---- one world for a planning fleet and reacting traffic (emp_world_core.h, emp_world_kernels.h) -----------------------------------
+namespace {
+
+wx::Sizes exchange_sizes(int W, int max_world, int B, int max_global, int max_act, int max_other, int lane_window, int see_egos) {
+    return wx::Sizes{W, B, max_world, max_global, max_act, max_other, lane_window, see_egos};
+}
+
+int launch_exchange(emp_ctx* ctx, const wx::ExchangePlan& plan, const wx::Sizes& z, const double* agent_state, const wx::In& in,
+                    const wx::Out& out) {
+    return launch(ctx, "world_exchange", wx::world_exchange_kernel, dim3(plan.grid), dim3(plan.block), 0, z, agent_state, in, out);
+}
+
+// emp_world_drive's periods around drive_impl's: the arrays of the traffic and of the exchange, staged once, and the two launches
+struct WorldPeriods : DriveWorld {
+    emp_ctx* ctx;
+    const emp_agent_params* p;
+    const emp_behavior_params* bp;
+    const emp_vehicle_params* avp;
+    const emp_hazard_params* hp;
+    const emp_world_params* wp;
+    const emp_world_io* w;
+    wx::Sizes z;
+    wx::ExchangePlan xplan;
+    bhv::BehaviorPlan tplan;
+    wx::WorldClockPlan clock;
+    bool host;
+    size_t nA = 0, nB = 0;
+    bhv::WorldIO io{};
+    hz::HazardIO hio{};
+    const int* d_off = nullptr;
+    const double* d_extent = nullptr;
+    const int* d_elane = nullptr;
+    double *x_actors = nullptr, *x_other = nullptr, *l_astate = nullptr, *l_gap = nullptr, *l_wgap = nullptr;
+    int *x_nact = nullptr, *x_status = nullptr, *x_okey = nullptr, *x_nother = nullptr;
+    int *l_wx = nullptr, *l_nact = nullptr, *l_status = nullptr, *l_done = nullptr, *l_modes = nullptr, *l_causes = nullptr;
+
+    void stage_in(Stage& st) override {
+        d_off = st.in(w->ego_off, (size_t)z.W + 1);
+        d_extent = st.in(w->ego_extent, nB);
+        d_elane = st.in(w->ego_lane, nB * z.max_global);
+    }
+    void stage_out(Stage& st, size_t nK) override {
+        // the others are the exchange's: emp_behavior_io's are not read
+        stage_traffic_hazards(st, w->agents, w->hazards, (size_t)z.W, (size_t)z.max_world, (size_t)wp->max_path, 0, (size_t)wp->max_light,
+                              (size_t)wp->max_walker, clock.atick0, host, &io, &hio);
+        io.T = io.log_every = clock.Ta;
+        x_actors = st.tmp<double>(nB * z.max_act * 4);
+        x_nact = st.tmp<int>(nB);
+        x_status = st.tmp<int>(nB);
+        if (z.max_other > 0) {
+            x_other = st.tmp<double>((size_t)z.W * z.max_other * 5);
+            x_okey = st.tmp<int>((size_t)z.W * z.max_other);
+            x_nother = st.tmp<int>((size_t)z.W);
+        }
+        io.max_other = z.max_other;
+        io.n_other = x_nother;
+        io.other = x_other;
+        io.other_lane = x_okey;
+        l_wx = st.out(w->log_wx_status, nK * nB, false);
+        l_nact = st.out(w->log_n_act, nK * nB, false);
+        l_astate = st.out(w->log_agent_state, nK * nA * 6, false);
+        l_status = st.out(w->log_agent_status, nK * nA, false);
+        l_done = st.out(w->log_done_tick, nK * nA, false);
+        l_modes = st.out(w->log_mode_ticks, nK * nA * bhv::kCountedModes, false);
+        l_causes = st.out(w->log_cause_ticks, nK * nA * hz::kCountedCauses, false);
+        l_gap = st.out(w->log_min_gap, nK * nA, false);
+        l_wgap = st.out(w->log_min_walker_gap, nK * nA, false);
+    }
+    // a log row is the period's output array as it stands
+    template <typename T>
+    int keep(T* log, int k, const T* src, size_t n) {
+        if (!log) return EMP_OK;
+        EMP_HIP(ctx, hipMemcpyAsync(log + (size_t)k * n, src, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        return EMP_OK;
+    }
+    int exchange(int k, const double* global_path, const int* n_global, const double* state, const int* pre_match_index) override {
+        if (k) {                                           // the agents go on from where the last period left them
+            io.state = io.state_out;
+            io.st.head_in = io.st.head_out;
+            io.st.past_in = io.st.past_out;
+            io.st.lon_in = io.st.lon_out;
+            io.st.n_lon_in = io.st.n_lon_out;
+            io.st.lat_in = io.st.lat_out;
+            io.st.n_lat_in = io.st.n_lat_out;
+            hio.last_light = hio.last_light_out;
+        }
+        const wx::In in{io.n_world, d_off, state, d_extent, global_path, n_global, d_elane, pre_match_index};
+        int* nact = l_nact ? l_nact + (size_t)k * nB : x_nact;
+        const wx::Out out{x_actors, nact, x_other, x_okey, x_nother, l_wx ? l_wx + (size_t)k * nB : x_status};
+        actors = x_actors;
+        n_act = nact;
+        return launch_exchange(ctx, xplan, z, io.state, in, out);
+    }
+    int traffic(int k) override {
+        if (const int rc = keep(l_astate, k, io.state, nA * 6)) return rc;
+        io.tick0 = io.other_tick0 = (long long)clock.tick(k);
+        if (const int rc = launch_traffic_hazards(ctx, tplan, p, bp, hp, avp, nA, io, hio)) return rc;
+        if (const int rc = keep(l_status, k, (const int*)io.status, nA)) return rc;
+        if (const int rc = keep(l_done, k, (const int*)io.done_tick, nA)) return rc;
+        if (const int rc = keep(l_modes, k, (const int*)io.mode_ticks, nA * bhv::kCountedModes)) return rc;
+        if (const int rc = keep(l_causes, k, (const int*)hio.cause_ticks, nA * hz::kCountedCauses)) return rc;
+        if (const int rc = keep(l_gap, k, (const double*)io.min_gap, nA)) return rc;
+        return keep(l_wgap, k, (const double*)hio.min_walker_gap, nA);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+void emp_world_params_default(emp_world_params* p) {
+    if (!p) return;
+    p->W = 0;
+    p->max_world = 1;
+    p->max_path = 1;
+    p->max_other = 0;
+    p->max_light = p->max_walker = 0;
+    p->Ta = 1;
+    p->lane_window = 50;
+    p->see_egos = 0;
+    p->reserved = 0;
+    p->atick0 = 0;
+}
+
+int emp_world_exchange(emp_ctx* ctx, int32_t W, int32_t max_world, int32_t B, int32_t max_global, int32_t max_act, int32_t max_other,
+                       int32_t lane_window, int32_t see_egos, const emp_world_exchange_io* a, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE, "emp_world_exchange takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, a != nullptr, "NULL parameter struct");
+    EMP_REQUIRE(ctx, a->reserved == 0, "emp_world_exchange_io.reserved must be 0");
+    const wx::ExchangePlan plan = wx::plan_exchange(W, B, max_world, max_global, max_act, max_other, lane_window, see_egos);
+    if (const int rc = plan_refused(ctx, plan.error)) return rc;
+    EMP_REQUIRE(ctx, a->n_world && a->agent_state && a->ego_off && a->ego_state && a->ego_extent && a->global_path && a->n_global &&
+                         a->ego_lane && a->pre_match_index && a->actors && a->n_act && a->wx_status,
+                "NULL array");
+    EMP_REQUIRE(ctx, max_other == 0 || (a->other && a->other_lane && a->n_other), "max_other > 0 needs other, other_lane and n_other");
+    if (where == EMP_HOST)
+        if (const int rc = plan_refused(ctx, wx::ego_off_error(a->ego_off, W, B))) return rc;
+    if (W == 0 || B == 0) return EMP_OK;
+    const size_t nA = (size_t)W * max_world, nB = (size_t)B;
+    EMP_STAGE(st, where);
+    const double* d_agents = st.in(a->agent_state, nA * 6);
+    wx::In in{};
+    in.n_world = st.in(a->n_world, (size_t)W);
+    in.ego_off = st.in(a->ego_off, (size_t)W + 1);
+    in.ego_state = st.in(a->ego_state, nB * 6);
+    in.ego_extent = st.in(a->ego_extent, nB);
+    in.global_path = st.in(a->global_path, nB * max_global * 4);
+    in.n_global = st.in(a->n_global, nB);
+    in.ego_lane = st.in(a->ego_lane, nB * max_global);
+    in.pre_match_index = st.in(a->pre_match_index, nB);
+    wx::Out out{};
+    out.actors = st.out(a->actors, nB * max_act * 4, false);
+    out.n_act = st.out(a->n_act, nB, false);
+    out.wx_status = st.out(a->wx_status, nB, false);
+    if (max_other > 0) {
+        out.other = st.out(a->other, (size_t)W * max_other * 5, false);
+        out.other_lane = st.out(a->other_lane, (size_t)W * max_other, false);
+        out.n_other = st.out(a->n_other, (size_t)W, false);
+    }
+    if (const int rc = st.ready()) return rc;
+    if (const int rc = launch_exchange(ctx, plan, exchange_sizes(W, max_world, B, max_global, max_act, max_other, lane_window, see_egos),
+                                       d_agents, in, out))
         return rc;
     return st.finish();
+}
+
+int emp_world_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
+                    const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp, const emp_drive_params* drv,
+                    const emp_drive_timed_params* tp, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
+                    const emp_vehicle_params* vp, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* avp,
+                    const emp_hazard_params* hp, const emp_world_params* wp, int32_t B, int32_t max_global, int32_t max_obs,
+                    int32_t max_pts, int32_t max_act, int32_t max_dyn, int32_t K, int32_t T, int32_t tick0, const double* target_speed,
+                    const emp_world_io* io, emp_mem where) {
+    EMP_REQUIRE(ctx, ctx != nullptr, "ctx is NULL");
+    EMP_REQUIRE(ctx, dp && qp && smooth && sdp && sqp && drv && tp && lat && pid && vp && p && bp && avp && hp && wp && io,
+                "NULL parameter struct");
+    EMP_REQUIRE(ctx, io->agents && io->hazards, "NULL parameter struct");
+    EMP_REQUIRE(ctx, drv->reserved == 0, "emp_drive_params.reserved must be 0");
+    EMP_REQUIRE(ctx, tp->reserved == 0, "emp_drive_timed_params.reserved must be 0");
+    EMP_REQUIRE(ctx, std::isfinite(tp->plan_lead), "emp_drive_timed_params.plan_lead must be finite");
+    EMP_REQUIRE(ctx, wp->reserved == 0, "emp_world_params.reserved must be 0");
+    EMP_REQUIRE(ctx, io->reserved == 0, "emp_world_io.reserved must be 0");
+    if (const int rc = rollout_args_ok(ctx, lateral, vp, T, 1)) return rc;
+    EMP_REQUIRE(ctx, qp_reserved_ok(qp), "emp_qp_params.reserved must be 0 (start from emp_qp_params_default)");
+    EMP_REQUIRE(ctx, where == EMP_HOST || where == EMP_DEVICE,
+                "emp_world_drive takes EMP_HOST or EMP_DEVICE arrays (EMP_HOST_PINNED is emp_plan_cycle's)");
+    EMP_REQUIRE(ctx, K >= 1 && K <= EMP_DRIVE_MAX_PERIODS, "K must be in [1, 4096]");
+    // the exchange's rules, the traffic's, the two clocks'
+    WorldPeriods wd;
+    wd.xplan = wx::plan_exchange(wp->W, B, wp->max_world, max_global, max_act, wp->max_other, wp->lane_window, wp->see_egos);
+    if (const int rc = plan_refused(ctx, wd.xplan.error)) return rc;
+    wd.clock = wx::plan_world_clock(K, T, vp->dt, wp->Ta, p->dt, wp->atick0);
+    if (const int rc = plan_refused(ctx, wd.clock.error)) return rc;
+    wd.tplan = hz::plan_hazards(wp->W, wp->max_world, wp->max_other, wp->max_light, wp->max_walker, wp->max_path, wp->Ta, wp->Ta,
+                                wd.clock.tick(K - 1));
+    if (const int rc = traffic_hazards_checks(ctx, p, bp, avp, io->agents, 0, where, wd.tplan, hp, wp->max_light, wp->max_walker, io->hazards))
+        return rc;
+    EMP_REQUIRE(ctx, !io->agents->log_state && !io->agents->log_control && !io->agents->log_head && !io->agents->log_mode &&
+                         !io->agents->log_target && !io->hazards->log_cause,
+                "emp_world_drive keeps no tick logs: the log_* arrays of emp_behavior_io and emp_hazard_io must be NULL");
+    EMP_REQUIRE(ctx, io->ego_off && io->ego_extent && io->ego_lane, "NULL input array");
+    if (where == EMP_HOST)
+        if (const int rc = plan_refused(ctx, wx::ego_off_error(io->ego_off, wp->W, B))) return rc;
+    // emp_drive_timed's arrays under their names
+    emp_drive_timed_io tio{};
+    tio.global_path = io->global_path;
+    tio.n_global = io->n_global;
+    tio.state = io->state;
+    tio.accel = io->accel;
+    tio.pre_match_index = io->pre_match_index;
+    tio.track = io->track;
+    tio.track_len = io->track_len;
+    tio.held = io->held;
+    tio.t0 = io->t0;
+    tio.profile = io->profile;
+    tio.cursor = io->cursor;
+    tio.speed_held = io->speed_held;
+    tio.state_out = io->state_out;
+    tio.accel_out = io->accel_out;
+    tio.actors_out = io->actors_out;
+    tio.pre_match_index_out = io->pre_match_index_out;
+    tio.track_out = io->track_out;
+    tio.track_len_out = io->track_len_out;
+    tio.held_out = io->held_out;
+    tio.profile_out = io->profile_out;
+    tio.cursor_out = io->cursor_out;
+    tio.speed_held_out = io->speed_held_out;
+    tio.log_state = io->log_state;
+    tio.log_plan_status = io->log_plan_status;
+    tio.log_roll_status = io->log_roll_status;
+    tio.log_held = io->log_held;
+    tio.log_counts = io->log_counts;
+    tio.log_traj = io->log_traj;
+    tio.log_traj_len = io->log_traj_len;
+    tio.log_speed_status = io->log_speed_status;
+    tio.log_speed_held = io->log_speed_held;
+    tio.log_tgt_status = io->log_tgt_status;
+    tio.log_cursor = io->log_cursor;
+    tio.log_profile = io->log_profile;
+    if (B == 0 || wp->W == 0) {                            // nothing runs; emp_drive_timed's own refusals still hold
+        if (const int rc = plan_refused(ctx, plan_drive_clock(tick0, K, T).error)) return rc;
+        return EMP_OK;
+    }
+    wd.ctx = ctx;
+    wd.p = p;
+    wd.bp = bp;
+    wd.avp = avp;
+    wd.hp = hp;
+    wd.wp = wp;
+    wd.w = io;
+    wd.z = exchange_sizes(wp->W, wp->max_world, B, max_global, max_act, wp->max_other, wp->lane_window, wp->see_egos);
+    wd.host = where == EMP_HOST;
+    wd.nA = (size_t)wp->W * wp->max_world;
+    wd.nB = (size_t)B;
+    return drive_timed_impl(ctx, dp, qp, smooth, sdp, sqp, drv, tp, lateral, lat, pid, vp, B, max_global, max_obs, max_pts, max_act, max_dyn, K, T,
+                            tick0, target_speed, &tio, where, &wd);
 }
 
 }  // extern "C"

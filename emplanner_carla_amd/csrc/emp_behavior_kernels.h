@@ -28,6 +28,7 @@ namespace bhv {
 struct WorldIO {
     int max_world, max_path, max_other;
     long long tick0;
+    long long other_tick0;         // the tick index the others' rows were taken at (the rollouts; 0 but for emp_traffic_rollout_epoch)
     const int* n_world;            // [W]
     const double* path;            // [A][max_path][4], A = W * max_world
     const int* n_path;             // [A]
@@ -201,7 +202,7 @@ __global__ __launch_bounds__(64) void traffic_rollout_kernel(agt::Params ap, Par
         }
         __syncthreads();
         if (w.live) {
-            const Scene sc = scene(l, buf, lane, w, (double)(io.tick0 + t) * ap.dt);
+            const Scene sc = scene(l, buf, lane, w, (double)(io.tick0 + t - io.other_tick0) * ap.dt);
             const Out r = behave(ap, bp, path, lrow, np_, s.x, s.y, o.c, o.s, o.kmh, limit, extent, sc, g);
             if (t % io.log_every == 0) {
                 const size_t row = (size_t)(t / io.log_every) * A + a;

@@ -170,7 +170,8 @@ __global__ __launch_bounds__(64) void traffic_rollout_hazards_kernel(agt::Params
         if (w.live) {
             hs.k = io.tick0 + t;
             hs.tau = (double)hs.k * ap.dt;
-            const bhv::Scene sc = bhv::scene(l, buf, lane, w, hs.tau);
+            // the others move from the tick their rows were taken at; lights and walkers stay on k
+            const bhv::Scene sc = bhv::scene(l, buf, lane, w, (double)(hs.k - io.other_tick0) * ap.dt);
             const Out r = behave(ap, bp, hp, path, lrow, np_, s.x, s.y, o.c, o.s, o.kmh, limit, extent, sc, hs, g, last);
             if (t % io.log_every == 0) {
                 const size_t row = (size_t)(t / io.log_every) * A + a;

@@ -273,3 +273,67 @@ class BehaviorTraffic(TrafficAgents):
 
     def done(self):
         return self._world(super().done())
+
+
+class World:
+    """A planning fleet and a ``BehaviorTraffic`` in the same W worlds, driven together by ``Planner.world_drive``: world w holds
+    the traffic's agents of that world and the egos ego_off[w] <= b < ego_off[w + 1] (ego_off (W + 1,), non-decreasing; an ego
+    outside every range is in no world).  ``params`` are ``drive_timed``'s nine parameter blocks in its order (p, q, sp, sdp, sqp,
+    dp, lat, pid, vp).  The ego arrays - global_path (B, G, 4), n_global (B,), ego_lane (B, G) (``RouteResult.lane_key(graph)``),
+    state (B, 6), target_speed (B,) km/h, t0 (B,) (None: zeros), ego_extent (a number, or (B,)) - are of the traffic's kind (NumPy
+    or torch CUDA); what changes is held here and updated in place.  ``drive(K)`` runs K periods of T ego ticks and
+    Ta = round(T * vp.dt / traffic.params.dt) agent ticks and advances both clocks: ``tick`` here, ``traffic.tick`` there - the
+    traffic's clock is never reset, so its lights keep their phase.  ``traffic.set_others`` is not used: the egos are exchanged
+    every period."""
+
+    def __init__(self, planner, traffic: BehaviorTraffic, params, global_path, n_global, ego_lane, state, target_speed, ego_off, T,
+                 max_obs, max_act=None, max_other=None, max_dyn=8, ego_extent=2.4, t0=None, see_egos=False, lane_window=50,
+                 lateral="mpc", tp=None, max_pts=None):
+        if len(params) != 9:
+            raise ValueError("params: drive_timed's nine parameter blocks (p, q, sp, sdp, sqp, dp, lat, pid, vp)")
+        self.planner, self.traffic, self.params = planner, traffic, tuple(params)
+        tr = traffic
+        if api._is_torch(state) != tr._torch:
+            raise ValueError("the egos' arrays and the traffic's must both be torch device tensors or both be host arrays")
+        B, G = int(global_path.shape[0]), int(global_path.shape[1])
+        self.B, self.T = B, int(T)
+        vp = self.params[8]
+        self.Ta = max(1, round(self.T * vp.dt / tr.params.dt))
+        if abs(self.T * vp.dt - self.Ta * tr.params.dt) > 1e-9:
+            raise ValueError(f"T * vp.dt = {self.T * vp.dt} s is no whole number of agent ticks of {tr.params.dt} s")
+        self.max_obs, self.max_dyn, self.max_pts = int(max_obs), int(max_dyn), (int(max_pts) if max_pts else api.max_path_points(self.params[0]))
+        self.max_act = int(max_act) if max_act is not None else min(64, tr.N + (B if see_egos else 0))
+        self.max_other = int(max_other) if max_other is not None else min(64, max(B, 1))
+        self.see_egos, self.lane_window, self.lateral, self.tp = bool(see_egos), int(lane_window), lateral, tp
+        own, zeros = tr._own, tr._zeros
+        self.global_path, self.n_global, self.ego_lane = own(global_path, np.float64), own(n_global, np.int32), own(ego_lane, np.int32)
+        self.ego_off = own(ego_off, np.int32)
+        self.state = own(state, np.float64, copy=True)
+        self.target_speed = zeros((B,), np.float64)
+        tr._fill(self.target_speed, target_speed)
+        self.ego_extent = zeros((B,), np.float64)
+        tr._fill(self.ego_extent, ego_extent)
+        self.t0 = zeros((B,), np.float64) if t0 is None else own(t0, np.float64)
+        self.accel = zeros((B, 2), np.float64)
+        self.pre_match_index, self.track_len = zeros((B,), np.int32), zeros((B,), np.int32)
+        self.track = zeros((B, self.max_pts + 1, 4), np.float64)
+        self.held, self.cursor, self.speed_held = zeros((B,), np.int32), zeros((B,), np.int32), zeros((B,), np.int32)
+        self.profile = zeros((B, 7, L.TIMED_POINTS), np.float64)
+        tr._fill(self.profile, float("nan"))                  # no profile yet: the cap is tracked until a plan is adopted
+        self.tick = 0                                          # ego ticks done
+
+    def drive(self, K, logs=True):
+        """K periods in one call -> ``WorldDriveResult``; both fleets' state and both clocks advance."""
+        tr, v = self.traffic, self.traffic._world
+        r = self.planner.world_drive(
+            *self.params, tr.params, tr.behavior, tr._hazard_params(), tr.vp, self.global_path, self.n_global, self.state, self.accel,
+            self.pre_match_index, self.track, self.track_len, self.held, self.t0, self.profile, self.cursor, self.speed_held,
+            self.target_speed, self.ego_off, self.ego_extent, self.ego_lane, tr.n_world, v(tr.paths), v(tr.n_path), tr.lane,
+            v(tr.state), tr.speed_limit, tr.extent, *tr._state_args(), tr.last_light, K, self.T, self.Ta, self.max_obs, self.max_act,
+            self.max_other, max_dyn=self.max_dyn, tick0=self.tick, atick0=tr.tick, lights=tr.lights, walkers=tr.walkers,
+            see_egos=self.see_egos, lane_window=self.lane_window, tp=self.tp, max_pts=self.max_pts, lateral=self.lateral, logs=logs,
+            in_place=True)
+        tr.status = r.traffic.status.reshape(tr.A)
+        self.tick += int(K) * self.T
+        tr.tick += int(K) * self.Ta
+        return r

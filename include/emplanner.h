@@ -1698,6 +1698,167 @@ int emp_traffic_rollout_hazards(emp_ctx* ctx, const emp_agent_params* p, const e
                                 int64_t tick0, const emp_behavior_io* io, emp_mem where, const emp_hazard_params* hp, int32_t max_light,
                                 int32_t max_walker, const emp_hazard_io* hio);
 
+/* ---- one world for a planning fleet and reacting traffic (new with ABI 13's library; EMP_ABI_VERSION is unchanged) ---------------
+ * The reference has no counterpart: CARLA's world tick couples its vehicles.  Here the two fleets of the sections above - the egos
+ * of emp_drive_timed and the agents of emp_traffic_rollout_hazards - are put in W worlds, and K periods of both run in ONE call.
+ * Nothing above changes: emp_traffic_rollout and emp_traffic_rollout_hazards are emp_traffic_rollout_epoch with other_tick0 = 0.
+ *
+ * WORLDS.  World w holds the agents of slots [w * max_world, w * max_world + n_world[w]) (as above) and the egos
+ * b in [ego_off[w], ego_off[w + 1]): ego_off [W + 1] int32, non-decreasing, inside [0, B].  EMP_HOST offsets that are not are
+ * refused; EMP_DEVICE offsets are clamped in the kernel (e0 = clamp(ego_off[w], 0, B), e1 = clamp(ego_off[w + 1], e0, B); no world:
+ * b < clamp(ego_off[0]) or b >= clamp(ego_off[W])), which keeps every access inside the arrays and promises nothing else.  An ego in
+ * no world sees nothing, and nobody sees it.
+ *
+ * emp_world_exchange: who sees whom, from the states of both fleets (one kernel, one 64-lane block per world).
+ *   actors [B][max_act][4], n_act [B]: for ego b of world w the rows emp_agent_observe gives for the world's live agents, in slot
+ *     order; with see_egos == 1 the world's other egos follow in index order, without b itself.  The rows come from the device
+ *     function emp_agent_observe uses: they equal its output BIT FOR BIT.  n_act = min(rows, max_act); rows past max_act are dropped
+ *     and EMP_WX_ACT_TRUNCATED is set; slots at and past n_act are written as 0.  An ego in no world: n_act 0, all rows 0,
+ *     EMP_WX_NO_WORLD.
+ *   other [W][max_other][5], other_lane [W][max_other], n_other [W]: emp_behavior_io's others of world w - for its egos in index
+ *     order the ego's observe row and ego_extent[b], and the lane key it shows.  n_other = min(egos, max_other); an ego past
+ *     max_other is not listed and EMP_WX_NOT_LISTED is set on it; slots at and past n_other are written as 0 with key -1.
+ *     max_other == 0: the three arrays are not touched (they may be NULL) and every ego of a world is EMP_WX_NOT_LISTED.
+ *   wx_status [B]: the OR of the EMP_WX_* bits.
+ * THE LANE KEY an ego shows is a windowed nearest match on its global path: n = n_global[b] clamped to [0, max_global];
+ * lo = clamp(pre_match_index[b], 0, n - 1), hi = min(lo + lane_window, n - 1); d2_i = (dx * dx) + (dy * dy) with
+ * (dx, dy) = (global_path[b][i] x - x_b, ... y - y_b), every operation rounded on its own; i* = the LOWEST index with the smallest
+ * d2 in [lo, hi]; a NaN d2 never wins, and if all are NaN i* = lo.  The key is ego_lane[b][i*] (ego_lane [B][max_global] int32:
+ * the lane key of each global waypoint); n == 0: -1.
+ * Refused (EMP_ERR_INVALID) before any launch: a NULL required pointer (everything but other / other_lane / n_other with
+ * max_other == 0); W < 0, B < 0, max_global < 1, max_world outside [1, EMP_TRAFFIC_MAX_WORLD], max_act outside [1, 64], max_other
+ * outside [0, 64], lane_window < 0, see_egos not 0 or 1; reserved != 0; EMP_HOST_PINNED; bad EMP_HOST offsets.  W == 0 or B == 0:
+ * EMP_OK, nothing is written.
+ *
+ * emp_traffic_rollout_epoch: emp_traffic_rollout_hazards with one more argument, other_tick0.  At tick index k = tick0 + t an
+ * other stands at x + vx * ((double)(k - other_tick0) * dt) (the subtraction in int64): `other` holds the rows as they were at
+ * tick other_tick0.  Lights and walkers stay on k.  Everything else is that call, from the same kernel; other_tick0 == 0 IS that
+ * call, bit for bit.  Refused beyond what it refuses: other_tick0 < 0 or other_tick0 > tick0.
+ *
+ * emp_world_drive: K periods on emp_stream(), stream-ordered, without a host synchronisation or a copy to the host between them.
+ * Period k, with tick_k = tick0 + k * T (emp_drive_timed's clock) and a_k = atick0 + k * Ta (int64, the agents' clock):
+ *   1. emp_world_exchange on the egos' and the agents' states, with the pre_match_index the period starts from
+ *   2. the period of emp_drive_timed (its steps 1-5, the same code) on the exchanged actors and n_act at tick_k
+ *   3. emp_traffic_rollout_epoch: Ta ticks at tick0 = a_k with the exchanged others, other_tick0 = a_k, log_every = Ta
+ * 2 and 3 both read the snapshot of 1: inside a period each fleet sees the other move straight, the rule both calls have.
+ * EVERY OUTPUT AND LOG EQUALS, BIT FOR BIT, K iterations of the three public calls and the adopt rule on the same arrays, and a
+ * call cut in two resumes bit for bit with tick0 advanced by k * T and atick0 by k * Ta.
+ * emp_world_io holds
+ *   the egos: emp_drive_timed_io's fields without actors and n_act (actors_out stays: the last period's exchanged rows, advanced
+ *     as emp_drive_request_timed leaves them), and the exchange's ego_off, ego_extent, ego_lane;
+ *   the traffic: agents (emp_behavior_io) and hazards (emp_hazard_io) exactly as emp_traffic_rollout_hazards takes them - state in
+ *     and out, last_light included, each output possibly the memory of its input - but for n_other / other / other_lane, which are
+ *     not read (the exchange makes them), and the five log_* arrays of emp_behavior_io and log_cause, which must be NULL.  status,
+ *     done_tick, mode_ticks, min_gap, actors_out, cause_ticks, min_walker_gap come back as the LAST period's;
+ *   per-period logs, NULL to skip, each row that period's call output: log_wx_status [K][B], log_n_act [K][B], log_agent_state
+ *     [K][A][6] (the state at the period's start), log_agent_status [K][A], log_done_tick [K][A], log_mode_ticks [K][A][5],
+ *     log_cause_ticks [K][A][3], log_min_gap [K][A], log_min_walker_gap [K][A], A = W * max_world.  A log row is a copy of the
+ *     call's output array, padding slots included.
+ * Everything runs on the one stream: no second stream, no graph capture.  Refused before any launch: what the three calls refuse;
+ * the agents' clock (Ta < 1, atick0 < 0, atick0 + K * Ta > INT32_MAX); periods of different length,
+ * |T * vp->dt - Ta * agent_params->dt| > 1e-9.  B == 0 or W == 0: EMP_OK, nothing runs. */
+#define EMP_WX_ACT_TRUNCATED 1
+#define EMP_WX_NOT_LISTED 2
+#define EMP_WX_NO_WORLD 4
+typedef struct emp_world_exchange_io {
+    const int32_t* n_world;                /* [W] */
+    const double* agent_state;             /* [W * max_world][6] */
+    const int32_t* ego_off;                /* [W + 1] */
+    const double* ego_state;               /* [B][6] */
+    const double* ego_extent;              /* [B] */
+    const double* global_path;             /* [B][max_global][4] */
+    const int32_t* n_global;               /* [B] */
+    const int32_t* ego_lane;               /* [B][max_global] */
+    const int32_t* pre_match_index;        /* [B] */
+    double* actors;                        /* [B][max_act][4] */
+    int32_t* n_act;                        /* [B] */
+    double* other;                         /* [W][max_other][5] */
+    int32_t* other_lane;                   /* [W][max_other] */
+    int32_t* n_other;                      /* [W] */
+    int32_t* wx_status;                    /* [B] */
+    int32_t reserved;                      /* must be 0 */
+} emp_world_exchange_io;
+int emp_world_exchange(emp_ctx* ctx, int32_t W, int32_t max_world, int32_t B, int32_t max_global, int32_t max_act, int32_t max_other,
+                       int32_t lane_window, int32_t see_egos, const emp_world_exchange_io* io, emp_mem where);
+int emp_traffic_rollout_epoch(emp_ctx* ctx, const emp_agent_params* p, const emp_behavior_params* bp, const emp_vehicle_params* vp,
+                              int32_t W, int32_t max_world, int32_t max_path, int32_t max_other, int32_t T, int32_t log_every,
+                              int64_t tick0, const emp_behavior_io* io, emp_mem where, const emp_hazard_params* hp, int32_t max_light,
+                              int32_t max_walker, const emp_hazard_io* hio, int64_t other_tick0);
+
+typedef struct emp_world_params {
+    int32_t W, max_world, max_path, max_other, max_light, max_walker;      /* the traffic's sizes */
+    int32_t Ta;                            /* agent ticks per period */
+    int32_t lane_window;                   /* 50 */
+    int32_t see_egos;                      /* 0 or 1 */
+    int32_t reserved;                      /* must be 0 */
+    int64_t atick0;                        /* the agents' tick index at the call's first period */
+} emp_world_params;
+void emp_world_params_default(emp_world_params* p);
+typedef struct emp_world_io {
+    /* the egos: emp_drive_timed_io's inputs without actors and n_act */
+    const double* global_path;
+    const int32_t* n_global;
+    const double* state;
+    const double* accel;
+    const int32_t* pre_match_index;
+    const double* track;
+    const int32_t* track_len;
+    const int32_t* held;
+    const double* t0;
+    const double* profile;
+    const int32_t* cursor;
+    const int32_t* speed_held;
+    /* ... and the exchange's */
+    const int32_t* ego_off;                /* [W + 1] */
+    const double* ego_extent;              /* [B] */
+    const int32_t* ego_lane;               /* [B][max_global] */
+    /* the egos' outputs (required; each may alias the input of its name) */
+    double* state_out;
+    double* accel_out;
+    double* actors_out;                    /* [B][max_act][4] */
+    int32_t* pre_match_index_out;
+    double* track_out;
+    int32_t* track_len_out;
+    int32_t* held_out;
+    double* profile_out;
+    int32_t* cursor_out;
+    int32_t* speed_held_out;
+    /* the egos' per-period logs, NULL to skip: emp_drive_timed_io's */
+    double* log_state;
+    int32_t* log_plan_status;
+    int32_t* log_roll_status;
+    int32_t* log_held;
+    int32_t* log_counts;
+    double* log_traj;
+    int32_t* log_traj_len;
+    int32_t* log_speed_status;
+    int32_t* log_speed_held;
+    int32_t* log_tgt_status;
+    int32_t* log_cursor;
+    double* log_profile;
+    /* the traffic, as emp_traffic_rollout_hazards takes it */
+    const emp_behavior_io* agents;
+    const emp_hazard_io* hazards;
+    /* the world's per-period logs, NULL to skip */
+    int32_t* log_wx_status;                /* [K][B] */
+    int32_t* log_n_act;                    /* [K][B] */
+    double* log_agent_state;               /* [K][A][6] */
+    int32_t* log_agent_status;             /* [K][A] */
+    int32_t* log_done_tick;                /* [K][A] */
+    int32_t* log_mode_ticks;               /* [K][A][5] */
+    int32_t* log_cause_ticks;              /* [K][A][3] */
+    double* log_min_gap;                   /* [K][A] */
+    double* log_min_walker_gap;            /* [K][A] */
+    int32_t reserved;                      /* must be 0 */
+} emp_world_io;
+int emp_world_drive(emp_ctx* ctx, const emp_dp_params* dp, const emp_qp_params* qp, const emp_smooth_params* smooth,
+                    const emp_speed_dp_params* sdp, const emp_speed_qp_params* sqp, const emp_drive_params* drive_params,
+                    const emp_drive_timed_params* timed_params, int32_t lateral, const emp_mpc_params* lat, const emp_pid_params* pid,
+                    const emp_vehicle_params* vp, const emp_agent_params* agent_params, const emp_behavior_params* behavior_params,
+                    const emp_vehicle_params* agent_vp, const emp_hazard_params* hazard_params, const emp_world_params* world,
+                    int32_t B, int32_t max_global, int32_t max_obs, int32_t max_pts, int32_t max_act, int32_t max_dyn, int32_t K,
+                    int32_t T, int32_t tick0, const double* target_speed, const emp_world_io* io, emp_mem where);
+
 #ifdef __cplusplus
 }
 #endif
